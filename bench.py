@@ -16,7 +16,12 @@ reduce(sum) of the float3 framebuffer to rank / device 0 inside the timed region
   * plain `python bench.py --gpus N`: ONE process, art_init_devices(N) -- the library shards and reduces by itself
     (what the single-task Ada host gets).
 
-Extra objects on the line:
+A plain run sets up, warms up, times --steps steps and prints the headline line (metric, value, unit, ms_per_step, config, multi_gpu);
+"roofline", "whole_job_roofline", "stages" and "cpu_baseline" are null there.  --full adds them (the untimed counting pass, the CPU
+oracle leg, the stage figures), as below.  --dump-outputs DIR writes what the timed path computed in its last step as DIR/<name>.npy
+(dump_outputs); the inputs are seeded, so two builds run with the same arguments can be compared array for array.
+
+Extra objects on the line (--full):
   "roofline"      the trace kernel against the memory roofline it is bound by.  achieved = rays x algorithmic bytes per ray /
                   trace-kernel time (HIP events around every launch, on the launch stream); algorithmic bytes per ray =
                   node_bytes x node visits + 48 x triangle tests + 64, the visits and tests counted on this very workload by
@@ -54,6 +59,7 @@ STAGE_IN_B, STAGE_IN_B0, STAGE_GATHER_B, STAGE_FOLDREC_B, STAGE_OUT_B = 60.0, 16
 FOLD_B = 56.0            # k_fold_level per item of a level: w 12 + child 4 + e 12 + the level below 12 + its child word 4, writes 12
 RAYGEN_B = 80.0          # per camera path: trace record 64 + hit record 16
 ACCUM_B = 12.0           # k_accumulate reads the per-sample radiance
+DUMP_BUDGET_B = 64 * 10 ** 6     # --dump-outputs: bytes of array data in all; a larger frame is written as a seeded sample of its pixels
 
 
 def build_scene(art, args):
@@ -171,6 +177,25 @@ def cpu_baseline(art, sd, args, be):
     return out
 
 
+def dump_outputs(be, spp, out_dir):
+    """What a caller of the timed path receives after its last step (art_download): the float3 framebuffer (row-major [H, W, 3]), the
+    resolved frame (screen_buffer, r | g << 8 | b << 16: its three bytes as float32 [H, W, 3]) and the sample count.  A frame whose two
+    arrays exceed DUMP_BUDGET_B is written as a fixed, seeded sample of its pixels: [n, 3] each, with their row-major indices in pixel_index."""
+    accum, screen = be.download(spp, want_screen=True)
+    rgb = screen.view(np.uint8).reshape(screen.shape + (4,))[..., :3].astype(np.float32)
+    out = {"accum": accum, "screen_rgb": rgb}
+    n_px = accum.shape[0] * accum.shape[1]
+    if n_px * 24 > DUMP_BUDGET_B:
+        k = (DUMP_BUDGET_B - 4096) // (24 + 8)
+        idx = np.sort(np.random.default_rng(0).choice(n_px, k, replace=False))
+        out = {name: a.reshape(n_px, 3)[idx] for name, a in out.items()}
+        out["pixel_index"] = idx.astype(np.float64)
+    out["spp"] = np.array([spp], np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -192,6 +217,8 @@ def main():
     ap.add_argument("--simulate-shard", default="", help="R/N: render only rank R's pixel tiles of an N-GPU job on this one GPU (scaling rehearsal)")
     ap.add_argument("--contexts", type=int, default=0, help="rehearse the one-process N-device path with N contexts on GPU 0 (a 1-GPU box)")
     ap.add_argument("--opt", action="append", default=[], help="backend option name=value (art_set_option), e.g. bvh_leaf_base_milli=1000")
+    ap.add_argument("--full", action="store_true", help="also the roofline (untimed counting pass), the stage figures and the cpu_baseline leg")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR", help="write the framebuffer of the last timed step as DIR/<name>.npy")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -317,9 +344,11 @@ def main():
                      "passes": int(r1.passes - r0.passes), "passes_overlapped": int(r1.passes_overlapped - r0.passes_overlapped)}
 
     if rank == 0:
+        if args.dump_outputs:          # before the counting pass below, which accumulates into the same framebuffer
+            dump_outputs(be, spp, args.dump_outputs)
         # ---- roofline of the dominant kernel (trace): algorithmic bytes / HIP-event time, device 0's launches
         roofline = None
-        if not args.no_counters and info.n_tris > 0:      # a scene without a BVH mesh never launches the trace kernel; one-process N-GPU mode: device 0's launches
+        if args.full and not args.no_counters and info.n_tris > 0:      # a scene without a BVH mesh never launches the trace kernel; one-process N-GPU mode: device 0's launches
             be.set_option("count_tests", 1)
             c0 = be.stats()
             be.render_pass_device(art.Backend.pass_params(art.PT_MIS, True, 8, 1, seed=1), spp)   # untimed, counting variant
@@ -382,7 +411,7 @@ def main():
         # ---- the stages around the trace kernel and the whole-job roofline (device 0 / this rank; cumulative counters of the timed steps)
         stages = None
         whole = None
-        if args.kernel == "coop" and g1.batches > g0.batches:
+        if args.full and args.kernel == "coop" and g1.batches > g0.batches:
             nb = g1.batches - g0.batches
             ins = [g1.items_in[k] - g0.items_in[k] for k in range(16)]; outs = [g1.items_out[k] - g0.items_out[k] for k in range(16)]
             depth = max(k + 1 for k in range(16) if ins[k] > 0)
@@ -407,12 +436,13 @@ def main():
                                                 "fold_accumulate": round(fold_ms * 1e-3 / elapsed, 4), "raygen": round(raygen_ms * 1e-3 / elapsed, 4)},
                          "note": "every kernel's algorithmic bytes of the timed steps / the driver-visible wall time / HBM peak"}
         cpu = None
-        if not args.no_cpu and n_gpus == 1 and args.scene != "i64":          # timed on rank 0 at N = 1 only
-            cpu = cpu_baseline(art, sd, args, be)
-        elif args.scene == "i64":
-            cpu = {"value": None, "note": "the oracle has no instancing: tests/test_gpu_instanced.py compares with its render of the flattened scene"}
-        elif n_gpus > 1:
-            cpu = {"value": None, "note": "the CPU leg is timed at N = 1 only (bench contract); see the N = 1 line"}
+        if args.full:
+            if not args.no_cpu and n_gpus == 1 and args.scene != "i64":          # timed on rank 0 at N = 1 only
+                cpu = cpu_baseline(art, sd, args, be)
+            elif args.scene == "i64":
+                cpu = {"value": None, "note": "the oracle has no instancing: tests/test_gpu_instanced.py compares with its render of the flattened scene"}
+            elif n_gpus > 1:
+                cpu = {"value": None, "note": "the CPU leg is timed at N = 1 only (bench contract); see the N = 1 line"}
         value = total_rays / elapsed / 1e6
         spp_step = 4 * args.vthreads
         render_256_s = elapsed / max(1, args.steps) * (256.0 / spp_step)

@@ -14,7 +14,7 @@ Block executions come from the counting variant of the kernel (bench.py roofline
 wave_iters): the inner pop + node loop runs node_phase_iters (+ wave_iters for the pop that ends it), everything else in the outer
 loop about once per wave iteration (the leaf phase runs in 99 % of them on C4).  The prediction VALU / ray is printed next to the
 measured one as a check of the weights.
-usage: python profiles/valu_mix.py <bench line json with roofline.wave_occupancy> [valu_rate.json] > profiles/<tag>/valu_mix.json"""
+usage: python profiles/valu_mix.py <bench line json of bench.py --full, with roofline.wave_occupancy> [valu_rate.json] > profiles/<tag>/valu_mix.json"""
 import json
 import os
 import re

@@ -68,7 +68,7 @@ def test_python_mirror_of_ray_tracer_package(art, backend):
 
 def test_bench_contract(art):
     r = subprocess.run([sys.executable, os.path.join(art.ROOT, "bench.py"), "--scene", "c3", "--width", "256", "--height", "144", "--steps", "1",
-                        "--warmup", "1", "--vthreads", "1", "--cpu-seconds", "1", "--cpu-width", "64", "--cpu-height", "36"],
+                        "--warmup", "1", "--vthreads", "1", "--cpu-seconds", "1", "--cpu-width", "64", "--cpu-height", "36", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -82,11 +82,34 @@ def test_bench_contract(art):
     assert line["cpu_baseline"]["kind"] == "port" and line["cpu_baseline"]["value"] > 0 and line["cpu_baseline"]["mode_a"] is None
 
 
+def test_bench_plain_run_dumps_the_same_frame_twice(art, tmp_path):
+    """A plain run (no --full) prints the headline figure only; --dump-outputs writes the framebuffer of its last timed step, and two
+    processes with the same arguments write the same bits."""
+    lines = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(art.ROOT, "bench.py"), "--scene", "c3", "--width", "256", "--height", "144", "--steps", "2",
+                            "--warmup", "1", "--vthreads", "1", "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr
+        lines.append(json.loads(r.stdout.strip().splitlines()[-1]))
+    for line in lines:
+        assert line["metric"] == "Mrays/s" and line["value"] > 0 and line["steps"] == 2 and line["ms_per_step"] > 0 and line["dtype"] == "f32"
+        assert line["roofline"] is None and line["whole_job_roofline"] is None and line["stages"] is None and line["cpu_baseline"] is None
+    a = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("accum", "screen_rgb", "spp")}
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in ("accum", "screen_rgb", "spp")}
+    assert a["accum"].shape == a["screen_rgb"].shape == (144, 256, 3) and a["accum"].dtype == a["screen_rgb"].dtype == np.float32
+    assert a["spp"].tolist() == [12.0]                       # (1 warm-up + 2 timed passes) x 4 spp
+    assert np.isfinite(a["accum"]).all() and a["accum"].max() > 0
+    for n in a:
+        assert np.array_equal(a[n].view(np.uint8), b[n].view(np.uint8)), n
+    screen = orc.resolve(a["accum"], 12)                     # the resolved frame is the one the oracle makes of that framebuffer
+    assert np.array_equal(screen.view(np.uint8).reshape(144, 256, 4)[..., :3].astype(np.float32), a["screen_rgb"])
+
+
 def test_bench_c2_comes_from_the_product_and_reports_mode_a(art):
     """--scene c2: Scene.Init by the product's host layer (no oracle in the workload), and the reference-faithful CPU organisation
     (brute-force mesh, Threads_Num = 28 whole-frame tasks) next to the pixel-parallel port."""
     r = subprocess.run([sys.executable, os.path.join(art.ROOT, "bench.py"), "--scene", "c2", "--width", "128", "--height", "128", "--steps", "1",
-                        "--warmup", "1", "--vthreads", "1", "--cpu-seconds", "1", "--cpu-width", "48", "--cpu-height", "48"],
+                        "--warmup", "1", "--vthreads", "1", "--cpu-seconds", "1", "--cpu-width", "48", "--cpu-height", "48", "--full"],
                        capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
@@ -98,7 +121,7 @@ def test_bench_c2_comes_from_the_product_and_reports_mode_a(art):
 def test_bench_one_process_many_contexts(art):
     """bench.py --contexts 4: the one-process N-device path of the library (art_init_devices) rehearsed on this box's single GPU."""
     r = subprocess.run([sys.executable, os.path.join(art.ROOT, "bench.py"), "--scene", "c3", "--width", "256", "--height", "144", "--steps", "1",
-                        "--warmup", "1", "--vthreads", "1", "--contexts", "4", "--no-cpu"], capture_output=True, text=True, timeout=600)
+                        "--warmup", "1", "--vthreads", "1", "--contexts", "4", "--no-cpu", "--full"], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr
     line = json.loads(r.stdout.strip().splitlines()[-1])
     # four contexts on ONE physical GPU are reported as that: n_gpus 1, contexts_on_one_gpu 4 (ADVICE r2); the roofline object is

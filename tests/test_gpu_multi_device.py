@@ -136,7 +136,7 @@ def test_bench_under_torchrun_with_one_rank(art):
     env = dict(os.environ, ART_BENCH_FORCE_DIST="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "1", "--master-addr", "127.0.0.1", "--master-port", "29517",
                         os.path.join(art.ROOT, "bench.py"), "--gpus", "1", "--scene", "c3", "--width", "256", "--height", "144", "--steps", "1", "--warmup", "1",
-                        "--vthreads", "1", "--no-cpu"], capture_output=True, text=True, timeout=900, env=env)
+                        "--vthreads", "1", "--no-cpu", "--full"], capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     line = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert line["metric"] == "Mrays/s" and line["value"] > 0 and line["n_gpus"] == 1
