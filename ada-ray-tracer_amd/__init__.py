@@ -9,6 +9,7 @@ The directory name contains a hyphen, so import it through ``__graft_entry__.loa
 registers it as ``ada_ray_tracer_amd``).  There is no CPU fallback: every call needs the HIP library
 and a GPU and raises ``ArtError`` otherwise.
 """
+import collections
 import ctypes as C
 import os
 import subprocess
@@ -118,6 +119,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
+    "art_trace_rays_device", "art_occluded_rays_device",
     "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -155,6 +157,8 @@ def load_library():
     L.art_bind_accum.argtypes = [C.c_void_p]
     L.art_download.argtypes = [f32p, u32p, C.c_int32, C.c_int32]
     L.art_trace_rays.argtypes = [f32p, f32p, f32p, C.c_int64, C.POINTER(ArtHit), C.c_int32, C.POINTER(ArtStats)]
+    L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
+    L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
@@ -186,6 +190,32 @@ def _ip(a):
 
 def _up(a):
     return None if a is None else a.ctypes.data_as(u32p)
+
+
+RayHits = collections.namedtuple("RayHits", "t is_hit prim_type prim_index mat_id mat normal uv raw")
+RayHits.__doc__ = """Backend.trace_rays_torch: views of ONE [N, 11] int32 tensor (`raw`) whose bytes are the ArtHit array.
+t, normal [N, 3], uv [N, 2]: float32; is_hit, prim_type, prim_index, mat_id, mat: int32."""
+
+HIP_STREAM_LEGACY = 1      # hipStreamLegacy: torch's default stream is the null stream (handle 0), and NULL means the library's stream to the C ABI
+
+
+def _query_tensors(torch, origins, dirs, tnear, tfar):
+    """Checks of the device queries that need no GPU: float32, [N, 3] rays, [N] intervals; everything made contiguous."""
+    def f32(name, x, shape):
+        if not isinstance(x, torch.Tensor):
+            raise ArtError("%s: a torch tensor is required, not %s" % (name, type(x).__name__))
+        if x.dtype != torch.float32:
+            raise ArtError("%s: dtype must be torch.float32, not %s" % (name, x.dtype))
+        if tuple(x.shape) != shape:
+            raise ArtError("%s: shape %s, expected %s" % (name, tuple(x.shape), shape))
+        return x.contiguous()
+    if not isinstance(origins, torch.Tensor) or origins.dim() != 2:
+        raise ArtError("origins: a [N, 3] float32 tensor is required")
+    n = origins.shape[0]
+    o = f32("origins", origins, (n, 3)); d = f32("dirs", dirs, (n, 3))
+    tn = None if tnear is None else f32("tnear", tnear, (n,))
+    tf = None if tfar is None else f32("tfar", tfar, (n,))
+    return o, d, tn, tf, n
 
 
 class SceneDesc:
@@ -343,6 +373,37 @@ class Backend:
         tf = None if tfar is None else np.ascontiguousarray(tfar, np.float32)
         _check(self.lib.art_trace_rays(_fp(o), _fp(d), _fp(tf), n, out, kernel, C.byref(st) if want_stats else None))
         return (out, st) if want_stats else out
+
+    def _query(self, origins, dirs, tnear, tfar):
+        """Validated, contiguous inputs of a device query, and the HIP stream it runs on (torch's current stream of their device)."""
+        import torch
+        o, d, tn, tf, n = _query_tensors(torch, origins, dirs, tnear, tfar)
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+        dev = o.device
+        for name, x in (("origins", o), ("dirs", d), ("tnear", tn), ("tfar", tf)):
+            if x is not None and (x.device.type != "cuda" or x.device != dev):
+                raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        return torch, o, d, tn, tf, n, stream or HIP_STREAM_LEGACY
+
+    def trace_rays_torch(self, origins, dirs, tnear=None, tfar=None, kernel=TRACE_COOP):
+        """Closest hit of N rays held in torch tensors on the GPU (origins, dirs [N, 3] float32; tnear, tfar [N] or None), enqueued on
+        torch.cuda.current_stream() without waiting for it.  Returns RayHits on the same device (art_trace_rays_device)."""
+        torch, o, d, tn, tf, n, stream = self._query(origins, dirs, tnear, tfar)
+        raw = torch.empty((n, 11), dtype=torch.int32, device=o.device)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        _check(self.lib.art_trace_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, raw.data_ptr() if n else None, kernel, stream))
+        f = raw.view(torch.float32)
+        return RayHits(f[:, 0], raw[:, 1], raw[:, 2], raw[:, 3], raw[:, 4], raw[:, 5], f[:, 6:9], f[:, 9:11], raw)
+
+    def occluded_torch(self, origins, dirs, tnear=None, tfar=None):
+        """Occlusion of N rays held in torch tensors on the GPU: a bool [N] tensor, equal to trace_rays_torch(...).is_hit != 0 on the same
+        rays and intervals (art_occluded_rays_device)."""
+        torch, o, d, tn, tf, n, stream = self._query(origins, dirs, tnear, tfar)
+        out = torch.empty((n,), dtype=torch.bool, device=o.device)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        _check(self.lib.art_occluded_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, out.data_ptr() if n else None, stream))
+        return out
 
     def bvh_info(self):
         info = ArtBvhInfo()

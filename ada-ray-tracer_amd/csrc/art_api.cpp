@@ -449,7 +449,9 @@ static int ev_begin(int kind, int trial = 0) {      // trial: 1 / 2 = a shade la
 }
 static int ev_end() { Ctx& c = g_ctx; HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used + 1], c.stream)); c.ev_used += 2; return 0; }
 
-static int trace(const DevPaths& q, int n_rays, bool timed = true, const int* item_count = nullptr, const RecordQueue* records = nullptr) {
+// live_rays: where the launch counts the rays it issued (nullptr: d_counters[0], ArtStats::rays)
+static int trace(const DevPaths& q, int n_rays, bool timed = true, const int* item_count = nullptr, const RecordQueue* records = nullptr,
+                 unsigned long long* live_rays = nullptr) {
   Ctx& c = g_ctx;
   const bool coop = (c.trace_kernel == TRACE_COOP);
   if ((int64_t)n_rays > (1ll << 28)) return fail("internal: more than 2^28 rays in one trace launch (32-bit byte offsets of the 16-byte hit records)");
@@ -457,6 +459,7 @@ static int trace(const DevPaths& q, int n_rays, bool timed = true, const int* it
   if (coop && !records && ensure(c.b_queue, ((size_t)n_rays + kRecSlack) * kTraceRecBytes)) return 1;      // live-ray queue: one 64-byte trace record per queued ray (+ one chunk of slack for the chunk prefetch)
   TraceArgs a; fill_trace_args(a, q, n_rays);
   a.item_count = item_count;
+  if (live_rays) a.live_rays = live_rays;
   if (records) { a.rec = (float4*)q.rec; a.queue_fixed = records->fixed; a.queue_items = records->items; a.queue_mul = records->mul; }
   if (coop && a.stack_overflow && ensure(c.b_ovf, (size_t)n_rays * sizeof(int))) return 1;
   a.ovf_queue = (int*)c.b_ovf.p;
@@ -931,6 +934,90 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
   return 0;
 }
 
+// ---- device-resident ray queries (art_trace_rays_device / art_occluded_rays_device) ----------------------------------------------
+// A caller's buffer must be device memory of this context's GPU, and (where HIP knows the allocation) hold `bytes` from `p` on.
+static int check_device_ptr(const void* p, size_t bytes, const char* what) {
+  Ctx& c = g_ctx;
+  hipPointerAttribute_t at;
+  std::memset(&at, 0, sizeof at);
+  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail(std::string(what) + " is not device memory (hipPointerGetAttributes failed)"); }
+  if (at.type != hipMemoryTypeDevice) return fail(std::string(what) + " is not device memory (host or unregistered pointer)");
+  if (at.device != c.device) return fail(std::string(what) + " is memory of device " + std::to_string(at.device) + ", the library runs on device " + std::to_string(c.device));
+  hipDeviceptr_t base = nullptr; size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
+    if ((const char*)p + bytes > (const char*)base + size) return fail(std::string(what) + " is smaller than the query needs (" + std::to_string(bytes) + " bytes)");
+  } else (void)hipGetLastError();       // (memory HIP cannot size, e.g. a virtual-memory mapping: the type and the device were checked)
+  return 0;
+}
+
+// hits (closest hit) or occluded (occlusion): n rays in slices of query_slice, every launch on `st` (nullptr: the context stream;
+// hipStreamLegacy: the null stream).  The scratch (b_query, b_queue, b_ovf) is shared with the render passes on the context stream:
+// on another stream the query waits for what the context stream holds, and the context stream waits for the query.
+int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st) {
+  Ctx& c = g_ctx;
+  const char* name = hits ? "art_trace_rays_device" : "art_occluded_rays_device";
+  if (ensure_device()) return 1;
+  if (n < 0 || n > 0x7fffffffll) return fail(std::string(name) + ": n must be 0 .. 2^31 - 1");
+  if (kernel != TRACE_COOP && kernel != TRACE_SIMPLE) return fail(std::string(name) + ": unknown kernel");
+  if (n == 0) return 0;
+  if (!c.scene_ready) return fail("no scene uploaded");
+  if (!o3 || !d3 || (!hits && !occluded)) return fail(std::string(name) + ": null ray or output buffer");
+  const size_t N = (size_t)n;
+  if (check_device_ptr(o3, 12 * N, "origins") || check_device_ptr(d3, 12 * N, "dirs") || (tnear && check_device_ptr(tnear, 4 * N, "tnear")) ||
+      (tfar && check_device_ptr(tfar, 4 * N, "tfar")) || (hits && check_device_ptr(hits, sizeof(ArtHit) * N, "hits_out")) ||
+      (occluded && check_device_ptr(occluded, N, "occluded_out")))
+    return 1;
+  hipStream_t qs = (st == nullptr) ? c.stream : (st == hipStreamLegacy ? nullptr : st);
+  const bool other = (qs != c.stream);
+  const size_t S = (size_t)std::min<int64_t>(n, c.query_slice);
+  const bool coop = (kernel == TRACE_COOP);
+  int entries; bool ovf; stack_plan(kernel, entries, ovf);
+  const size_t q_bytes = 256 + S * (8 * 4 + sizeof(DevHit));      // counter sink | 7 SoA floats + the shadow minimum | hit records
+  const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
+  if (grow) {                           // growing the scratch may wait: nothing enqueued may still use the old buffers
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (other) HIP_TRY(hipStreamSynchronize(qs));
+    if (ensure(c.b_query, q_bytes)) return 1;
+    if (coop && ensure(c.b_queue, (S + kRecSlack) * kTraceRecBytes)) return 1;
+    if (coop && ovf && ensure(c.b_ovf, S * sizeof(int))) return 1;
+  }
+  if (other) {
+    for (hipEvent_t& e : c.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c.q_ev[0], c.stream));
+    HIP_TRY(hipStreamWaitEvent(qs, c.q_ev[0], 0));
+  }
+  char* base = (char*)c.b_query.p;
+  unsigned long long* sink = (unsigned long long*)base;
+  float* f = (float*)(base + 256);
+  DevHit* dh = (DevHit*)(f + 8 * S);                                 // 16-byte aligned: 256 + 32 S bytes
+  const hipStream_t saved_stream = c.stream; const int saved_kernel = c.trace_kernel; const bool saved_count = c.count_tests;
+  c.stream = qs; c.trace_kernel = kernel; c.count_tests = false;
+  int rc = 0;
+  for (size_t s0 = 0; s0 < N && !rc; s0 += S) {
+    const int m = (int)std::min(S, N - s0);
+    QueryArgs Q; std::memset(&Q, 0, sizeof Q);
+    Q.n = m; Q.o3 = o3 + 3 * s0; Q.d3 = d3 + 3 * s0; Q.tnear = tnear ? tnear + s0 : nullptr; Q.tfar = tfar ? tfar + s0 : nullptr;
+    Q.ox = f; Q.oy = f + S; Q.oz = f + 2 * S; Q.dx = f + 3 * S; Q.dy = f + 4 * S; Q.dz = f + 5 * S; Q.tf = f + 6 * S;
+    Q.shm = occluded ? f + 7 * S : nullptr; Q.hit = dh;
+    Q.out = hits ? (uint32_t*)(hits + s0) : nullptr; Q.occluded = occluded ? occluded + s0 : nullptr;
+    launch_query_pack(qs, Q);
+    DevPaths q; std::memset(&q, 0, sizeof q);
+    q.ray_ox = Q.ox; q.ray_oy = Q.oy; q.ray_oz = Q.oz; q.ray_dx = Q.dx; q.ray_dy = Q.dy; q.ray_dz = Q.dz; q.ray_tfar = Q.tf; q.hit = dh;
+    q.sh_min_t = Q.shm; q.P = 0;                                     // occlusion: every ray is a shadow ray (shadow_begin = 0)
+    rc = trace(q, m, /*timed=*/false, nullptr, nullptr, sink);
+    if (rc) break;
+    if (hits) launch_query_finalize(qs, c.scene, Q);
+    else launch_query_occluded(qs, Q);
+    if (hipGetLastError() != hipSuccess) rc = fail(std::string(name) + ": kernel launch failed");
+  }
+  c.stream = saved_stream; c.trace_kernel = saved_kernel; c.count_tests = saved_count;
+  if (other) {                          // (also after a failed launch: what was enqueued stays ordered before the context stream's next work)
+    HIP_TRY(hipEventRecord(c.q_ev[1], qs));
+    HIP_TRY(hipStreamWaitEvent(c.stream, c.q_ev[1], 0));
+  }
+  return rc;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) reset_reduce_info();
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -944,7 +1031,7 @@ void shutdown() {
     DevBuf* bufs[] = {&c.b_spheres, &c.b_sphere_mat, &c.b_lights, &c.b_materials, &c.b_bf_pos, &c.b_bf_nrm, &c.b_bf_uv, &c.b_bf_idx,
                       &c.b_nodes, &c.b_qnodes, &c.b_tris, &c.b_qtris, &c.b_m_shade, &c.b_accum, &c.b_screen, &c.b_stage,
                       &c.b_pixmap, &c.b_paths, &c.b_rays, &c.b_ids, &c.b_queue, &c.b_ovf,
-                      &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris};
+                      &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query};
     for (DevBuf* b : bufs) b->release();
     if (c.d_cursor) (void)hipFree(c.d_cursor);
     if (c.d_scene) (void)hipFree(c.d_scene);
@@ -953,6 +1040,7 @@ void shutdown() {
     if (c.d_items) (void)hipFree(c.d_items);
     for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : c.pass_events) (void)hipEventDestroy(e);
+    for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
     for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
     c.b_reduced.release();
     if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
@@ -1005,7 +1093,7 @@ int art_init_devices(int32_t n, const int32_t* ordinals) {
     c = Ctx();
     c.trace_kernel = opts.trace_kernel; c.batch_paths = opts.batch_paths; c.bvh_params = opts.bvh_params; c.node_min = opts.node_min; c.refill_min = opts.refill_min;
     c.queue_segments = opts.queue_segments; c.ray_chunk = opts.ray_chunk; c.shadow_anyhit = opts.shadow_anyhit; c.shade_split = opts.shade_split; c.skip_null_shadow = opts.skip_null_shadow; c.inst_coop = opts.inst_coop; c.opt_shade_per = opts.opt_shade_per; c.lds_stack_cap = opts.lds_stack_cap; c.paths_contiguous = opts.paths_contiguous; c.hot_pad = opts.hot_pad; c.paths_spread_mb = opts.paths_spread_mb; c.paths_spread_holes = opts.paths_spread_holes;
-    c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests;
+    c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests; c.query_slice = opts.query_slice;
     c.device = ord[k]; c.rank = k; c.nranks = n; c.tile = 32;
     if (use_dev(k) || ensure_device()) { shutdown(); return 1; }
     if (n > 1) {
@@ -1080,6 +1168,18 @@ int art_synchronize(void) { std::lock_guard<std::mutex> lk(g_mu); return synchro
 int art_trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int32_t kernel, ArtStats* stats) {
   std::lock_guard<std::mutex> lk(g_mu);          // ray queries run on device 0
   return trace_rays(origins, dirs, tfar, n, out, kernel, stats);
+}
+
+int art_trace_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n, ArtHit* hits_out, int32_t kernel, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // ray queries run on device 0
+  if (!hits_out && n > 0) return fail("art_trace_rays_device: null hits_out");
+  return query_rays(origins3f, dirs3f, tnear, tfar, n, hits_out, nullptr, kernel, (hipStream_t)hip_stream);
+}
+
+int art_occluded_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n, uint8_t* occluded_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!occluded_out && n > 0) return fail("art_occluded_rays_device: null occluded_out");
+  return query_rays(origins3f, dirs3f, tnear, tfar, n, nullptr, occluded_out, TRACE_COOP, (hipStream_t)hip_stream);
 }
 
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
@@ -1179,6 +1279,7 @@ static int set_option_one(const std::string& n, int64_t value) {
   else if (n == "paths_contiguous") { g_ctx.paths_contiguous = value != 0; g_ctx.b_paths.release(); }
   else if (n == "inject_lost") { g_ctx.inject_lost = value != 0; }      // test option: the next pass counts one lost path in its first batch
   else if (n == "blocks_per_cu") { g_ctx.opt_blocks_per_cu = (int)value; g_ctx.blocks_per_cu = 0; }
+  else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.query_slice = value; }
   else if (n == "count_tests") { g_ctx.count_tests = value != 0; }
   else if (n == "shadow_anyhit") { g_ctx.shadow_anyhit = value != 0; }
   else if (n == "shade_split") { g_ctx.shade_split = value != 0; }

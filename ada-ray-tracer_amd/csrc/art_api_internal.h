@@ -39,6 +39,9 @@ struct Ctx {
   int rank = 0, nranks = 1, tile = 32, npix_local = 0;
   DevBuf b_inst, b_tlas_nodes, b_tlas_tris, b_blas_nodes, b_blas_tris;      // instanced scene (DevScene::n_inst > 0)
   DevBuf b_accum, b_screen, b_stage, b_pixmap, b_paths, b_rays, b_ids, b_queue, b_ovf;
+  DevBuf b_query;                              // device-resident ray queries: SoA rays + shadow minima + hit records of one slice, and a counter sink
+  hipEvent_t q_ev[2] = {nullptr, nullptr};     // ... their ordering with the context stream when they run on another stream (library -> query, query -> library)
+  int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
   float* ext_accum = nullptr;
@@ -115,6 +118,7 @@ int ensure_device();
 int upload_scene(const ArtSceneDesc* d);
 int resize(int w, int h);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
+int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 void shutdown();
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 

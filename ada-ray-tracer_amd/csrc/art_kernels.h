@@ -76,4 +76,21 @@ void launch_trace(hipStream_t st, const DevScene* d_scene, const TraceArgs& A, i
 void launch_analytic(hipStream_t st, const DevScene& scene, const TraceArgs& A, bool stats);
 int  trace_coop_blocks_per_cu(int stack_entries, int width);
 
+// device-resident ray queries (art_query.hip): one slice of at most 2^28 rays.  o3 / d3 / tnear / tfar / out / occluded are the
+// caller's buffers advanced to the slice, the rest is the library's scratch.
+constexpr int kArtHitWords = 11;      // sizeof(ArtHit) / 4
+struct QueryArgs {
+  int32_t n;
+  const float* o3; const float* d3;   // float3 AoS
+  const float* tnear; const float* tfar;   // nullptr: 0 / kInfinity (art_trace_rays' bound)
+  float *ox, *oy, *oz, *dx, *dy, *dz, *tf;  // SoA slots of the trace launch (tf < 0: a dead ray)
+  float* shm;                         // occlusion: the shadow rule's minimum per ray (written 0); nullptr: closest hit
+  DevHit* hit;
+  uint32_t* out;                      // ArtHit records (11 dwords each)
+  uint8_t* occluded;
+};
+void launch_query_pack(hipStream_t st, const QueryArgs& Q);
+void launch_query_finalize(hipStream_t st, const DevScene& S, const QueryArgs& Q);
+void launch_query_occluded(hipStream_t st, const QueryArgs& Q);
+
 }  // namespace art

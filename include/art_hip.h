@@ -199,6 +199,22 @@ int  art_synchronize(void);
 int  art_trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n,
                     ArtHit* out, int32_t kernel, ArtStats* stats);
 
+/* Device-resident ray queries (device 0 under art_init_devices).  Every pointer is device memory of the device the library runs on:
+ * origins3f / dirs3f are float3 arrays (12 bytes per ray), tnear / tfar one float per ray or NULL (0 / Float'Last, the bound
+ * art_trace_rays uses).  n: 0 .. 2^31 - 1, traced in slices of the option "query_slice".  Pointers are checked before anything is
+ * launched (host memory or another device's memory: the call fails with art_last_error set).
+ * Stream-ordered on hip_stream (NULL: the library's stream, art_set_stream; hipStreamLegacy: the null stream); the host is never made to
+ * wait, except when the library's scratch has to grow.  On a stream other than the library's, a query runs after everything the library
+ * has enqueued and before anything it enqueues later.
+ * Closest hit: with t0 = tnear > 0 ? tnear : 0 (no shift without tnear) the ray traced is o + t0 d, bounded by tfar - t0; an empty interval
+ * (!(tfar - t0 > 0)) is a miss.  hits_out[i] is the ArtHit art_trace_rays returns for that ray (byte for byte; a miss holds t = the
+ * bound, u = v = 0), except that a hit's t is t0 + t.  kernel: as in art_trace_rays.
+ * Occlusion: occluded_out[i] = hits_out[i].is_hit of the closest-hit query on the same ray and interval (the shadow rule's early exit). */
+int  art_trace_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n,
+                           ArtHit* hits_out, int32_t kernel, void* hip_stream);
+int  art_occluded_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n,
+                              uint8_t* occluded_out, void* hip_stream);
+
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 int  art_get_stats(ArtStats* out);
 /* The wavefront stages around the trace kernel (device 0, cumulative since art_resize; cooperative schedule): GPU time per kind of
@@ -226,6 +242,7 @@ int  art_get_stage_stats(ArtStageStats* out);
  * about half of the processes); "paths_spread_holes" [0] 1: spacer chunks between the chunks, released after mapping; "paths_contiguous"
  * [0] 1: physically contiguous memory (the slowest and the one deterministic placement: for A/B work on the stage); "hot_pad" [0] items
  * between the fields of a bank's block (a multiple of 64; moves nothing).
+ * Device queries: "query_slice" [2^24] rays per slice (112 bytes of scratch per ray of a slice; 1 .. 2^28).
  * Test options: "inject_lost" (the next pass counts one lost path: art_synchronize must fail), "spread_fail_at" (creating that chunk of the
  * path state fails: everything created so far is undone and the path state comes from hipMalloc), "lds_stack_cap". */
 int  art_set_option(const char* name, int64_t value);
