@@ -127,10 +127,9 @@ void DevBuf::release() {
 }
 
 // `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Ctx::paths_spread_mb: the driver
-// then maps the range in pieces no larger than a chunk, which is what the shade stage's forty streams want).  holes: a spacer chunk is
-// created behind every chunk and released at the end (the first form of the experiment; not what helps).  Every failure undoes what was
-// done and reports it; the caller falls back to hipMalloc.
-static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, bool holes, int fail_at = -1) {      // fail_at: test option spread_fail_at -- chunk number whose creation is made to fail
+// then maps the range in pieces no larger than a chunk, which is what the shade stage's forty streams want).  Every failure undoes what
+// was done and reports it; the caller falls back to hipMalloc.
+static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, int fail_at = -1) {      // fail_at: test option spread_fail_at -- chunk number whose creation is made to fail
   hipMemAllocationProp prop; std::memset(&prop, 0, sizeof prop);
   prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
   size_t gran = 0;
@@ -141,12 +140,11 @@ static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device
   void* va = nullptr;
   e = hipMemAddressReserve(&va, n * chunk, 0, nullptr, 0);
   if (e != hipSuccess) return e;
-  std::vector<hipMemGenericAllocationHandle_t> got, spacers;
+  std::vector<hipMemGenericAllocationHandle_t> got;
   size_t mapped = 0;
   auto undo = [&]() {
     for (size_t i = 0; i < mapped; ++i) (void)hipMemUnmap((char*)va + i * chunk, chunk);
     for (auto h : got) (void)hipMemRelease(h);
-    for (auto h : spacers) (void)hipMemRelease(h);
     (void)hipMemAddressFree(va, n * chunk);
     (void)hipGetLastError();
   };
@@ -155,8 +153,6 @@ static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device
     e = ((int64_t)i == (int64_t)fail_at) ? hipErrorOutOfMemory : hipMemCreate(&h, chunk, &prop, 0);
     if (e != hipSuccess) { undo(); return e; }
     got.push_back(h);
-    hipMemGenericAllocationHandle_t sp;                  // the hole behind it (none if the device is too full: the layout degrades, nothing fails)
-    if (holes && i + 1 < n) { if (hipMemCreate(&sp, chunk, &prop, 0) == hipSuccess) spacers.push_back(sp); else (void)hipGetLastError(); }
   }
   for (size_t i = 0; i < n; ++i) {
     e = hipMemMap((char*)va + i * chunk, chunk, 0, got[i], 0);
@@ -167,7 +163,6 @@ static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device
   acc.location = prop.location; acc.flags = hipMemAccessFlagsProtReadWrite;
   e = hipMemSetAccess(va, n * chunk, &acc, 1);
   if (e != hipSuccess) { undo(); return e; }
-  for (auto h : spacers) (void)hipMemRelease(h);
   b.p = va; b.bytes = bytes; b.chunks = std::move(got); b.chunk_bytes = chunk; b.reserved = n * chunk;
   return hipSuccess;
 }
@@ -329,25 +324,33 @@ static int download_from(const float* acc_dev, float* accum_host, uint32_t* scre
 // records in one array shared by the banks.  Plain layout (one-ray-per-lane schedule, debug pass): rays as SoA arrays, 29 words.
 constexpr size_t kRecSlack = 4096;       // records past the last one the trace kernel's chunk prefetch may touch
 // (record schedule: 6 ray words, ONE 16-byte hit record + the shadow ray's result word, 7 per-path words)
-static size_t hot_stride(size_t P) { return ((P + 63) & ~(size_t)63) + (size_t)g_ctx.hot_pad; }      // (+ option hot_pad: items between the fields of a bank's block, Ctx::hot_pad)
+static size_t hot_stride(size_t P) { return (P + 63) & ~(size_t)63; }
 static size_t hot_floats(size_t P, bool rec) { return rec ? (size_t)kHotFields * hot_stride(P) + 64 : (14 + 8 + 7) * P; }
 // (the trace records are not double-banked: a bank's records are dead once its rays are traced, and the next stage reads none of them)
 // cold state: e (depth + 1 levels: dense fold records keep e_k at level k + 1) and w (depth levels) x 3, child (depth levels), term, rad, final flags
-// (+ 4 P words: the queue of the items k_shade_compact defers to its heavy-material instantiation, 16 B each, worst case every item)
-static size_t path_floats(size_t P, int depth, bool rec) { return 2 * hot_floats(P, rec) + (rec ? 32 * P + kRecSlack * 16 + 16 + 4 * P + 4 : 0) + (7 * (size_t)depth + 3 + 3 + 3 + 1) * P + 64; }
+static size_t path_floats(size_t P, int depth, bool rec) { return 2 * hot_floats(P, rec) + (rec ? 32 * P + kRecSlack * 16 + 16 : 0) + (7 * (size_t)depth + 3 + 3 + 3 + 1) * P + 64; }
 
-static int ensure_paths(size_t P, int depth, bool rec) { return ensure(g_ctx.b_paths, path_floats(P, depth, rec) * 4 + 256); }
+// Every release of the path state goes through here.  hipFree waits for the device, but unmapping a spread path state (alloc_spread) does
+// not, and work queued on the context's stream may still use it.
+static void release_paths(Ctx& c) {
+  if (c.b_paths.reserved) (void)hipStreamSynchronize(c.stream);
+  c.b_paths.release();
+}
+static int ensure_paths(size_t P, int depth, bool rec) {
+  const size_t bytes = path_floats(P, depth, rec) * 4 + 256;
+  if (g_ctx.b_paths.bytes < bytes) release_paths(g_ctx);
+  return ensure(g_ctx.b_paths, bytes);
+}
 
 // q[0], q[1]: the two banks (slot_id = their own map); both share the cold arrays.  An identity-layout user takes q[0] with slot_id = nullptr
 // and final_flags = flags.
-static void carve(DevPaths q[2], int P, int depth, bool rec, uint4** heavy = nullptr) {
+static void carve(DevPaths q[2], int P, int depth, bool rec) {
   float* const f0 = (float*)g_ctx.b_paths.p;
   float* f = f0; const size_t p = (size_t)P;
   auto take = [&](size_t n) { float* r = f; f += n; return r; };
   auto align = [&](size_t floats) { f += (floats - ((size_t)(f - f0) & (floats - 1))) & (floats - 1); };
   Rec4* records = nullptr;
   if (rec) { align(16); records = (Rec4*)take(32 * p + kRecSlack * 16); }       // 64-byte records, ONE array for both banks
-  if (rec) { uint4* const h = (uint4*)take(4 * p); if (heavy) *heavy = h; }     // (still 16-byte aligned)
   for (int k = 0; k < 2; ++k) {
     DevPaths& b = q[k];
     if (rec) {
@@ -565,27 +568,23 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   if (npix > 0) {
     int64_t cap = std::max<int64_t>(c.batch_paths, per);
     // Two buffers belong to a batch: the path state and the live-ray queue (one 64-byte trace record for each of the up to 2 rays of a path).
-    auto try_alloc = [&](DevBuf& b, size_t bytes, hipError_t& e) {          // true: b holds at least `bytes`
+    auto try_alloc = [&](size_t bytes, hipError_t& e) {          // true: the path state holds at least `bytes`
+      DevBuf& b = c.b_paths;
       e = hipSuccess;
       if (b.p && b.bytes >= bytes) return true;
-      b.release();
-      // physically contiguous if the driver can (option paths_contiguous; art_api_internal.h Ctx::paths_contiguous says why), else as it comes
-      e = hipErrorOutOfMemory; c.paths_are_contiguous = false; c.paths_are_spread = false;
+      release_paths(c);
+      e = hipErrorOutOfMemory; c.paths_are_spread = false;
       // the default (-1): 64 MB chunks for a path state of a gigabyte or more -- where the mapping granularity decides the stage's rate
-      const int chunk_mb = c.paths_spread_mb > 0 ? c.paths_spread_mb : (c.paths_spread_mb < 0 && !c.paths_contiguous && bytes >= ((size_t)1 << 30)) ? 64 : 0;
+      const int chunk_mb = c.paths_spread_mb > 0 ? c.paths_spread_mb : (c.paths_spread_mb < 0 && bytes >= ((size_t)1 << 30)) ? 64 : 0;
       if (chunk_mb > 0) {
         const auto t0 = std::chrono::steady_clock::now();
-        e = alloc_spread(b, bytes, (size_t)chunk_mb << 20, c.device, c.paths_spread_holes, c.spread_fail_at);
+        e = alloc_spread(b, bytes, (size_t)chunk_mb << 20, c.device, c.spread_fail_at);
         if (g_debug_addr) std::fprintf(stderr, "ART_DEBUG_ADDR alloc_spread %.2f GB in chunks of %d MB: %s, %.1f ms\n", (double)bytes / 1e9, chunk_mb, hipGetErrorString(e),
                                        std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
         if (e == hipSuccess) { c.paths_are_spread = true; return true; }
         b.p = nullptr; (void)hipGetLastError();
       }
-      if (c.paths_contiguous) {
-        e = hipExtMallocWithFlags(&b.p, bytes, hipDeviceMallocContiguous);
-        if (e == hipSuccess) c.paths_are_contiguous = true; else { b.p = nullptr; (void)hipGetLastError(); }
-      }
-      if (e != hipSuccess) e = hipMalloc(&b.p, bytes);
+      e = hipMalloc(&b.p, bytes);
       if (e == hipSuccess) { b.bytes = bytes; return true; }
       b.p = nullptr; (void)hipGetLastError();
       return false;
@@ -595,12 +594,12 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
       pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / per));
       sc = (int)std::min<int64_t>(S, std::max<int64_t>(per, (cap / pc) / per * per));
       hipError_t e;
-      if (try_alloc(g_ctx.b_paths, path_floats((size_t)pc * sc, p->max_depth, rec_layout) * 4 + 256, e)) {
+      if (try_alloc(path_floats((size_t)pc * sc, p->max_depth, rec_layout) * 4 + 256, e)) {
         if (g_debug_live) std::fprintf(stderr, "path state: %d pixels x %d samples per batch, %.2f GB\n", pc, sc, (double)g_ctx.b_paths.bytes / 1e9);
         if (g_debug_addr) {
           DevPaths bk[2]; std::memset(bk, 0, sizeof bk);
           carve(bk, pc * sc, p->max_depth, rec_layout);
-          std::fprintf(stderr, "ART_DEBUG_ADDR spread %d contiguous %d paths %p bytes %zu P %d rec %p hot0 %p hot1 %p stride %d cold %p live %p counters %p cursor %p\n", c.paths_are_spread ? 1 : 0, c.paths_are_contiguous ? 1 : 0, g_ctx.b_paths.p, g_ctx.b_paths.bytes, pc * sc,
+          std::fprintf(stderr, "ART_DEBUG_ADDR spread %d paths %p bytes %zu P %d rec %p hot0 %p hot1 %p stride %d cold %p live %p counters %p cursor %p\n", c.paths_are_spread ? 1 : 0, g_ctx.b_paths.p, g_ctx.b_paths.bytes, pc * sc,
                        (void*)bk[0].rec, (void*)bk[0].hot, (void*)bk[1].hot, bk[0].stride, (void*)bk[0].cold, (void*)c.d_live, (void*)c.d_counters, (void*)c.d_cursor);
         }
         break;
@@ -625,13 +624,12 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
         const int sn = std::min(sc, S - s0);
         DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
         for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = (const uint32_t*)c.b_pixmap.p + px0; b.sample_base = (uint32_t)(c.spp + s0); }
-        uint4* heavy = nullptr;
-        carve(bank, bank[0].P, p->max_depth, c.trace_kernel == TRACE_COOP, &heavy);
+        carve(bank, bank[0].P, p->max_depth, c.trace_kernel == TRACE_COOP);
         // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_api_internal.h Ctx::opt_shade_per).
         // Nothing here waits for the GPU: a trial batch only tags its shade launches' event pairs, and the next call that synchronises
         // anyway reads them (collect_timing) -- Render_Pass releases all its workers before it waits for any (ray_tracer.adb:271-277).
         int trial = 0, shade_per = c.opt_shade_per ? c.opt_shade_per : (c.auto_phase >= 4 ? c.auto_per : 4);
-        if (c.opt_shade_per == 0 && c.auto_phase < 3 && c.trace_kernel == TRACE_COOP && !c.shade_split) {
+        if (c.opt_shade_per == 0 && c.auto_phase < 3 && c.trace_kernel == TRACE_COOP) {
           const int64_t Pb = (int64_t)pn * sn;
           if (c.auto_phase == 0) c.auto_phase = 1;                                      // the warm batch: 4 items per thread, not measured
           else if (c.auto_phase == 1) { trial = 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; c.auto_phase = 2; }
@@ -661,10 +659,10 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
             const bool last = b + 1 >= p->max_depth;
             bank[out].rec_mode = (p->render_type == ART_PT_STUPID) ? REC_EXT : (last ? REC_SHADOW : REC_BOTH);
             int* const n_in = c.d_live + 32 * b; int* const n_out = c.d_live + 32 * (b + 1);      // per level: the fold walks them again
-            HIP_TRY(hipMemsetAsync(n_out, 0, 2 * sizeof(int), c.stream));         // n_out[1]: the items this stage defers to its heavy-material kernel
+            HIP_TRY(hipMemsetAsync(n_out, 0, sizeof(int), c.stream));
             if (ev_begin(1, trial)) return 1;
             launch_shade_compact(c.stream, F, c.scene, qi, bank[out], b, b == 0 ? nullptr : n_in, n_out,
-                                 const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + 15, c.d_counters, rays_b, c.shade_split ? heavy : nullptr, n_out + 1, shade_per);
+                                 const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + 15, c.d_counters, rays_b, shade_per);
             if (ev_end()) return 1;
             if (b == 0 && c.inject_lost) { launch_bump(c.stream, c.d_counters + 15, nullptr, 1ull); c.inject_lost = 0; }      // test option: what a stage does when it loses a path
             if (g_debug_live) {
@@ -1092,7 +1090,7 @@ int art_init_devices(int32_t n, const int32_t* ordinals) {
     Ctx& c = g_devs[k];
     c = Ctx();
     c.trace_kernel = opts.trace_kernel; c.batch_paths = opts.batch_paths; c.bvh_params = opts.bvh_params; c.node_min = opts.node_min; c.refill_min = opts.refill_min;
-    c.queue_segments = opts.queue_segments; c.ray_chunk = opts.ray_chunk; c.shadow_anyhit = opts.shadow_anyhit; c.shade_split = opts.shade_split; c.skip_null_shadow = opts.skip_null_shadow; c.inst_coop = opts.inst_coop; c.opt_shade_per = opts.opt_shade_per; c.lds_stack_cap = opts.lds_stack_cap; c.paths_contiguous = opts.paths_contiguous; c.hot_pad = opts.hot_pad; c.paths_spread_mb = opts.paths_spread_mb; c.paths_spread_holes = opts.paths_spread_holes;
+    c.queue_segments = opts.queue_segments; c.ray_chunk = opts.ray_chunk; c.shadow_anyhit = opts.shadow_anyhit; c.skip_null_shadow = opts.skip_null_shadow; c.inst_coop = opts.inst_coop; c.opt_shade_per = opts.opt_shade_per; c.lds_stack_cap = opts.lds_stack_cap; c.paths_spread_mb = opts.paths_spread_mb;
     c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests; c.query_slice = opts.query_slice;
     c.device = ord[k]; c.rank = k; c.nranks = n; c.tile = 32;
     if (use_dev(k) || ensure_device()) { shutdown(); return 1; }
@@ -1272,17 +1270,13 @@ static int set_option_one(const std::string& n, int64_t value) {
   if (n == "trace_kernel") { if (value != TRACE_COOP && value != TRACE_SIMPLE) return fail("trace_kernel: 0 (cooperative) or 1 (simple)"); g_ctx.trace_kernel = (int)value; }
   else if (n == "queue_segments") { if (value != 1 && value != 2 && value != 4 && value != 8) return fail("queue_segments: 1, 2, 4 or 8"); g_ctx.queue_segments = (int)value; }
   else if (n == "batch_paths") { if (value < 1024 || value > (1ll << 27)) return fail("batch_paths: 1024..2^27 (2 rays per path slot; the trace kernel addresses a ray's 16-byte hit record by a 32-bit byte offset)"); g_ctx.batch_paths = value; g_ctx.auto_phase = 0; g_ctx.auto_redo = 0; g_ctx.auto_gen += 1; }
-  else if (n == "hot_pad") { if (value < 0 || value > (1 << 24) || (value & 63)) return fail("hot_pad: a multiple of 64 items, 0 .. 2^24"); g_ctx.hot_pad = (int)value; g_ctx.b_paths.release(); }
-  else if (n == "paths_spread") { if (value < -1 || value > 65536) return fail("paths_spread: chunk size in MB, 0 = off (plain hipMalloc), -1 = automatic"); g_ctx.paths_spread_mb = (int)value; g_ctx.b_paths.release(); }
-  else if (n == "spread_fail_at") { g_ctx.spread_fail_at = (int)value; g_ctx.b_paths.release(); }      // test option: creating chunk number `value` of the path state fails (-1: never)
-  else if (n == "paths_spread_holes") { g_ctx.paths_spread_holes = value != 0; g_ctx.b_paths.release(); }
-  else if (n == "paths_contiguous") { g_ctx.paths_contiguous = value != 0; g_ctx.b_paths.release(); }
+  else if (n == "paths_spread") { if (value < -1 || value > 65536) return fail("paths_spread: chunk size in MB, 0 = off (plain hipMalloc), -1 = automatic"); g_ctx.paths_spread_mb = (int)value; release_paths(g_ctx); }
+  else if (n == "spread_fail_at") { g_ctx.spread_fail_at = (int)value; release_paths(g_ctx); }      // test option: creating chunk number `value` of the path state fails (-1: never)
   else if (n == "inject_lost") { g_ctx.inject_lost = value != 0; }      // test option: the next pass counts one lost path in its first batch
   else if (n == "blocks_per_cu") { g_ctx.opt_blocks_per_cu = (int)value; g_ctx.blocks_per_cu = 0; }
   else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.query_slice = value; }
   else if (n == "count_tests") { g_ctx.count_tests = value != 0; }
   else if (n == "shadow_anyhit") { g_ctx.shadow_anyhit = value != 0; }
-  else if (n == "shade_split") { g_ctx.shade_split = value != 0; }
   else if (n == "skip_null_shadow") { g_ctx.skip_null_shadow = value != 0; }
   else if (n == "inst_coop") { g_ctx.inst_coop = value != 0; }
   else if (n == "shade_per") { if (value != 0 && value != 2 && value != 4) return fail("shade_per: 0 (measured), 2 or 4"); g_ctx.opt_shade_per = (int)value; }

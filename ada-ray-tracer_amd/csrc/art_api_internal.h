@@ -86,16 +86,11 @@ struct Ctx {
   // paths_spread_mb: the path state as one address range over separately created physical chunks of that many MB (HIP virtual memory
   // management, art_api.cpp alloc_spread): the fast mode in every process measured, 13-17 ms to set up, no extra memory; any failure falls
   // back to hipMalloc.  -1 (default): 64 MB chunks when the path state is 1 GB or more; 0: plain hipMalloc; n > 0: n MB chunks always.
-  // paths_spread_holes: a spacer chunk between two chunks, released after mapping (twice the memory for a moment; measured: not what helps).
-  // paths_contiguous: hipExtMallocWithFlags(hipDeviceMallocContiguous) -- the slowest and the one deterministic placement (A/B tool).
-  int paths_spread_mb = -1; bool paths_are_spread = false; bool paths_spread_holes = false;
+  int paths_spread_mb = -1; bool paths_are_spread = false;
   int spread_fail_at = -1;       // test option: the creation of this chunk is made to fail, so that the undo + hipMalloc fallback runs (tests/test_gpu_parity.py)
-  bool paths_contiguous = false, paths_are_contiguous = false;
-  int hot_pad = 0;               // items added to the stride between the fields of a bank's hot block (art_scene.h HotField): the frame sizes make that stride a multiple of 256 KB
 
   bool skip_null_shadow = false;   // DevFrame::skip_null_shadow: shadow rays that cannot change the picture are not traced (fewer rays than the reference issues: off by default)
   bool inst_coop = true;       // instanced scenes: the cooperative kernel crosses the instance boundary (k_trace_coop<.., INST>); false: k_trace_inst, one ray per lane (A/B, cross-check)
-  bool shade_split = false;    // k_shade_compact as one instantiation per register class (light materials / deferred heavy ones); false: the round-4 kernel with every material (A/B)
   // timing
   std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
   std::vector<uint8_t> ev_kind;                // per event pair: 0 trace kernel, 1 shade stage, 2 raygen, 3 fold group (art_get_stage_stats) | trial (1 / 2: A / B of the items-per-thread trial) << 4 | the trial's generation << 6

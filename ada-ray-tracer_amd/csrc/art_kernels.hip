@@ -160,22 +160,15 @@ __device__ __forceinline__ void lds_store(uint32_t addr, uint2 v) {       // two
 // ---- "x = mask ? y : x" as ONE vector instruction under EXEC = mask (round 3).  The kernel's VALU is saturated (issue fraction 1.0,
 // profiles/r3_final) while its scalar unit is 40 % busy: a v_cndmask holds the SIMD for 1.85 ns, the v_mov / v_add that does the same
 // under a lane mask for 0.94 / 1.1 ns, and the two s_mov that set and restore EXEC issue beside the other waves' vector instructions.
-// Only used where all 64 lanes are enabled (the step code of k_trace_coop).  ART_EXECM selects which selects are replaced (bit 0 node
-// load, 1 pop, 2 push + sort key, 3 stack pointer = address of the top entry).  Measured on C4, trace launch average (two boxes, A/B in
-// one call each): 0 -> 57.35 / 57.58 ms, 13 -> 56.73 / 56.85 (-1.2 %), 15 -> 57.15 / 57.18, 5 -> 57.06; alone, bit 1 (the pop) is 0.5 %
-// slower, bits 0 / 2 / 3 are within noise: the step answers to the shape of its dependency chains more than to its instruction count.
-#ifndef ART_EXECM
-#define ART_EXECM 13
-#endif
+// Only used where all 64 lanes are enabled (the step code of k_trace_coop): the node load, the push and its sort key.  The pop stays a
+// pair of selects (masked, it was slower), and the stack pointer holds the address of the top entry itself (DESIGN_HISTORY.md: the
+// exec-masked instructions row).
 typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-// Contract of the four helpers below: they are entered with ALL 64 lanes enabled and leave EXEC = -1.  They are `volatile`
+// Contract of the three helpers below: they are entered with ALL 64 lanes enabled and leave EXEC = -1.  They are `volatile`
 // (never duplicated, hoisted or sunk across each other; EXEC cannot be named as a clobber -- the compiler rejects reserved registers
 // there).  A caller that wrapped them in a per-lane branch would switch masked-off lanes on: k_trace_coop checks its side of the
 // contract in builds with -DART_CHECK_EXEC (EXEC == -1 at the head of every node step, else the kernel traps): libart_hip_check.so,
 // run by tests/test_gpu_widths.py::test_trace_kernel_keeps_its_exec_contract.
-__device__ __forceinline__ void pop_masked(mask_t v1, mask_t ok1, uint32_t& sa, uint32_t& pend, uint32_t entry) {     // sa -= 8 in v1, pend = entry in ok1
-  asm volatile("s_mov_b64 exec, %2\n\tv_add_u32 %0, -8, %0\n\ts_mov_b64 exec, %3\n\tv_mov_b32 %1, %4\n\ts_mov_b64 exec, -1" : "+v"(sa), "+v"(pend) : "s"(v1), "s"(ok1), "v"(entry));
-}
 __device__ __forceinline__ u32x4 load_node_masked(mask_t m, const char* base, uint32_t off) {                        // lanes outside m keep garbage: their results are masked
   u32x4 r;
   asm volatile("s_mov_b64 exec, %1\n\tglobal_load_dwordx4 %0, %2, %3\n\ts_mov_b64 exec, -1\n\ts_waitcnt vmcnt(0)" : "=&v"(r) : "s"(m), "v"(off), "s"(base) : "memory");
@@ -222,12 +215,11 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
   constexpr int NG = 64 / G;                                   // ray groups per wave
   const int j = lane & (G - 1), g = lane / G;
   const int gbase = lane & ~(G - 1);
-  // Stack of one ray in LDS (bytes from sb):  0, 8: guard entries | 16 + 8 i: entry i | 16 + 8 entries: sink of masked pushes.
+  // Stack of one ray in LDS (bytes from sb):  0, 8: guard entries | 16 + 8 i: entry i | 16 + 8 entries: one spare entry.
   // The stack pointer is the LDS address `sa = sb + 8 sp`: the top entry is at sa + 8 (an empty stack reads a guard, no clamping),
   // and a push goes to sa + 8 (nh - rank) + 8.
   const uint32_t lds0 = (uint32_t)(uintptr_t)lds_stack;
   const uint32_t sb = lds0 + (uint32_t)(wave * NG + g) * (uint32_t)(A.stack_entries + 3) * 8u;
-  const uint32_t sink = sb + 16u + (uint32_t)A.stack_entries * 8u;
   const uint32_t slimit = sb + (uint32_t)A.stack_entries * 8u;      // sa + 8 nh > slimit: the push does not fit
   const mask_t leaders = (G == 8) ? 0x0101010101010101ull : 0x1111111111111111ull;
   // kernel-argument bases stay in SGPRs; per-lane addressing is a 32-bit byte offset (scalar base + vector offset loads).
@@ -246,7 +238,7 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
   const int n_seg = A.segments, seg_shift = __builtin_ctz((unsigned)n_seg);
   int seg = (int)blockIdx.x & (n_seg - 1), segs_left = n_seg;   // wave-uniform
   mask_t has_ray = 0, pend_valid = 0;                 // group-uniform bits: the group holds a ray / a popped entry waiting for its phase
-  constexpr uint32_t kSaBias = (ART_EXECM & 8) ? 8u : 0u;      // the stack pointer register holds sb + 8 sp + kSaBias (bit 3: the address of the top entry itself)
+  constexpr uint32_t kSaBias = 8u;                             // the stack pointer register holds sb + 8 sp + kSaBias: the address of the top entry itself
   const uint32_t se = sb + kSaBias;                            // its value for an empty stack
   uint32_t sa = se; int ray = 0;
   int rec_i = 0;                                      // OVF / INST: the ray's record (k_trace_overflow; the world-space state to restore on leaving an instance)
@@ -317,8 +309,8 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
     if (has_ray == 0) break;
 
     // The step code below is branch-free on purpose: on CDNA a divergent `if` costs three scalar instructions (save/restore exec +
-    // skip branch).  Inactive lanes compute on clamped operands and are masked by selects; LDS pushes of non-hit lanes go to the
-    // group's sink slot.  Bookkeeping (retire / refill / leaf vote) is kept out of the inner node loop.
+    // skip branch).  Inactive lanes compute on clamped operands and are masked by selects; LDS pushes are made under EXEC = the
+    // lanes that push.  Bookkeeping (retire / refill / leaf vote) is kept out of the inner node loop.
 
     // ---------------- inner loop: pop + node phase, as long as enough of the wave's groups have a node to expand
     mask_t want_leaf = 0;
@@ -333,8 +325,7 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
         const uint2 e1 = lds_load(sa + (8u - kSaBias));
         const mask_t v1 = has_ray & ~pend_valid & vcmp(sa > se);
         const mask_t ok1 = v1 & vcmp(!(__builtin_bit_cast(float, e1.y) > best_t));
-        if (ART_EXECM & 2) pop_masked(v1, ok1, sa, pend, e1.x);
-        else { pend = sel(ok1, e1.x, pend); sa = sel(v1, sa - 8u, sa); }
+        pend = sel(ok1, e1.x, pend); sa = sel(v1, sa - 8u, sa);
         pend_valid |= ok1;
       }
       if (INST) {
@@ -373,10 +364,9 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
       uint32_t diag_x[ART_DIAG_LOAD] = {};
 #endif
       if (G == 4) {
-        const uint32_t noff = (ART_EXECM & 1) ? pend : sel(want_node, pend, 0u);
-        uint4 rec;
-        if (ART_EXECM & 1) { const u32x4 rr = load_node_masked(want_node, nodes_b, noff + jrec); rec = make_uint4(rr.x, rr.y, rr.z, rr.w); }
-        else rec = *reinterpret_cast<const uint4*>(nodes_b + (noff + jrec));              // ONE load: the quad reads the node's 64 contiguous bytes
+        const uint32_t noff = pend;
+        const u32x4 rr = load_node_masked(want_node, nodes_b, noff + jrec);              // ONE load: the quad reads the node's 64 contiguous bytes
+        const uint4 rec = make_uint4(rr.x, rr.y, rr.z, rr.w);
         const uint32_t c0 = rec.x, c1 = rec.y; entry = rec.z;
         asm volatile("s_setprio 1" :: "v"(c0));           // a wave whose node has arrived goes ahead of the waves that pop, refill or test leaves (+0.7 % on C4, +3 % on C5)
         const float4 h = make_float4(__builtin_bit_cast(float, dpp_i<0x00>((int)rec.w)), __builtin_bit_cast(float, dpp_i<0x55>((int)rec.w)),
@@ -414,15 +404,13 @@ __global__ __launch_bounds__(256, ART_COOP_WAVES_PER_SIMD) void k_trace_coop(con
       // the counting variant (STATS) walks with exactly the timed kernel's predicate: at G = 4 an empty slot is never masked out, it
       // simply cannot pass the interval test (and if a degenerate node ever let it, both variants would pop the same zero-triangle leaf)
       const mask_t hit = (G == 4) ? (want_node & vcmp(tmn <= tmx)) : (want_node & valid & vcmp(tmn <= tmx));
-      const int key = (ART_EXECM & 4) ? (int)key_masked(hit, __builtin_bit_cast(uint32_t, tmn), (uint32_t)j, 0x7fffffffu)
-                                      : (int)sel(hit, (__builtin_bit_cast(uint32_t, tmn) & ~7u) | (uint32_t)j, 0x7fffffffu);
+      const int key = (int)key_masked(hit, __builtin_bit_cast(uint32_t, tmn), (uint32_t)j, 0x7fffffffu);
       const int nh = group_sum_g<G>((int)sel(hit, 1u, 0u));
       const int nh_minus_rank = (G == 4) ? quad_sub_rank(key, nh) : nh - group_rank_g<G>(key);
       const uint32_t top = sa + (uint32_t)nh * 8u;
       const mask_t ovf = OVF ? (want_node & vcmp(top > slimit + kSaBias)) : 0;        // the ray moves to k_trace_overflow
       const uint32_t dst_hit = (sa + (8u - kSaBias)) + (uint32_t)nh_minus_rank * 8u;
-      if (ART_EXECM & 4) lds_store_masked(hit & ~ovf, dst_hit, make_uint2(entry, __builtin_bit_cast(uint32_t, tmn)));
-      else lds_store(sel(hit & ~ovf, dst_hit, sink), make_uint2(entry, __builtin_bit_cast(uint32_t, tmn)));
+      lds_store_masked(hit & ~ovf, dst_hit, make_uint2(entry, __builtin_bit_cast(uint32_t, tmn)));
       sa = OVF ? sel(ovf, se, top) : top;
       if (OVF) {
         if (ovf != 0) {
@@ -846,118 +834,52 @@ __global__ __launch_bounds__(256) void k_shade(const DevFrame F, const DevScene 
 // The survivors of a wave's round are consecutive output items: their trace records are one contiguous piece of the output bank, the
 // extension rays first, then the shadow rays (REC_BOTH).  The wave builds the records of one kind (make_record: analytic primitives
 // intersected = the starting bound, slab set-up), stages them in LDS and copies them out 16 bytes per lane to consecutive addresses.
-// In the shipped configuration (ART_SHADE_DEFER = 0) that copy-out sits inside shade_item's emit_ray: every kept item of a wave is a
-// surface item and takes the surface branch together, which rests on the compiler keeping ONE call site for it; it is therefore checked
-// at run time -- every record copied must name the hit slot its position implies, else the stage counts a lost path, and a lost path
-// fails art_synchronize.  ART_SHADE_DEFER = 1 builds and copies the records after shade_item at a point every lane of the
-// wave reaches (30 more VGPRs: slower).
+// That copy-out sits inside shade_item's emit_ray: every kept item of a wave is a surface item and takes the surface branch together,
+// which rests on the compiler keeping ONE call site for it; it is therefore checked at run time -- every record copied must name the hit
+// slot its position implies, else the stage counts a lost path, and a lost path fails art_synchronize.  (Copying out at
+// a point every lane of the wave reaches costs 30 more VGPRs: DESIGN_HISTORY.md, the ADVICE (low) staged copy-out row.)
 // ------------------------------------------------------------------------------------------------
-// items per workgroup = 256 x kShadePerThread, one global atomic per workgroup.  Rounds 1-2 used 16 per thread (a single hot word serves
-// ~88 atomics / us); measured in round 3 with the fused stage: 4 per thread is faster at every size -- a thread's items one after the other
-// are its critical path (C2, 4 M paths per step: 3.87 -> 2.03 ms per step; C3 +2.8 %, C5 +2.9 %, C4 +0.6 %), and 130 k atomics per launch of
-// the largest batch still spread over 6 ms.
-#ifndef ART_SHADE_PER
-#define ART_SHADE_PER 4
-#endif
-constexpr int kShadePerThread = ART_SHADE_PER;
-#ifndef ART_SHADE_DEFER
-#define ART_SHADE_DEFER 0         // 1: the kernel builds and copies the records after shade_item, at a wave-uniform point (costs 30 more VGPRs: spills at 6 waves per SIMD, +25 % launch time); 0: shade_item's own emit_ray does (round 3)
-#endif
-#ifndef ART_SHADE_HINT
-#define ART_SHADE_HINT 1          // 1: the classification's key and material index go along to shade_item (all of an item's loads start at once)
-#endif
-#ifndef ART_SHADE_SORT
-#define ART_SHADE_SORT 1          // 1: sort the items of a round by material class (see above); 0: input order (one class for all surfaces).  A/B in one call on the final stage (profiles/r4_shade/ab_sort_final.txt): C4 5.28 vs 5.70 ms per launch, C3 1.70-1.83 vs 1.88-1.90, C5 33.4 vs 33.7 ms per batch
-#endif
-
-#ifndef ART_SHADE_WAVES
-#define ART_SHADE_WAVES 6
-#endif
+// items per workgroup = 256 x kShadePerThread, one global atomic per workgroup.  4 per thread, not 16: a thread's items one after the
+// other are its critical path (round 3, DESIGN_HISTORY.md; profiles/r4_shade/ab_waves_per_thread_sweep.txt).
+constexpr int kShadePerThread = 4;
+// 6 waves per SIMD (80 VGPRs): left to itself the compiler takes 111 VGPRs = 4 waves, slower (round 3; 5 / 7 waves: profiles/r5_shade/ab17_stage_waves_final_kernel.txt)
+constexpr int kShadeWavesPerSimd = 6;
 // CAMERA: bounce 0 over raygen's bank (DevPaths::synth0: flags, previous pdf and the camera ray are recomputed, not read) -- its own
 // instantiation, so that the other bounces' code is exactly what it was (as one kernel the extra branch cost 17 more spilled VGPRs: +7 %)
 // The stage's arguments as ONE struct: about 240 dwords of scene header and array pointers.  Taken by value the compiler loads all of them
-// into SGPRs at the kernel's entry and keeps them live to its end: 320 of them spilled to VGPR lanes (v_writelane / v_readlane: 15 % of the
-// kernel's VALU instructions, and the VGPRs that hold them).  ART_SHADE_KERNARG = 1: the code reads the fields through a pointer to the
-// kernarg segment instead, laundered at the head of every round so that a field is a scalar load (scalar cache) where it is used:
-// 80 spilled SGPRs instead of 320, 0-2 spilled VGPRs instead of 5-7, 6 % fewer VALU instructions; A/B in one call
-// (profiles/r4_shade/ab_kernarg.txt): C4 5.01 vs 5.26 ms per launch (bounce 0: 7.4 vs 8.0), C3 1.58 vs 1.82 (2.98 vs 3.61), C5 3.61 vs 3.67.
-// (0: the struct by value -- which as ONE parameter allocates worse than the eleven parameters of before: 29 spilled VGPRs, 6.0 ms.)
+// into SGPRs at the kernel's entry and keeps them live to its end (spilled to VGPR lanes).  The code reads the fields through a pointer
+// to the kernarg segment instead, laundered at the head of every round so that a field is a scalar load (scalar cache) where it is used
+// (profiles/r4_shade/ab_kernarg.txt).
 struct ShadeKernArgs {
   DevFrame F; DevScene S; DevPaths Qi; DevPaths Qo; int bounce;
   const int* n_in_ptr; int* n_out_ptr; uint32_t* slot_out; unsigned long long* lost; unsigned long long* rays_a; unsigned long long* rays_b;
-  uint4* heavy; int* n_heavy_ptr;          // the deferred items of the heavy material classes (SET_LIGHT appends, SET_HEAVY consumes) and their count
 };
-#ifndef ART_SHADE_KERNARG
-#define ART_SHADE_KERNARG 1
-#endif
 static_assert(sizeof(ShadeKernArgs) <= 4096 && __is_trivially_copyable(ShadeKernArgs), "ShadeKernArgs is the kernel's ONLY parameter: it sits at offset 0 of the kernarg segment");
 typedef const __attribute__((address_space(4))) ShadeKernArgs* ShadeKArgs;
 __device__ __forceinline__ ShadeKArgs launder_kargs(ShadeKArgs k) { unsigned long long r = (unsigned long long)k; asm volatile("" : "+s"(r)); return (ShadeKArgs)r; }
 
-// ---- one instantiation per REGISTER CLASS (round 5).  Until round 4 ONE kernel carried every material: it sat at the 80-VGPR cap of 6 waves
-// per SIMD with spills, for a Lambert majority that needs none of Phong's four binary64 pow evaluations or the glass branch.  Now:
-//   SET_LIGHT   shades the classes outside kHeavyClasses (Lambert, mirror, and the paths that end: CLS_CHEAP) and contains no instruction of
-//               the heavy materials; the heavy items it meets are appended, { item, hit key, material | class << 24 }, to a queue in HBM
-//               (one global atomic per workgroup, 16 B per deferred item);
-//   SET_HEAVY   a second launch over that queue: the same three steps (sort by class, reserve, shade), compiled for the heavy materials only.
-//               Its survivors follow the light kernel's in the output bank (the order of the items of a bank carries no meaning: item -> slot
-//               map, fold records linked by child index).
-//   SET_ALL     the round-4 kernel (every class in one instantiation), kept for A/B: -DART_SHADE_SPLIT=0.
-enum ShadeSet : int { SET_ALL = 0, SET_LIGHT = 1, SET_HEAVY = 2 };
-#ifndef ART_SHADE_SPLIT
-#define ART_SHADE_SPLIT 1
-#endif
-#ifndef ART_HEAVY_CLASSES
-#define ART_HEAVY_CLASSES ((1 << CLS_PHONG) | (1 << CLS_GLASS))
-#endif
-constexpr int kHeavyClasses = ART_HEAVY_CLASSES;
-constexpr int kHeavyMats = ((kHeavyClasses >> CLS_PHONG & 1) ? mat_bit(MAT_PHONG) : 0) | ((kHeavyClasses >> CLS_GLASS & 1) ? mat_bit(MAT_GLASS) : 0) |
-                           ((kHeavyClasses >> CLS_MIRROR & 1) ? mat_bit(MAT_MIRROR) : 0) | ((kHeavyClasses >> CLS_LAMBERT & 1) ? mat_bit(MAT_LAMBERT) : 0);
-constexpr int set_mats(int set) { return set == SET_ALL ? kMatsAll : set == SET_LIGHT ? (kMatsAll & ~kHeavyMats) : (kHeavyMats | mat_bit(MAT_NULL)); }
-constexpr bool class_in_set(int set, int q) { return set == SET_ALL ? true : set == SET_LIGHT ? !(kHeavyClasses >> q & 1) : (kHeavyClasses >> q & 1) != 0; }
-#ifndef ART_SHADE_LIGHT_HINT
-#define ART_SHADE_LIGHT_HINT 1
-#endif
-#ifndef ART_SHADE_WAVES_LIGHT
-#define ART_SHADE_WAVES_LIGHT ART_SHADE_WAVES
-#endif
-#ifndef ART_SHADE_WAVES_HEAVY
-#define ART_SHADE_WAVES_HEAVY ART_SHADE_WAVES
-#endif
-constexpr int set_waves(int set) { return set == SET_LIGHT ? ART_SHADE_WAVES_LIGHT : set == SET_HEAVY ? ART_SHADE_WAVES_HEAVY : ART_SHADE_WAVES; }
-
-template <int PER, bool CAMERA, int SET>
-// SET_ALL: 6 waves per SIMD (80 VGPRs): left to itself the compiler takes 111 VGPRs = 4 waves (6.6 -> 6.2 ms per launch on C4, round 3)
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(set_waves(SET)))) void k_shade_compact(const ShadeKernArgs A_by_value) {
-#if ART_SHADE_KERNARG
+template <int PER, bool CAMERA>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kShadeWavesPerSimd))) void k_shade_compact(const ShadeKernArgs A_by_value) {
   ShadeKArgs K = launder_kargs((ShadeKArgs)__builtin_amdgcn_kernarg_segment_ptr());
-#define ART_KREF(T, field) (*(const T*)&K->field)
-#else
-  const ShadeKernArgs* const K = &A_by_value;
-#define ART_KREF(T, field) (K->field)
-#endif
-  constexpr int MATS = set_mats(SET);
-  const DevFrame& F = ART_KREF(DevFrame, F); const DevScene& S = ART_KREF(DevScene, S); const DevPaths& Qi = ART_KREF(DevPaths, Qi); const DevPaths& Qo = ART_KREF(DevPaths, Qo);
+  const DevFrame& F = *(const DevFrame*)&K->F; const DevScene& S = *(const DevScene*)&K->S; const DevPaths& Qi = *(const DevPaths*)&K->Qi; const DevPaths& Qo = *(const DevPaths*)&K->Qo;
   const int bounce_arg = K->bounce;
   const int* const n_in_ptr = K->n_in_ptr; int* const n_out_ptr = K->n_out_ptr;
   unsigned long long* const rays_a = K->rays_a; unsigned long long* const rays_b = K->rays_b;
   const int bounce = CAMERA ? 0 : bounce_arg;            // (a literal for the camera instantiation: no shadow test can be owed, nothing is pending)
   constexpr int kShadeChunk = 256 * PER;
   __shared__ int s_tot[PER * kItemClasses];                // items of each class in each round (256 items) of the chunk
-  __shared__ int s_base, s_rays, s_hbase;
+  __shared__ int s_base, s_rays;
   __shared__ int s_nall[PER], s_nkeep[PER], s_out0[PER];   // per round: items, survivors, first output item (relative to s_base)
   // [round][sorted position] -> { hit key, thread that classified the item | surface flag << 8 | material index << 9 }: what the
   // classification fetched goes along (ItemHint), so that shade_item asks for the triangle's normals and the material record at once
-  constexpr bool kHints = (ART_SHADE_HINT != 0) && !(SET == SET_LIGHT && ART_SHADE_LIGHT_HINT == 0);      // SET_LIGHT without hints: one byte per item (the thread that classified it) -- 1 KB instead of 8: with it the workgroup's LDS fits 8 times into a CU
-  __shared__ typename std::conditional<kHints, uint2, uint8_t>::type s_hint[kShadeChunk];
+  __shared__ uint2 s_hint[kShadeChunk];
   // a wave's trace records of one kind, [quarter][record] (+1: four consecutive records' quarters fall into four banks)
   constexpr int kStagePitch = 64 + 1;
   __shared__ Rec4 s_stage[4][4 * kStagePitch];
   constexpr int kShadeLdsLights = 8;                    // (8, not k_analytic's 16: with the hints the workgroup's LDS must stay below 160 KB / 6)
   __shared__ DevSphere s_sph[kAnalyticLdsSpheres];      // the scene's spheres and lights, fetched once per workgroup (every emitted ray is tested against them)
   __shared__ DevLight s_lgt[kShadeLdsLights];
-  // the input set: the bank's items (n_in of them), or -- SET_HEAVY -- the entries of the deferred queue
-  const int n_in = (SET == SET_HEAVY) ? *K->n_heavy_ptr : (n_in_ptr ? *n_in_ptr : Qi.P);
+  const int n_in = n_in_ptr ? *n_in_ptr : Qi.P;
   const int c0 = blockIdx.x * kShadeChunk;
   if (c0 >= n_in) return;                                // the grid covers Qi.P items; the work set has shrunk to n_in
   // (the material table stays in global memory: a 40-byte per-lane-indexed record out of LDS measured 7 % slower than the cached global read)
@@ -989,23 +911,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(set_waves(S
     int wk[PER]; bool on[PER];
 #pragma unroll
     for (int k = 0; k < PER; ++k) { wk[k] = c0 + k * 256 + (int)threadIdx.x; on[k] = wk[k] < n_in; hint[k].key = KEY_MISS; hint[k].mat = 0; cls[k] = kItemClasses; }
-    if (SET == SET_HEAVY) {
-      uint4 e[PER];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) e[k] = K->heavy[on[k] ? wk[k] : 0];
-#pragma unroll
-      for (int k = 0; k < PER; ++k) if (on[k]) { hint[k].key = e[k].y; hint[k].mat = (int32_t)(e[k].z & 0xffffffu); cls[k] = (int)(e[k].z >> 24); }
-    } else item_classes<PER>(S, Qi, wk, on, tables, CAMERA, cls, hint);
+    item_classes<PER>(S, Qi, wk, on, tables, CAMERA, cls, hint);
   }
   ART_TPROBE(tables.tprobe, 64);      // classification loads
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
-    int c = cls[k];
+    const int c = cls[k];
     const bool surface = c < CLS_CHEAP;
-    if (SET == SET_LIGHT && c < kItemClasses && !class_in_set(SET_LIGHT, c)) hint[k].mat |= c << 24;          // (a deferred item's queue entry carries its class)
-    else hint[k].mat = (int32_t)(threadIdx.x | (surface ? 256u : 0u) | ((uint32_t)hint[k].mat << 9));
-    if (!ART_SHADE_SORT && SET == SET_ALL && c < CLS_CHEAP) c = CLS_LAMBERT;
-    cls[k] = c; rank[k] = 0;
+    hint[k].mat = (int32_t)(threadIdx.x | (surface ? 256u : 0u) | ((uint32_t)hint[k].mat << 9));
+    rank[k] = 0;
 #pragma unroll
     for (int q = 0; q < kItemClasses; ++q) {
       const uint64_t m = __builtin_amdgcn_ballot_w64(c == q);
@@ -1024,122 +938,52 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(set_waves(S
   // The sort stays inside a round's 256 items: the four waves of the workgroup then read one 1-KB window of every array at the same time
   // (sorted over the whole chunk, a wave's loads touched lines whose other halves were fetched again three rounds later: +43 % bytes
   // fetched, +22 % written back, 16-27 % slower although it ran 29 % fewer VALU instructions -- profiles/r4_shade/ab_sort_chunk.txt)
-  // SET_LIGHT: the classes of kHeavyClasses are left out of the rounds; their items go to the deferred queue, class by class and round by round
   const bool keeps = stage_keeps_surfaces(F, bounce);
-  if (SET == SET_LIGHT) {
-    if (threadIdx.x == 0) {
-      int nh = 0;
-      for (int k = 0; k < PER; ++k)
-        for (int q = 0; q < kItemClasses; ++q) if (!class_in_set(SET_LIGHT, q)) nh += s_tot[k * kItemClasses + q];
-      s_hbase = nh ? atomicAdd(K->n_heavy_ptr, nh) : 0;
-    }
-  }
-  int total_keep = 0, total_heavy = 0;
+  int total_keep = 0;
 #pragma unroll
   for (int k = 0; k < PER; ++k) {
-    int st = 0, mine = 0, nkeep = 0, hv = total_heavy, hmine = 0;
+    int st = 0, mine = 0, nkeep = 0;
 #pragma unroll
     for (int q = 0; q < kItemClasses; ++q) {
       if (q == CLS_CHEAP) nkeep = keeps ? st : 0;
-      const int nq = s_tot[k * kItemClasses + q];
-      if (SET == SET_LIGHT && !class_in_set(SET_LIGHT, q)) { hmine = (cls[k] == q) ? hv : hmine; hv += nq; continue; }
       mine = (cls[k] == q) ? st : mine;
-      st += nq;
+      st += s_tot[k * kItemClasses + q];
     }
     if (threadIdx.x == 0) { s_nall[k] = st; s_nkeep[k] = nkeep; s_out0[k] = total_keep; }
-    total_keep += nkeep; total_heavy = hv;
-    const bool deferred = (SET == SET_LIGHT) && cls[k] < kItemClasses && !class_in_set(SET_LIGHT, cls[k]);
-    if (deferred) rank[k] += hmine - (1 << 30);           // its place in the workgroup's piece of the queue (marked: written once s_hbase is known)
-    else if (cls[k] < kItemClasses) {
-      if constexpr (kHints) s_hint[k * 256 + mine + rank[k]] = make_uint2(hint[k].key, (uint32_t)hint[k].mat);
-      else s_hint[k * 256 + mine + rank[k]] = (uint8_t)threadIdx.x;
-    }
+    total_keep += nkeep;
+    if (cls[k] < kItemClasses) s_hint[k * 256 + mine + rank[k]] = make_uint2(hint[k].key, (uint32_t)hint[k].mat);
   }
   if (threadIdx.x == 0) s_base = total_keep ? atomicAdd(n_out_ptr, total_keep) : 0;
   __syncthreads();
-  if (SET == SET_LIGHT) {
-    const int hbase = s_hbase;
-#pragma unroll
-    for (int k = 0; k < PER; ++k)
-      if (rank[k] < 0) K->heavy[hbase + rank[k] + (1 << 30)] = make_uint4((uint32_t)(c0 + k * 256 + (int)threadIdx.x), hint[k].key, (uint32_t)hint[k].mat, 0u);
-  }
   const int base = s_base;
   ART_TPROBE(tables.tprobe, 67);      // sort, output reservation (global atomic), barrier 2
   // ---- 3. shade in sorted order
   const bool staged = (Qo.rec != nullptr) && Qo.has_bvh;
-  const int mode = Qo.rec_mode;
-  StageCtx cx = tables;
   int n_rays = 0;
 #pragma unroll 1
   for (int k = 0; k < PER; ++k) {
-#if ART_SHADE_KERNARG
     const ShadeKArgs K2 = launder_kargs(K);               // the round's own view of the arguments: nothing loaded before survives in a register
     const DevFrame& F = *(const DevFrame*)&K2->F; const DevScene& S = *(const DevScene*)&K2->S; const DevPaths& Qi = *(const DevPaths*)&K2->Qi; const DevPaths& Qo = *(const DevPaths*)&K2->Qo;
     unsigned long long* const lost = K2->lost;            // (the output items' slot words are written by shade_item: Qo's HF_SLOT field IS K->slot_out)
-#else
-    unsigned long long* const lost = K->lost;
-    const ShadeKernArgs* const K2 = K;
-#endif
     ART_TPROBE(tables.tprobe, 70);    // round bookkeeping (and, after the first round, whatever followed the last probe of the item before)
-    // Which 64 sorted positions of the round this wave takes: tile (wave + k) mod 4 (round 5).  A sorted round is [Lambert ...][Phong][glass]
-    // [mirror][cheap]: its last tile is where the classes meet -- on C4 a few Lambert lanes, the round's 13 Phong items and its ~33 ended
-    // paths, three code paths one after the other, about three times a one-class tile's time.  With tile = wave that tile went to wave 3 of
-    // every workgroup in every round, i.e. to the same SIMD of the CU (a workgroup's four waves sit on its four SIMDs); rotated, every wave
-    // gets it once per chunk.
-#ifndef ART_SHADE_ROTATE
-#define ART_SHADE_ROTATE 0   // measured (profiles/r5_shade/ab8_rotate.txt): no gain on C3 / C5, bounce 0 4 % slower on C4 / S4 -- the hardware does not pin wave 3 to one SIMD
-#endif
-    const int tile = ART_SHADE_ROTATE ? ((wave + k) & 3) : wave;
-    const int r = tile * 64 + lane;                       // position in the sorted round
+    // Wave w takes the sorted positions [64 w, 64 w + 64) of every round (rotating the tiles over the waves gained nothing:
+    // profiles/r5_shade/ab8_rotate.txt).
+    const int r = wave * 64 + lane;                       // position in the sorted round
     const int n_all_k = s_nall[k], n_keep_k = s_nkeep[k], out0_k = s_out0[k];
-    const bool keep = r < n_keep_k;
-    const int wo = keep ? base + out0_k + r : -1;
-    RayOut ro; ro.alive = false; ro.shadow = false; ro.no = ro.nd = ro.so = ro.sd = mk3(0.0f, 0.0f, 0.0f); ro.s_tfar = -1.0f; ro.sh_min = 0.0f;
+    const int wo = r < n_keep_k ? base + out0_k + r : -1;
     if (r < n_all_k) {
-      uint2 hk;
-      if constexpr (kHints) hk = s_hint[k * 256 + r]; else hk = make_uint2(KEY_MISS, (uint32_t)s_hint[k * 256 + r]);
-      int w = c0 + k * 256 + (int)(hk.y & 255u);
-      if (SET == SET_HEAVY) w = (int)K2->heavy[w].x;       // the queue entry names the item
-      ItemHint ih; ih.key = hk.x; ih.mat = (ART_SHADE_HINT && (hk.y & 256u)) ? (int32_t)(hk.y >> 9) : -1;      // mat < 0: no hint (shade_item)
-      const ItemHint* const hp = &ih;
+      const uint2 hk = s_hint[k * 256 + r];
+      const int w = c0 + k * 256 + (int)(hk.y & 255u);
+      ItemHint ih; ih.key = hk.x; ih.mat = (hk.y & 256u) ? (int32_t)(hk.y >> 9) : -1;      // mat < 0: no hint (shade_item)
       // (the output item's slot word is written by shade_item with the item's other words: qo.slot_id IS slot_out)
-      if (ART_SHADE_DEFER) n_rays += shade_item<MATS>(F, S, Qi, Qo, w, wo, bounce, lost, cx, &ro, hp, CAMERA ? 1 : 0, 1);
-      else {
-        StageCtx cy = tables;
-        if (staged) {
-          const int nk = min(64, max(0, n_keep_k - tile * 64)), per = (Qo.rec_mode == REC_BOTH) ? 2 : 1;
-          const size_t first = (size_t)per * (size_t)(base + out0_k + tile * 64);
-          cy.stage = s_stage[wave]; cy.stage_pitch = kStagePitch; cy.stage_item = lane; cy.stage_count = nk; cy.lost = lost;
-          cy.rec_base[0] = first; cy.rec_base[1] = (per == 2) ? first + (size_t)nk : first;
-        }
-        n_rays += shade_item<MATS>(F, S, Qi, Qo, w, wo, bounce, lost, cy, nullptr, hp, CAMERA ? 1 : 0, 1);
+      StageCtx cy = tables;
+      if (staged) {
+        const int nk = min(64, max(0, n_keep_k - wave * 64)), per = (Qo.rec_mode == REC_BOTH) ? 2 : 1;
+        const size_t first = (size_t)per * (size_t)(base + out0_k + wave * 64);
+        cy.stage = s_stage[wave]; cy.stage_pitch = kStagePitch; cy.stage_item = lane; cy.stage_count = nk; cy.lost = lost;
+        cy.rec_base[0] = first; cy.rec_base[1] = (per == 2) ? first + (size_t)nk : first;
       }
-    }
-    if (ART_SHADE_DEFER && Qo.rec != nullptr) {
-      // every lane of the wave is here.  The wave's survivors of this round are its lanes [0, nk): consecutive output items.
-      const int r0 = tile * 64;
-      const int nk = min(64, max(0, n_keep_k - r0));
-      if (nk > 0) {                                        // wave-uniform
-        const int per = (mode == REC_BOTH) ? 2 : 1;
-        const size_t first = (size_t)per * (size_t)(base + out0_k + r0);
-#pragma unroll
-        for (int kind = 0; kind < 2; ++kind) {             // 0: extension rays, 1: shadow rays
-          if ((kind == 0 && mode == REC_SHADOW) || (kind == 1 && mode == REC_EXT)) continue;
-          TraceRec t;
-          if (keep) {
-            t = (kind == 0) ? make_record(S, Qo, (size_t)wo, ro.alive, ro.no, ro.nd, kInfinity, -1.0f, cx)
-                            : make_record(S, Qo, Qo.sh_t ? (size_t)(kShadowWord | (uint32_t)wo) : (size_t)Qo.P + (size_t)wo, ro.shadow, ro.so, ro.sd, ro.s_tfar, Qo.shadow_rule ? ro.sh_min : -1.0f, cx);
-          }
-          if (staged) {
-            Rec4* const stage = s_stage[wave];
-            if (keep) { stage[lane] = t.r0; stage[kStagePitch + lane] = t.r1; stage[2 * kStagePitch + lane] = t.r2; stage[3 * kStagePitch + lane] = t.r3; }
-            wave_lds_sync();
-            Rec4* out = Qo.rec + 4 * (first + ((kind == 1 && per == 2) ? (size_t)nk : 0));
-            for (int g = lane; g < 4 * nk; g += 64) out[g] = stage[(g & 3) * kStagePitch + (g >> 2)];
-            wave_lds_sync();
-          }
-        }
-      }
+      n_rays += shade_item(F, S, Qi, Qo, w, wo, bounce, lost, cy, &ih, CAMERA ? 1 : 0, 1);
     }
   }
   ART_TPROBE(tables.tprobe, 68);      // end of the last round
@@ -1274,35 +1118,20 @@ __global__ void k_probe_on(int v) { g_lane_probe_on = v; }
 #endif
 void launch_shade_compact(hipStream_t st, const DevFrame& F, const DevScene& S, const DevPaths& Qi, const DevPaths& Qo, int bounce,
                           const int* n_in, int* n_out, uint32_t* slot_out, unsigned long long* lost, unsigned long long* rays_a, unsigned long long* rays_b,
-                          uint4* heavy, int* n_heavy, int per) {
+                          int per) {
   const bool camera = Qi.synth0 && Qi.slot_id == nullptr;
-  const int per_now = (per == 2 && !(ART_SHADE_SPLIT && heavy != nullptr && n_heavy != nullptr)) ? 2 : kShadePerThread;      // items per thread of this launch (2: the one-kernel form only)
+  const int per_now = (per == 2) ? 2 : kShadePerThread;      // items per thread of this launch
   const dim3 grid((Qi.P + 256 * per_now - 1) / (256 * per_now));
 #if defined(ART_LANE_PROBE)
   hipLaunchKernelGGL(k_probe_on, dim3(1), dim3(1), 0, st, 1);
 #endif
   ShadeKernArgs A; A.F = F; A.S = S; A.Qi = Qi; A.Qo = Qo; A.bounce = bounce; A.n_in_ptr = n_in; A.n_out_ptr = n_out; A.slot_out = slot_out; A.lost = lost; A.rays_a = rays_a; A.rays_b = rays_b;
-  A.heavy = heavy; A.n_heavy_ptr = n_heavy;
-  const bool split = ART_SHADE_SPLIT && heavy != nullptr && n_heavy != nullptr;
-  if (!split) {
-    if (per_now == 2) {
-      if (camera) hipLaunchKernelGGL((k_shade_compact<2, true, SET_ALL>), grid, dim3(256), 0, st, A);
-      else hipLaunchKernelGGL((k_shade_compact<2, false, SET_ALL>), grid, dim3(256), 0, st, A);
-    } else {
-      if (camera) hipLaunchKernelGGL((k_shade_compact<kShadePerThread, true, SET_ALL>), grid, dim3(256), 0, st, A);
-      else hipLaunchKernelGGL((k_shade_compact<kShadePerThread, false, SET_ALL>), grid, dim3(256), 0, st, A);
-    }
+  if (per_now == 2) {
+    if (camera) hipLaunchKernelGGL((k_shade_compact<2, true>), grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((k_shade_compact<2, false>), grid, dim3(256), 0, st, A);
   } else {
-    // the light classes, then the deferred items of the heavy ones (their count is only known on the device: the grid covers the
-    // worst case, workgroups past the queue's end return at once)
-    const dim3 hgrid = grid;
-    if (camera) {
-      hipLaunchKernelGGL((k_shade_compact<kShadePerThread, true, SET_LIGHT>), grid, dim3(256), 0, st, A);
-      hipLaunchKernelGGL((k_shade_compact<kShadePerThread, true, SET_HEAVY>), hgrid, dim3(256), 0, st, A);
-    } else {
-      hipLaunchKernelGGL((k_shade_compact<kShadePerThread, false, SET_LIGHT>), grid, dim3(256), 0, st, A);
-      hipLaunchKernelGGL((k_shade_compact<kShadePerThread, false, SET_HEAVY>), hgrid, dim3(256), 0, st, A);
-    }
+    if (camera) hipLaunchKernelGGL((k_shade_compact<kShadePerThread, true>), grid, dim3(256), 0, st, A);
+    else hipLaunchKernelGGL((k_shade_compact<kShadePerThread, false>), grid, dim3(256), 0, st, A);
   }
 #if defined(ART_LANE_PROBE)
   hipLaunchKernelGGL(k_probe_on, dim3(1), dim3(1), 0, st, 0);
@@ -1360,7 +1189,7 @@ void launch_add_f32(hipStream_t st, const float* src, float* dst, size_t n) {
   hipLaunchKernelGGL(k_add_f32, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, src, dst, n);
 }
 
-size_t trace_coop_lds_bytes(int stack_entries, int width) { return (size_t)4 * (64 / width) * (stack_entries + 3) * sizeof(uint2); }   // + 2 guards + sink
+size_t trace_coop_lds_bytes(int stack_entries, int width) { return (size_t)4 * (64 / width) * (stack_entries + 3) * sizeof(uint2); }   // + 2 guards + a spare entry
 
 void launch_analytic(hipStream_t st, const DevScene& S, const TraceArgs& A, bool stats) {
   TraceArgs B = A;

@@ -38,18 +38,6 @@ ART_HD float* cold_e(const DevPaths& q, int c, int level) { return q.cold + ((si
 ART_HD float* cold_w(const DevPaths& q, int c, int level) { return q.cold + ((size_t)3 * (size_t)(q.depth + 1) + (size_t)c * (size_t)q.depth + (size_t)level) * (size_t)q.P; }
 ART_HD int32_t* cold_child(const DevPaths& q, int level) { return reinterpret_cast<int32_t*>(q.cold + ((size_t)3 * (size_t)(q.depth + 1) + (size_t)3 * (size_t)q.depth + (size_t)level) * (size_t)q.P); }
 
-// The rays an item leaves a bounce with, for a caller that writes the trace records itself (k_shade_compact: the wave stages one kind of
-// ray at a time and copies it out at a point every lane of the wave reaches).
-struct RayOut { bool alive, shadow; f3 no, nd, so, sd; float s_tfar, sh_min; };
-
-// Diagnostic builds only (wrong pictures; profiles/r4_shade/sensitivity.txt): -DART_DIAG_SKIP=<bits> leaves out one kind of the stage's traffic --
-// 1 trace-record copy-out, 2 the triangle-normal gather, 4 the next ray as SoA words, 8 the hit-record (starting bound) stores, 16 the fold records
-#ifndef ART_DIAG_SKIP
-#define ART_DIAG_SKIP 0
-#endif
-#ifndef ART_SYNTH_DIR
-#define ART_SYNTH_DIR 1           // DevPaths::synth0: 1 = bounce 0 recomputes the camera direction as well (raygen then stores a hit and a record, nothing else), 0 = raygen stores the direction (measured equal within noise on C3 / C4, 2 % slower on C5)
-#endif
 ART_HD void wave_fence() {
 #if defined(__HIP_DEVICE_COMPILE__)
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
@@ -203,14 +191,6 @@ ART_HD LightSample light_sample(L lp, float u1, float u2, f3 p) {
 // ---------------------------------------------------------------- materials
 struct BsdfSample { f3 color, dir; float pdf; bool specular; };
 
-// Material sets (round 5).  The per-item code below is compiled once per SET of material types (template parameter MATS, one bit per
-// MatType): a kernel instantiated for a set contains no instruction of the other materials, so that the Lambert majority of a scene does
-// not carry the registers of Phong's binary64 pow or of the glass branch (k_shade_compact: one instantiation per register class).
-// A material outside the set cannot reach the instantiation (the caller sorts the items by class first); should one ever, it shades
-// as MaterialLight's default (black) and shade_item counts a lost path.
-constexpr int mat_bit(int type) { return ((unsigned)type < 8u) ? (1 << type) : 0; }
-constexpr int kMatsAll = mat_bit(MAT_NULL) | mat_bit(MAT_LIGHT) | mat_bit(MAT_LAMBERT) | mat_bit(MAT_MIRROR) | mat_bit(MAT_GLASS) | mat_bit(MAT_PHONG);
-
 ART_HD float fresnel_unpolarised(float cos1, float eta_ext_in, float eta_int_in) {   // materials.adb:70-99
   float ext = eta_ext_in, in = eta_int_in;
   if (cos1 < 0.0f) { const float tmp = ext; ext = in; in = tmp; }
@@ -224,12 +204,10 @@ ART_HD float fresnel_unpolarised(float cos1, float eta_ext_in, float eta_int_in)
   return (rs * rs + rp * rp) / 2.0f;
 }
 
-template <int MATS = kMatsAll>
 ART_HD BsdfSample bsdf_sample(const DevMaterial& m, float xi1, float xi2, f3 ray_dir, f3 n) {
   BsdfSample r;
-  const int32_t type = (MATS & mat_bit(m.type)) ? m.type : (int32_t)MAT_LIGHT;      // outside the set: the default case
-  switch (type) {
-    case MAT_LAMBERT: if (MATS & mat_bit(MAT_LAMBERT)) {        // materials.adb:197-215
+  switch (m.type) {
+    case MAT_LAMBERT: {                                         // materials.adb:197-215
       ART_PROBE(20);
       const f3 nd = sample_cosine(xi1, xi2, n, n, 1.0f);
       const float ct = dot(nd, n);
@@ -238,15 +216,15 @@ ART_HD BsdfSample bsdf_sample(const DevMaterial& m, float xi1, float xi2, f3 ray
       if (ct < kEpsCos) r.color = mk3(0.0f, 0.0f, 0.0f);
       r.dir = nd; r.specular = false;
       return r;
-    } break;
-    case MAT_MIRROR: if (MATS & mat_bit(MAT_MIRROR)) {          // :247-254
+    }
+    case MAT_MIRROR: {                                          // :247-254
       ART_PROBE(21);
       const f3 nd = reflect(ray_dir, n);
       const float cdiv = 1.0f / amax(dot(nd, n), kEpsDiv);
       r.color = ld3(m.p) * cdiv; r.dir = nd; r.pdf = 1.0f; r.specular = true;
       return r;
-    } break;
-    case MAT_GLASS: if (MATS & mat_bit(MAT_GLASS)) {            // :285-331
+    }
+    case MAT_GLASS: {                                           // :285-331
       ART_PROBE(22);
       const float ior = m.p[6];
       const float f = fresnel_unpolarised(dot(ray_dir, n), ior, 1.0f);
@@ -275,8 +253,8 @@ ART_HD BsdfSample bsdf_sample(const DevMaterial& m, float xi1, float xi2, f3 ray
       const float cdiv = 1.0f / amax(fabsf(dot(nd, n)), kEpsDiv);
       r.color = bx * cdiv; r.dir = nd; r.pdf = 1.0f; r.specular = true;
       return r;
-    } break;
-    case MAT_PHONG: if (MATS & mat_bit(MAT_PHONG)) {            // :363-387
+    }
+    case MAT_PHONG: {                                           // :363-387
       ART_PROBE(23);
       const float pw = m.p[3];
       const f3 rr = reflect(ray_dir, n);
@@ -290,23 +268,21 @@ ART_HD BsdfSample bsdf_sample(const DevMaterial& m, float xi1, float xi2, f3 ray
       if (cg < kEpsCos) col = mk3(0.0f, 0.0f, 0.0f);
       r.color = col * cdiv; r.dir = nd; r.specular = false;
       return r;
-    } break;
+    }
     default: break;
   }
   r.color = mk3(0.0f, 0.0f, 0.0f); r.dir = r.color; r.pdf = 1.0f; r.specular = false;      // MaterialLight :163-166
   return r;
 }
 
-template <int MATS = kMatsAll>
 ART_HD void bsdf_eval(const DevMaterial& m, f3 l, f3 v, f3 n, f3& bxdf, float& pdf) {
-  const int32_t type = (MATS & mat_bit(m.type)) ? m.type : (int32_t)MAT_LIGHT;
-  switch (type) {
-    case MAT_LAMBERT: if (MATS & mat_bit(MAT_LAMBERT)) {        // :217-226
+  switch (m.type) {
+    case MAT_LAMBERT: {                                         // :217-226
       bxdf = ld3(m.p) * kInvPi;
       pdf = amax(dot(n, l), 0.0f) * kInvPi;
       return;
-    } break;
-    case MAT_PHONG: if (MATS & mat_bit(MAT_PHONG)) {            // :389-410
+    }
+    case MAT_PHONG: {                                           // :389-410
       const float pw = m.p[3];
       const f3 rr = reflect(neg(v), n);
       const float ct = aclamp(dot(l, rr), 0.0f, kPhongClamp);
@@ -315,7 +291,7 @@ ART_HD void bsdf_eval(const DevMaterial& m, f3 l, f3 v, f3 n, f3& bxdf, float& p
       bxdf = ((((ld3(m.p) * (pw + 2.0f)) * 0.5f) * kInvPi) * lobe) * cdiv;
       pdf = lobe * (pw + 1.0f) * (0.5f * kInvPi);
       return;
-    } break;
+    }
     default: break;
   }
   bxdf = mk3(0.0f, 0.0f, 0.0f); pdf = 1.0f;                       // light / mirror / glass
@@ -410,19 +386,16 @@ ART_HD TraceRec make_record(const DevScene& s, const DevPaths& qo, size_t hit_in
   ART_PROBE(30);
   if (live) {
     ART_PROBE(31);
-#ifndef ART_SHARE_RCP
-#define ART_SHARE_RCP 1
-#endif
     const f3 rcp = ray_rcp(d);                                   // three divisions per ray: the Cornell box, the brute-force mesh's box and the slab set-up below share them
     const Cand best = analytic_bound(s, cx, o, d, rcp, tfar);
     if (word) put_s(sh_t_out, (int)((uint32_t)hit_index & ~kShadowWord), (best.key != KEY_MISS) ? best.t : -1.0f);
     else if (cx.hot_layout) put_s(hotf<DevHit>(qo, HF_HIT), (int)hit_index, DevHit{best.t, best.key, best.u, best.v});
-    else if (!(ART_DIAG_SKIP & 8)) qo.hit[hit_index] = DevHit{best.t, best.key, best.u, best.v};
+    else qo.hit[hit_index] = DevHit{best.t, best.key, best.u, best.v};
     const bool near_done = (shm >= 0.0f) && (best.key != KEY_MISS) && (best.t <= shm);       // shadow_rule: decided
     if (!near_done && qo.has_bvh) {
       ART_PROBE(32);
       f3 inv, noi;
-      if (ART_SHARE_RCP) slab_setup_rcp(o, d, rcp, inv, noi); else slab_setup(o, d, inv, noi);
+      slab_setup_rcp(o, d, rcp, inv, noi);
       const bool far_found = (shm >= 0.0f) && (best.key != KEY_MISS);
       const float bt = far_found ? next_up_pos(shm) : best.t;
       const uint32_t bk = far_found ? KEY_MISS : best.key;
@@ -455,11 +428,11 @@ ART_HD void emit_ray(const DevScene& s, const DevPaths& qo, size_t hit_index, si
       // keeping this call at ONE place that all of them reach together.  Checked at run time: the last quarter of record q of the wave
       // must name hit slot (first item + q) of this kind, else the stage counts a lost path (tests assert the counter stays 0).
       const uint32_t hit0 = (uint32_t)hit_index - (uint32_t)stage_slot; (void)hit0;
-      if (!(ART_DIAG_SKIP & 1)) for (int it = 0; it < 4; ++it) {
+      for (int it = 0; it < 4; ++it) {
         const int g = it * cx.stage_count + stage_slot;
         const Rec4 v = stage[(g & 3) * stage_pitch + (g >> 2)];
-#if (ART_NT & 1) && defined(__HIP_DEVICE_COMPILE__)
-        { typedef float f4nt __attribute__((ext_vector_type(4))); __builtin_nontemporal_store(f4nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f4nt*>(&out[g])); }      // experiment: written once, read once by the trace kernel
+#if defined(__HIP_DEVICE_COMPILE__)
+        { typedef float f4nt __attribute__((ext_vector_type(4))); __builtin_nontemporal_store(f4nt{v.x, v.y, v.z, v.w}, reinterpret_cast<f4nt*>(&out[g])); }      // written once, read once by the trace kernel
 #else
         out[g] = v;
 #endif
@@ -500,8 +473,10 @@ ART_HD void raygen_slot(const DevFrame& f, const DevScene& s, const DevPaths& q,
   uint32_t pixel, sample;
   slot_to_sample(q, slot, pixel, sample);
   const f3 d = camera_dir(f, s, pixel, sample);
-  if (!q.synth0) { q.ray_ox[slot] = s.cam_pos[0]; q.ray_oy[slot] = s.cam_pos[1]; q.ray_oz[slot] = s.cam_pos[2]; }
-  if (!q.synth0 || !ART_SYNTH_DIR) { q.ray_dx[slot] = d.x; q.ray_dy[slot] = d.y; q.ray_dz[slot] = d.z; }
+  if (!q.synth0) {
+    q.ray_ox[slot] = s.cam_pos[0]; q.ray_oy[slot] = s.cam_pos[1]; q.ray_oz[slot] = s.cam_pos[2];
+    q.ray_dx[slot] = d.x; q.ray_dy[slot] = d.y; q.ray_dz[slot] = d.z;
+  }
   if (q.rec) emit_ray(s, q, (size_t)slot, (size_t)slot, true, ld3(s.cam_pos), d, kInfinity, -1.0f, cx, cx.stage_item);     // REC_EXT: record `slot`
   else {
     q.ray_tfar[slot] = kInfinity;
@@ -644,13 +619,11 @@ ART_HD bool item_survives(const DevFrame& f, const DevScene& s, const DevPaths& 
 }
 
 // Returns the number of rays the item emits (the closest-hit queries of the next trace: Mrays/s counts them).
-// defer != nullptr (and qo.rec): the trace records are left to the caller, who gets the rays in *defer.
 // hint != nullptr: the item is a surface item and *hint holds its hit key and material index (k_shade_compact's classification): the
 // triangle's normals and the material record are then requested together with the item's own words, one round trip instead of three
 // dependent ones (hit -> triangle shading record -> material).
-template <int MATS = kMatsAll>
 ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, const DevPaths& qo, int w, int wo, int bounce, unsigned long long* lost = nullptr,
-                      const StageCtx& cx = StageCtx(), RayOut* defer = nullptr, const ItemHint* hint_in = nullptr, int camera_mode = -1, int dense_mode = -1) {
+                      const StageCtx& cx = StageCtx(), const ItemHint* hint_in = nullptr, int camera_mode = -1, int dense_mode = -1) {
   ART_PROBE(0);
   // dense_mode: 1 / 0 = the caller knows which fold records the schedule keeps (k_shade_compact: dense; the dead branches and their
   // pointer loads then drop out of the kernel), -1 = look at the bank
@@ -674,7 +647,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   DevMaterial pre_m = DevMaterial{MAT_NULL, 0, {0, 0, 0, 0, 0, 0, 0, 0}};
   if (hinted || batch) {
     pre_m = (cx.materials ? cx.materials : s.materials)[hinted ? hint_v.mat : 0];
-    const bool tri = hinted && !(ART_DIAG_SKIP & 2) && (hint_v.key & ~KEY_INDEX_MASK) == KEY_TRI;
+    const bool tri = hinted && (hint_v.key & ~KEY_INDEX_MASK) == KEY_TRI;
     if (tri || batch) {
       const float* r = (s.m_shade ? s.m_shade : (const float*)(const void*)s.materials) + (size_t)kTriShadeFloats * (tri ? shade_record(s, hint_v.key & KEY_INDEX_MASK) : (size_t)0);
       pre_n.a = ld3(r); pre_n.b = ld3(r + 3); pre_n.c = ld3(r + 6); pre_n.on = tri;
@@ -696,11 +669,9 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   int slot_v = slot_loaded;
   if (camera) {
     o = ld3(s.cam_pos); prev_pdf = 1.0f;
-    if (ART_SYNTH_DIR) {
-      uint32_t cpix, csam;
-      slot_to_sample(qi, slot_loaded, cpix, csam);
-      d = camera_dir(f, s, cpix, csam);                                         // raygen_slot's own expression: the same bits
-    } else d = mk3(at(qi.ray_dx, w), at(qi.ray_dy, w), at(qi.ray_dz, w));
+    uint32_t cpix, csam;
+    slot_to_sample(qi, slot_loaded, cpix, csam);
+    d = camera_dir(f, s, cpix, csam);                                           // raygen_slot's own expression: the same bits
   } else {
     if (batch) {
       o = mk3(at_s(hotf<const float>(qi, HF_OX), w), at_s(hotf<const float>(qi, HF_OY), w), at_s(hotf<const float>(qi, HF_OZ), w));
@@ -770,13 +741,8 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
     const bool mat_ok = hinted ? true : ((key != KEY_MISS) && sf.mat >= 0 && sf.mat < s.n_materials);
     const DevMaterial m = hinted ? pre_m : (mat_ok ? (cx.materials ? cx.materials : s.materials)[sf.mat] : DevMaterial{MAT_NULL, 0, {0, 0, 0, 0, 0, 0, 0, 0}});
     ART_PROBE(3);
-    if (MATS != kMatsAll && mat_ok && !(MATS & mat_bit(m.type)) && lost != nullptr) {   // a material this instantiation was not compiled for: the caller's sort is broken
-#if defined(__HIP_DEVICE_COMPILE__)
-      atomicAdd(lost, 1ull);
-#endif
-    }
     if (!mat_ok || m.type == MAT_NULL) kill(bounce, zero);                            // integrators.adb:218-220
-    else if ((MATS & mat_bit(MAT_LIGHT)) && m.type == MAT_LIGHT) {                    // :102-108 / :155-157 / :222-247
+    else if (m.type == MAT_LIGHT) {                                                   // :102-108 / :155-157 / :222-247
       ART_PROBE(4);
       const f3 n = sf.normal;
       const float sel_pdf = 1.0f / (float)s.n_lights;
@@ -818,7 +784,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
         const float lp = ls.pdf * sel_pdf;
         ART_PROBE(7);
         f3 bx; float bp;
-        bsdf_eval<MATS>(m, sdir, neg(d), n, bx, bp);
+        bsdf_eval(m, sdir, neg(d), n, bx, bp);
         const float c1 = amax(dot(sdir, n), 0.0f);
         if (f.render_type == PT_MIS) {
           const float mis = lp * lp / (lp * lp + bp * bp);
@@ -847,7 +813,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
       }
       ART_PROBE(8);
       ART_TPROBE(cx.tprobe, 73);    // light sample, bsdf_eval, shadow ray done
-      const BsdfSample bs = bsdf_sample<MATS>(m, u01(rnd.z), u01(rnd.w), d, n);          // :116-124 / :183-191 / :291-299
+      const BsdfSample bs = bsdf_sample(m, u01(rnd.z), u01(rnd.w), d, n);          // :116-124 / :183-191 / :291-299
       ART_PROBE(9);
       const f3 bxv = bs.color * (1.0f / amax(bs.pdf, kGEpsilonDiv));
       const float ct = dot(bs.dir, n);
@@ -863,7 +829,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   }
   ART_PROBE(40);
   ART_TPROBE(cx.tprobe, 74);        // bsdf_sample done (all lanes)
-  if (dense && !(ART_DIAG_SKIP & 16)) {                      // dense stores: consecutive items, consecutive addresses
+  if (dense) {                      // dense stores: consecutive items, consecutive addresses
     const size_t l0 = (size_t)bounce * P;                   // (the level's base is wave-uniform: a scalar add; the item's offset stays 32 bits)
     const int32_t cw = fold_child_word((rec_child == -2 && wo >= 0) ? wo : rec_child, rec_shadowed);
     if (batch) { put_s(cold_w(qi, 0, bounce), w, rec_w.x); put_s(cold_w(qi, 1, bounce), w, rec_w.y); put_s(cold_w(qi, 2, bounce), w, rec_w.z); put_s(cold_child(qi, bounce), w, cw); }
@@ -888,7 +854,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
     if (shadow || null_shadow) {      // (null_shadow: the ray is not traced, DevFrame::skip_null_shadow -- the level's explicit light is still this exact zero)
       put_s(cold_e(qi, 0, bounce + 1), wo, cand.x); put_s(cold_e(qi, 1, bounce + 1), wo, cand.y); put_s(cold_e(qi, 2, bounce + 1), wo, cand.z);
     }
-    if (alive && !(ART_DIAG_SKIP & 4)) {
+    if (alive) {
       put_s(hotf<float>(qo, HF_OX), wo, no.x); put_s(hotf<float>(qo, HF_OY), wo, no.y); put_s(hotf<float>(qo, HF_OZ), wo, no.z);
       put_s(hotf<float>(qo, HF_DX), wo, nd.x); put_s(hotf<float>(qo, HF_DY), wo, nd.y); put_s(hotf<float>(qo, HF_DZ), wo, nd.z);
     }
@@ -903,7 +869,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
       put(qi.e_r + l1, wo, cand.x); put(qi.e_g + l1, wo, cand.y); put(qi.e_b + l1, wo, cand.z);
     } else if (shadow) { qo.cand_r[wo] = cand.x; qo.cand_g[wo] = cand.y; qo.cand_b[wo] = cand.z; }
   }
-  if (alive && !(ART_DIAG_SKIP & 4)) {
+  if (alive) {
     put(qo.ray_ox, wo, no.x); put(qo.ray_oy, wo, no.y); put(qo.ray_oz, wo, no.z);
     put(qo.ray_dx, wo, nd.x); put(qo.ray_dy, wo, nd.y); put(qo.ray_dz, wo, nd.z);
   }
@@ -913,15 +879,11 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
     // the item's rays go out as trace records, at positions given by the item index (REC_BOTH: 2 wo and 2 wo + 1).  A ray the bank's
     // mode has no record for cannot exist (the modes follow the integrator: art_api.cpp); should it ever, the self-check counts it.
     const int mode = qo.rec_mode;
-    if (defer) {
-      defer->alive = alive; defer->shadow = shadow; defer->no = no; defer->nd = nd; defer->so = so; defer->sd = sd; defer->s_tfar = s_tfar; defer->sh_min = sh_min;
-    } else {
-      const int per = (mode == REC_BOTH) ? 2 : 1;
-      const bool blocks = cx.stage_count > 0;      // k_shade_compact: each kind of ray is its own contiguous block of the wave's records
-      if (mode != REC_SHADOW) emit_ray(s, qo, (size_t)wo, rec_slot(mode, wo, false), alive, no, nd, kInfinity, -1.0f, cx, blocks ? cx.stage_item : per * cx.stage_item, 0);
-      ART_TPROBE(cx.tprobe, 76);    // extension ray's record out
-      if (mode != REC_EXT) emit_ray(s, qo, (batch || qo.sh_t) ? (size_t)(kShadowWord | (uint32_t)wo) : so_i, rec_slot(mode, wo, true), shadow, so, sd, s_tfar, qo.shadow_rule ? sh_min : -1.0f, cx, blocks ? cx.stage_item : per * cx.stage_item + (per - 1), 1);
-    }
+    const int per = (mode == REC_BOTH) ? 2 : 1;
+    const bool blocks = cx.stage_count > 0;      // k_shade_compact: each kind of ray is its own contiguous block of the wave's records
+    if (mode != REC_SHADOW) emit_ray(s, qo, (size_t)wo, rec_slot(mode, wo, false), alive, no, nd, kInfinity, -1.0f, cx, blocks ? cx.stage_item : per * cx.stage_item, 0);
+    ART_TPROBE(cx.tprobe, 76);    // extension ray's record out
+    if (mode != REC_EXT) emit_ray(s, qo, (batch || qo.sh_t) ? (size_t)(kShadowWord | (uint32_t)wo) : so_i, rec_slot(mode, wo, true), shadow, so, sd, s_tfar, qo.shadow_rule ? sh_min : -1.0f, cx, blocks ? cx.stage_item : per * cx.stage_item + (per - 1), 1);
     ART_TPROBE(cx.tprobe, 77);      // shadow ray's record out
     if (lost != nullptr && ((mode == REC_SHADOW && alive) || (mode == REC_EXT && shadow))) {
 #if defined(__HIP_DEVICE_COMPILE__)

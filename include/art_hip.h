@@ -232,16 +232,14 @@ int  art_get_stage_stats(ArtStageStats* out);
  * "lds_stack_cap" [0 = automatic];  BVH build (take effect at the next art_upload_scene): "bvh_width" [4] lanes per ray = children
  * per node, 4 or 8;  "bvh_builder" [3] 3 binned SAH on the GPU (the tree of 0, built in milliseconds), 0 binned SAH on the host, 1 LBVH on the GPU, 2 PLOC on the GPU;  "bvh_ploc_radius" [8];  "bvh_spatial_splits" [0];  "bvh_max_leaf" [width];
  * "bvh_leaf_base_milli", "bvh_node_cost_milli", "bvh_tri_cost_milli".  The wavefront stages: "shade_per" [0 = measured; 2 | 4 items per thread],
- * "shade_split" [0], "skip_null_shadow" [0] (1: a shadow ray whose explicit colour is exactly zero under either verdict -- the light sample behind the
+ * "skip_null_shadow" [0] (1: a shadow ray whose explicit colour is exactly zero under either verdict -- the light sample behind the
  * surface, a BxDF that is zero there -- is not traced: the same picture 7-10 % sooner, but fewer rays than the reference issues, integrators.adb:270).  Instanced scenes: "inst_coop" [1] the cooperative kernel crosses the instance boundary (0: one ray per lane, the cross-check);
  * "inst_open" [0] entry points per instance the instance tree ends at (1 whole instances, n > 1 about n subtrees of the mesh's tree per
  * instance, 0 chosen from how much the instances' boxes overlap; takes effect at the next art_upload_scene).  How the path state is mapped
  * (round 6, profiles/r6_bimodal: the shade stage's rate depends on the size of the pieces its 35-74 GB are mapped in; the picture never does):
  * "paths_spread" [-1] chunk size in MB -- the path state as one address range over separately created physical chunks (HIP virtual memory
  * management; falls back to hipMalloc); -1: 64 MB chunks for a path state of 1 GB or more, 0: plain hipMalloc (13-17 % slower stages in
- * about half of the processes); "paths_spread_holes" [0] 1: spacer chunks between the chunks, released after mapping; "paths_contiguous"
- * [0] 1: physically contiguous memory (the slowest and the one deterministic placement: for A/B work on the stage); "hot_pad" [0] items
- * between the fields of a bank's block (a multiple of 64; moves nothing).
+ * about half of the processes).  The options "shade_split", "paths_spread_holes", "paths_contiguous" and "hot_pad" are removed.
  * Device queries: "query_slice" [2^24] rays per slice (112 bytes of scratch per ray of a slice; 1 .. 2^28).
  * Test options: "inject_lost" (the next pass counts one lost path: art_synchronize must fail), "spread_fail_at" (creating that chunk of the
  * path state fails: everything created so far is undone and the path state comes from hipMalloc), "lds_stack_cap". */

@@ -90,6 +90,8 @@ def test_scene_validation_errors_are_reported_without_a_gpu(art):
     p = art.Backend.pass_params()
     assert L.art_render_pass(C.byref(p), None, None, None) != 0 and "no scene" in L.art_last_error().decode()
     assert L.art_set_option(b"no_such_option", 1) != 0 and L.art_set_shard(3, 2, 32) != 0
+    for removed in (b"shade_split", b"paths_contiguous", b"paths_spread_holes", b"hot_pad"):      # retired options are refused, not ignored
+        assert L.art_set_option(removed, 0) != 0 and "unknown option" in L.art_last_error().decode()
 
 
 def test_product_host_layer_builds_the_reference_scene(art):
