@@ -111,6 +111,10 @@ class ArtBvhInfo(C.Structure):
                 ("build_ms", C.c_double)]
 
 
+class ArtRefitInfo(C.Structure):
+    _fields_ = [("refits", C.c_uint64), ("refit_ms", C.c_double), ("plan_ms", C.c_double), ("bad_vertices", C.c_uint64)]
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -119,7 +123,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
     "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -159,6 +163,8 @@ def load_library():
     L.art_trace_rays.argtypes = [f32p, f32p, f32p, C.c_int64, C.POINTER(ArtHit), C.c_int32, C.POINTER(ArtStats)]
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
@@ -404,6 +410,49 @@ class Backend:
         ptr = lambda x: None if x is None else x.data_ptr()
         _check(self.lib.art_occluded_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, out.data_ptr() if n else None, stream))
         return out
+
+    def refit_torch(self, pos, nrm=None, check=True):
+        """Move the vertices of the scene's CLOSEST mesh and refit its tree in place (art_refit_device): pos, nrm float32 [nverts, 3] tensors on
+        the library's GPU, in the vertex order of the uploaded mesh; nrm None keeps the normals.  Enqueued on torch.cuda.current_stream()
+        without waiting for it: work enqueued before sees the old geometry, work enqueued after the new.  The tree keeps its topology.
+        check=True raises ValueError before any launch when a coordinate is not finite or beyond 1e18 in magnitude (or a normal is not
+        finite); that check costs ONE host synchronisation with the stream.  check=False skips it: boxes holding a bad vertex are then
+        emptied on the GPU and the next synchronize fails with the count."""
+        import torch
+        if not isinstance(pos, torch.Tensor) or pos.dim() != 2:
+            raise ArtError("pos: a [nverts, 3] float32 tensor is required")
+        n = pos.shape[0]
+
+        def f32(name, x):
+            if not isinstance(x, torch.Tensor):
+                raise ArtError("%s: a torch tensor is required, not %s" % (name, type(x).__name__))
+            if x.dtype != torch.float32:
+                raise ArtError("%s: dtype must be torch.float32, not %s" % (name, x.dtype))
+            if tuple(x.shape) != (n, 3):
+                raise ArtError("%s: shape %s, expected %s" % (name, tuple(x.shape), (n, 3)))
+            return x.contiguous()
+        p = f32("pos", pos)
+        q = None if nrm is None else f32("nrm", nrm)
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+        dev = p.device
+        for name, x in (("pos", p), ("nrm", q)):
+            if x is not None and (x.device.type != "cuda" or x.device != dev):
+                raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
+        stream = torch.cuda.current_stream(dev)
+        if check and n:
+            with torch.cuda.stream(stream):
+                bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
+                badn = torch.zeros_like(bad) if q is None else (~torch.isfinite(q)).any(dim=1).sum()
+                counts = torch.stack([bad, badn]).tolist()                     # the one host synchronisation
+            if counts[0] or counts[1]:
+                raise ValueError("refit_torch: %d vertex position(s) not finite or beyond 1e18 in magnitude, %d normal(s) not finite" % tuple(counts))
+        _check(self.lib.art_refit_device(p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+
+    def refit_info(self):
+        """ArtRefitInfo: refits, refit_ms (GPU time of device 0's refit kernels), plan_ms, bad_vertices -- cumulative since the upload (waits)"""
+        ri = ArtRefitInfo()
+        _check(self.lib.art_get_refit_info(C.byref(ri)))
+        return ri
 
     def bvh_info(self):
         info = ArtBvhInfo()

@@ -37,6 +37,7 @@ static std::vector<hipEvent_t> g_reduce_events;
 static double g_reduce_ms = 0.0; static int g_reduces = 0, g_reduce_path = 0;
 static bool g_multi_api = false;       // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
 static std::vector<hipEvent_t> g_reduce_free;     // event pairs folded into g_reduce_ms, ready for the next reduce (a host that downloads every frame re-uses two events)
+static ArtRefitInfo g_refit_info = ArtRefitInfo();   // art_get_refit_info: cumulative since the last upload
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
   for (hipEvent_t e : g_reduce_events) (void)hipEventDestroy(e);
@@ -124,6 +125,16 @@ void DevBuf::release() {
     chunks.clear(); reserved = 0; chunk_bytes = 0;
   } else if (p) (void)hipFree(p);
   p = nullptr; bytes = 0;
+}
+
+// the refit plan of a context goes with its scene (upload_scene, shutdown); its events are kept for the next plan
+static void release_refit(Ctx& c) {
+  Ctx::RefitPlan& R = c.refit;
+  R.b_idx.release(); R.b_levels.release(); R.b_tight.release(); R.b_bad.release(); R.b_stage.release();
+  R.level_off.clear();
+  for (hipEvent_t e : R.ev) R.ev_free.push_back(e);
+  R.ev.clear();
+  R.ready = false; R.unread = false; R.bad_last = R.bad_total = 0; R.bad_reported = true;
 }
 
 // `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Ctx::paths_spread_mb: the driver
@@ -224,9 +235,12 @@ int upload_scene(const ArtSceneDesc* d) {
   const std::vector<float> tri9 = std::move(hs.deferred_tri9);                    // option bvh_builder >= 1: every device builds its own tree
   hs.deferred_tri9.clear();
   Dev0Guard guard;
+  g_refit_info = ArtRefitInfo();
   for (int k = 0; k < g_ndev; ++k) {                                              // scene + BVH replicated on every GPU
     if (use_dev(k)) return 1;
     Ctx& c = g_ctx;
+    if (c.refit.ready) HIP_TRY(hipStreamSynchronize(c.stream));                  // (a refit still in flight reads the plan)
+    release_refit(c);
     c.bvh_params = g_devs[0].bvh_params;
     if (ensure_device()) return 1;
     int dev_stack = hs.bvh.max_stack;
@@ -711,6 +725,29 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   return 0;
 }
 
+// the current context's refit event pairs and bad-vertex counters; its stream is idle (a refit on another stream is ordered before the
+// context stream's later work, refit_device)
+static int fold_refit() {
+  Ctx& c = g_ctx;
+  Ctx::RefitPlan& R = c.refit;
+  for (size_t i = 0; i + 1 < R.ev.size(); i += 2) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(R.ev[i + 1]));
+    HIP_TRY(hipEventElapsedTime(&ms, R.ev[i], R.ev[i + 1]));
+    if (&c == &g_devs[0]) g_refit_info.refit_ms += ms;
+    R.ev_free.push_back(R.ev[i]); R.ev_free.push_back(R.ev[i + 1]);
+  }
+  R.ev.clear();
+  if (R.unread && R.b_bad.p) {
+    unsigned long long w[2];
+    HIP_TRY(hipMemcpy(w, R.b_bad.p, sizeof w, hipMemcpyDeviceToHost));
+    R.unread = false;
+    R.bad_last = w[0]; R.bad_total = w[1]; R.bad_reported = (w[0] == 0);
+    if (&c == &g_devs[0]) g_refit_info.bad_vertices = w[1];
+  }
+  return 0;
+}
+
 static int synchronize_one();
 int synchronize() {
   Dev0Guard guard;
@@ -731,6 +768,12 @@ static int synchronize_one() {
   }
   c.pass_events.clear();
   if (collect_timing()) return 1;
+  if (fold_refit()) return 1;
+  if (!c.refit.bad_reported) {            // (reported once per bad refit, like a lost path; the boxes stay empty until a good refit or an upload)
+    c.refit.bad_reported = true;
+    return fail("art_refit_device: " + std::to_string(c.refit.bad_last) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes "
+                "holding them are empty (no ray enters them) until a good refit or art_upload_scene");
+  }
   // a lost path is a wrong picture, not a statistic -- a stage that found a path without an output item, a ray its bank has no
   // record for, a material its instantiation was not compiled for, or a staged trace record that did not name the hit slot its position
   // implies (art_shade.h emit_ray) fails the call that waits for the render
@@ -912,6 +955,10 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
   HIP_TRY(hipStreamSynchronize(c.stream));
   HIP_TRY(hipGetLastError());
   HostScene& hs = c.host_scene;
+  if (hs.m_shade_stale) {                                            // a refit rewrote the normals in HBM (the stream is idle: synchronised above)
+    HIP_TRY(hipMemcpy(hs.m_shade.data(), c.b_m_shade.p, hs.m_shade.size() * sizeof(float), hipMemcpyDeviceToHost));
+    hs.m_shade_stale = false;
+  }
   bind_host_pointers(hs);
   for (size_t i = 0; i < N; ++i) {
     ArtHit& h = out[i];
@@ -1016,6 +1063,155 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
   return rc;
 }
 
+// ---- moving geometry (art_refit_device, art_refit.hip) ----------------------------------------------------------------------------
+// The plan of the current context: its tree's inner nodes grouped by depth (read back from HBM once: the GPU builders leave the tree
+// there only, and every builder orders its nodes differently), the mesh's index triples, the tight-box scratch and the counters.
+static int build_refit_plan(const HostScene& hs) {
+  Ctx& c = g_ctx;
+  Ctx::RefitPlan& R = c.refit;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int W = c.scene.node_width, NF = node_floats(W), N = c.scene.n_nodes;
+  if (N < 1 || !c.b_nodes.p) return fail("art_refit_device: the scene has no tree");
+  std::vector<float> nodes((size_t)N * NF);
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> order;
+  order.reserve((size_t)N);
+  order.push_back(0);
+  R.level_off.assign(1, 0);
+  for (size_t b = 0; b < order.size();) {                       // breadth first: level L = order[level_off[L] .. level_off[L + 1])
+    const size_t e = order.size();
+    for (size_t i = b; i < e; ++i) {
+      const float* nd = &nodes[(size_t)order[i] * NF];
+      for (int j = 0; j < W; ++j) {
+        int32_t ref, cnt;
+        std::memcpy(&ref, nd + 4 * j + 3, 4); std::memcpy(&cnt, nd + 4 * W + 4 * j + 3, 4);
+        if (ref < 0) continue;
+        if (cnt > 0) {
+          if (cnt > kMaxLeafTris || (int64_t)ref + cnt > (int64_t)c.scene.n_tris) return fail("art_refit_device: internal: a leaf outside the triangle records");
+          continue;
+        }
+        if (ref >= N || order.size() >= (size_t)N) return fail("art_refit_device: internal: the uploaded nodes do not form a tree");
+        order.push_back(ref);
+      }
+    }
+    R.level_off.push_back((int)e);
+    b = e;
+  }
+  if (order.size() != (size_t)N) return fail("art_refit_device: internal: unreachable nodes in the uploaded tree");
+  if (upload(R.b_idx, hs.m_idx) || upload(R.b_levels, order) || ensure(R.b_tight, (size_t)N * 6 * sizeof(float)) || ensure(R.b_bad, 2 * sizeof(unsigned long long)))
+    return 1;
+  HIP_TRY(hipMemset(R.b_bad.p, 0, 2 * sizeof(unsigned long long)));
+  if (&c != &g_devs[0]) {
+    if (ensure(R.b_stage, 2 * 12 * (size_t)hs.m_nverts)) return 1;
+    if (!R.done_ev) HIP_TRY(hipEventCreateWithFlags(&R.done_ev, hipEventDisableTiming));
+  } else if (g_ndev > 1 && !R.ready_ev) HIP_TRY(hipEventCreateWithFlags(&R.ready_ev, hipEventDisableTiming));
+  g_refit_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  R.ready = true;
+  return 0;
+}
+
+// the current context's refit on stream s, from positions (and normals) in this context's device memory
+static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hipStream_t s) {
+  Ctx& c = g_ctx;
+  Ctx::RefitPlan& P = c.refit;
+  RefitArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.pos3f = pos; A.nrm3f = nrm; A.idx = (const int32_t*)P.b_idx.p;
+  A.nverts = hs.m_nverts; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.n_recs = c.scene.n_tris;
+  A.tris = (float*)c.b_tris.p; A.qtris = (float*)c.b_qtris.p; A.m_shade = (float*)c.b_m_shade.p;
+  A.bad = (unsigned long long*)P.b_bad.p;
+  A.nodes = (float*)c.b_nodes.p; A.qnodes = (c.scene.node_width == 4) ? (QNode*)c.b_qnodes.p : nullptr;
+  A.tight = (float*)P.b_tight.p;
+  A.width = c.scene.node_width; A.inflate_rel = c.bvh_params.inflate_rel; A.inflate_abs = c.bvh_params.inflate_abs;
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (P.ev_free.size() >= 2) { e1 = P.ev_free.back(); P.ev_free.pop_back(); e0 = P.ev_free.back(); P.ev_free.pop_back(); }
+  else {
+    HIP_TRY(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
+  }
+  if (hipEventRecord(e0, s) != hipSuccess) { P.ev_free.push_back(e0); P.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
+  P.ev.push_back(e0); P.ev.push_back(e1);
+  struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop{e1, s};      // recorded on every way out
+  P.unread = true;
+  HIP_TRY(hipMemsetAsync(A.bad, 0, sizeof(unsigned long long), s));      // [0]: this refit's bad vertices ([1] counts since the upload)
+  launch_refit_tris(s, A);
+  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                 // deepest level first
+    launch_refit_level(s, A, (const int32_t*)P.b_levels.p + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(std::string("art_refit_device: kernel launch failed: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// Every check comes before the first launch.  Device 0 refits on the caller's stream, ordered against its context stream with the
+// query events; every other context waits for the caller's stream, copies the positions (and normals) from device 0 and refits on its
+// own stream, and the caller's stream waits for it -- so the caller may overwrite its buffers after whatever it enqueues next.
+int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail("art_refit_device: no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (c0.scene.n_inst > 0) return fail("art_refit_device: the scene is instanced (n_instances > 0); only the tree of a flat CLOSEST mesh is refitted");
+  if (hs.m_nverts == 0) return fail("art_refit_device: the scene has no ART_MESH_CLOSEST mesh");
+  if (hs.gcore_seam) return fail("art_refit_device: the scene was committed through gcore_commit_scene, whose host copy of the tree a refit would leave stale");
+  if (nverts != hs.m_nverts) return fail("art_refit_device: nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.m_nverts));
+  if (!pos) return fail("art_refit_device: null pos3f");
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const size_t bytes = 12 * (size_t)nverts;
+  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (!g_ctx.refit.ready && build_refit_plan(hs)) return 1;
+  }
+  if (use_dev(0)) return 1;
+  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
+  const bool other = (qs != c0.stream);
+  if (other) {
+    for (hipEvent_t& e : c0.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c0.q_ev[0], c0.stream));
+    HIP_TRY(hipStreamWaitEvent(qs, c0.q_ev[0], 0));
+  }
+  // from here on the tree in HBM changes: the host copies of it (art_export_bvh's cache, a host-built tree) and of the positions are stale
+  std::vector<float>().swap(hs.bvh.nodes); std::vector<float>().swap(hs.bvh.tris); std::vector<uint32_t>().swap(hs.bvh.qnodes);
+  std::vector<float>().swap(hs.m_pos);
+  hs.refitted = true;
+  if (nrm) hs.m_shade_stale = true;                                      // (art_trace_rays reads the shading records on the host)
+  g_refit_info.refits += 1;
+  int rc = 0;
+  if (g_ndev > 1 && hipEventRecord(c0.refit.ready_ev, qs) != hipSuccess) rc = fail("art_refit_device: hipEventRecord failed");
+  if (!rc) rc = refit_one(hs, pos, nrm, qs);
+  for (int k = 1; k < g_ndev && !rc; ++k) {
+    if (use_dev(k)) { rc = 1; break; }
+    Ctx& c = g_ctx;
+    float* sp = (float*)c.refit.b_stage.p;
+    float* sn = nrm ? sp + 3 * (size_t)nverts : nullptr;
+    if (hipStreamWaitEvent(c.stream, c0.refit.ready_ev, 0) != hipSuccess || hipMemcpyPeerAsync(sp, c.device, pos, c0.device, bytes, c.stream) != hipSuccess ||
+        (nrm && hipMemcpyPeerAsync(sn, c.device, nrm, c0.device, bytes, c.stream) != hipSuccess)) { rc = fail("art_refit_device: copy to device " + std::to_string(c.device) + " failed"); break; }
+    rc = refit_one(hs, sp, sn, c.stream);
+    if (hipEventRecord(c.refit.done_ev, c.stream) != hipSuccess || hipStreamWaitEvent(qs, c.refit.done_ev, 0) != hipSuccess) rc = rc ? rc : fail("art_refit_device: event ordering failed");
+  }
+  if (use_dev(0)) return 1;
+  if (other) {                          // (also after a failure: what was enqueued stays ordered before the context stream's next work)
+    HIP_TRY(hipEventRecord(c0.q_ev[1], qs));
+    HIP_TRY(hipStreamWaitEvent(c0.stream, c0.q_ev[1], 0));
+  }
+  return rc;
+}
+
+// cumulative since the upload; waits for every context's stream (a refit on the caller's stream is ordered before it)
+int get_refit_info(ArtRefitInfo* out) {
+  if (!out) return fail("null ArtRefitInfo");
+  Dev0Guard guard;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (!g_ctx.device_ready) continue;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    if (fold_refit()) return 1;
+  }
+  *out = g_refit_info;
+  return 0;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) reset_reduce_info();
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -1039,6 +1235,10 @@ void shutdown() {
     for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : c.pass_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
+    release_refit(c);
+    for (hipEvent_t e : c.refit.ev_free) (void)hipEventDestroy(e);
+    if (c.refit.ready_ev) (void)hipEventDestroy(c.refit.ready_ev);
+    if (c.refit.done_ev) (void)hipEventDestroy(c.refit.done_ev);
     for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
     c.b_reduced.release();
     if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
@@ -1180,12 +1380,20 @@ int art_occluded_rays_device(const float* origins3f, const float* dirs3f, const 
   return query_rays(origins3f, dirs3f, tnear, tfar, n, nullptr, occluded_out, TRACE_COOP, (hipStream_t)hip_stream);
 }
 
+int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return refit_device(pos3f, nrm3f, nverts, (hipStream_t)hip_stream);
+}
+
+int art_get_refit_info(ArtRefitInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_refit_info(out); }
+
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (!g_ctx.scene_ready) return fail("no scene uploaded");
   Bvh8& b = g_ctx.host_scene.bvh;
   if (g_ctx.scene.n_inst > 0 && (nodes || tris)) return fail("art_export_bvh: an instanced scene has a two-level tree; only its sizes are reported (ArtBvhInfo)");
-  if (g_ctx.host_scene.gpu_built && b.nodes.empty() && (nodes || tris)) {     // the GPU-built tree is fetched on first request
+  if (g_ctx.host_scene.tree_in_hbm_only() && b.nodes.empty() && (nodes || tris)) {     // a GPU-built or refitted tree is fetched on first request
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));                                         // (a refit on another stream is ordered before it)
     b.nodes.resize((size_t)b.n_nodes * node_floats(b.width)); b.tris.resize((size_t)b.n_tris * kTriFloats);
     HIP_TRY(hipMemcpy(b.nodes.data(), g_ctx.b_nodes.p, b.nodes.size() * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(b.tris.data(), g_ctx.b_tris.p, b.tris.size() * 4, hipMemcpyDeviceToHost));
@@ -1204,9 +1412,10 @@ int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& wid
   if (!c.scene_ready) return fail("no scene uploaded");
   Bvh8& b = c.host_scene.bvh;
   width = b.width; n_tris = b.n_tris;
-  if (c.host_scene.gpu_built && b.nodes.empty()) {
+  if (c.host_scene.tree_in_hbm_only() && b.nodes.empty()) {
     nodes.resize((size_t)b.n_nodes * node_floats(b.width)); tris.resize((size_t)b.n_tris * kTriFloats);
     if (use_dev(0)) return 1;
+    HIP_TRY(hipStreamSynchronize(c.stream));
     HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(tris.data(), c.b_tris.p, tris.size() * 4, hipMemcpyDeviceToHost));
   } else { nodes = b.nodes; tris = b.tris; }

@@ -41,6 +41,18 @@ struct Ctx {
   DevBuf b_accum, b_screen, b_stage, b_pixmap, b_paths, b_rays, b_ids, b_queue, b_ovf;
   DevBuf b_query;                              // device-resident ray queries: SoA rays + shadow minima + hit records of one slice, and a counter sink
   hipEvent_t q_ev[2] = {nullptr, nullptr};     // ... their ordering with the context stream when they run on another stream (library -> query, query -> library)
+  // art_refit_device (art_refit.hip): the plan is built on the first refit after an upload (the upload drops it); per context, because
+  // the GPU builders may number the nodes differently on every device
+  struct RefitPlan {
+    bool ready = false;
+    DevBuf b_idx, b_levels, b_tight, b_bad, b_stage;   // index triples | node ids level by level, root first | tight box per node (24 B) | bad-vertex counters | contexts k > 0: peer copy of pos (+ nrm)
+    std::vector<int> level_off;                        // level L: b_levels[level_off[L] .. level_off[L + 1])
+    std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's refit kernels: not yet folded / free for reuse
+    hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // device 0: the caller's positions are ready (contexts k > 0 wait for it); k > 0: this context's refit is done
+    bool unread = false;                               // a refit was enqueued whose bad-vertex count no fold has read yet
+    uint64_t bad_last = 0, bad_total = 0;              // bad vertices of the last refit read / since the upload
+    bool bad_reported = true;                          // the last refit's bad vertices were reported by a synchronize (or there were none)
+  } refit;
   int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
@@ -115,6 +127,8 @@ int resize(int w, int h);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 void shutdown();
+int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
+int get_refit_info(ArtRefitInfo* out);
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 
 }  // namespace art

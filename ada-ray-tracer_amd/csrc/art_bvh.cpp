@@ -245,9 +245,6 @@ struct Builder {
   }
 };
 
-inline float next_down(float v) { return std::nextafterf(v, -INFINITY); }
-inline float next_up(float v) { return std::nextafterf(v, INFINITY); }
-
 }  // namespace
 
 bool build_bvh8(const float* tri9, const int32_t* prim_ids, int32_t n, const BvhBuildParams& prm, Bvh8& out, std::string& err) {
@@ -379,11 +376,7 @@ bool build_bvh8(const float* tri9, const int32_t* prim_ids, int32_t n, const Bvh
       float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
       if (j < nch) {
         const Node2& c = B.nodes[ch[j]];
-        for (int a = 0; a < 3; ++a) {
-          const float m = std::max(std::fabs(c.box.lo[a]), std::fabs(c.box.hi[a]));
-          const float pad = inflate_abs + inflate_rel * m;
-          lo[a] = next_down(c.box.lo[a] - pad); hi[a] = next_up(c.box.hi[a] + pad);
-        }
+        pad_child_box(c.box.lo, c.box.hi, inflate_rel, inflate_abs, lo, hi);
         if (c.count > 0) { ref = emit_leaf_tris(c); cnt = c.count; }
         else {
           ref = new_node8(); cnt = 0;

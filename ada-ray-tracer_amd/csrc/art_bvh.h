@@ -48,6 +48,19 @@ struct Bvh8 {
   int32_t max_stack = 1;         // worst-case traversal stack entries for this tree
 };
 
+// The child-box rule of every builder (build_bvh8 below, k_col_emit of art_sah.hip, k_collapse of art_lbvh.hip) and of the refit (art_refit.hip):
+// the tight box l..h of the child's triangles, padded per axis by inflate_abs + inflate_rel * max(|l|, |h|) and then moved one ulp outward.
+// Host and device evaluate the same binary32 operations (-ffp-contract=off), so a refit of an unmoved mesh reproduces the built boxes bit
+// for bit.  Finite input only.
+ART_HD float box_next_dn(float v) { return (v == 0.0f) ? -1.401298464e-45f : __builtin_bit_cast(float, __builtin_bit_cast(int32_t, v) + (v > 0.0f ? -1 : 1)); }
+ART_HD float box_next_up(float v) { return (v == 0.0f) ? 1.401298464e-45f : __builtin_bit_cast(float, __builtin_bit_cast(int32_t, v) + (v > 0.0f ? 1 : -1)); }
+ART_HD void pad_child_box(const float l[3], const float h[3], float inflate_rel, float inflate_abs, float lo[3], float hi[3]) {
+  for (int a = 0; a < 3; ++a) {
+    const float pad = inflate_abs + inflate_rel * fmaxf(fabsf(l[a]), fabsf(h[a]));
+    lo[a] = box_next_dn(l[a] - pad); hi[a] = box_next_up(h[a] + pad);
+  }
+}
+
 // tri9: 9 floats per triangle (A,B,C); prim_ids: id written into each triangle record (nullptr = 0..n-1)
 bool build_bvh8(const float* tri9, const int32_t* prim_ids, int32_t n, const BvhBuildParams& prm, Bvh8& out, std::string& err);
 

@@ -138,6 +138,7 @@ bool flatten_scene(const ArtSceneDesc& d, const BvhBuildParams& bp, HostScene& o
       if (!m.matid) { err = "scene: CLOSEST mesh needs material_ids"; return false; }
       for (int i = 0; i < m.ntris; ++i) if (!mat_ok(m.matid[i])) { err = "scene: triangle material id out of range"; return false; }
       out.m_pos.assign(m.pos, m.pos + 3 * (size_t)m.nverts);
+      out.m_idx.assign(m.idx, m.idx + 3 * (size_t)m.ntris); out.m_nverts = m.nverts;
       out.m_shade.assign((size_t)kTriShadeFloats * (size_t)m.ntris, 0.0f);        // texcoords are zeroed by the reference's loader and never read
       for (int i = 0; i < m.ntris; ++i) {
         float* r = &out.m_shade[(size_t)kTriShadeFloats * (size_t)i];

@@ -19,10 +19,15 @@ struct HostScene {
   int32_t bf_ntris = 0;
   // closest-hit mesh
   std::vector<float> m_shade;   // kTriShadeFloats per triangle: vertex normals of A, B, C and the material id (art_scene.h)
-  std::vector<float> m_pos;   // kept for gcore-style geometric normals / export
+  std::vector<float> m_pos;   // the uploaded vertex positions (nothing in the library reads them back; art_refit_device empties them: they would be stale)
+  std::vector<int32_t> m_idx; int64_t m_nverts = 0;   // index triples and vertex count of the CLOSEST mesh: what art_refit_device gathers through (copied to HBM on the first refit)
   Bvh8 bvh;
   std::vector<float> deferred_tri9;   // builder == 1: triangle corners for the GPU build (bvh stays empty until then)
   bool gpu_built = false;             // nodes / tris live only in HBM (art_export_bvh copies them back on demand)
+  bool refitted = false;              // art_refit_device moved the tree's boxes: the HBM copy is the only current one, whichever builder made it
+  bool m_shade_stale = false;         // art_refit_device rewrote the normals in HBM: art_trace_rays copies m_shade back before it reads it
+  bool gcore_seam = false;           // committed by gcore_commit_scene (which keeps its own host copy of the tree: not refittable)
+  bool tree_in_hbm_only() const { return gpu_built || refitted; }
   double bvh_build_ms = 0.0;
   // instanced scene (ArtSceneDesc::n_instances > 0): m_shade then holds the MESHES' records (object-space normals), one block per mesh
   TwoLevelHost two; std::vector<DevInstance> inst;

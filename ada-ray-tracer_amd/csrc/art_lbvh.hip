@@ -255,9 +255,6 @@ __global__ __launch_bounds__(256) void k_ploc_number_nodes(PlocOut O, const int*
 
 struct Item { int n2, n8, stack_before; };
 
-__device__ __forceinline__ float next_dn(float v) { return (v == 0.0f) ? -1.401298464e-45f : __int_as_float(__float_as_int(v) + (v > 0.0f ? -1 : 1)); }
-__device__ __forceinline__ float next_up(float v) { return (v == 0.0f) ? 1.401298464e-45f : __int_as_float(__float_as_int(v) + (v > 0.0f ? 1 : -1)); }
-
 // node_cap: capacity of `nodes` in wide nodes.  A child that would need node >= node_cap is written as an empty slot and *overflow is set
 // (the host then fails the build): the kernel never writes outside its allocation.
 __global__ __launch_bounds__(128) void k_collapse(Lbvh T, const Item* __restrict__ in, int n_in, Item* __restrict__ out, int* out_count, int* node_count,
@@ -298,10 +295,7 @@ __global__ __launch_bounds__(128) void k_collapse(Lbvh T, const Item* __restrict
       const int id = ch[j];
       const float4 l4 = lo_of(id), h4 = hi_of(id);
       const float l[3] = {l4.x, l4.y, l4.z}, h[3] = {h4.x, h4.y, h4.z};
-      for (int a = 0; a < 3; ++a) {
-        const float pad = inflate_abs + inflate_rel * fmaxf(fabsf(l[a]), fabsf(h[a]));
-        lo[a] = next_dn(l[a] - pad); hi[a] = next_up(h[a] + pad);
-      }
+      pad_child_box(l, h, inflate_rel, inflate_abs, lo, hi);
       const int c = count_of(id);
       if (c <= max_leaf) { ref = first_of(id); cnt = c; }
       else {

@@ -457,9 +457,6 @@ __global__ __launch_bounds__(128) void k_col_pick(Nodes N, const Item* __restric
   kids[q] = K; n_inner[q] = K.n_inner;
 }
 
-__device__ __forceinline__ float next_dn(float v) { return (v == 0.0f) ? -1.401298464e-45f : __int_as_float(__float_as_int(v) + (v > 0.0f ? -1 : 1)); }
-__device__ __forceinline__ float next_up(float v) { return (v == 0.0f) ? 1.401298464e-45f : __int_as_float(__float_as_int(v) + (v > 0.0f ? 1 : -1)); }
-
 __global__ __launch_bounds__(128) void k_col_emit(Nodes N, const Item* __restrict__ items, int n_items, int width, const Kids* __restrict__ kids, const int* __restrict__ off,
                                                   int next_base, Item* __restrict__ next_items, int* max_stack, float* __restrict__ nodes,
                                                   float inflate_rel, float inflate_abs) {
@@ -479,10 +476,7 @@ __global__ __launch_bounds__(128) void k_col_emit(Nodes N, const Item* __restric
       const int id = K.ch[j];
       const int4 l4 = N.blo[id], h4 = N.bhi[id];
       const float l[3] = {dec(l4.x), dec(l4.y), dec(l4.z)}, h[3] = {dec(h4.x), dec(h4.y), dec(h4.z)};
-      for (int a = 0; a < 3; ++a) {
-        const float pad = inflate_abs + inflate_rel * fmaxf(fabsf(l[a]), fabsf(h[a]));
-        lo[a] = next_dn(l[a] - pad); hi[a] = next_up(h[a] + pad);
-      }
+      pad_child_box(l, h, inflate_rel, inflate_abs, lo, hi);
       if (N.child[id].x < 0) { ref = l4.w; cnt = h4.w; }                           // leaf: first reference position = first triangle record
       else {
         const int slot = off[q] + inner_k; ++inner_k;

@@ -199,6 +199,7 @@ void gcore_commit_scene(void) {
   sd.n_lights = 1; sd.lights = &light; sd.n_materials = 1; sd.materials = &mat; sd.n_meshes = 1; sd.meshes = &mesh;
   sd.cam_matrix[0] = sd.cam_matrix[5] = sd.cam_matrix[10] = sd.cam_matrix[15] = 1.0f;
   if (art::upload_scene(&sd)) { std::printf("[c_gcore]: %s\n", art_last_error()); return; }
+  art::g_devs[0].host_scene.gcore_seam = true;        // (art_refit_device refuses it: h_nodes below would go stale)
   g.h_nodes.clear(); g.h_tris.clear(); g_h_ready = false;
   g.committed = true;
 }

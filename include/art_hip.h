@@ -215,6 +215,23 @@ int  art_trace_rays_device(const float* origins3f, const float* dirs3f, const fl
 int  art_occluded_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n,
                               uint8_t* occluded_out, void* hip_stream);
 
+/* Moving geometry.  Moves the vertices of the scene's ART_MESH_CLOSEST mesh and refits its tree in place: same
+ * topology, same leaf order, new boxes (the builders' padding rule, quantised again at width 4), for every builder and both widths.
+ * pos3f: device memory, 3*nverts floats, in the vertex order of the ArtMesh.pos uploaded; nrm3f: the same for normals, or NULL = keep
+ * them.  Material ids stay.  Stream-ordered like art_trace_rays_device (NULL = the library's stream; hipStreamLegacy: the null stream):
+ * work enqueued before the call sees the old geometry, work enqueued after it the new; the host waits only on the first call after an
+ * upload, which builds the refit plan (the nodes grouped by depth) and its scratch.  Under art_init_devices every context is refitted,
+ * the others from a peer copy of pos3f / nrm3f (device 0 memory).  Refused before anything is launched: no scene, an instanced scene,
+ * no CLOSEST mesh, a scene committed through gcore_commit_scene, nverts other than the uploaded count, host memory or another device's
+ * memory.  A vertex coordinate that is not finite or whose magnitude exceeds 1e18 empties every box holding it (no ray enters it) and
+ * makes the next art_synchronize fail with the count; a later good refit or an upload clears that state.  The tree keeps the topology
+ * it was built with: after large deformations traversal costs more, and art_upload_scene builds a new tree. */
+int  art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream);
+/* Cumulative since art_upload_scene (waits for the refits enqueued so far): refit_ms = HIP events around device 0's refit kernels,
+ * plan_ms = host time of building the refit plans, bad_vertices = bad vertex coordinates counted on device 0 over all refits. */
+typedef struct ArtRefitInfo { uint64_t refits; double refit_ms; double plan_ms; uint64_t bad_vertices; } ArtRefitInfo;
+int  art_get_refit_info(ArtRefitInfo* out);
+
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 int  art_get_stats(ArtStats* out);
 /* The wavefront stages around the trace kernel (device 0, cumulative since art_resize; cooperative schedule): GPU time per kind of
