@@ -115,6 +115,14 @@ class ArtRefitInfo(C.Structure):
     _fields_ = [("refits", C.c_uint64), ("refit_ms", C.c_double), ("plan_ms", C.c_double), ("bad_vertices", C.c_uint64)]
 
 
+class ArtRebuildInfo(C.Structure):
+    _fields_ = [("rebuilds", C.c_uint64), ("gather_ms", C.c_double), ("build_ms", C.c_double), ("host_ms", C.c_double)]
+
+
+class ArtTreeCost(C.Structure):
+    _fields_ = [("root_area", C.c_double), ("node_visits", C.c_double), ("leaf_visits", C.c_double), ("tri_tests", C.c_double)]
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -124,6 +132,7 @@ EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
+    "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost",
     "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -165,6 +174,9 @@ def load_library():
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
+    L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.art_get_rebuild_info.argtypes = [C.POINTER(ArtRebuildInfo)]
+    L.art_get_tree_cost.argtypes = [C.POINTER(ArtTreeCost)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
@@ -411,13 +423,8 @@ class Backend:
         _check(self.lib.art_occluded_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, out.data_ptr() if n else None, stream))
         return out
 
-    def refit_torch(self, pos, nrm=None, check=True):
-        """Move the vertices of the scene's CLOSEST mesh and refit its tree in place (art_refit_device): pos, nrm float32 [nverts, 3] tensors on
-        the library's GPU, in the vertex order of the uploaded mesh; nrm None keeps the normals.  Enqueued on torch.cuda.current_stream()
-        without waiting for it: work enqueued before sees the old geometry, work enqueued after the new.  The tree keeps its topology.
-        check=True raises ValueError before any launch when a coordinate is not finite or beyond 1e18 in magnitude (or a normal is not
-        finite); that check costs ONE host synchronisation with the stream.  check=False skips it: boxes holding a bad vertex are then
-        emptied on the GPU and the next synchronize fails with the count."""
+    def _vertex_tensors(self, pos, nrm):
+        """Validated, contiguous vertex tensors of refit_torch / rebuild_torch, and torch's current stream of their device."""
         import torch
         if not isinstance(pos, torch.Tensor) or pos.dim() != 2:
             raise ArtError("pos: a [nverts, 3] float32 tensor is required")
@@ -438,7 +445,16 @@ class Backend:
         for name, x in (("pos", p), ("nrm", q)):
             if x is not None and (x.device.type != "cuda" or x.device != dev):
                 raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
-        stream = torch.cuda.current_stream(dev)
+        return torch, p, q, n, torch.cuda.current_stream(dev)
+
+    def refit_torch(self, pos, nrm=None, check=True):
+        """Move the vertices of the scene's CLOSEST mesh and refit its tree in place (art_refit_device): pos, nrm float32 [nverts, 3] tensors on
+        the library's GPU, in the vertex order of the uploaded mesh; nrm None keeps the normals.  Enqueued on torch.cuda.current_stream()
+        without waiting for it: work enqueued before sees the old geometry, work enqueued after the new.  The tree keeps its topology.
+        check=True raises ValueError before any launch when a coordinate is not finite or beyond 1e18 in magnitude (or a normal is not
+        finite); that check costs ONE host synchronisation with the stream.  check=False skips it: boxes holding a bad vertex are then
+        emptied on the GPU and the next synchronize fails with the count."""
+        torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
         if check and n:
             with torch.cuda.stream(stream):
                 bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
@@ -453,6 +469,27 @@ class Backend:
         ri = ArtRefitInfo()
         _check(self.lib.art_get_refit_info(C.byref(ri)))
         return ri
+
+    def rebuild_torch(self, pos, nrm=None):
+        """Build a new tree for the scene's CLOSEST mesh at new vertex positions, on the GPU (art_rebuild_device): the tree the next
+        upload_scene of the moved mesh would build under the options as they stand.  pos, nrm as for refit_torch; enqueued on
+        torch.cuda.current_stream(), but unlike a refit the call returns only when the tree is committed (the builders read counts
+        back).  A bad vertex (not finite, beyond 1e18) fails the call with the count and leaves the scene unchanged."""
+        torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
+        _check(self.lib.art_rebuild_device(p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+
+    def rebuild_info(self):
+        """ArtRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
+        ri = ArtRebuildInfo()
+        _check(self.lib.art_get_rebuild_info(C.byref(ri)))
+        return ri
+
+    def tree_cost(self):
+        """ArtTreeCost of the tree in HBM (device 0; waits): root_area and the surface-area expectation of node visits, leaf visits and
+        triangle tests per line through the root.  Compare a refitted tree's figure with a rebuilt one's to decide when to rebuild."""
+        tc = ArtTreeCost()
+        _check(self.lib.art_get_tree_cost(C.byref(tc)))
+        return tc
 
     def bvh_info(self):
         info = ArtBvhInfo()

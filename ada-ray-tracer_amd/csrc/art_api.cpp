@@ -38,6 +38,7 @@ static double g_reduce_ms = 0.0; static int g_reduces = 0, g_reduce_path = 0;
 static bool g_multi_api = false;       // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
 static std::vector<hipEvent_t> g_reduce_free;     // event pairs folded into g_reduce_ms, ready for the next reduce (a host that downloads every frame re-uses two events)
 static ArtRefitInfo g_refit_info = ArtRefitInfo();   // art_get_refit_info: cumulative since the last upload
+static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
   for (hipEvent_t e : g_reduce_events) (void)hipEventDestroy(e);
@@ -227,6 +228,17 @@ static int upload_scene_arrays(HostScene& hs) {
   return 0;
 }
 
+// What the trace kernels can address and walk (art_upload_scene, art_rebuild_device): nodes and triangles by 32-bit byte offsets (the
+// 4-wide entry word keeps bit 31 for the leaf flag), quantised nodes for a 4-wide tree built on the GPU, at most kStackEntries on the stack.
+static int check_tree_limits(int width, int64_t n_nodes, int64_t n_tris, bool flat, bool gpu_built, bool have_qnodes, int stack) {
+  const uint64_t off_limit = (width == 4) ? (1ull << 31) : (1ull << 32);
+  if (flat && ((uint64_t)n_nodes * node_floats(width) * 4 >= (1ull << 32) || (uint64_t)n_tris * (width == 4 ? kQTriBytes : kTriBytes) >= off_limit))
+    return fail("mesh too large: the trace kernel addresses nodes and triangles with 32-bit byte offsets (max ~33M triangles at width 4, ~89M at width 8)");
+  if (width == 4 && n_nodes > 0 && gpu_built && !have_qnodes) return fail("internal: GPU build returned no quantised nodes");
+  if (stack > kStackEntries) return fail("BVH traversal stack bound " + std::to_string(stack) + " exceeds " + std::to_string(kStackEntries));
+  return 0;
+}
+
 int upload_scene(const ArtSceneDesc* d) {
   if (!d) return fail("art_upload_scene: null scene");
   std::string err;
@@ -235,7 +247,7 @@ int upload_scene(const ArtSceneDesc* d) {
   const std::vector<float> tri9 = std::move(hs.deferred_tri9);                    // option bvh_builder >= 1: every device builds its own tree
   hs.deferred_tri9.clear();
   Dev0Guard guard;
-  g_refit_info = ArtRefitInfo();
+  g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo();
   for (int k = 0; k < g_ndev; ++k) {                                              // scene + BVH replicated on every GPU
     if (use_dev(k)) return 1;
     Ctx& c = g_ctx;
@@ -263,12 +275,7 @@ int upload_scene(const ArtSceneDesc* d) {
       }
       hs.hdr.n_nodes = g.n_nodes; hs.hdr.n_tris = g.n_tris;                       // node numbering may differ between devices (atomics), sizes do not
     }
-    // the trace kernel addresses nodes and triangles with 32-bit byte offsets; the 4-wide entry word keeps bit 31 for the leaf flag
-    const uint64_t off_limit = (hs.hdr.node_width == 4) ? (1ull << 31) : (1ull << 32);
-    if (hs.hdr.n_inst == 0 && ((uint64_t)hs.hdr.n_nodes * node_floats(hs.hdr.node_width) * 4 >= (1ull << 32) || (uint64_t)hs.hdr.n_tris * (hs.hdr.node_width == 4 ? kQTriBytes : kTriBytes) >= off_limit)
-        )  return fail("mesh too large: the trace kernel addresses nodes and triangles with 32-bit byte offsets (max ~33M triangles at width 4, ~89M at width 8)");
-    if (hs.hdr.node_width == 4 && hs.hdr.n_nodes > 0 && hs.gpu_built && !c.b_qnodes.p) return fail("internal: GPU build returned no quantised nodes");
-    if (dev_stack > kStackEntries) return fail("BVH traversal stack bound " + std::to_string(dev_stack) + " exceeds " + std::to_string(kStackEntries));
+    if (check_tree_limits(hs.hdr.node_width, hs.hdr.n_nodes, hs.hdr.n_tris, hs.hdr.n_inst == 0, hs.gpu_built, c.b_qnodes.p != nullptr, dev_stack)) return 1;
     if (upload_scene_arrays(hs)) return 1;
     c.b_qtris.release();
     if (hs.hdr.node_width == 4 && hs.hdr.n_tris > 0 && hs.hdr.n_inst == 0) {       // 64-byte padded copy of the triangle records for the 4-wide kernel
@@ -1198,6 +1205,194 @@ int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t
   return rc;
 }
 
+// ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
+// What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
+// anywhere leaves every context's scene as it was.
+struct PendingTree {
+  int device = -1; GpuBvh g; DevBuf qtris;
+  DevBuf idx;                                  // the mesh's index triples where no refit plan held them (or, after the commit, the plan's)
+  ~PendingTree() {
+    if (device >= 0) (void)hipSetDevice(device);
+    if (g.nodes) (void)hipFree(g.nodes);
+    if (g.tris) (void)hipFree(g.tris);
+    if (g.qnodes) (void)hipFree(g.qnodes);
+    qtris.release(); idx.release();
+  }
+};
+
+// the current context's new tree on stream s, from positions in this context's device memory: gather, count the bad vertices, build,
+// check, pad.  Returns with s idle.  Nothing of the context's scene is touched.
+static int rebuild_one(const HostScene& hs, const BvhBuildParams& bp, const float* pos, hipStream_t s, PendingTree& out, float* gather_ms) {
+  Ctx& c = g_ctx;
+  const int32_t n_prims = (int32_t)(hs.m_idx.size() / 3);
+  DevBuf t9, bad;
+  struct Free { DevBuf &a, &b; ~Free() { a.release(); b.release(); } } fr{t9, bad};
+  out.device = c.device;
+  const int32_t* idx = (const int32_t*)c.refit.b_idx.p;                   // the refit plan keeps the index triples in HBM
+  if (!c.refit.ready || !idx) { if (upload(out.idx, hs.m_idx)) return 1; idx = (const int32_t*)out.idx.p; }
+  if (ensure(t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(bad, sizeof(unsigned long long))) return 1;
+  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
+  GatherArgs G;
+  G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)t9.p; G.bad = (unsigned long long*)bad.p;
+  HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
+  HIP_TRY(hipEventRecord(ev.a, s));
+  launch_gather_tri9(s, G);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.b, s));
+  unsigned long long n_bad = 0;
+  HIP_TRY(hipMemcpyAsync(&n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (gather_ms) HIP_TRY(hipEventElapsedTime(gather_ms, ev.a, ev.b));
+  if (n_bad) return fail("art_rebuild_device: " + std::to_string(n_bad) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
+  std::string err;
+  if (!build_bvh8_gpu((const float*)t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
+  if (check_tree_limits(bp.width, out.g.n_nodes, out.g.n_tris, true, true, out.g.qnodes != nullptr, out.g.max_stack)) return 1;
+  if (bp.width == 4) {                                                    // 64-byte padded copy of the triangle records for the 4-wide kernel
+    if (ensure(out.qtris, (size_t)out.g.n_tris * kQTriBytes)) return 1;
+    launch_pad_tris(s, out.g.tris, (float*)out.qtris.p, out.g.n_tris);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The current context takes its new tree (its streams are idle, its refit events are folded).  The one step that can fail, the copy
+// of the new header to d_scene, comes first: when it does (a lost device), the context's buffers are still the old ones.
+static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
+  Ctx& c = g_ctx;
+  {
+    DevScene s = c.scene;
+    s.nodes = t.g.nodes; s.tris = t.g.tris; s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
+    HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
+  }
+  if (!t.idx.p) { t.idx = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
+  release_refit(c);                                                       // the next refit plans against the new tree
+  c.bvh_params = g_devs[0].bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
+  c.b_nodes.release(); c.b_qnodes.release(); c.b_tris.release(); c.b_qtris.release();
+  GpuBvh& g = t.g;
+  c.b_nodes.p = g.nodes; c.b_nodes.bytes = (size_t)g.n_nodes * node_floats(bp.width) * 4;
+  c.b_qnodes.p = g.qnodes; c.b_qnodes.bytes = g.qnodes ? (size_t)g.n_nodes * kQNodeBytes : 0;
+  c.b_tris.p = g.tris; c.b_tris.bytes = (size_t)g.n_tris * kTriFloats * 4;
+  c.b_qtris = t.qtris;
+  g.nodes = nullptr; g.qnodes = nullptr; g.tris = nullptr; t.qtris = DevBuf();      // (owned by the context now)
+  DevScene& s = c.scene;
+  s.nodes = (const float*)c.b_nodes.p; s.tris = (const float*)c.b_tris.p;
+  s.n_nodes = g.n_nodes; s.n_tris = g.n_tris; s.node_width = bp.width;
+  c.bvh_stack_bound = std::max(8, g.max_stack);
+  c.blocks_per_cu = 0;   // re-query occupancy
+  return 0;
+}
+
+// Every check comes before the first launch; every context builds into new buffers before any context's scene changes.
+int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail("art_rebuild_device: no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (c0.scene.n_inst > 0) return fail("art_rebuild_device: the scene is instanced (n_instances > 0); only the tree of a flat CLOSEST mesh is rebuilt");
+  if (hs.m_nverts == 0) return fail("art_rebuild_device: the scene has no ART_MESH_CLOSEST mesh");
+  if (hs.gcore_seam) return fail("art_rebuild_device: the scene was committed through gcore_commit_scene, whose host copy of the tree a rebuild would leave stale");
+  if (nverts != hs.m_nverts) return fail("art_rebuild_device: nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.m_nverts));
+  if (!pos) return fail("art_rebuild_device: null pos3f");
+  BvhBuildParams bp = c0.bvh_params;
+  if (bp.spatial_alpha >= 0.0f) return fail("art_rebuild_device: option bvh_spatial_splits is set; reference splitting exists in the host builder only (art_upload_scene builds that tree)");
+  if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
+  if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const size_t bytes = 12 * (size_t)nverts;
+  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
+  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
+  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  }
+  if (use_dev(0)) return 1;
+  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
+  std::vector<PendingTree> built((size_t)g_ndev);
+  std::vector<DevBuf> stage((size_t)g_ndev);                              // contexts k > 0: peer copy of pos (+ nrm)
+  struct FreeStage { std::vector<DevBuf>& v; ~FreeStage() { for (size_t k = 0; k < v.size(); ++k) { if (v[k].p && g_devs[k].device >= 0) (void)hipSetDevice(g_devs[k].device); v[k].release(); } } } fs{stage};
+  float gather_ms = 0.0f;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    Ctx& c = g_ctx;
+    const float* p = pos;
+    if (k > 0) {
+      if (ensure(stage[(size_t)k], nrm ? 2 * bytes : bytes)) return 1;
+      float* sp = (float*)stage[(size_t)k].p;
+      if (hipMemcpyPeer(sp, c.device, pos, c0.device, bytes) != hipSuccess || (nrm && hipMemcpyPeer(sp + 3 * (size_t)nverts, c.device, nrm, c0.device, bytes) != hipSuccess))
+        return fail("art_rebuild_device: copy to device " + std::to_string(c.device) + " failed");
+      p = sp;
+    }
+    if (rebuild_one(hs, bp, p, k == 0 ? qs : c.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
+  }
+  // everything else that can fail without a lost device comes before the first swap: the refit events and counters of every context
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_refit()) return 1; }
+  // ---- commit: from here on the scene changes.  No step below allocates or waits for anything but its own launch; a failure here
+  // means the device is lost, and is the one case in which contexts may end up with different trees.
+  const double build_ms = built[0].g.build_ms;
+  const int32_t n_nodes = built[0].g.n_nodes, n_tris = built[0].g.n_tris, max_stack = built[0].g.max_stack;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k) || commit_tree(bp, built[(size_t)k])) return 1;
+    if (k > 0) continue;
+    hs.hdr.n_nodes = n_nodes; hs.hdr.n_tris = n_tris; hs.hdr.node_width = bp.width;
+    hs.bvh.width = bp.width; hs.bvh.n_nodes = n_nodes; hs.bvh.n_tris = n_tris; hs.bvh.max_stack = max_stack;
+    hs.bvh_build_ms = build_ms; hs.gpu_built = true; hs.refitted = false;
+    // the host copies of the old tree and of the positions are stale
+    std::vector<float>().swap(hs.bvh.nodes); std::vector<float>().swap(hs.bvh.tris); std::vector<uint32_t>().swap(hs.bvh.qnodes);
+    std::vector<float>().swap(hs.m_pos);
+  }
+  for (int k = 0; k < g_ndev && nrm; ++k) {                               // the shading records: k_refit_tris' normals branch, no triangle records (n_recs = 0)
+    if (use_dev(k)) return 1;
+    Ctx& c = g_ctx;
+    const hipStream_t s = (k == 0) ? qs : c.stream;
+    const float* n = (k == 0) ? nrm : (const float*)stage[(size_t)k].p + 3 * (size_t)nverts;
+    RefitArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.nrm3f = n; A.idx = (const int32_t*)built[(size_t)k].idx.p; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.m_shade = (float*)c.b_m_shade.p;
+    hs.m_shade_stale = true;                                              // (art_trace_rays reads the shading records on the host)
+    launch_refit_tris(s, A);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("art_rebuild_device: rewriting the shading records failed");
+  }
+  g_rebuild_info.rebuilds += 1; g_rebuild_info.gather_ms += gather_ms; g_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
+  g_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int get_rebuild_info(ArtRebuildInfo* out) {
+  if (!out) return fail("null ArtRebuildInfo");
+  *out = g_rebuild_info;
+  return 0;
+}
+
+// device 0's tree as it lies in HBM (a refit on another stream is ordered before the context stream's later work)
+int get_tree_cost(ArtTreeCost* out) {
+  if (!out) return fail("null ArtTreeCost");
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail("art_get_tree_cost: no scene uploaded");
+  if (c.scene.n_inst > 0) return fail("art_get_tree_cost: the scene is instanced (n_instances > 0); the figure is defined for the tree of a flat CLOSEST mesh");
+  if (c.scene.n_nodes < 1 || !c.b_nodes.p) return fail("art_get_tree_cost: the scene has no tree (no ART_MESH_CLOSEST mesh)");
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  DevBuf sums;
+  struct Free { DevBuf& b; ~Free() { b.release(); } } fr{sums};
+  if (ensure(sums, 4 * sizeof(double))) return 1;
+  double h[4] = {0.0, 0.0, 0.0, 0.0};
+  HIP_TRY(hipMemsetAsync(sums.p, 0, sizeof h, c.stream));
+  launch_tree_cost(c.stream, (const float*)c.b_nodes.p, c.scene.n_nodes, c.scene.node_width, (double*)sums.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, sums.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  out->root_area = h[3];
+  const bool any = h[3] > 0.0;                                            // (no usable child box under the root: no ray enters the tree)
+  out->node_visits = 1.0 + (any ? h[0] / h[3] : 0.0);
+  out->leaf_visits = any ? h[1] / h[3] : 0.0;
+  out->tri_tests = any ? h[2] / h[3] : 0.0;
+  return 0;
+}
+
 // cumulative since the upload; waits for every context's stream (a refit on the caller's stream is ordered before it)
 int get_refit_info(ArtRefitInfo* out) {
   if (!out) return fail("null ArtRefitInfo");
@@ -1386,6 +1581,15 @@ int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, voi
 }
 
 int art_get_refit_info(ArtRefitInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_refit_info(out); }
+
+int art_rebuild_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return rebuild_device(pos3f, nrm3f, nverts, (hipStream_t)hip_stream);
+}
+
+int art_get_rebuild_info(ArtRebuildInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_rebuild_info(out); }
+
+int art_get_tree_cost(ArtTreeCost* out) { std::lock_guard<std::mutex> lk(g_mu); return get_tree_cost(out); }
 
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
   std::lock_guard<std::mutex> lk(g_mu);

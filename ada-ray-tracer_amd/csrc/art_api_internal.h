@@ -129,6 +129,9 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);
+int rebuild_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
+int get_rebuild_info(ArtRebuildInfo* out);
+int get_tree_cost(ArtTreeCost* out);
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 
 }  // namespace art

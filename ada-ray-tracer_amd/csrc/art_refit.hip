@@ -133,7 +133,7 @@ __global__ __launch_bounds__(kRefitLevelBlock) void k_refit_level(const RefitArg
 }
 
 void launch_refit_tris(hipStream_t st, const RefitArgs& R) {
-  const int64_t lanes = std::max<int64_t>(R.nverts, (int64_t)R.n_recs);
+  const int64_t lanes = std::max<int64_t>({R.nverts, (int64_t)R.n_recs, R.nrm3f ? (int64_t)R.n_prims : 0});   // (n_recs = 0: art_rebuild_device, the shading records only)
   if (lanes <= 0) return;
   hipLaunchKernelGGL(k_refit_tris, dim3((unsigned)((lanes + kRefitTrisBlock - 1) / kRefitTrisBlock)), dim3(kRefitTrisBlock), 0, st, R);
 }

@@ -225,12 +225,49 @@ int  art_occluded_rays_device(const float* origins3f, const float* dirs3f, const
  * no CLOSEST mesh, a scene committed through gcore_commit_scene, nverts other than the uploaded count, host memory or another device's
  * memory.  A vertex coordinate that is not finite or whose magnitude exceeds 1e18 empties every box holding it (no ray enters it) and
  * makes the next art_synchronize fail with the count; a later good refit or an upload clears that state.  The tree keeps the topology
- * it was built with: after large deformations traversal costs more, and art_upload_scene builds a new tree. */
+ * it was built with: after large deformations traversal costs more (art_get_tree_cost says how much), and art_rebuild_device builds a
+ * new tree without leaving the GPU (art_upload_scene does it through the host). */
 int  art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream);
 /* Cumulative since art_upload_scene (waits for the refits enqueued so far): refit_ms = HIP events around device 0's refit kernels,
  * plan_ms = host time of building the refit plans, bad_vertices = bad vertex coordinates counted on device 0 over all refits. */
 typedef struct ArtRefitInfo { uint64_t refits; double refit_ms; double plan_ms; uint64_t bad_vertices; } ArtRefitInfo;
 int  art_get_refit_info(ArtRefitInfo* out);
+
+/* A new tree for the moved mesh, built on the GPU.  The arguments are art_refit_device's: device memory of the
+ * library's device, in the vertex order of the uploaded ArtMesh.pos; nrm3f == NULL keeps the normals; material ids stay.  The tree is the
+ * one the next art_upload_scene of the same mesh at these positions would build under the options as they stand at the call (bvh_width,
+ * bvh_builder, bvh_max_leaf, the cost options, bvh_ploc_radius): byte for byte with builder 3, the same tree from the GPU binned-SAH
+ * builder with builder 0, a tree whose node numbering may differ from one build to the next with builders 1 and 2.  Nothing goes through
+ * the host: the corners are gathered in HBM, every context builds into new buffers, and only the tree, its padded triangle copy and (with
+ * nrm3f) the normals of the shading records are replaced -- no other array of the scene is touched.
+ * Work already enqueued on hip_stream and on the library's stream runs before the rebuild; work enqueued afterwards sees the new
+ * geometry.  UNLIKE A REFIT THE CALL RETURNS ONLY WHEN THE NEW TREE IS COMMITTED: the builders size their output from counts they read
+ * back, level by level, so the host waits for hip_stream and for the library's stream.
+ * Refused before anything is launched: everything art_refit_device refuses (no scene, an instanced scene, no CLOSEST mesh, a scene
+ * committed through gcore_commit_scene, a wrong nverts, host memory or another device's memory), the option bvh_spatial_splits (reference
+ * splitting exists in the host builder only), and a mesh of fewer than two triangles (it has no GPU-built tree; refit it).  Bad vertices
+ * (the refit's rule: not finite, or beyond 1e18 in magnitude) are counted by the gather kernel and the count is read before a builder
+ * starts: the call fails with the count.  A rebuild that fails (a bad vertex, the allocator, a builder, a traversal-stack bound above
+ * kStackEntries, the limit art_upload_scene applies) leaves the scene of every context exactly as it was: every context builds into
+ * new buffers, and everything that can fail on a working device happens before the first context swaps.  The swap itself copies one
+ * header per context and launches one kernel for the normals; it fails only when a device is lost, the one case in which the contexts
+ * of art_init_devices may be left with different trees.  A failed call is not counted in ArtRebuildInfo.  A successful one clears a
+ * bad refit's state and drops the refit plan; the next art_refit_device plans against the new tree.  Under art_init_devices every
+ * context is rebuilt from a peer copy. */
+int  art_rebuild_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream);
+/* Cumulative since art_upload_scene: gather_ms = HIP events around device 0's gather kernel, build_ms = HIP events around device 0's
+ * builds (ArtBvhInfo::build_ms of each), host_ms = host time inside art_rebuild_device (all contexts, commit included). */
+typedef struct ArtRebuildInfo { uint64_t rebuilds; double gather_ms; double build_ms; double host_ms; } ArtRebuildInfo;
+int  art_get_rebuild_info(ArtRebuildInfo* out);   /* cumulative since art_upload_scene */
+
+/* How good is the tree in HBM right now (device 0; waits for the library's stream): the surface-area expectation of the work of a random
+ * line through the root, from the binary32 child boxes the walk tests (at width 4 the dequantised tree).  With A(box) the half surface
+ * area in binary64: root_area = A(union of the root's used child boxes), node_visits = 1 + sum over inner child slots of A / root_area,
+ * leaf_visits = sum over leaf slots of A / root_area, tri_tests = sum over leaf slots of count * A / root_area.  An empty slot adds
+ * nothing, nor does one a bad-vertex refit emptied.  A caller compares the figure of a refitted tree with that of a rebuilt one to
+ * decide when to rebuild; the library sets no policy.  Fails without a scene, on an instanced scene, and on a scene without a tree. */
+typedef struct ArtTreeCost { double root_area, node_visits, leaf_visits, tri_tests; } ArtTreeCost;
+int  art_get_tree_cost(ArtTreeCost* out);   /* device 0; waits for the library's stream */
 
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 int  art_get_stats(ArtStats* out);
