@@ -133,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost",
-    "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_set_option", "art_last_error", "art_shutdown",
+    "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
 ]
@@ -181,6 +181,7 @@ def load_library():
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
     L.art_get_stage_stats.argtypes = [C.POINTER(ArtStageStats)]
+    L.art_get_camera_rays_traced.argtypes = [C.POINTER(C.c_uint64)]
     L.art_set_option.argtypes = [C.c_char_p, C.c_int64]
     L.gcore_add_mesh_3f.argtypes = [f32p, C.c_int, i32p, C.c_int]
     L.gcore_add_mesh_3f.restype = C.c_int
@@ -376,6 +377,13 @@ class Backend:
         st = ArtStageStats()
         _check(self.lib.art_get_stage_stats(C.byref(st)))
         return st
+
+    def camera_rays_traced(self):
+        """camera rays the render passes generated and traced since resize(): with option camera_dedup (default) each distinct ray of a
+        batch once, else one per sample; stats().rays counts one camera query per sample either way"""
+        n = C.c_uint64(0)
+        _check(self.lib.art_get_camera_rays_traced(C.byref(n)))
+        return n.value
 
     def reduce_info(self):
         """what the multi-device path did: ranks of the RCCL communicator, GPU time of the reduces, GPU time of every device's passes"""

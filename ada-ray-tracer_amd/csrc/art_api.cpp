@@ -329,7 +329,7 @@ static int resize_one(int w, int h) {
   c.auto_phase = 0; c.auto_redo = 0; c.auto_gen += 1;    // (the batch size follows the frame: measure again)
   c.lost_reported = 0;                                   // (the device counters are zeroed below)
   if (c.d_items) HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream));
-  c.camera_rays = 0;
+  c.camera_rays = 0; c.camera_traced = 0;
   HIP_TRY(hipMemsetAsync(c.d_counters, 0, 16 * sizeof(unsigned long long), c.stream));
   return build_shard();
 }
@@ -659,6 +659,14 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
           else { trial = 1; c.auto_gen += 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; }    // a batch of another size: trial A again, on this size (new generation: the old trial's events no longer count)
         }
         c.camera_rays += (uint64_t)bank[0].P;
+        // Option camera_dedup: the batch's distinct camera rays -- one per (pixel, sample & 3), DevPaths::cam_dedup -- are generated and traced
+        // once; bounce 0 still runs over all P slots and reads every slot's hit from its distinct ray.  The counting variant traces every
+        // sample's camera ray: its contract is "equal to the oracle's walk".
+        const bool dedup = c.camera_dedup && !c.count_tests && c.trace_kernel == TRACE_COOP;
+        // U distinct rays per pixel: 4 with AA on (a sample chunk is a whole number of Generate4RayDirections groups: sc and S are multiples of 4), 1 with AA off
+        const int cam_u = p->aa_on ? 4 : 1;
+        const int cam_n = dedup ? cam_u * pn : bank[0].P;      // camera rays this batch generates and traces
+        c.camera_traced += (uint64_t)cam_n;
         if (c.trace_kernel == TRACE_COOP) {
           // Compacted work sets: raygen fills bank 0 (one item per slot); stage b shades the items of bank b & 1 and writes the survivors
           // densely into the other bank.  d_live[0] / d_live[32]: the banks' item counts.  Every stage leaves its rays as trace records in
@@ -668,12 +676,14 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
           bank[0].rec_mode = REC_EXT;
           DevPaths q = bank[0];                            // identity layout for raygen
           q.slot_id = nullptr;
+          q.cam_dedup = dedup ? cam_u : 0;
+          DevPaths qgen = q; qgen.P = cam_n;               // raygen's slots: [0, cam_n) are the distinct rays (slot = (sample & 3 within the batch) * pn + pixel)
           if (!c.d_items) { HIP_TRY(hipMalloc(&c.d_items, 32 * sizeof(unsigned long long))); HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream)); }
           if (ev_begin(2)) return 1;
-          launch_raygen(c.stream, F, c.scene, q);
+          launch_raygen(c.stream, F, c.scene, qgen);
           if (ev_end()) return 1;
-          launch_bump(c.stream, c.d_counters, rays_b, (unsigned long long)q.P);
-          { const RecordQueue rq = {q.P, nullptr, 1}; if (trace(q, q.P, true, nullptr, &rq)) return 1; }
+          launch_bump(c.stream, c.d_counters, rays_b, (unsigned long long)q.P);      // ArtStats::rays: one camera query per sample (the reference's Find_Closest_Hit calls), however many were traced
+          { const RecordQueue rq = {cam_n, nullptr, 1}; if (trace(q, cam_n, true, nullptr, &rq)) return 1; }
           for (int b = 0; b < p->max_depth; ++b) {
             const int in = b & 1, out = in ^ 1;
             const DevPaths& qi = (b == 0) ? q : bank[in];
@@ -1486,7 +1496,7 @@ int art_init_devices(int32_t n, const int32_t* ordinals) {
     c = Ctx();
     c.trace_kernel = opts.trace_kernel; c.batch_paths = opts.batch_paths; c.bvh_params = opts.bvh_params; c.node_min = opts.node_min; c.refill_min = opts.refill_min;
     c.queue_segments = opts.queue_segments; c.ray_chunk = opts.ray_chunk; c.shadow_anyhit = opts.shadow_anyhit; c.skip_null_shadow = opts.skip_null_shadow; c.inst_coop = opts.inst_coop; c.opt_shade_per = opts.opt_shade_per; c.lds_stack_cap = opts.lds_stack_cap; c.paths_spread_mb = opts.paths_spread_mb;
-    c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests; c.query_slice = opts.query_slice;
+    c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests; c.query_slice = opts.query_slice; c.camera_dedup = opts.camera_dedup;
     c.device = ord[k]; c.rank = k; c.nranks = n; c.tile = 32;
     if (use_dev(k) || ensure_device()) { shutdown(); return 1; }
     if (n > 1) {
@@ -1668,6 +1678,14 @@ int art_get_stats(ArtStats* out) {
   return 0;
 }
 
+int art_get_camera_rays_traced(uint64_t* out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!out) return fail("null camera ray count");
+  *out = 0;
+  for (int k = 0; k < g_ndev; ++k) *out += g_devs[k].camera_traced;      // the whole job, like ArtStats::rays
+  return 0;
+}
+
 static int set_option_one(const std::string& n, int64_t value);
 int art_set_option(const char* name, int64_t value) {      // applies to every device of the process
   std::lock_guard<std::mutex> lk(g_mu);
@@ -1689,6 +1707,7 @@ static int set_option_one(const std::string& n, int64_t value) {
   else if (n == "blocks_per_cu") { g_ctx.opt_blocks_per_cu = (int)value; g_ctx.blocks_per_cu = 0; }
   else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.query_slice = value; }
   else if (n == "count_tests") { g_ctx.count_tests = value != 0; }
+  else if (n == "camera_dedup") { if (value != 0 && value != 1) return fail("camera_dedup: 0 (every sample's camera ray is traced) or 1 (each distinct camera ray once per batch)"); g_ctx.camera_dedup = value != 0; }
   else if (n == "shadow_anyhit") { g_ctx.shadow_anyhit = value != 0; }
   else if (n == "skip_null_shadow") { g_ctx.skip_null_shadow = value != 0; }
   else if (n == "inst_coop") { g_ctx.inst_coop = value != 0; }

@@ -61,12 +61,14 @@ struct Ctx {
   int* d_cursor = nullptr;
   unsigned long long* d_counters = nullptr;   // [0] rays issued by shade, [3..7] box, tri, node, leaf, rays of counting traces
   uint64_t camera_rays = 0;
+  uint64_t camera_traced = 0;     // camera rays the render passes generated and traced since art_resize (art_get_camera_rays_traced; host-side count)
   // options
   int trace_kernel = TRACE_COOP;
   int64_t batch_paths = 128ll << 20;  // path slots per batch (328 B each at depth 8 -> up to 44 GB of the 288 GB HBM; buffers are sized to the frame,
                                       // so a small render takes less): big batches keep late bounces wide (8M -> 32M: +7 %, -> 128M: +1.7 %)
   int opt_blocks_per_cu = 0, blocks_per_cu = 0;
   bool count_tests = false;
+  bool camera_dedup = true;      // each distinct camera ray of a batch is generated and traced once (DevPaths::cam_dedup); false: once per sample
   int node_min = 0;              // the trace kernel leaves its node loop when fewer than 8 x node_min lanes still expand nodes.  0: 4 (the optimum on C4, profiles/r2_sensitivity.json);
                                  // 2 for an instanced scene -- its groups also wait for instance entries, and leaving the loop for them less often is worth 6 % on I64 (profiles/r5_inst_sweep.py)
   int refill_min = 2;            // idle ray groups of a wave take new rays when two of them are idle (1: at once; measured 0.5-1 % slower)

@@ -189,6 +189,11 @@ struct DevPaths {
   int32_t rec_mode;             // RecMode of `rec`
   int32_t shadow_rule;          // shadow rays carry Compute_Shadow's 10*eps so that the search may use the visibility rule (option shadow_anyhit)
   int32_t has_bvh;              // the scene has a BVH mesh: records are only worth writing if a trace kernel will read them
+  // Camera rays traced once per batch (option camera_dedup; raygen's bank of the record schedule only, else 0).  A camera ray depends on
+  // (pixel, sample & 3) alone -- camera_dir() takes the sample through the four Generate4RayDirections offsets, and with AA off not at
+  // all -- so raygen writes, and the first trace launch walks, only the batch's DISTINCT rays: cam_dedup = 4 (AA on) or 1 (AA off) per
+  // pixel, slots [0, cam_dedup * npix) of the bank (with AA on a batch holds whole groups of 4 samples).  Bounce 0 reads item w's hit from camera_hit_item(w) (art_shade.h).
+  int32_t cam_dedup;
 };
 
 constexpr uint32_t FLAG_ALIVE = 1u, FLAG_PREV_SPEC = 2u, FLAG_SHADOW_PENDING = 4u;

@@ -449,10 +449,27 @@ ART_HD void emit_ray(const DevScene& s, const DevPaths& qo, size_t hit_index, si
 }
 
 // ---------------------------------------------------------------- camera (ray_tracer.adb:61-97, integrators.adb:37-58)
-ART_HD void slot_to_sample(const DevPaths& q, int slot, uint32_t& pixel, uint32_t& sample) {
-  const int sl = slot / q.npix, pl = slot - sl * q.npix;
+// slot = sl * npix + pl: local sample, local pixel (the ONE integer division of a slot; its users share it)
+ART_HD void slot_split(const DevPaths& q, int slot, int& sl, int& pl) { sl = slot / q.npix; pl = slot - sl * q.npix; }
+ART_HD void split_to_sample(const DevPaths& q, int sl, int pl, uint32_t& pixel, uint32_t& sample) {
   pixel = q.pixmap ? q.pixmap[pl] : (uint32_t)pl;
   sample = q.sample_base + (uint32_t)sl;
+}
+ART_HD void slot_to_sample(const DevPaths& q, int slot, uint32_t& pixel, uint32_t& sample) {
+  int sl, pl;
+  slot_split(q, slot, sl, pl);
+  split_to_sample(q, sl, pl, pixel, sample);
+}
+
+// DevPaths::cam_dedup: where bounce 0 finds the hit of item w's camera ray.  Consecutive local samples cycle through sample & 3 whatever
+// sample_base is, so the distinct ray of slot (sl, pl) is slot (sl & 3, pl) with AA on, (0, pl) with AA off: the slot raygen wrote it from.
+// (sl, pl): slot_split of w, for a caller that needs them anyway.
+ART_HD int camera_hit_item(const DevPaths& q, int w, int sl, int pl) { return (q.cam_dedup == 0) ? w : (sl & (q.cam_dedup - 1)) * q.npix + pl; }
+ART_HD int camera_hit_item(const DevPaths& q, int w) {
+  if (q.cam_dedup == 0) return w;
+  int sl, pl;
+  slot_split(q, w, sl, pl);
+  return camera_hit_item(q, w, sl, pl);
 }
 
 ART_HD f3 camera_dir(const DevFrame& f, const DevScene& s, uint32_t pixel, uint32_t sample) {
@@ -521,7 +538,7 @@ ART_HD int32_t item_class(const DevScene& s, const DevPaths& qi, int w, const St
   const bool camera = (camera_mode >= 0) ? (camera_mode != 0) : (qi.synth0 && qi.slot_id == nullptr);         // raygen's bank: every item is a live camera ray (DevPaths::synth0)
   const uint32_t fl = camera ? (FLAG_ALIVE | FLAG_PREV_SPEC) : qi.flags[w];
   if (!(fl & FLAG_ALIVE)) return CLS_CHEAP;                       // only owed a shadow test: resolved now
-  const uint32_t key = qi.hit[w].key;
+  const uint32_t key = qi.hit[camera ? camera_hit_item(qi, w) : w].key;
   if (key == KEY_MISS) return CLS_CHEAP;
   const uint32_t cls = key & ~KEY_INDEX_MASK, idx = key & KEY_INDEX_MASK;
   int32_t mat;
@@ -561,7 +578,7 @@ ART_HD void item_classes(const DevScene& s, const DevPaths& qi, const int (&w)[N
   for (int k = 0; k < N; ++k) {                                   // step 1: flags and hit keys
     const int wk = on[k] ? w[k] : 0;
     fl[k] = camera ? (FLAG_ALIVE | FLAG_PREV_SPEC) : at(hotf<const uint32_t>(qi, HF_FLAGS), wk);      // (cached: shade_item reads the line again)      // (k_shade_compact only: the record schedule's block)
-    key[k] = ld_off(hotf<const uint32_t>(qi, HF_HIT), (uint32_t)wk * 16u + 4u);
+    key[k] = ld_off(hotf<const uint32_t>(qi, HF_HIT), (uint32_t)(camera ? camera_hit_item(qi, wk) : wk) * 16u + 4u);      // (camera: DevPaths::cam_dedup)
   }
   if (!camera) pin_loads(fl);
   pin_loads(key);
@@ -637,7 +654,9 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   // each into the branch that uses it and waited for them one by one -- eight memory round trips in a row at the head of every item, at the
   // stage's 80-VGPR cap -- so the loads a hint makes possible are unconditional (an item without a hint reads record 0 / material 0 and
   // ignores them), and on the device an empty asm that names every loaded value pins them all before the first use.
-  DevHit hw = at_s(batch ? hotf<const DevHit>(qi, HF_HIT) : qi.hit, w);
+  int cam_sl = 0, cam_pl = 0;                          // camera: the slot's sample and pixel, for the hit's index here and the camera ray below (one division)
+  if (camera) slot_split(qi, slot_loaded, cam_sl, cam_pl);
+  DevHit hw = at_s(batch ? hotf<const DevHit>(qi, HF_HIT) : qi.hit, camera ? camera_hit_item(qi, w, cam_sl, cam_pl) : w);      // (camera: the distinct ray's hit, DevPaths::cam_dedup; an item of raygen's bank is its slot.  at_s is an ordinary cached load: the sn / U items that share a hit are served by L2)
   // (hint_in may point at a record that says "no hint" (mat < 0): the caller then need not choose between a pointer and nullptr per lane --
   // which forced the record into scratch memory, with a scratch load and an s_waitcnt vmcnt(0) at each of its four uses, round 5)
   const bool hinted = (hint_in != nullptr) && (hint_in->mat >= 0);
@@ -670,7 +689,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   if (camera) {
     o = ld3(s.cam_pos); prev_pdf = 1.0f;
     uint32_t cpix, csam;
-    slot_to_sample(qi, slot_loaded, cpix, csam);
+    split_to_sample(qi, cam_sl, cam_pl, cpix, csam);
     d = camera_dir(f, s, cpix, csam);                                           // raygen_slot's own expression: the same bits
   } else {
     if (batch) {
