@@ -123,6 +123,10 @@ class ArtTreeCost(C.Structure):
     _fields_ = [("root_area", C.c_double), ("node_visits", C.c_double), ("leaf_visits", C.c_double), ("tri_tests", C.c_double)]
 
 
+class ArtMoveInfo(C.Structure):
+    _fields_ = [("moves", C.c_uint64), ("move_ms", C.c_double), ("plan_ms", C.c_double), ("bad_matrices", C.c_uint64), ("repads", C.c_uint64)]
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -132,7 +136,7 @@ EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
-    "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost",
+    "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -177,6 +181,8 @@ def load_library():
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_rebuild_info.argtypes = [C.POINTER(ArtRebuildInfo)]
     L.art_get_tree_cost.argtypes = [C.POINTER(ArtTreeCost)]
+    L.art_move_instances_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
+    L.art_get_move_info.argtypes = [C.POINTER(ArtMoveInfo)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
@@ -498,6 +504,41 @@ class Backend:
         tc = ArtTreeCost()
         _check(self.lib.art_get_tree_cost(C.byref(tc)))
         return tc
+
+    def move_instances_torch(self, m, check=True):
+        """Move the instances of an instanced scene (art_move_instances_device): m is a float32 tensor [n_instances, 3, 4] or
+        [n_instances, 12] on the library's GPU, instance i's object -> world matrix in the order of the uploaded instance list.  Enqueued
+        on torch.cuda.current_stream() without waiting for it: work enqueued before sees the old placement, work enqueued after the new
+        one.  The picture is the one of upload_scene at the new matrices; the instance tree keeps its topology.  check=True raises
+        ValueError before any launch when an element is not finite; that check costs ONE host synchronisation with the stream.
+        check=False skips it: a bad matrix (also a singular one, which check=True does not look for) empties its instance on the GPU
+        and the next synchronize fails with the count."""
+        import torch
+        if not isinstance(m, torch.Tensor):
+            raise ArtError("m: a torch tensor is required, not %s" % type(m).__name__)
+        if m.dtype != torch.float32:
+            raise ArtError("m: dtype must be torch.float32, not %s" % m.dtype)
+        if not ((m.dim() == 3 and tuple(m.shape[1:]) == (3, 4)) or (m.dim() == 2 and m.shape[1] == 12)):
+            raise ArtError("m: shape %s, expected [n_instances, 3, 4] or [n_instances, 12]" % (tuple(m.shape),))
+        m = m.contiguous()
+        n = m.shape[0]
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+        if m.device.type != "cuda":
+            raise ArtError("m: must be a GPU tensor on the library's device, not on %s" % m.device)
+        stream = torch.cuda.current_stream(m.device)
+        if check and n:
+            with torch.cuda.stream(stream):
+                bad = int((~torch.isfinite(m.reshape(n, 12))).any(dim=1).sum().item())      # the one host synchronisation
+            if bad:
+                raise ValueError("move_instances_torch: %d matrix(es) with an element that is not finite" % bad)
+        _check(self.lib.art_move_instances_device(m.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+
+    def move_info(self):
+        """ArtMoveInfo: moves, move_ms (GPU time of device 0's move kernels), plan_ms, bad_matrices, repads (meshes whose boxes a move
+        had to widen) -- cumulative since the upload (waits)"""
+        mi = ArtMoveInfo()
+        _check(self.lib.art_get_move_info(C.byref(mi)))
+        return mi
 
     def bvh_info(self):
         info = ArtBvhInfo()

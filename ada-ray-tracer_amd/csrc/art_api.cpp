@@ -39,6 +39,7 @@ static bool g_multi_api = false;       // the process came up through art_init_d
 static std::vector<hipEvent_t> g_reduce_free;     // event pairs folded into g_reduce_ms, ready for the next reduce (a host that downloads every frame re-uses two events)
 static ArtRefitInfo g_refit_info = ArtRefitInfo();   // art_get_refit_info: cumulative since the last upload
 static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
+static ArtMoveInfo g_move_info = ArtMoveInfo();      // art_get_move_info: the same
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
   for (hipEvent_t e : g_reduce_events) (void)hipEventDestroy(e);
@@ -136,6 +137,16 @@ static void release_refit(Ctx& c) {
   for (hipEvent_t e : R.ev) R.ev_free.push_back(e);
   R.ev.clear();
   R.ready = false; R.unread = false; R.bad_last = R.bad_total = 0; R.bad_reported = true;
+}
+
+// the same for the move plan (art_move_instances_device)
+static void release_move(Ctx& c) {
+  Ctx::MovePlan& P = c.move;
+  P.b_plan.release(); P.b_work.release(); P.b_stage.release();
+  P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs();
+  for (hipEvent_t e : P.ev) P.ev_free.push_back(e);
+  P.ev.clear();
+  P.ready = false; P.unread = false; P.bad_last = 0; P.bad_reported = true;
 }
 
 // `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Ctx::paths_spread_mb: the driver
@@ -247,12 +258,13 @@ int upload_scene(const ArtSceneDesc* d) {
   const std::vector<float> tri9 = std::move(hs.deferred_tri9);                    // option bvh_builder >= 1: every device builds its own tree
   hs.deferred_tri9.clear();
   Dev0Guard guard;
-  g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo();
+  g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo();
   for (int k = 0; k < g_ndev; ++k) {                                              // scene + BVH replicated on every GPU
     if (use_dev(k)) return 1;
     Ctx& c = g_ctx;
-    if (c.refit.ready) HIP_TRY(hipStreamSynchronize(c.stream));                  // (a refit still in flight reads the plan)
+    if (c.refit.ready || c.move.ready) HIP_TRY(hipStreamSynchronize(c.stream));  // (a refit or a move still in flight reads the plan)
     release_refit(c);
+    release_move(c);
     c.bvh_params = g_devs[0].bvh_params;
     if (ensure_device()) return 1;
     int dev_stack = hs.bvh.max_stack;
@@ -765,6 +777,28 @@ static int fold_refit() {
   return 0;
 }
 
+// the same for the moves of an instanced scene: event pairs, and the counters k_move_matrices / k_move_pads_mesh keep
+static int fold_move() {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  for (size_t i = 0; i + 1 < P.ev.size(); i += 2) {
+    float ms = 0.0f;
+    HIP_TRY(hipEventSynchronize(P.ev[i + 1]));
+    HIP_TRY(hipEventElapsedTime(&ms, P.ev[i], P.ev[i + 1]));
+    if (&c == &g_devs[0]) g_move_info.move_ms += ms;
+    P.ev_free.push_back(P.ev[i]); P.ev_free.push_back(P.ev[i + 1]);
+  }
+  P.ev.clear();
+  if (P.unread && P.args.state) {
+    unsigned long long w[4];
+    HIP_TRY(hipMemcpy(w, P.args.state, sizeof w, hipMemcpyDeviceToHost));
+    P.unread = false;
+    P.bad_last = w[1]; P.bad_reported = (w[1] == 0);
+    if (&c == &g_devs[0]) { g_move_info.bad_matrices = w[2]; g_move_info.repads = w[3]; }
+  }
+  return 0;
+}
+
 static int synchronize_one();
 int synchronize() {
   Dev0Guard guard;
@@ -790,6 +824,12 @@ static int synchronize_one() {
     c.refit.bad_reported = true;
     return fail("art_refit_device: " + std::to_string(c.refit.bad_last) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes "
                 "holding them are empty (no ray enters them) until a good refit or art_upload_scene");
+  }
+  if (fold_move()) return 1;
+  if (!c.move.bad_reported) {             // (the same convention for a bad instance matrix)
+    c.move.bad_reported = true;
+    return fail("art_move_instances_device: " + std::to_string(c.move.bad_last) + " instance matrix(es) with an element that is not finite, without an inverse, or "
+                "reaching beyond 1e18; their instances are empty (no ray enters them) until a good move or art_upload_scene");
   }
   // a lost path is a wrong picture, not a statistic -- a stage that found a path without an output item, a ray its bank has no
   // record for, a material its instantiation was not compiled for, or a staged trace record that did not name the hit slot its position
@@ -975,6 +1015,10 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
   if (hs.m_shade_stale) {                                            // a refit rewrote the normals in HBM (the stream is idle: synchronised above)
     HIP_TRY(hipMemcpy(hs.m_shade.data(), c.b_m_shade.p, hs.m_shade.size() * sizeof(float), hipMemcpyDeviceToHost));
     hs.m_shade_stale = false;
+  }
+  if (hs.inst_stale) {                                               // a move rewrote the matrices in HBM
+    HIP_TRY(hipMemcpy(hs.inst.data(), c.b_inst.p, hs.inst.size() * sizeof(DevInstance), hipMemcpyDeviceToHost));
+    hs.inst_stale = false;
   }
   bind_host_pointers(hs);
   for (size_t i = 0; i < N; ++i) {
@@ -1215,6 +1259,155 @@ int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t
   return rc;
 }
 
+// ---- moving instances (art_move_instances_device, art_move.hip) -------------------------------------------------------------------
+// The plan of the current context, from the two-level build the upload kept: MovePlanHost's arrays in one buffer, the kernels' own
+// arrays in another, and MoveArgs pointing into both and into the scene's arrays.
+static int build_move_plan(const HostScene& hs) {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  const auto t0 = std::chrono::steady_clock::now();
+  MovePlanHost H;
+  std::string err;
+  if (!build_move_plan_host(hs.two, H, err)) return fail("art_move_instances_device: " + err);
+  const size_t n_entry = hs.two.entry.size(), n_inst = hs.two.inst.size(), nm = (size_t)H.n_mesh, n_tlas = (size_t)hs.two.tlas.n_nodes, n_blas = H.node_mesh.size();
+  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
+      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != hs.two.blas_tris.size() * 4)
+    return fail("art_move_instances_device: internal: the arrays in HBM are not the kept build's");
+  std::vector<uint8_t> img;                                                // every section 16-byte aligned
+  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (bytes) std::memcpy(&img[at], p, bytes); return at; };
+  const size_t o_roff = put(H.range_off.data(), H.range_off.size() * 4), o_rng = put(H.ranges.data(), H.ranges.size() * 4), o_prox = put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
+  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbox = put(H.mesh_box.data(), H.mesh_box.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
+  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_tight = put(H.blas_tight.data(), H.blas_tight.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
+  if (upload(P.b_plan, img)) return 1;
+  std::vector<uint8_t> work;
+  auto room = [&](size_t bytes) { const size_t at = work.size(); work.resize(at + ((bytes + 15) & ~(size_t)15), 0); return at; };
+  const size_t w_state = room(4 * 8), w_need = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
+  std::memcpy(&work[w_pad], H.pad_abs.data(), nm * 4);
+  if (upload(P.b_work, work)) return 1;
+  const char* pb = (const char*)P.b_plan.p; char* wb = (char*)P.b_work.p;
+  MoveArgs& A = P.args;
+  A = MoveArgs();
+  A.n_inst = (int32_t)n_inst; A.n_entry = (int32_t)n_entry; A.n_mesh = (int32_t)nm; A.n_blas_nodes = (int32_t)n_blas;
+  A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p;
+  A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
+  A.range_off = (const int32_t*)(pb + o_roff); A.ranges = (const int32_t*)(pb + o_rng); A.proxy_rec = (const int32_t*)(pb + o_prox); A.inst_mesh = (const int32_t*)(pb + o_imesh);
+  A.mesh_box = (const float*)(pb + o_mbox); A.mesh_base = (const int32_t*)(pb + o_mbase); A.node_mesh = (const int32_t*)(pb + o_nmesh); A.blas_tight = (const float*)(pb + o_tight);
+  A.state = (unsigned long long*)(wb + w_state); A.needed = (unsigned long long*)(wb + w_need); A.tlas_tight = (float*)(wb + w_tight); A.ent_box = (float*)(wb + w_box);
+  A.inst_ok = (int32_t*)(wb + w_ok); A.pad_cur = (float*)(wb + w_pad); A.repad = (int32_t*)(wb + w_repad);
+  A.extent = (double)hs.two.scene_extent; A.mesh_pad_rel = hs.two.mesh_pad_rel; A.mesh_pad_min = hs.two.mesh_pad_min;
+  const BvhBuildParams tp;                                                 // the instance tree builder's pad rule: the defaults, as build_two_level_host applied them
+  A.tlas_pad_rel = tp.inflate_rel; A.tlas_pad_abs = tp.inflate_abs;
+  P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off;
+  P.small_entries = H.records <= 64 * (int64_t)n_entry;
+  if (&c != &g_devs[0]) {
+    if (ensure(P.b_stage, 48 * n_inst)) return 1;
+    if (!P.done_ev) HIP_TRY(hipEventCreateWithFlags(&P.done_ev, hipEventDisableTiming));
+  } else if (g_ndev > 1 && !P.ready_ev) HIP_TRY(hipEventCreateWithFlags(&P.ready_ev, hipEventDisableTiming));
+  g_move_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  P.ready = true;
+  return 0;
+}
+
+// the current context's move on stream s, from matrices in this context's device memory
+static int move_one(const float* m12f, hipStream_t s) {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  MoveArgs A = P.args;
+  A.m12f = m12f;
+  // event pairs of earlier moves that have completed are folded here, so that a host that moves every frame and never synchronises
+  // keeps a list as long as the moves in flight
+  size_t kept = 0;
+  for (size_t i = 0; i + 1 < P.ev.size(); i += 2) {
+    float ms = 0.0f;
+    if (hipEventQuery(P.ev[i + 1]) == hipSuccess && hipEventElapsedTime(&ms, P.ev[i], P.ev[i + 1]) == hipSuccess) {
+      if (&c == &g_devs[0]) g_move_info.move_ms += ms;
+      P.ev_free.push_back(P.ev[i]); P.ev_free.push_back(P.ev[i + 1]);
+    } else { P.ev[kept] = P.ev[i]; P.ev[kept + 1] = P.ev[i + 1]; kept += 2; }
+  }
+  P.ev.resize(kept);
+  (void)hipGetLastError();                                                 // (hipErrorNotReady of a pair still in flight)
+  hipEvent_t e0 = nullptr, e1 = nullptr;
+  if (P.ev_free.size() >= 2) { e1 = P.ev_free.back(); P.ev_free.pop_back(); e0 = P.ev_free.back(); P.ev_free.pop_back(); }
+  else {
+    HIP_TRY(hipEventCreate(&e0));
+    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
+  }
+  if (hipEventRecord(e0, s) != hipSuccess) { P.ev_free.push_back(e0); P.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
+  P.ev.push_back(e0); P.ev.push_back(e1);
+  struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop{e1, s};      // recorded on every way out
+  P.unread = true;
+  launch_move_matrices(s, A);
+  launch_move_repad(s, A);
+  launch_move_entry_boxes(s, A, P.small_entries);
+  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                   // deepest level first
+    launch_move_tlas_level(s, A, P.levels + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(std::string("art_move_instances_device: kernel launch failed: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// Every check comes before the first launch; the streams are ordered as refit_device orders them.
+int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st) {
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail("art_move_instances_device: no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail("art_move_instances_device: the scene was committed through gcore_commit_scene, which keeps its own instances");
+  if (c0.scene.n_inst <= 0) return fail("art_move_instances_device: the scene is not instanced (n_instances = 0); art_refit_device moves the vertices of a flat mesh");
+  if (n_instances != (int64_t)c0.scene.n_inst) return fail("art_move_instances_device: n_instances " + std::to_string(n_instances) + " differs from the uploaded scene's " + std::to_string(c0.scene.n_inst));
+  if (!m12f) return fail("art_move_instances_device: null m12f");
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const size_t bytes = 48 * (size_t)n_instances;
+  if (check_device_ptr(m12f, bytes, "m12f")) return 1;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (!g_ctx.move.ready && build_move_plan(hs)) return 1;
+  }
+  if (use_dev(0)) return 1;
+  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
+  const bool other = (qs != c0.stream);
+  if (other) {
+    for (hipEvent_t& e : c0.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    HIP_TRY(hipEventRecord(c0.q_ev[0], c0.stream));
+    HIP_TRY(hipStreamWaitEvent(qs, c0.q_ev[0], 0));
+  }
+  hs.inst_stale = true;                                                    // (art_trace_rays reads the matrices on the host)
+  g_move_info.moves += 1;
+  int rc = 0;
+  if (g_ndev > 1 && hipEventRecord(c0.move.ready_ev, qs) != hipSuccess) rc = fail("art_move_instances_device: hipEventRecord failed");
+  if (!rc) rc = move_one(m12f, qs);
+  for (int k = 1; k < g_ndev && !rc; ++k) {
+    if (use_dev(k)) { rc = 1; break; }
+    Ctx& c = g_ctx;
+    float* sm = (float*)c.move.b_stage.p;
+    if (hipStreamWaitEvent(c.stream, c0.move.ready_ev, 0) != hipSuccess || hipMemcpyPeerAsync(sm, c.device, m12f, c0.device, bytes, c.stream) != hipSuccess) {
+      rc = fail("art_move_instances_device: copy to device " + std::to_string(c.device) + " failed"); break;
+    }
+    rc = move_one(sm, c.stream);
+    if (hipEventRecord(c.move.done_ev, c.stream) != hipSuccess || hipStreamWaitEvent(qs, c.move.done_ev, 0) != hipSuccess) rc = rc ? rc : fail("art_move_instances_device: event ordering failed");
+  }
+  if (use_dev(0)) return 1;
+  if (other) {                          // (also after a failure: what was enqueued stays ordered before the context stream's next work)
+    HIP_TRY(hipEventRecord(c0.q_ev[1], qs));
+    HIP_TRY(hipStreamWaitEvent(c0.stream, c0.q_ev[1], 0));
+  }
+  return rc;
+}
+
+// cumulative since the upload; waits for every context's stream (a move on the caller's stream is ordered before it)
+int get_move_info(ArtMoveInfo* out) {
+  if (!out) return fail("null ArtMoveInfo");
+  Dev0Guard guard;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (!g_ctx.device_ready) continue;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    if (fold_move()) return 1;
+  }
+  *out = g_move_info;
+  return 0;
+}
+
 // ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
 // What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
 // anywhere leaves every context's scene as it was.
@@ -1444,6 +1637,10 @@ void shutdown() {
     for (hipEvent_t e : c.refit.ev_free) (void)hipEventDestroy(e);
     if (c.refit.ready_ev) (void)hipEventDestroy(c.refit.ready_ev);
     if (c.refit.done_ev) (void)hipEventDestroy(c.refit.done_ev);
+    release_move(c);
+    for (hipEvent_t e : c.move.ev_free) (void)hipEventDestroy(e);
+    if (c.move.ready_ev) (void)hipEventDestroy(c.move.ready_ev);
+    if (c.move.done_ev) (void)hipEventDestroy(c.move.done_ev);
     for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
     c.b_reduced.release();
     if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
@@ -1600,6 +1797,13 @@ int art_rebuild_device(const float* pos3f, const float* nrm3f, int64_t nverts, v
 int art_get_rebuild_info(ArtRebuildInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_rebuild_info(out); }
 
 int art_get_tree_cost(ArtTreeCost* out) { std::lock_guard<std::mutex> lk(g_mu); return get_tree_cost(out); }
+
+int art_move_instances_device(const float* m12f, int64_t n_instances, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return move_instances_device(m12f, n_instances, (hipStream_t)hip_stream);
+}
+
+int art_get_move_info(ArtMoveInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_move_info(out); }
 
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
   std::lock_guard<std::mutex> lk(g_mu);

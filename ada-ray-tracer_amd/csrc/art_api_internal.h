@@ -53,6 +53,19 @@ struct Ctx {
     uint64_t bad_last = 0, bad_total = 0;              // bad vertices of the last refit read / since the upload
     bool bad_reported = true;                          // the last refit's bad vertices were reported by a synchronize (or there were none)
   } refit;
+  // art_move_instances_device (art_move.hip): the plan is built on the first move after an upload (the upload drops it)
+  struct MovePlan {
+    bool ready = false;
+    DevBuf b_plan, b_work, b_stage;                    // MovePlanHost's arrays, one after the other | what the kernels write (MoveArgs) | contexts k > 0: peer copy of the matrices
+    MoveArgs args = MoveArgs();                        // everything but m12f
+    std::vector<int> level_off; const int32_t* levels = nullptr;   // the instance tree's level L: levels[level_off[L] .. level_off[L + 1])
+    bool small_entries = false;                        // few records per entry point: one wave each (launch_move_entry_boxes)
+    std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's move kernels: not yet folded / free for reuse
+    hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // as RefitPlan's
+    bool unread = false;                               // a move was enqueued whose counters no fold has read yet
+    uint64_t bad_last = 0;                             // bad matrices of the last move read
+    bool bad_reported = true;                          // ... were reported by a synchronize (or there were none)
+  } move;
   int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
@@ -134,6 +147,8 @@ int get_refit_info(ArtRefitInfo* out);
 int rebuild_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_rebuild_info(ArtRebuildInfo* out);
 int get_tree_cost(ArtTreeCost* out);
+int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st);
+int get_move_info(ArtMoveInfo* out);
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 
 }  // namespace art

@@ -26,6 +26,7 @@ struct HostScene {
   bool gpu_built = false;             // nodes / tris live only in HBM (art_export_bvh copies them back on demand)
   bool refitted = false;              // art_refit_device moved the tree's boxes: the HBM copy is the only current one, whichever builder made it
   bool m_shade_stale = false;         // art_refit_device rewrote the normals in HBM: art_trace_rays copies m_shade back before it reads it
+  bool inst_stale = false;            // art_move_instances_device rewrote the instance table in HBM: art_trace_rays copies `inst` back before it reads it
   bool gcore_seam = false;           // committed by gcore_commit_scene (which keeps its own host copy of the tree: not refittable)
   bool tree_in_hbm_only() const { return gpu_built || refitted; }
   double bvh_build_ms = 0.0;

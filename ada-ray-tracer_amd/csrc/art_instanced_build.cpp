@@ -29,6 +29,7 @@ bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vect
   BvhBuildParams bp; bp.width = 4;
   if (pad_rel >= 0.0f) bp.inflate_rel = pad_rel;
   if (pad_abs >= 0.0f) bp.inflate_abs = pad_abs;
+  T.scene_extent = std::max(0.0f, scene_extent); T.mesh_pad_rel = bp.inflate_rel; T.mesh_pad_min = bp.inflate_abs;
   const size_t nm = meshes.size();
   std::vector<int32_t> node_base(nm, 0), tri_base(nm, 0), ntris(nm, 0);
   std::vector<std::array<float, 6>> mesh_box(nm);
@@ -295,6 +296,161 @@ bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vect
       }
     }
   }
+  return true;
+}
+
+// Everything here is read from the finished build, and every index the kernels will follow is checked here: they follow them blindly.
+bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& err) {
+  P = MovePlanHost();
+  constexpr int W = 4, NF = 32;
+  const size_t nm = T.mesh_pad_abs.size(), n_inst = T.inst.size(), n_entry = T.entry.size();
+  const int64_t n_tlas = T.tlas.n_nodes, n_blas = (int64_t)(T.blas_nodes.size() / NF), n_rec = (int64_t)(T.blas_tris.size() / kTriFloats), n_proxy = (int64_t)(T.tlas.tris.size() / kTriFloats);
+  if (nm == 0 || n_inst == 0 || n_entry < n_inst || T.qnode_base.size() != nm || T.qnodes.size() != (size_t)(n_tlas + n_blas) * (kQNodeBytes / 4) || T.tlas.nodes.size() != (size_t)n_tlas * NF) {
+    err = "move plan: not a one-sided two-level build"; return false;
+  }
+  P.n_mesh = (int32_t)nm;
+  P.pad_abs = T.mesh_pad_abs;
+  P.mesh_box.assign(6 * nm, 0.0f); P.mesh_base.assign(3 * nm, -1);
+  std::vector<int64_t> mesh_nodes(nm, 0), mesh_recs(nm, 0);
+  for (size_t mi = 0; mi < nm; ++mi) {
+    const int64_t nb = (int64_t)T.qnode_base[mi] - n_tlas, ne = ((mi + 1 < nm) ? (int64_t)T.qnode_base[mi + 1] : n_tlas + n_blas) - n_tlas;
+    if (nb < 0 || ne <= nb || ne > n_blas) { err = "move plan: a mesh's nodes lie outside the node array"; return false; }
+    P.mesh_base[3 * mi] = (int32_t)nb; P.mesh_base[3 * mi + 2] = T.qnode_base[mi];
+    mesh_nodes[mi] = ne - nb;
+  }
+  P.inst_mesh.resize(n_inst);
+  for (size_t i = 0; i < n_inst; ++i) {
+    const InstRec& R = T.inst[i];
+    if (R.mesh < 0 || (size_t)R.mesh >= nm || R.node_base != P.mesh_base[3 * (size_t)R.mesh] || R.tri_base < 0 || R.n_tris < 1 || (int64_t)R.tri_base + R.n_tris > n_rec) {
+      err = "move plan: an instance outside its mesh's arrays"; return false;
+    }
+    P.inst_mesh[i] = R.mesh;
+    int32_t& tb = P.mesh_base[3 * (size_t)R.mesh + 1];
+    if (tb >= 0 && tb != R.tri_base) { err = "move plan: two record ranges for one mesh"; return false; }
+    if (tb < 0) {
+      tb = R.tri_base; mesh_recs[(size_t)R.mesh] = R.n_tris;
+      float* b = &P.mesh_box[6 * (size_t)R.mesh];
+      for (int a = 0; a < 3; ++a) { b[a] = 3.4e38f; b[a + 3] = -3.4e38f; }
+      for (int64_t r = 0; r < R.n_tris; ++r) {
+        const float* tr = &T.blas_tris[(size_t)(R.tri_base + r) * kTriFloats];
+        for (int q = 0; q < 9; ++q) { b[q % 3] = std::min(b[q % 3], tr[q]); b[q % 3 + 3] = std::max(b[q % 3 + 3], tr[q]); }
+      }
+    }
+  }
+  // the meshes' nodes by depth, their mesh, and the tight box below each of them (deepest level first)
+  P.node_mesh.assign((size_t)n_blas, -1); P.blas_tight.assign(6 * (size_t)n_blas, 0.0f);
+  {
+    std::vector<int32_t> cur, next, blas_levels;                             // the meshes' nodes by depth inside their mesh, all meshes together
+    std::vector<int> blas_level_off;
+    for (size_t mi = 0; mi < nm; ++mi) { cur.push_back(P.mesh_base[3 * mi]); P.node_mesh[(size_t)P.mesh_base[3 * mi]] = (int32_t)mi; }
+    blas_level_off.assign(1, 0);
+    while (!cur.empty()) {
+      next.clear();
+      for (const int32_t g : cur) {
+        const int32_t mi = P.node_mesh[(size_t)g];
+        const float* nd = &T.blas_nodes[(size_t)g * NF];
+        for (int j = 0; j < W; ++j) {
+          const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+          if (ref < 0) continue;
+          if (cnt > 0) {
+            if (P.mesh_base[3 * (size_t)mi + 1] >= 0 && (cnt > kMaxLeafTris || (int64_t)ref + cnt > mesh_recs[(size_t)mi])) { err = "move plan: a leaf outside its mesh's records"; return false; }
+            continue;
+          }
+          const int64_t c = (int64_t)P.mesh_base[3 * (size_t)mi] + ref;
+          if (ref >= mesh_nodes[(size_t)mi] || P.node_mesh[(size_t)c] >= 0) { err = "move plan: a mesh's nodes do not form a tree"; return false; }
+          P.node_mesh[(size_t)c] = mi; next.push_back((int32_t)c);
+        }
+      }
+      blas_levels.insert(blas_levels.end(), cur.begin(), cur.end());
+      blas_level_off.push_back((int)blas_levels.size());
+      cur.swap(next);
+    }
+    if ((int64_t)blas_levels.size() != n_blas) { err = "move plan: unreachable nodes in a mesh's tree"; return false; }
+    for (int L = (int)blas_level_off.size() - 2; L >= 0; --L)
+      for (int k = blas_level_off[(size_t)L]; k < blas_level_off[(size_t)L + 1]; ++k) {
+        const int32_t g = blas_levels[(size_t)k], mi = P.node_mesh[(size_t)g];
+        const float* nd = &T.blas_nodes[(size_t)g * NF];
+        float* b = &P.blas_tight[6 * (size_t)g];
+        for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[a + 3] = -INFINITY; }
+        if (P.mesh_base[3 * (size_t)mi + 1] < 0) continue;                       // (a mesh nobody shows is never re-padded)
+        for (int j = 0; j < W; ++j) {
+          const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+          if (ref < 0) continue;
+          if (cnt > 0) {
+            for (int r = 0; r < cnt; ++r) {
+              const float* tr = &T.blas_tris[((size_t)P.mesh_base[3 * (size_t)mi + 1] + (size_t)ref + (size_t)r) * kTriFloats];
+              for (int q = 0; q < 9; ++q) { b[q % 3] = std::min(b[q % 3], tr[q]); b[q % 3 + 3] = std::max(b[q % 3 + 3], tr[q]); }
+            }
+          } else {
+            const float* cb = &P.blas_tight[6 * ((size_t)P.mesh_base[3 * (size_t)mi] + (size_t)ref)];
+            for (int a = 0; a < 3; ++a) { b[a] = std::min(b[a], cb[a]); b[a + 3] = std::max(b[a + 3], cb[a + 3]); }
+          }
+        }
+      }
+  }
+  // the triangle records below every entry point
+  P.range_off.assign(1, 0);
+  std::vector<int32_t> walk; std::vector<std::pair<int32_t, int32_t>> found;
+  for (size_t e = 0; e < n_entry; ++e) {
+    const TwoLevelHost::EntryPoint& E = T.entry[e];
+    if (E.inst < 0 || (size_t)E.inst >= n_inst || (e < n_inst && (size_t)E.inst != e)) { err = "move plan: an entry point of a missing instance"; return false; }
+    const InstRec& R = T.inst[(size_t)E.inst];
+    found.clear();
+    if (E.root_entry == 0) found.emplace_back(R.tri_base, R.n_tris);
+    else {
+      walk.assign(1, E.root_entry);
+      while (!walk.empty()) {
+        const int32_t w = walk.back(); walk.pop_back();
+        const int32_t ref = w >> 4, cnt = w & 15;
+        if (cnt) {
+          if (cnt > kMaxLeafTris || ref < 0 || ref + cnt > R.n_tris) { err = "move plan: an entry point outside its mesh's records"; return false; }
+          found.emplace_back(R.tri_base + ref, cnt);
+          continue;
+        }
+        if (ref < 0 || ref >= mesh_nodes[(size_t)R.mesh] || found.size() + walk.size() > (size_t)n_rec + (size_t)n_blas) { err = "move plan: an entry point outside its mesh's tree"; return false; }
+        const float* nd = &T.blas_nodes[((size_t)R.node_base + (size_t)ref) * NF];
+        for (int j = 0; j < W; ++j) {
+          const int32_t rj = __builtin_bit_cast(int32_t, nd[4 * j + 3]);
+          if (rj >= 0) walk.push_back((rj << 4) | __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]));
+        }
+      }
+      std::sort(found.begin(), found.end());
+    }
+    for (size_t k = 0; k < found.size(); ++k) {
+      P.records += found[k].second;
+      const size_t n = P.ranges.size();
+      if (k > 0 && P.ranges[n - 2] + P.ranges[n - 1] == found[k].first) P.ranges[n - 1] += found[k].second;      // (adjacent leaves: one range)
+      else { P.ranges.push_back(found[k].first); P.ranges.push_back(found[k].second); }
+    }
+    if (P.ranges.size() / 2 >= (size_t)0x7fffffff) { err = "move plan: too many record ranges"; return false; }
+    P.range_off.push_back((int32_t)(P.ranges.size() / 2));
+  }
+  // the proxies, and the instance tree's nodes by depth
+  P.proxy_rec.assign(n_entry, -1);
+  for (int64_t r = 0; r < n_proxy; ++r) {
+    const int32_t id = __builtin_bit_cast(int32_t, T.tlas.tris[(size_t)r * kTriFloats + 9]);
+    if (id < 0 || (size_t)id >= n_entry || P.proxy_rec[(size_t)id] >= 0) { err = "move plan: a proxy names no entry point, or one twice"; return false; }
+    P.proxy_rec[(size_t)id] = (int32_t)r;
+  }
+  for (size_t e = 0; e < n_entry; ++e) if (P.proxy_rec[e] < 0) { err = "move plan: an entry point without a proxy"; return false; }
+  std::vector<uint8_t> seen((size_t)n_tlas, 0);
+  P.tlas_levels.assign(1, 0); P.tlas_level_off.assign(1, 0); seen[0] = 1;
+  for (size_t b = 0; b < P.tlas_levels.size();) {
+    const size_t e = P.tlas_levels.size();
+    for (size_t i = b; i < e; ++i) {
+      const float* nd = &T.tlas.nodes[(size_t)P.tlas_levels[i] * NF];
+      for (int j = 0; j < W; ++j) {
+        const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+        if (ref < 0) continue;
+        if (cnt > 0) { if (cnt > kMaxLeafTris || (int64_t)ref + cnt > n_proxy) { err = "move plan: an instance tree leaf outside the proxies"; return false; } continue; }
+        if (ref >= n_tlas || seen[(size_t)ref]) { err = "move plan: the instance tree's nodes do not form a tree"; return false; }
+        seen[(size_t)ref] = 1; P.tlas_levels.push_back(ref);
+      }
+    }
+    P.tlas_level_off.push_back((int)e);
+    b = e;
+  }
+  if ((int64_t)P.tlas_levels.size() != n_tlas) { err = "move plan: unreachable nodes in the instance tree"; return false; }
   return true;
 }
 

@@ -28,6 +28,7 @@ struct TwoLevelHost {
   int32_t open_factor = 1;              // entry points per instance asked of the build (the automatic choice, if that was left to it)
   int32_t blas_max_stack = 0;           // the largest worst-case traversal stack of the meshes' trees
   std::vector<float> mesh_pad_abs;      // per mesh: the absolute pad its tree's boxes were built with (>= the caller's; follows the mesh's instances)
+  float scene_extent = 0.0f, mesh_pad_rel = 0.0f, mesh_pad_min = 0.0f;   // what the build was given: the caller's extent, the meshes' relative pad and the floor of their absolute pad (art_move_instances_device pads by the same rule)
   InstScene view() const {
     InstScene S;
     S.tlas_nodes = tlas.nodes.data(); S.tlas_tris = tlas.tris.data(); S.blas_nodes = blas_nodes.data(); S.blas_tris = blas_tris.data();
@@ -47,5 +48,21 @@ struct TwoLevelHost {
 // absolute pad of a mesh's boxes is derived from it and from the mesh's instances (their inverse matrices): TwoLevelHost::mesh_pad_abs.
 bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vector<InstIn>& insts, TwoLevelHost& out, std::string& err,
                           bool two_sided = true, float pad_rel = -1.0f, float pad_abs = -1.0f, int open_factor = 1, float scene_extent = 0.0f);
+
+// ---- what art_move_instances_device (art_move.hip) needs besides the arrays in HBM, from a one-sided build: built once per upload
+struct MovePlanHost {
+  int32_t n_mesh = 0;
+  std::vector<int32_t> range_off, ranges;   // entry point e: the triangle records below it, (first record in blas_tris, count) pairs ranges[2k], ranges[2k + 1], k in [range_off[e], range_off[e + 1])
+  std::vector<int32_t> proxy_rec;           // entry point e: its proxy record in tlas.tris
+  std::vector<int32_t> inst_mesh;           // instance i: its mesh
+  std::vector<float> mesh_box;              // 6 per mesh: the object-space box of its records (zeros: a mesh nobody shows)
+  std::vector<int32_t> mesh_base;           // 3 per mesh: first node in blas_nodes, first record in blas_tris (-1: a mesh nobody shows), first node in qnodes
+  std::vector<int32_t> tlas_levels; std::vector<int> tlas_level_off;   // the instance tree's nodes, level L = tlas_levels[tlas_level_off[L] .. tlas_level_off[L + 1]), root first
+  std::vector<int32_t> node_mesh;           // per node of blas_nodes: its mesh
+  std::vector<float> blas_tight;            // 6 per node of blas_nodes: the tight box of the records below it (they never move: computed here, once)
+  std::vector<float> pad_abs;               // per mesh: the pad its boxes carry (mesh_pad_abs to begin with)
+  int64_t records = 0;                      // sum over the entry points of the records below them
+};
+bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& err);
 
 }  // namespace art

@@ -119,4 +119,31 @@ void launch_gather_tri9(hipStream_t st, const GatherArgs& G);
 // sums4 (zeroed by the caller): half areas of the inner child slots | of the leaf slots | of the leaf slots x triangle count | of the root's union
 void launch_tree_cost(hipStream_t st, const float* nodes, int n_nodes, int width, double* sums4);
 
+// the instances of an instanced scene move (art_move.hip, art_api.cpp art_move_instances_device).  Everything but m12f is the library's:
+// the scene's arrays in HBM and the plan (art_instanced_build.h MovePlanHost) next to them.
+struct MoveArgs {
+  const float* m12f;                           // the caller's matrices: 12 floats per instance
+  int32_t n_inst, n_entry, n_mesh, n_blas_nodes;
+  DevInstance* inst;                           // the instance table, one record per entry point
+  float* tlas_nodes; float* tlas_tris;         // the instance tree and its proxy records
+  float* blas_nodes; const float* blas_tris;   // the meshes' trees and their (unchanged) object-space records
+  QNode* qnodes;                               // the merged quantised array: the instance tree first, then every mesh's tree
+  const int32_t* range_off; const int32_t* ranges; const int32_t* proxy_rec; const int32_t* inst_mesh;
+  const float* mesh_box; const int32_t* mesh_base; const int32_t* node_mesh; const float* blas_tight;
+  float* tlas_tight;                           // 6 floats per node of the instance tree: the tight box below it
+  float* ent_box;                              // 6 floats per entry point: its world box (lo > hi: a bad matrix's, empty)
+  int32_t* inst_ok;                            // per instance: 1 = a good matrix
+  unsigned long long* state;                   // [0] the bits of E (binary64, >= 0), [1] bad matrices of this move, [2] since the upload, [3] meshes re-padded since the upload
+  unsigned long long* needed;                  // per mesh: the bits of the pad this placement asks for (binary64, >= 0)
+  float* pad_cur; int32_t* repad;              // per mesh: the pad its boxes carry; 1 = this move widens them
+  double extent;                               // the scene's extent without the instances (TwoLevelHost::scene_extent)
+  float mesh_pad_rel, mesh_pad_min;            // the meshes' relative pad and the floor of their absolute pad
+  float tlas_pad_rel, tlas_pad_abs;            // the instance tree builder's pad rule
+};
+constexpr double kMoveMaxReach = 1.0e18;       // an instance reaching further out than this (kRefitMaxCoord) has a bad matrix
+void launch_move_matrices(hipStream_t st, const MoveArgs& M);                  // begin + matrices + pads
+void launch_move_repad(hipStream_t st, const MoveArgs& M);
+void launch_move_entry_boxes(hipStream_t st, const MoveArgs& M, bool small);   // small: few records per entry point, one wave each
+void launch_move_tlas_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n);
+
 }  // namespace art

@@ -1,0 +1,281 @@
+// art_move.hip -- gfx950 kernels of art_move_instances_device: the instances of an instanced scene take new object -> world matrices.
+// Topology, entry points and the meshes' records stay as built; matrices and boxes are rewritten, in this order (one launch each, every
+// launch reads only what earlier launches wrote: gfx950's per-XCD L2s are not coherent within a launch):
+//
+//   k_move_begin        E = the scene's extent without the instances, this move's bad count = 0, every mesh's needed pad = 0.
+//   k_move_matrices     one lane per entry-point record: DevInstance::m, and minv in invert_3x4's arithmetic (art_instanced_build.cpp:
+//                       binary64, rounded once -- the bytes an upload writes).  The first n_inst lanes (one per instance) count the bad
+//                       matrices and raise E to the instance's reach (atomicMax on the bits of a non-negative binary64).
+//   k_move_pads_inst    one lane per instance: the upload's bound 8 * 2^-24 * (sum_j |minv_rj| * 3 E + |minv_r3|), maximised over the rows,
+//                       folded into needed[mesh].
+//   k_move_pads_mesh    one lane per mesh: repad = needed > current, current = max(current, needed).  Pads only grow.
+//   k_move_repad        one lane per node of the meshes' trees; a lane whose mesh is not re-padded returns at once.  The others do what
+//                       k_refit_level<4> does with inflate_abs = current[mesh].  The records never move, so the tight box below every
+//                       node is a constant of the plan and the whole forest is one launch, not one per level.  The entry words of the
+//                       merged quantised array are absolute and stay as stored: only planes and header are rewritten.
+//   k_move_entry_boxes  one workgroup per entry point: the three corners of every record below it through world_box's arithmetic
+//                       (binary64 products and sums, the four-term pad, one rounding) -- the upload's tight box -- and its proxy record.
+//   k_move_tlas_level   one launch per level of the instance tree, deepest first: a leaf child's box is its proxies' box under the
+//                       builder's pad rule, an inner child's the tight box below; quantised again, instance markers kept.
+//
+// A bad matrix (an element not finite, a determinant failing invert_3x4's test, or a reach beyond kMoveMaxReach) gives every entry
+// point of its instance an empty box, which the instance tree refit treats as art_refit.hip treats a box with a bad vertex.
+#include <hip/hip_runtime.h>
+
+#include "art_bvh.h"
+#include "art_kernels.h"
+
+namespace art {
+
+constexpr int kMoveBlock = 128;
+
+__device__ __forceinline__ bool move_invert_3x4(const float m[12], float out[12]) {      // art_instanced_build.cpp invert_3x4, expression for expression
+  const double a = m[0], b = m[1], c = m[2], d = m[4], e = m[5], f = m[6], g0 = m[8], h = m[9], i = m[10];
+  const double det = a * (e * i - f * h) - b * (d * i - f * g0) + c * (d * h - e * g0);
+  if (!(fabs(det) > 1.0e-300) || !isfinite(det)) return false;
+  const double r[9] = {(e * i - f * h) / det, (c * h - b * i) / det, (b * f - c * e) / det,
+                       (f * g0 - d * i) / det, (a * i - c * g0) / det, (c * d - a * f) / det,
+                       (d * h - e * g0) / det, (b * g0 - a * h) / det, (a * e - b * d) / det};
+  for (int row = 0; row < 3; ++row) {
+    for (int k = 0; k < 3; ++k) out[4 * row + k] = (float)r[3 * row + k];
+    out[4 * row + 3] = (float)-(r[3 * row] * (double)m[3] + r[3 * row + 1] * (double)m[7] + r[3 * row + 2] * (double)m[11]);
+  }
+  return true;
+}
+
+__device__ __forceinline__ double wave_max(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_down(v, off));
+  return v;
+}
+__device__ __forceinline__ double wave_min(double v) {
+  for (int off = 32; off > 0; off >>= 1) v = fmin(v, __shfl_down(v, off));
+  return v;
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_begin(const MoveArgs M) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (t == 0) { M.state[0] = (unsigned long long)__double_as_longlong(M.extent); M.state[1] = 0ull; }
+  if (t < M.n_mesh) M.needed[t] = 0ull;
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_matrices(const MoveArgs M) {
+  const int e = blockIdx.x * kMoveBlock + threadIdx.x;
+  double reach_max = 0.0;
+  bool first = false;
+  if (e < M.n_entry) {
+    DevInstance* const D = M.inst + e;
+    const int inst = D->inst;
+    float m[12], minv[12];
+    bool ok = true;
+    for (int k = 0; k < 12; ++k) { m[k] = M.m12f[12 * (size_t)inst + k]; ok = ok && isfinite(m[k]); }
+    const bool inv = ok && move_invert_3x4(m, minv);
+    ok = inv;
+    const float* mb = M.mesh_box + 6 * (size_t)M.inst_mesh[inst];
+    for (int r = 0; r < 3; ++r) {                                          // how far out the instance reaches in the world
+      double reach = fabs((double)m[4 * r + 3]);
+      for (int j = 0; j < 3; ++j) reach += fabs((double)m[4 * r + j]) * fmax(fabs((double)mb[j]), fabs((double)mb[j + 3]));
+      if (!(reach <= kMoveMaxReach)) ok = false;                           // (also a NaN)
+      else reach_max = fmax(reach_max, reach);
+    }
+    for (int k = 0; k < 12; ++k) { D->m[k] = m[k]; D->minv[k] = inv ? minv[k] : 0.0f; }
+    first = (e < M.n_inst);
+    if (first) {
+      M.inst_ok[e] = ok ? 1 : 0;
+      if (!ok) { atomicAdd(&M.state[1], 1ull); atomicAdd(&M.state[2], 1ull); }
+    }
+    if (!first || !ok) reach_max = 0.0;
+  }
+  const double wm = wave_max(reach_max);                                   // (every lane of the wave takes part)
+  if ((threadIdx.x & 63) == 0 && wm > 0.0) atomicMax(&M.state[0], (unsigned long long)__double_as_longlong(wm));
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_pads_inst(const MoveArgs M) {
+  const int i = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (i >= M.n_inst || !M.inst_ok[i]) return;
+  const double E = __longlong_as_double((long long)M.state[0]);
+  const float* q0 = M.inst[i].minv;
+  double best = 0.0;
+  for (int r = 0; r < 3; ++r) {
+    const float* q = q0 + 4 * r;
+    const double bound = 8.0 * 5.9604644775390625e-8 * ((fabs((double)q[0]) + fabs((double)q[1]) + fabs((double)q[2])) * 3.0 * E + fabs((double)q[3]));
+    if (isfinite(bound)) best = fmax(best, bound);
+  }
+  const unsigned long long bits = (unsigned long long)__double_as_longlong(best);
+  unsigned long long* const cell = M.needed + M.inst_mesh[i];
+  if (bits > *cell) atomicMax(cell, bits);                                 // (a stale read is a smaller value: the atomic is then issued for nothing, never skipped wrongly)
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_pads_mesh(const MoveArgs M) {
+  const int m = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (m >= M.n_mesh) return;
+  const double need = __longlong_as_double((long long)M.needed[m]);
+  const float nf = fmaxf(M.mesh_pad_min, (float)fmin(need, 1.0e30));
+  const bool rp = nf > M.pad_cur[m];
+  M.repad[m] = rp ? 1 : 0;
+  if (rp) { M.pad_cur[m] = nf; atomicAdd(&M.state[3], 1ull); }
+}
+
+// nd: a 4-wide packet whose good children carry padded boxes, bad[j]: children to be written as empty boxes.  Quantises, keeps the entry
+// words already stored in *dst (absolute offsets, instance markers), and writes the packet and the quantised node.
+__device__ __forceinline__ void move_store_node(float* nd, const bool bad[4], float4* np, QNode* dst) {
+  int32_t keep[4];
+#pragma unroll
+  for (int j = 0; j < 4; ++j) { keep[j] = __float_as_int(nd[4 * j + 3]); if (bad[j]) nd[4 * j + 3] = __int_as_float(-1); }   // hidden from quantise_node
+  QNode q;
+  quantise_node(nd, q);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) {
+    if (bad[j]) { nd[4 * j + 3] = __int_as_float(keep[j]); q.rec[j].c0 = 0x00ffffffu; q.rec[j].c1 = 0u; }   // lo = 255, hi = 0
+    q.rec[j].entry = dst->rec[j].entry;
+  }
+  *dst = q;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) np[k] = make_float4(nd[4 * k], nd[4 * k + 1], nd[4 * k + 2], nd[4 * k + 3]);
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_repad(const MoveArgs M) {
+  const int g = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (g >= M.n_blas_nodes) return;
+  const int mi = M.node_mesh[g];
+  if (!M.repad[mi]) return;
+  const int32_t nb = M.mesh_base[3 * mi], tb = M.mesh_base[3 * mi + 1], qb = M.mesh_base[3 * mi + 2];
+  if (tb < 0) return;
+  const float pad_abs = M.pad_cur[mi];
+  constexpr int W = 4;
+  float4* const np = reinterpret_cast<float4*>(M.blas_nodes + (size_t)g * 32);
+  float nd[32];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const float4 v = np[k]; nd[4 * k] = v.x; nd[4 * k + 1] = v.y; nd[4 * k + 2] = v.z; nd[4 * k + 3] = v.w; }
+  bool bad[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    bad[j] = false;
+    const int32_t ref = __float_as_int(nd[4 * j + 3]), cnt = __float_as_int(nd[4 * W + 4 * j + 3]);
+    if (ref < 0) continue;
+    float l[3], h[3];
+    if (cnt > 0) {
+      l[0] = l[1] = l[2] = INFINITY; h[0] = h[1] = h[2] = -INFINITY;
+      for (int r = 0; r < cnt && r < kMaxLeafTris; ++r) {
+        const float* tr = M.blas_tris + (size_t)kTriFloats * (size_t)(tb + ref + r);
+        for (int q = 0; q < 9; ++q) { const float v = tr[q]; l[q % 3] = fminf(l[q % 3], v); h[q % 3] = fmaxf(h[q % 3], v); }
+      }
+    } else {
+      const float* b = M.blas_tight + 6 * (size_t)(nb + ref);
+      l[0] = b[0]; l[1] = b[1]; l[2] = b[2]; h[0] = b[3]; h[1] = b[4]; h[2] = b[5];
+    }
+    float lo[3], hi[3];
+    pad_child_box(l, h, M.mesh_pad_rel, pad_abs, lo, hi);
+    for (int a = 0; a < 3; ++a) { nd[4 * j + a] = lo[a]; nd[4 * W + 4 * j + a] = hi[a]; }
+  }
+  move_store_node(nd, bad, np, M.qnodes + (size_t)qb + (size_t)(g - nb));
+}
+
+template <int B>
+__global__ __launch_bounds__(B) void k_move_entry_boxes(const MoveArgs M) {
+  const int e = blockIdx.x, tid = threadIdx.x;
+  const DevInstance* const D = M.inst + e;
+  float* const box = M.ent_box + 6 * (size_t)e;
+  if (!M.inst_ok[D->inst]) {                                               // (the same for the whole workgroup)
+    if (tid == 0) { box[0] = box[1] = box[2] = INFINITY; box[3] = box[4] = box[5] = -INFINITY; }
+    return;
+  }
+  double Mx[12];
+  for (int k = 0; k < 12; ++k) Mx[k] = (double)D->m[k];
+  double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, mag[3] = {0.0, 0.0, 0.0};
+  for (int k = M.range_off[e]; k < M.range_off[e + 1]; ++k) {
+    const int32_t first = M.ranges[2 * k], n3 = 3 * M.ranges[2 * k + 1];
+    for (int c = tid; c < n3; c += B) {
+      const float* p = M.blas_tris + (size_t)kTriFloats * (size_t)(first + c / 3) + 3 * (c % 3);
+      const double x = p[0], y = p[1], z = p[2];
+      for (int r = 0; r < 3; ++r) {                                        // world_box of art_instanced_build.cpp
+        const double a = Mx[4 * r] * x, b = Mx[4 * r + 1] * y, cc = Mx[4 * r + 2] * z, w = a + b + cc + Mx[4 * r + 3];
+        lo[r] = fmin(lo[r], w); hi[r] = fmax(hi[r], w);
+        mag[r] = fmax(mag[r], fabs(a) + fabs(b) + fabs(cc) + fabs(Mx[4 * r + 3]));
+      }
+    }
+  }
+  __shared__ double red[(B / 64) * 9];
+  for (int r = 0; r < 3; ++r) { lo[r] = wave_min(lo[r]); hi[r] = wave_max(hi[r]); mag[r] = wave_max(mag[r]); }
+  if (B > 64) {
+    if ((tid & 63) == 0) for (int r = 0; r < 3; ++r) { red[9 * (tid >> 6) + r] = lo[r]; red[9 * (tid >> 6) + 3 + r] = hi[r]; red[9 * (tid >> 6) + 6 + r] = mag[r]; }
+    __syncthreads();
+  }
+  if (tid != 0) return;
+  for (int w = 1; w < B / 64; ++w)
+    for (int r = 0; r < 3; ++r) { lo[r] = fmin(lo[r], red[9 * w + r]); hi[r] = fmax(hi[r], red[9 * w + 3 + r]); mag[r] = fmax(mag[r], red[9 * w + 6 + r]); }
+  float flo[3], fhi[3];
+  for (int r = 0; r < 3; ++r) {
+    const double pad = 1.0e-4 * (hi[r] - lo[r]) + 1.0e-5 * fmax(fabs(lo[r]), fabs(hi[r])) + 1.0e-6 * mag[r] + 1.0e-6;
+    flo[r] = (float)(lo[r] - pad); fhi[r] = (float)(hi[r] + pad);
+  }
+  for (int r = 0; r < 3; ++r) { box[r] = flo[r]; box[3 + r] = fhi[r]; }
+  float* const p = M.tlas_tris + (size_t)kTriFloats * (size_t)M.proxy_rec[e];   // ONE triangle whose corners span the box
+  p[0] = flo[0]; p[1] = flo[1]; p[2] = flo[2]; p[3] = fhi[0]; p[4] = fhi[1]; p[5] = fhi[2]; p[6] = flo[0]; p[7] = fhi[1]; p[8] = flo[2];
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_move_tlas_level(const MoveArgs M, const int32_t* __restrict__ level, int n) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (t >= n) return;
+  const int node = level[t];
+  constexpr int W = 4;
+  float4* const np = reinterpret_cast<float4*>(M.tlas_nodes + (size_t)node * 32);
+  float nd[32];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) { const float4 v = np[k]; nd[4 * k] = v.x; nd[4 * k + 1] = v.y; nd[4 * k + 2] = v.z; nd[4 * k + 3] = v.w; }
+  float tl[3] = {INFINITY, INFINITY, INFINITY}, th[3] = {-INFINITY, -INFINITY, -INFINITY};
+  bool bad[W];
+#pragma unroll
+  for (int j = 0; j < W; ++j) {
+    bad[j] = false;
+    const int32_t ref = __float_as_int(nd[4 * j + 3]), cnt = __float_as_int(nd[4 * W + 4 * j + 3]);
+    if (ref < 0) continue;
+    float l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
+    if (cnt > 0) {
+      for (int r = 0; r < cnt && r < kMaxLeafTris; ++r) {                   // the proxies of the leaf: each names its entry point (an empty box adds nothing)
+        const int32_t ent = __float_as_int(M.tlas_tris[(size_t)kTriFloats * (size_t)(ref + r) + 9]);
+        const float* b = M.ent_box + 6 * (size_t)ent;
+        for (int a = 0; a < 3; ++a) { l[a] = fminf(l[a], b[a]); h[a] = fmaxf(h[a], b[3 + a]); }
+      }
+    } else {
+      const float* b = M.tlas_tight + 6 * (size_t)ref;
+      for (int a = 0; a < 3; ++a) { l[a] = b[a]; h[a] = b[3 + a]; }
+    }
+    bad[j] = !(l[0] <= h[0]);                                               // nothing good below
+    if (bad[j]) {
+      for (int a = 0; a < 3; ++a) { nd[4 * j + a] = INFINITY; nd[4 * W + 4 * j + a] = INFINITY; }
+      continue;
+    }
+    for (int a = 0; a < 3; ++a) { tl[a] = fminf(tl[a], l[a]); th[a] = fmaxf(th[a], h[a]); }
+    float lo[3], hi[3];
+    pad_child_box(l, h, M.tlas_pad_rel, M.tlas_pad_abs, lo, hi);
+    for (int a = 0; a < 3; ++a) { nd[4 * j + a] = lo[a]; nd[4 * W + 4 * j + a] = hi[a]; }
+  }
+  float* const tb = M.tlas_tight + 6 * (size_t)node;
+  tb[0] = tl[0]; tb[1] = tl[1]; tb[2] = tl[2]; tb[3] = th[0]; tb[4] = th[1]; tb[5] = th[2];
+  move_store_node(nd, bad, np, M.qnodes + node);
+}
+
+static dim3 move_grid(int n) { return dim3((unsigned)((n + kMoveBlock - 1) / kMoveBlock)); }
+
+void launch_move_matrices(hipStream_t st, const MoveArgs& M) {
+  hipLaunchKernelGGL(k_move_begin, move_grid(M.n_mesh), dim3(kMoveBlock), 0, st, M);
+  hipLaunchKernelGGL(k_move_matrices, move_grid(M.n_entry), dim3(kMoveBlock), 0, st, M);
+  hipLaunchKernelGGL(k_move_pads_inst, move_grid(M.n_inst), dim3(kMoveBlock), 0, st, M);
+  hipLaunchKernelGGL(k_move_pads_mesh, move_grid(M.n_mesh), dim3(kMoveBlock), 0, st, M);
+}
+
+void launch_move_repad(hipStream_t st, const MoveArgs& M) {
+  hipLaunchKernelGGL(k_move_repad, move_grid(M.n_blas_nodes), dim3(kMoveBlock), 0, st, M);
+}
+
+void launch_move_entry_boxes(hipStream_t st, const MoveArgs& M, bool small) {
+  if (small) hipLaunchKernelGGL(k_move_entry_boxes<64>, dim3((unsigned)M.n_entry), dim3(64), 0, st, M);
+  else hipLaunchKernelGGL(k_move_entry_boxes<256>, dim3((unsigned)M.n_entry), dim3(256), 0, st, M);
+}
+
+void launch_move_tlas_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_move_tlas_level, move_grid(n), dim3(kMoveBlock), 0, st, M, level_nodes, n);
+}
+
+}  // namespace art

@@ -269,6 +269,28 @@ int  art_get_rebuild_info(ArtRebuildInfo* out);   /* cumulative since art_upload
 typedef struct ArtTreeCost { double root_area, node_visits, leaf_visits, tri_tests; } ArtTreeCost;
 int  art_get_tree_cost(ArtTreeCost* out);   /* device 0; waits for the library's stream */
 
+/* Moving the instances of an instanced scene.  m12f: device memory of the library's device, 12*n_instances
+ * floats: instance i's object -> world 3x4, row-major, in the order of ArtSceneDesc::instances.  Which mesh an instance shows and
+ * everything about the meshes stay as uploaded.  Kernels rewrite the instance table (m, and the inverse in invert_3x4's arithmetic:
+ * the bytes an upload would write), the world box and proxy record of every entry point (the upload's tight box), the instance tree's
+ * boxes (its topology, its entry points and the inst_open choice stay as built) and -- because the absolute pad of a mesh's boxes
+ * follows the inverse matrices of its instances -- the boxes of every mesh whose pad the new placement outgrows.  Pads only grow: a
+ * mesh's boxes are never narrower than an upload at the new transforms would make them.  Picture, ray count and hit records are those
+ * of art_upload_scene at the new transforms, bit for bit.  Stream-ordered exactly as art_refit_device is: work enqueued before the
+ * call sees the old placement, work enqueued after it the new one; the host waits only on the first call after an upload, which
+ * builds the plan.  Under art_init_devices every context is moved, the others from a peer copy of m12f.  Refused before anything is
+ * launched: no scene, a scene committed through gcore_commit_scene, a scene that is not instanced, n_instances other than the
+ * uploaded count, host memory or another device's memory.  A matrix with an element that is not finite, whose determinant fails
+ * the upload's test, or that places a coordinate of its mesh's box beyond 1e18 in magnitude (art_refit_device's limit for a vertex
+ * coordinate; the boxes are quantised by a loop that needs finite input) is a bad matrix: every entry point of its instance gets an empty box (no ray enters it) and the next
+ * art_synchronize fails with the count; a later good move or an upload clears that state.  After instances have travelled far the
+ * instance tree costs more to walk than the one a fresh art_upload_scene builds. */
+int  art_move_instances_device(const float* m12f, int64_t n_instances, void* hip_stream);
+/* moves = calls accepted, move_ms = HIP events around device 0's move kernels, plan_ms = host time of building the plans,
+ * bad_matrices = bad matrices counted on device 0 over all moves, repads = meshes whose boxes were re-padded, over all moves. */
+typedef struct ArtMoveInfo { uint64_t moves; double move_ms; double plan_ms; uint64_t bad_matrices; uint64_t repads; } ArtMoveInfo;
+int  art_get_move_info(ArtMoveInfo* out);   /* cumulative since art_upload_scene; waits for the moves enqueued so far */
+
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 int  art_get_stats(ArtStats* out);
 /* The wavefront stages around the trace kernel (device 0, cumulative since art_resize; cooperative schedule): GPU time per kind of
