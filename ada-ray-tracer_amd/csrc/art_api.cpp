@@ -7,6 +7,7 @@
 //            -> finish (inside-out radiance fold) -> accumulate (reference summation order)
 //   then resolve (gamma, clamp, pack) when the caller asks for the LDR image.
 //
+// The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_get_tree_cost): art_update.cpp.
 // There is no CPU fallback: every entry point that needs the GPU fails with art_last_error() set when
 // HIP reports no usable device.
 #include <hip/hip_runtime.h>
@@ -37,9 +38,6 @@ static std::vector<hipEvent_t> g_reduce_events;
 static double g_reduce_ms = 0.0; static int g_reduces = 0, g_reduce_path = 0;
 static bool g_multi_api = false;       // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
 static std::vector<hipEvent_t> g_reduce_free;     // event pairs folded into g_reduce_ms, ready for the next reduce (a host that downloads every frame re-uses two events)
-static ArtRefitInfo g_refit_info = ArtRefitInfo();   // art_get_refit_info: cumulative since the last upload
-static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
-static ArtMoveInfo g_move_info = ArtMoveInfo();      // art_get_move_info: the same
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
   for (hipEvent_t e : g_reduce_events) (void)hipEventDestroy(e);
@@ -87,32 +85,13 @@ static std::string g_err;
 
 int fail(const std::string& msg) { g_err = msg; return 1; }
 
-#define HIP_TRY(expr)                                                                       \
-  do {                                                                                      \
-    hipError_t _e = (expr);                                                                 \
-    if (_e != hipSuccess) return fail(std::string(#expr) + ": " + hipGetErrorString(_e));   \
-  } while (0)
-
 // make device k's context the current one (g_ctx) and its GPU the current HIP device
-static int use_dev(int k) {
+int use_dev(int k) {
   g_cur = &g_devs[k];
   if (g_cur->device >= 0) HIP_TRY(hipSetDevice(g_cur->device));
   return 0;
 }
-// multi-device loops leave device 0 current on every exit path
-struct Dev0Guard { ~Dev0Guard() { g_cur = &g_devs[0]; if (g_devs[0].device >= 0) (void)hipSetDevice(g_devs[0].device); } };
-
-template <typename T>
-static int upload(DevBuf& b, const std::vector<T>& v) {
-  b.release();
-  if (v.empty()) return 0;
-  HIP_TRY(hipMalloc(&b.p, v.size() * sizeof(T)));
-  b.bytes = v.size() * sizeof(T);
-  HIP_TRY(hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
-  return 0;
-}
-
-static int ensure(DevBuf& b, size_t bytes) {
+int ensure(DevBuf& b, size_t bytes) {
   if (b.bytes >= bytes && b.p) return 0;
   b.release();
   HIP_TRY(hipMalloc(&b.p, bytes));
@@ -127,26 +106,6 @@ void DevBuf::release() {
     chunks.clear(); reserved = 0; chunk_bytes = 0;
   } else if (p) (void)hipFree(p);
   p = nullptr; bytes = 0;
-}
-
-// the refit plan of a context goes with its scene (upload_scene, shutdown); its events are kept for the next plan
-static void release_refit(Ctx& c) {
-  Ctx::RefitPlan& R = c.refit;
-  R.b_idx.release(); R.b_levels.release(); R.b_tight.release(); R.b_bad.release(); R.b_stage.release();
-  R.level_off.clear();
-  for (hipEvent_t e : R.ev) R.ev_free.push_back(e);
-  R.ev.clear();
-  R.ready = false; R.unread = false; R.bad_last = R.bad_total = 0; R.bad_reported = true;
-}
-
-// the same for the move plan (art_move_instances_device)
-static void release_move(Ctx& c) {
-  Ctx::MovePlan& P = c.move;
-  P.b_plan.release(); P.b_work.release(); P.b_stage.release();
-  P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs();
-  for (hipEvent_t e : P.ev) P.ev_free.push_back(e);
-  P.ev.clear();
-  P.ready = false; P.unread = false; P.bad_last = 0; P.bad_reported = true;
 }
 
 // `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Ctx::paths_spread_mb: the driver
@@ -241,13 +200,34 @@ static int upload_scene_arrays(HostScene& hs) {
 
 // What the trace kernels can address and walk (art_upload_scene, art_rebuild_device): nodes and triangles by 32-bit byte offsets (the
 // 4-wide entry word keeps bit 31 for the leaf flag), quantised nodes for a 4-wide tree built on the GPU, at most kStackEntries on the stack.
-static int check_tree_limits(int width, int64_t n_nodes, int64_t n_tris, bool flat, bool gpu_built, bool have_qnodes, int stack) {
+int check_tree_limits(int width, int64_t n_nodes, int64_t n_tris, bool flat, bool gpu_built, bool have_qnodes, int stack) {
   const uint64_t off_limit = (width == 4) ? (1ull << 31) : (1ull << 32);
   if (flat && ((uint64_t)n_nodes * node_floats(width) * 4 >= (1ull << 32) || (uint64_t)n_tris * (width == 4 ? kQTriBytes : kTriBytes) >= off_limit))
     return fail("mesh too large: the trace kernel addresses nodes and triangles with 32-bit byte offsets (max ~33M triangles at width 4, ~89M at width 8)");
   if (width == 4 && n_nodes > 0 && gpu_built && !have_qnodes) return fail("internal: GPU build returned no quantised nodes");
   if (stack > kStackEntries) return fail("BVH traversal stack bound " + std::to_string(stack) + " exceeds " + std::to_string(kStackEntries));
   return 0;
+}
+
+void free_tree(GpuBvh& g) {
+  for (void* p : {(void*)g.nodes, (void*)g.tris, g.qnodes}) if (p) (void)hipFree(p);
+  g.nodes = nullptr; g.tris = nullptr; g.qnodes = nullptr;
+}
+
+void adopt_tree(Ctx& c, GpuBvh& g, int width) {
+  c.b_nodes.release(); c.b_tris.release(); c.b_qnodes.release();
+  c.b_qnodes.p = g.qnodes; c.b_qnodes.bytes = g.qnodes ? (size_t)g.n_nodes * kQNodeBytes : 0;
+  c.b_nodes.p = g.nodes; c.b_nodes.bytes = (size_t)g.n_nodes * node_floats(width) * 4;
+  c.b_tris.p = g.tris; c.b_tris.bytes = (size_t)g.n_tris * kTriFloats * 4;
+  g.nodes = nullptr; g.qnodes = nullptr; g.tris = nullptr;                // (owned by the context now)
+  c.bvh_stack_bound = std::max(8, g.max_stack);
+  c.blocks_per_cu = 0;   // re-query occupancy
+}
+
+int pad_tri_records(DevBuf& dst, const float* tris, int n, hipStream_t s) {      // (the 4-wide kernel reads triangle records padded to 64 bytes)
+  if (ensure(dst, (size_t)n * kQTriBytes)) return 1;
+  launch_pad_tris(s, tris, (float*)dst.p, n);
+  return hipGetLastError() == hipSuccess ? 0 : fail("padding the triangle records: kernel launch failed");
 }
 
 int upload_scene(const ArtSceneDesc* d) {
@@ -258,13 +238,12 @@ int upload_scene(const ArtSceneDesc* d) {
   const std::vector<float> tri9 = std::move(hs.deferred_tri9);                    // option bvh_builder >= 1: every device builds its own tree
   hs.deferred_tri9.clear();
   Dev0Guard guard;
-  g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo();
+  reset_update_info();
   for (int k = 0; k < g_ndev; ++k) {                                              // scene + BVH replicated on every GPU
     if (use_dev(k)) return 1;
     Ctx& c = g_ctx;
     if (c.refit.ready || c.move.ready) HIP_TRY(hipStreamSynchronize(c.stream));  // (a refit or a move still in flight reads the plan)
-    release_refit(c);
-    release_move(c);
+    release_updates(c);
     c.bvh_params = g_devs[0].bvh_params;
     if (ensure_device()) return 1;
     int dev_stack = hs.bvh.max_stack;
@@ -274,11 +253,8 @@ int upload_scene(const ArtSceneDesc* d) {
       GpuBvh g;
       const bool ok = build_bvh8_gpu((const float*)t9.p, (int)(tri9.size() / 9), c.bvh_params, c.stream, g, err);
       t9.release();
-      if (!ok) { if (g.nodes) (void)hipFree(g.nodes); if (g.tris) (void)hipFree(g.tris); if (g.qnodes) (void)hipFree(g.qnodes); return fail("GPU BVH build: " + err); }
-      c.b_nodes.release(); c.b_tris.release(); c.b_qnodes.release();
-      c.b_qnodes.p = g.qnodes; c.b_qnodes.bytes = g.qnodes ? (size_t)g.n_nodes * kQNodeBytes : 0;
-      c.b_nodes.p = g.nodes; c.b_nodes.bytes = (size_t)g.n_nodes * node_floats(c.bvh_params.width) * 4;
-      c.b_tris.p = g.tris; c.b_tris.bytes = (size_t)g.n_tris * kTriFloats * 4;
+      if (!ok) { free_tree(g); return fail("GPU BVH build: " + err); }
+      adopt_tree(c, g, c.bvh_params.width);
       dev_stack = g.max_stack;
       if (k == 0) {
         hs.bvh.width = c.bvh_params.width;
@@ -290,14 +266,11 @@ int upload_scene(const ArtSceneDesc* d) {
     if (check_tree_limits(hs.hdr.node_width, hs.hdr.n_nodes, hs.hdr.n_tris, hs.hdr.n_inst == 0, hs.gpu_built, c.b_qnodes.p != nullptr, dev_stack)) return 1;
     if (upload_scene_arrays(hs)) return 1;
     c.b_qtris.release();
-    if (hs.hdr.node_width == 4 && hs.hdr.n_tris > 0 && hs.hdr.n_inst == 0) {       // 64-byte padded copy of the triangle records for the 4-wide kernel
-      if (ensure(c.b_qtris, (size_t)hs.hdr.n_tris * kQTriBytes)) return 1;
-      launch_pad_tris(c.stream, (const float*)c.b_tris.p, (float*)c.b_qtris.p, hs.hdr.n_tris);
-      HIP_TRY(hipStreamSynchronize(c.stream));
-    } else if (hs.hdr.n_inst > 0) {                      // instanced scene: the meshes' object-space records, padded the same way
-      const int nrec = (int)(hs.two.blas_tris.size() / kTriFloats);
-      if (ensure(c.b_qtris, (size_t)nrec * kQTriBytes)) return 1;
-      launch_pad_tris(c.stream, (const float*)c.b_blas_tris.p, (float*)c.b_qtris.p, nrec);
+    // the 4-wide kernel's padded records: the flat tree's, or (instanced scene) the meshes' object-space records
+    const bool inst = hs.hdr.n_inst > 0;
+    const int nrec = inst ? (int)(hs.two.blas_tris.size() / kTriFloats) : (hs.hdr.node_width == 4 ? hs.hdr.n_tris : 0);
+    if (nrec > 0) {
+      if (pad_tri_records(c.b_qtris, (const float*)(inst ? c.b_blas_tris.p : c.b_tris.p), nrec, c.stream)) return 1;
       HIP_TRY(hipStreamSynchronize(c.stream));
     }
     c.bvh_stack_bound = std::max(8, dev_stack);
@@ -754,51 +727,6 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   return 0;
 }
 
-// the current context's refit event pairs and bad-vertex counters; its stream is idle (a refit on another stream is ordered before the
-// context stream's later work, refit_device)
-static int fold_refit() {
-  Ctx& c = g_ctx;
-  Ctx::RefitPlan& R = c.refit;
-  for (size_t i = 0; i + 1 < R.ev.size(); i += 2) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(R.ev[i + 1]));
-    HIP_TRY(hipEventElapsedTime(&ms, R.ev[i], R.ev[i + 1]));
-    if (&c == &g_devs[0]) g_refit_info.refit_ms += ms;
-    R.ev_free.push_back(R.ev[i]); R.ev_free.push_back(R.ev[i + 1]);
-  }
-  R.ev.clear();
-  if (R.unread && R.b_bad.p) {
-    unsigned long long w[2];
-    HIP_TRY(hipMemcpy(w, R.b_bad.p, sizeof w, hipMemcpyDeviceToHost));
-    R.unread = false;
-    R.bad_last = w[0]; R.bad_total = w[1]; R.bad_reported = (w[0] == 0);
-    if (&c == &g_devs[0]) g_refit_info.bad_vertices = w[1];
-  }
-  return 0;
-}
-
-// the same for the moves of an instanced scene: event pairs, and the counters k_move_matrices / k_move_pads_mesh keep
-static int fold_move() {
-  Ctx& c = g_ctx;
-  Ctx::MovePlan& P = c.move;
-  for (size_t i = 0; i + 1 < P.ev.size(); i += 2) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventSynchronize(P.ev[i + 1]));
-    HIP_TRY(hipEventElapsedTime(&ms, P.ev[i], P.ev[i + 1]));
-    if (&c == &g_devs[0]) g_move_info.move_ms += ms;
-    P.ev_free.push_back(P.ev[i]); P.ev_free.push_back(P.ev[i + 1]);
-  }
-  P.ev.clear();
-  if (P.unread && P.args.state) {
-    unsigned long long w[4];
-    HIP_TRY(hipMemcpy(w, P.args.state, sizeof w, hipMemcpyDeviceToHost));
-    P.unread = false;
-    P.bad_last = w[1]; P.bad_reported = (w[1] == 0);
-    if (&c == &g_devs[0]) { g_move_info.bad_matrices = w[2]; g_move_info.repads = w[3]; }
-  }
-  return 0;
-}
-
 static int synchronize_one();
 int synchronize() {
   Dev0Guard guard;
@@ -819,18 +747,7 @@ static int synchronize_one() {
   }
   c.pass_events.clear();
   if (collect_timing()) return 1;
-  if (fold_refit()) return 1;
-  if (!c.refit.bad_reported) {            // (reported once per bad refit, like a lost path; the boxes stay empty until a good refit or an upload)
-    c.refit.bad_reported = true;
-    return fail("art_refit_device: " + std::to_string(c.refit.bad_last) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes "
-                "holding them are empty (no ray enters them) until a good refit or art_upload_scene");
-  }
-  if (fold_move()) return 1;
-  if (!c.move.bad_reported) {             // (the same convention for a bad instance matrix)
-    c.move.bad_reported = true;
-    return fail("art_move_instances_device: " + std::to_string(c.move.bad_last) + " instance matrix(es) with an element that is not finite, without an inverse, or "
-                "reaching beyond 1e18; their instances are empty (no ray enters them) until a good move or art_upload_scene");
-  }
+  if (sync_updates()) return 1;
   // a lost path is a wrong picture, not a statistic -- a stage that found a path without an output item, a ray its bank has no
   // record for, a material its instantiation was not compiled for, or a staged trace record that did not name the hit slot its position
   // implies (art_shade.h emit_ray) fails the call that waits for the render
@@ -1042,7 +959,7 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
 
 // ---- device-resident ray queries (art_trace_rays_device / art_occluded_rays_device) ----------------------------------------------
 // A caller's buffer must be device memory of this context's GPU, and (where HIP knows the allocation) hold `bytes` from `p` on.
-static int check_device_ptr(const void* p, size_t bytes, const char* what) {
+int check_device_ptr(const void* p, size_t bytes, const char* what) {
   Ctx& c = g_ctx;
   hipPointerAttribute_t at;
   std::memset(&at, 0, sizeof at);
@@ -1056,9 +973,9 @@ static int check_device_ptr(const void* p, size_t bytes, const char* what) {
   return 0;
 }
 
-// hits (closest hit) or occluded (occlusion): n rays in slices of query_slice, every launch on `st` (nullptr: the context stream;
-// hipStreamLegacy: the null stream).  The scratch (b_query, b_queue, b_ovf) is shared with the render passes on the context stream:
-// on another stream the query waits for what the context stream holds, and the context stream waits for the query.
+// hits (closest hit) or occluded (occlusion): n rays in slices of query_slice, every launch on the stream `st` names (StreamOrder).
+// The scratch (b_query, b_queue, b_ovf) is shared with the render passes on the context stream: on another stream the query waits
+// for what the context stream holds, and the context stream waits for the query.
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st) {
   Ctx& c = g_ctx;
   const char* name = hits ? "art_trace_rays_device" : "art_occluded_rays_device";
@@ -1073,8 +990,8 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
       (tfar && check_device_ptr(tfar, 4 * N, "tfar")) || (hits && check_device_ptr(hits, sizeof(ArtHit) * N, "hits_out")) ||
       (occluded && check_device_ptr(occluded, N, "occluded_out")))
     return 1;
-  hipStream_t qs = (st == nullptr) ? c.stream : (st == hipStreamLegacy ? nullptr : st);
-  const bool other = (qs != c.stream);
+  StreamOrder order(c, st);
+  const hipStream_t qs = order.qs;
   const size_t S = (size_t)std::min<int64_t>(n, c.query_slice);
   const bool coop = (kernel == TRACE_COOP);
   int entries; bool ovf; stack_plan(kernel, entries, ovf);
@@ -1082,16 +999,12 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
   const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
   if (grow) {                           // growing the scratch may wait: nothing enqueued may still use the old buffers
     HIP_TRY(hipStreamSynchronize(c.stream));
-    if (other) HIP_TRY(hipStreamSynchronize(qs));
+    if (order.other()) HIP_TRY(hipStreamSynchronize(qs));
     if (ensure(c.b_query, q_bytes)) return 1;
     if (coop && ensure(c.b_queue, (S + kRecSlack) * kTraceRecBytes)) return 1;
     if (coop && ovf && ensure(c.b_ovf, S * sizeof(int))) return 1;
   }
-  if (other) {
-    for (hipEvent_t& e : c.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c.q_ev[0], c.stream));
-    HIP_TRY(hipStreamWaitEvent(qs, c.q_ev[0], 0));
-  }
+  if (order.enter()) return 1;
   char* base = (char*)c.b_query.p;
   unsigned long long* sink = (unsigned long long*)base;
   float* f = (float*)(base + 256);
@@ -1117,497 +1030,8 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
     if (hipGetLastError() != hipSuccess) rc = fail(std::string(name) + ": kernel launch failed");
   }
   c.stream = saved_stream; c.trace_kernel = saved_kernel; c.count_tests = saved_count;
-  if (other) {                          // (also after a failed launch: what was enqueued stays ordered before the context stream's next work)
-    HIP_TRY(hipEventRecord(c.q_ev[1], qs));
-    HIP_TRY(hipStreamWaitEvent(c.stream, c.q_ev[1], 0));
-  }
+  if (order.leave()) return 1;          // (also after a failed launch)
   return rc;
-}
-
-// ---- moving geometry (art_refit_device, art_refit.hip) ----------------------------------------------------------------------------
-// The plan of the current context: its tree's inner nodes grouped by depth (read back from HBM once: the GPU builders leave the tree
-// there only, and every builder orders its nodes differently), the mesh's index triples, the tight-box scratch and the counters.
-static int build_refit_plan(const HostScene& hs) {
-  Ctx& c = g_ctx;
-  Ctx::RefitPlan& R = c.refit;
-  const auto t0 = std::chrono::steady_clock::now();
-  const int W = c.scene.node_width, NF = node_floats(W), N = c.scene.n_nodes;
-  if (N < 1 || !c.b_nodes.p) return fail("art_refit_device: the scene has no tree");
-  std::vector<float> nodes((size_t)N * NF);
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
-  std::vector<int32_t> order;
-  order.reserve((size_t)N);
-  order.push_back(0);
-  R.level_off.assign(1, 0);
-  for (size_t b = 0; b < order.size();) {                       // breadth first: level L = order[level_off[L] .. level_off[L + 1])
-    const size_t e = order.size();
-    for (size_t i = b; i < e; ++i) {
-      const float* nd = &nodes[(size_t)order[i] * NF];
-      for (int j = 0; j < W; ++j) {
-        int32_t ref, cnt;
-        std::memcpy(&ref, nd + 4 * j + 3, 4); std::memcpy(&cnt, nd + 4 * W + 4 * j + 3, 4);
-        if (ref < 0) continue;
-        if (cnt > 0) {
-          if (cnt > kMaxLeafTris || (int64_t)ref + cnt > (int64_t)c.scene.n_tris) return fail("art_refit_device: internal: a leaf outside the triangle records");
-          continue;
-        }
-        if (ref >= N || order.size() >= (size_t)N) return fail("art_refit_device: internal: the uploaded nodes do not form a tree");
-        order.push_back(ref);
-      }
-    }
-    R.level_off.push_back((int)e);
-    b = e;
-  }
-  if (order.size() != (size_t)N) return fail("art_refit_device: internal: unreachable nodes in the uploaded tree");
-  if (upload(R.b_idx, hs.m_idx) || upload(R.b_levels, order) || ensure(R.b_tight, (size_t)N * 6 * sizeof(float)) || ensure(R.b_bad, 2 * sizeof(unsigned long long)))
-    return 1;
-  HIP_TRY(hipMemset(R.b_bad.p, 0, 2 * sizeof(unsigned long long)));
-  if (&c != &g_devs[0]) {
-    if (ensure(R.b_stage, 2 * 12 * (size_t)hs.m_nverts)) return 1;
-    if (!R.done_ev) HIP_TRY(hipEventCreateWithFlags(&R.done_ev, hipEventDisableTiming));
-  } else if (g_ndev > 1 && !R.ready_ev) HIP_TRY(hipEventCreateWithFlags(&R.ready_ev, hipEventDisableTiming));
-  g_refit_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  R.ready = true;
-  return 0;
-}
-
-// the current context's refit on stream s, from positions (and normals) in this context's device memory
-static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hipStream_t s) {
-  Ctx& c = g_ctx;
-  Ctx::RefitPlan& P = c.refit;
-  RefitArgs A;
-  std::memset(&A, 0, sizeof A);
-  A.pos3f = pos; A.nrm3f = nrm; A.idx = (const int32_t*)P.b_idx.p;
-  A.nverts = hs.m_nverts; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.n_recs = c.scene.n_tris;
-  A.tris = (float*)c.b_tris.p; A.qtris = (float*)c.b_qtris.p; A.m_shade = (float*)c.b_m_shade.p;
-  A.bad = (unsigned long long*)P.b_bad.p;
-  A.nodes = (float*)c.b_nodes.p; A.qnodes = (c.scene.node_width == 4) ? (QNode*)c.b_qnodes.p : nullptr;
-  A.tight = (float*)P.b_tight.p;
-  A.width = c.scene.node_width; A.inflate_rel = c.bvh_params.inflate_rel; A.inflate_abs = c.bvh_params.inflate_abs;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (P.ev_free.size() >= 2) { e1 = P.ev_free.back(); P.ev_free.pop_back(); e0 = P.ev_free.back(); P.ev_free.pop_back(); }
-  else {
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
-  }
-  if (hipEventRecord(e0, s) != hipSuccess) { P.ev_free.push_back(e0); P.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
-  P.ev.push_back(e0); P.ev.push_back(e1);
-  struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop{e1, s};      // recorded on every way out
-  P.unread = true;
-  HIP_TRY(hipMemsetAsync(A.bad, 0, sizeof(unsigned long long), s));      // [0]: this refit's bad vertices ([1] counts since the upload)
-  launch_refit_tris(s, A);
-  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                 // deepest level first
-    launch_refit_level(s, A, (const int32_t*)P.b_levels.p + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(std::string("art_refit_device: kernel launch failed: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// Every check comes before the first launch.  Device 0 refits on the caller's stream, ordered against its context stream with the
-// query events; every other context waits for the caller's stream, copies the positions (and normals) from device 0 and refits on its
-// own stream, and the caller's stream waits for it -- so the caller may overwrite its buffers after whatever it enqueues next.
-int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
-  Ctx& c0 = g_devs[0];
-  if (!c0.scene_ready) return fail("art_refit_device: no scene uploaded");
-  HostScene& hs = c0.host_scene;
-  if (c0.scene.n_inst > 0) return fail("art_refit_device: the scene is instanced (n_instances > 0); only the tree of a flat CLOSEST mesh is refitted");
-  if (hs.m_nverts == 0) return fail("art_refit_device: the scene has no ART_MESH_CLOSEST mesh");
-  if (hs.gcore_seam) return fail("art_refit_device: the scene was committed through gcore_commit_scene, whose host copy of the tree a refit would leave stale");
-  if (nverts != hs.m_nverts) return fail("art_refit_device: nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.m_nverts));
-  if (!pos) return fail("art_refit_device: null pos3f");
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  const size_t bytes = 12 * (size_t)nverts;
-  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (!g_ctx.refit.ready && build_refit_plan(hs)) return 1;
-  }
-  if (use_dev(0)) return 1;
-  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
-  const bool other = (qs != c0.stream);
-  if (other) {
-    for (hipEvent_t& e : c0.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c0.q_ev[0], c0.stream));
-    HIP_TRY(hipStreamWaitEvent(qs, c0.q_ev[0], 0));
-  }
-  // from here on the tree in HBM changes: the host copies of it (art_export_bvh's cache, a host-built tree) and of the positions are stale
-  std::vector<float>().swap(hs.bvh.nodes); std::vector<float>().swap(hs.bvh.tris); std::vector<uint32_t>().swap(hs.bvh.qnodes);
-  std::vector<float>().swap(hs.m_pos);
-  hs.refitted = true;
-  if (nrm) hs.m_shade_stale = true;                                      // (art_trace_rays reads the shading records on the host)
-  g_refit_info.refits += 1;
-  int rc = 0;
-  if (g_ndev > 1 && hipEventRecord(c0.refit.ready_ev, qs) != hipSuccess) rc = fail("art_refit_device: hipEventRecord failed");
-  if (!rc) rc = refit_one(hs, pos, nrm, qs);
-  for (int k = 1; k < g_ndev && !rc; ++k) {
-    if (use_dev(k)) { rc = 1; break; }
-    Ctx& c = g_ctx;
-    float* sp = (float*)c.refit.b_stage.p;
-    float* sn = nrm ? sp + 3 * (size_t)nverts : nullptr;
-    if (hipStreamWaitEvent(c.stream, c0.refit.ready_ev, 0) != hipSuccess || hipMemcpyPeerAsync(sp, c.device, pos, c0.device, bytes, c.stream) != hipSuccess ||
-        (nrm && hipMemcpyPeerAsync(sn, c.device, nrm, c0.device, bytes, c.stream) != hipSuccess)) { rc = fail("art_refit_device: copy to device " + std::to_string(c.device) + " failed"); break; }
-    rc = refit_one(hs, sp, sn, c.stream);
-    if (hipEventRecord(c.refit.done_ev, c.stream) != hipSuccess || hipStreamWaitEvent(qs, c.refit.done_ev, 0) != hipSuccess) rc = rc ? rc : fail("art_refit_device: event ordering failed");
-  }
-  if (use_dev(0)) return 1;
-  if (other) {                          // (also after a failure: what was enqueued stays ordered before the context stream's next work)
-    HIP_TRY(hipEventRecord(c0.q_ev[1], qs));
-    HIP_TRY(hipStreamWaitEvent(c0.stream, c0.q_ev[1], 0));
-  }
-  return rc;
-}
-
-// ---- moving instances (art_move_instances_device, art_move.hip) -------------------------------------------------------------------
-// The plan of the current context, from the two-level build the upload kept: MovePlanHost's arrays in one buffer, the kernels' own
-// arrays in another, and MoveArgs pointing into both and into the scene's arrays.
-static int build_move_plan(const HostScene& hs) {
-  Ctx& c = g_ctx;
-  Ctx::MovePlan& P = c.move;
-  const auto t0 = std::chrono::steady_clock::now();
-  MovePlanHost H;
-  std::string err;
-  if (!build_move_plan_host(hs.two, H, err)) return fail("art_move_instances_device: " + err);
-  const size_t n_entry = hs.two.entry.size(), n_inst = hs.two.inst.size(), nm = (size_t)H.n_mesh, n_tlas = (size_t)hs.two.tlas.n_nodes, n_blas = H.node_mesh.size();
-  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
-      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != hs.two.blas_tris.size() * 4)
-    return fail("art_move_instances_device: internal: the arrays in HBM are not the kept build's");
-  std::vector<uint8_t> img;                                                // every section 16-byte aligned
-  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (bytes) std::memcpy(&img[at], p, bytes); return at; };
-  const size_t o_roff = put(H.range_off.data(), H.range_off.size() * 4), o_rng = put(H.ranges.data(), H.ranges.size() * 4), o_prox = put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
-  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbox = put(H.mesh_box.data(), H.mesh_box.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
-  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_tight = put(H.blas_tight.data(), H.blas_tight.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
-  if (upload(P.b_plan, img)) return 1;
-  std::vector<uint8_t> work;
-  auto room = [&](size_t bytes) { const size_t at = work.size(); work.resize(at + ((bytes + 15) & ~(size_t)15), 0); return at; };
-  const size_t w_state = room(4 * 8), w_need = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
-  std::memcpy(&work[w_pad], H.pad_abs.data(), nm * 4);
-  if (upload(P.b_work, work)) return 1;
-  const char* pb = (const char*)P.b_plan.p; char* wb = (char*)P.b_work.p;
-  MoveArgs& A = P.args;
-  A = MoveArgs();
-  A.n_inst = (int32_t)n_inst; A.n_entry = (int32_t)n_entry; A.n_mesh = (int32_t)nm; A.n_blas_nodes = (int32_t)n_blas;
-  A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p;
-  A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
-  A.range_off = (const int32_t*)(pb + o_roff); A.ranges = (const int32_t*)(pb + o_rng); A.proxy_rec = (const int32_t*)(pb + o_prox); A.inst_mesh = (const int32_t*)(pb + o_imesh);
-  A.mesh_box = (const float*)(pb + o_mbox); A.mesh_base = (const int32_t*)(pb + o_mbase); A.node_mesh = (const int32_t*)(pb + o_nmesh); A.blas_tight = (const float*)(pb + o_tight);
-  A.state = (unsigned long long*)(wb + w_state); A.needed = (unsigned long long*)(wb + w_need); A.tlas_tight = (float*)(wb + w_tight); A.ent_box = (float*)(wb + w_box);
-  A.inst_ok = (int32_t*)(wb + w_ok); A.pad_cur = (float*)(wb + w_pad); A.repad = (int32_t*)(wb + w_repad);
-  A.extent = (double)hs.two.scene_extent; A.mesh_pad_rel = hs.two.mesh_pad_rel; A.mesh_pad_min = hs.two.mesh_pad_min;
-  const BvhBuildParams tp;                                                 // the instance tree builder's pad rule: the defaults, as build_two_level_host applied them
-  A.tlas_pad_rel = tp.inflate_rel; A.tlas_pad_abs = tp.inflate_abs;
-  P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off;
-  P.small_entries = H.records <= 64 * (int64_t)n_entry;
-  if (&c != &g_devs[0]) {
-    if (ensure(P.b_stage, 48 * n_inst)) return 1;
-    if (!P.done_ev) HIP_TRY(hipEventCreateWithFlags(&P.done_ev, hipEventDisableTiming));
-  } else if (g_ndev > 1 && !P.ready_ev) HIP_TRY(hipEventCreateWithFlags(&P.ready_ev, hipEventDisableTiming));
-  g_move_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  P.ready = true;
-  return 0;
-}
-
-// the current context's move on stream s, from matrices in this context's device memory
-static int move_one(const float* m12f, hipStream_t s) {
-  Ctx& c = g_ctx;
-  Ctx::MovePlan& P = c.move;
-  MoveArgs A = P.args;
-  A.m12f = m12f;
-  // event pairs of earlier moves that have completed are folded here, so that a host that moves every frame and never synchronises
-  // keeps a list as long as the moves in flight
-  size_t kept = 0;
-  for (size_t i = 0; i + 1 < P.ev.size(); i += 2) {
-    float ms = 0.0f;
-    if (hipEventQuery(P.ev[i + 1]) == hipSuccess && hipEventElapsedTime(&ms, P.ev[i], P.ev[i + 1]) == hipSuccess) {
-      if (&c == &g_devs[0]) g_move_info.move_ms += ms;
-      P.ev_free.push_back(P.ev[i]); P.ev_free.push_back(P.ev[i + 1]);
-    } else { P.ev[kept] = P.ev[i]; P.ev[kept + 1] = P.ev[i + 1]; kept += 2; }
-  }
-  P.ev.resize(kept);
-  (void)hipGetLastError();                                                 // (hipErrorNotReady of a pair still in flight)
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  if (P.ev_free.size() >= 2) { e1 = P.ev_free.back(); P.ev_free.pop_back(); e0 = P.ev_free.back(); P.ev_free.pop_back(); }
-  else {
-    HIP_TRY(hipEventCreate(&e0));
-    if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
-  }
-  if (hipEventRecord(e0, s) != hipSuccess) { P.ev_free.push_back(e0); P.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
-  P.ev.push_back(e0); P.ev.push_back(e1);
-  struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop{e1, s};      // recorded on every way out
-  P.unread = true;
-  launch_move_matrices(s, A);
-  launch_move_repad(s, A);
-  launch_move_entry_boxes(s, A, P.small_entries);
-  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                   // deepest level first
-    launch_move_tlas_level(s, A, P.levels + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(std::string("art_move_instances_device: kernel launch failed: ") + hipGetErrorString(e));
-  return 0;
-}
-
-// Every check comes before the first launch; the streams are ordered as refit_device orders them.
-int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st) {
-  Ctx& c0 = g_devs[0];
-  if (!c0.scene_ready) return fail("art_move_instances_device: no scene uploaded");
-  HostScene& hs = c0.host_scene;
-  if (hs.gcore_seam) return fail("art_move_instances_device: the scene was committed through gcore_commit_scene, which keeps its own instances");
-  if (c0.scene.n_inst <= 0) return fail("art_move_instances_device: the scene is not instanced (n_instances = 0); art_refit_device moves the vertices of a flat mesh");
-  if (n_instances != (int64_t)c0.scene.n_inst) return fail("art_move_instances_device: n_instances " + std::to_string(n_instances) + " differs from the uploaded scene's " + std::to_string(c0.scene.n_inst));
-  if (!m12f) return fail("art_move_instances_device: null m12f");
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  const size_t bytes = 48 * (size_t)n_instances;
-  if (check_device_ptr(m12f, bytes, "m12f")) return 1;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (!g_ctx.move.ready && build_move_plan(hs)) return 1;
-  }
-  if (use_dev(0)) return 1;
-  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
-  const bool other = (qs != c0.stream);
-  if (other) {
-    for (hipEvent_t& e : c0.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    HIP_TRY(hipEventRecord(c0.q_ev[0], c0.stream));
-    HIP_TRY(hipStreamWaitEvent(qs, c0.q_ev[0], 0));
-  }
-  hs.inst_stale = true;                                                    // (art_trace_rays reads the matrices on the host)
-  g_move_info.moves += 1;
-  int rc = 0;
-  if (g_ndev > 1 && hipEventRecord(c0.move.ready_ev, qs) != hipSuccess) rc = fail("art_move_instances_device: hipEventRecord failed");
-  if (!rc) rc = move_one(m12f, qs);
-  for (int k = 1; k < g_ndev && !rc; ++k) {
-    if (use_dev(k)) { rc = 1; break; }
-    Ctx& c = g_ctx;
-    float* sm = (float*)c.move.b_stage.p;
-    if (hipStreamWaitEvent(c.stream, c0.move.ready_ev, 0) != hipSuccess || hipMemcpyPeerAsync(sm, c.device, m12f, c0.device, bytes, c.stream) != hipSuccess) {
-      rc = fail("art_move_instances_device: copy to device " + std::to_string(c.device) + " failed"); break;
-    }
-    rc = move_one(sm, c.stream);
-    if (hipEventRecord(c.move.done_ev, c.stream) != hipSuccess || hipStreamWaitEvent(qs, c.move.done_ev, 0) != hipSuccess) rc = rc ? rc : fail("art_move_instances_device: event ordering failed");
-  }
-  if (use_dev(0)) return 1;
-  if (other) {                          // (also after a failure: what was enqueued stays ordered before the context stream's next work)
-    HIP_TRY(hipEventRecord(c0.q_ev[1], qs));
-    HIP_TRY(hipStreamWaitEvent(c0.stream, c0.q_ev[1], 0));
-  }
-  return rc;
-}
-
-// cumulative since the upload; waits for every context's stream (a move on the caller's stream is ordered before it)
-int get_move_info(ArtMoveInfo* out) {
-  if (!out) return fail("null ArtMoveInfo");
-  Dev0Guard guard;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (!g_ctx.device_ready) continue;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    if (fold_move()) return 1;
-  }
-  *out = g_move_info;
-  return 0;
-}
-
-// ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
-// What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
-// anywhere leaves every context's scene as it was.
-struct PendingTree {
-  int device = -1; GpuBvh g; DevBuf qtris;
-  DevBuf idx;                                  // the mesh's index triples where no refit plan held them (or, after the commit, the plan's)
-  ~PendingTree() {
-    if (device >= 0) (void)hipSetDevice(device);
-    if (g.nodes) (void)hipFree(g.nodes);
-    if (g.tris) (void)hipFree(g.tris);
-    if (g.qnodes) (void)hipFree(g.qnodes);
-    qtris.release(); idx.release();
-  }
-};
-
-// the current context's new tree on stream s, from positions in this context's device memory: gather, count the bad vertices, build,
-// check, pad.  Returns with s idle.  Nothing of the context's scene is touched.
-static int rebuild_one(const HostScene& hs, const BvhBuildParams& bp, const float* pos, hipStream_t s, PendingTree& out, float* gather_ms) {
-  Ctx& c = g_ctx;
-  const int32_t n_prims = (int32_t)(hs.m_idx.size() / 3);
-  DevBuf t9, bad;
-  struct Free { DevBuf &a, &b; ~Free() { a.release(); b.release(); } } fr{t9, bad};
-  out.device = c.device;
-  const int32_t* idx = (const int32_t*)c.refit.b_idx.p;                   // the refit plan keeps the index triples in HBM
-  if (!c.refit.ready || !idx) { if (upload(out.idx, hs.m_idx)) return 1; idx = (const int32_t*)out.idx.p; }
-  if (ensure(t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(bad, sizeof(unsigned long long))) return 1;
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-  GatherArgs G;
-  G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)t9.p; G.bad = (unsigned long long*)bad.p;
-  HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-  HIP_TRY(hipEventRecord(ev.a, s));
-  launch_gather_tri9(s, G);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev.b, s));
-  unsigned long long n_bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  if (gather_ms) HIP_TRY(hipEventElapsedTime(gather_ms, ev.a, ev.b));
-  if (n_bad) return fail("art_rebuild_device: " + std::to_string(n_bad) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
-  std::string err;
-  if (!build_bvh8_gpu((const float*)t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
-  if (check_tree_limits(bp.width, out.g.n_nodes, out.g.n_tris, true, true, out.g.qnodes != nullptr, out.g.max_stack)) return 1;
-  if (bp.width == 4) {                                                    // 64-byte padded copy of the triangle records for the 4-wide kernel
-    if (ensure(out.qtris, (size_t)out.g.n_tris * kQTriBytes)) return 1;
-    launch_pad_tris(s, out.g.tris, (float*)out.qtris.p, out.g.n_tris);
-    HIP_TRY(hipGetLastError());
-  }
-  HIP_TRY(hipStreamSynchronize(s));
-  return 0;
-}
-
-// The current context takes its new tree (its streams are idle, its refit events are folded).  The one step that can fail, the copy
-// of the new header to d_scene, comes first: when it does (a lost device), the context's buffers are still the old ones.
-static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
-  Ctx& c = g_ctx;
-  {
-    DevScene s = c.scene;
-    s.nodes = t.g.nodes; s.tris = t.g.tris; s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
-    HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
-  }
-  if (!t.idx.p) { t.idx = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
-  release_refit(c);                                                       // the next refit plans against the new tree
-  c.bvh_params = g_devs[0].bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
-  c.b_nodes.release(); c.b_qnodes.release(); c.b_tris.release(); c.b_qtris.release();
-  GpuBvh& g = t.g;
-  c.b_nodes.p = g.nodes; c.b_nodes.bytes = (size_t)g.n_nodes * node_floats(bp.width) * 4;
-  c.b_qnodes.p = g.qnodes; c.b_qnodes.bytes = g.qnodes ? (size_t)g.n_nodes * kQNodeBytes : 0;
-  c.b_tris.p = g.tris; c.b_tris.bytes = (size_t)g.n_tris * kTriFloats * 4;
-  c.b_qtris = t.qtris;
-  g.nodes = nullptr; g.qnodes = nullptr; g.tris = nullptr; t.qtris = DevBuf();      // (owned by the context now)
-  DevScene& s = c.scene;
-  s.nodes = (const float*)c.b_nodes.p; s.tris = (const float*)c.b_tris.p;
-  s.n_nodes = g.n_nodes; s.n_tris = g.n_tris; s.node_width = bp.width;
-  c.bvh_stack_bound = std::max(8, g.max_stack);
-  c.blocks_per_cu = 0;   // re-query occupancy
-  return 0;
-}
-
-// Every check comes before the first launch; every context builds into new buffers before any context's scene changes.
-int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
-  const auto t0 = std::chrono::steady_clock::now();
-  Ctx& c0 = g_devs[0];
-  if (!c0.scene_ready) return fail("art_rebuild_device: no scene uploaded");
-  HostScene& hs = c0.host_scene;
-  if (c0.scene.n_inst > 0) return fail("art_rebuild_device: the scene is instanced (n_instances > 0); only the tree of a flat CLOSEST mesh is rebuilt");
-  if (hs.m_nverts == 0) return fail("art_rebuild_device: the scene has no ART_MESH_CLOSEST mesh");
-  if (hs.gcore_seam) return fail("art_rebuild_device: the scene was committed through gcore_commit_scene, whose host copy of the tree a rebuild would leave stale");
-  if (nverts != hs.m_nverts) return fail("art_rebuild_device: nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.m_nverts));
-  if (!pos) return fail("art_rebuild_device: null pos3f");
-  BvhBuildParams bp = c0.bvh_params;
-  if (bp.spatial_alpha >= 0.0f) return fail("art_rebuild_device: option bvh_spatial_splits is set; reference splitting exists in the host builder only (art_upload_scene builds that tree)");
-  if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
-  if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  const size_t bytes = 12 * (size_t)nverts;
-  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
-  hipStream_t qs = (st == nullptr) ? c0.stream : (st == hipStreamLegacy ? nullptr : st);
-  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  }
-  if (use_dev(0)) return 1;
-  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
-  std::vector<PendingTree> built((size_t)g_ndev);
-  std::vector<DevBuf> stage((size_t)g_ndev);                              // contexts k > 0: peer copy of pos (+ nrm)
-  struct FreeStage { std::vector<DevBuf>& v; ~FreeStage() { for (size_t k = 0; k < v.size(); ++k) { if (v[k].p && g_devs[k].device >= 0) (void)hipSetDevice(g_devs[k].device); v[k].release(); } } } fs{stage};
-  float gather_ms = 0.0f;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    Ctx& c = g_ctx;
-    const float* p = pos;
-    if (k > 0) {
-      if (ensure(stage[(size_t)k], nrm ? 2 * bytes : bytes)) return 1;
-      float* sp = (float*)stage[(size_t)k].p;
-      if (hipMemcpyPeer(sp, c.device, pos, c0.device, bytes) != hipSuccess || (nrm && hipMemcpyPeer(sp + 3 * (size_t)nverts, c.device, nrm, c0.device, bytes) != hipSuccess))
-        return fail("art_rebuild_device: copy to device " + std::to_string(c.device) + " failed");
-      p = sp;
-    }
-    if (rebuild_one(hs, bp, p, k == 0 ? qs : c.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
-  }
-  // everything else that can fail without a lost device comes before the first swap: the refit events and counters of every context
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_refit()) return 1; }
-  // ---- commit: from here on the scene changes.  No step below allocates or waits for anything but its own launch; a failure here
-  // means the device is lost, and is the one case in which contexts may end up with different trees.
-  const double build_ms = built[0].g.build_ms;
-  const int32_t n_nodes = built[0].g.n_nodes, n_tris = built[0].g.n_tris, max_stack = built[0].g.max_stack;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k) || commit_tree(bp, built[(size_t)k])) return 1;
-    if (k > 0) continue;
-    hs.hdr.n_nodes = n_nodes; hs.hdr.n_tris = n_tris; hs.hdr.node_width = bp.width;
-    hs.bvh.width = bp.width; hs.bvh.n_nodes = n_nodes; hs.bvh.n_tris = n_tris; hs.bvh.max_stack = max_stack;
-    hs.bvh_build_ms = build_ms; hs.gpu_built = true; hs.refitted = false;
-    // the host copies of the old tree and of the positions are stale
-    std::vector<float>().swap(hs.bvh.nodes); std::vector<float>().swap(hs.bvh.tris); std::vector<uint32_t>().swap(hs.bvh.qnodes);
-    std::vector<float>().swap(hs.m_pos);
-  }
-  for (int k = 0; k < g_ndev && nrm; ++k) {                               // the shading records: k_refit_tris' normals branch, no triangle records (n_recs = 0)
-    if (use_dev(k)) return 1;
-    Ctx& c = g_ctx;
-    const hipStream_t s = (k == 0) ? qs : c.stream;
-    const float* n = (k == 0) ? nrm : (const float*)stage[(size_t)k].p + 3 * (size_t)nverts;
-    RefitArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.nrm3f = n; A.idx = (const int32_t*)built[(size_t)k].idx.p; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.m_shade = (float*)c.b_m_shade.p;
-    hs.m_shade_stale = true;                                              // (art_trace_rays reads the shading records on the host)
-    launch_refit_tris(s, A);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("art_rebuild_device: rewriting the shading records failed");
-  }
-  g_rebuild_info.rebuilds += 1; g_rebuild_info.gather_ms += gather_ms; g_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
-  g_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
-}
-
-int get_rebuild_info(ArtRebuildInfo* out) {
-  if (!out) return fail("null ArtRebuildInfo");
-  *out = g_rebuild_info;
-  return 0;
-}
-
-// device 0's tree as it lies in HBM (a refit on another stream is ordered before the context stream's later work)
-int get_tree_cost(ArtTreeCost* out) {
-  if (!out) return fail("null ArtTreeCost");
-  Ctx& c = g_devs[0];
-  if (!c.scene_ready) return fail("art_get_tree_cost: no scene uploaded");
-  if (c.scene.n_inst > 0) return fail("art_get_tree_cost: the scene is instanced (n_instances > 0); the figure is defined for the tree of a flat CLOSEST mesh");
-  if (c.scene.n_nodes < 1 || !c.b_nodes.p) return fail("art_get_tree_cost: the scene has no tree (no ART_MESH_CLOSEST mesh)");
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  DevBuf sums;
-  struct Free { DevBuf& b; ~Free() { b.release(); } } fr{sums};
-  if (ensure(sums, 4 * sizeof(double))) return 1;
-  double h[4] = {0.0, 0.0, 0.0, 0.0};
-  HIP_TRY(hipMemsetAsync(sums.p, 0, sizeof h, c.stream));
-  launch_tree_cost(c.stream, (const float*)c.b_nodes.p, c.scene.n_nodes, c.scene.node_width, (double*)sums.p);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(h, sums.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  out->root_area = h[3];
-  const bool any = h[3] > 0.0;                                            // (no usable child box under the root: no ray enters the tree)
-  out->node_visits = 1.0 + (any ? h[0] / h[3] : 0.0);
-  out->leaf_visits = any ? h[1] / h[3] : 0.0;
-  out->tri_tests = any ? h[2] / h[3] : 0.0;
-  return 0;
-}
-
-// cumulative since the upload; waits for every context's stream (a refit on the caller's stream is ordered before it)
-int get_refit_info(ArtRefitInfo* out) {
-  if (!out) return fail("null ArtRefitInfo");
-  Dev0Guard guard;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (!g_ctx.device_ready) continue;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-    if (fold_refit()) return 1;
-  }
-  *out = g_refit_info;
-  return 0;
 }
 
 void shutdown() {
@@ -1633,14 +1057,7 @@ void shutdown() {
     for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
     for (hipEvent_t e : c.pass_events) (void)hipEventDestroy(e);
     for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
-    release_refit(c);
-    for (hipEvent_t e : c.refit.ev_free) (void)hipEventDestroy(e);
-    if (c.refit.ready_ev) (void)hipEventDestroy(c.refit.ready_ev);
-    if (c.refit.done_ev) (void)hipEventDestroy(c.refit.done_ev);
-    release_move(c);
-    for (hipEvent_t e : c.move.ev_free) (void)hipEventDestroy(e);
-    if (c.move.ready_ev) (void)hipEventDestroy(c.move.ready_ev);
-    if (c.move.done_ev) (void)hipEventDestroy(c.move.done_ev);
+    destroy_updates(c);
     for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
     c.b_reduced.release();
     if (c.own_stream) (void)hipStreamDestroy(c.own_stream);

@@ -21,6 +21,15 @@ struct DevBuf {
   void release();
 };
 
+// What every kind of device-side scene update (art_update.cpp) keeps per context besides its own plan.
+struct UpdateLane {
+  std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's update kernels: not yet folded / free for reuse
+  hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // device 0: the caller's data is ready (contexts k > 0 wait for it); k > 0: this context's update is done
+  DevBuf b_stage;                                    // contexts k > 0: peer copy of the caller's data
+  bool unread = false;                               // an update was enqueued whose counters no fold has read yet
+  uint64_t bad_last = 0; bool bad_reported = true;   // bad items (vertices, matrices) of the last update read; a synchronize reported them (or there were none)
+};
+
 struct Ctx {
   int device = -1; bool device_ready = false; int num_cus = 0; int lds_per_cu = 160 * 1024; std::string arch;
   hipStream_t stream = nullptr;
@@ -45,26 +54,19 @@ struct Ctx {
   // the GPU builders may number the nodes differently on every device
   struct RefitPlan {
     bool ready = false;
-    DevBuf b_idx, b_levels, b_tight, b_bad, b_stage;   // index triples | node ids level by level, root first | tight box per node (24 B) | bad-vertex counters | contexts k > 0: peer copy of pos (+ nrm)
+    DevBuf b_idx, b_levels, b_tight, b_bad;            // index triples | node ids level by level, root first | tight box per node (24 B) | bad-vertex counters
     std::vector<int> level_off;                        // level L: b_levels[level_off[L] .. level_off[L + 1])
-    std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's refit kernels: not yet folded / free for reuse
-    hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // device 0: the caller's positions are ready (contexts k > 0 wait for it); k > 0: this context's refit is done
-    bool unread = false;                               // a refit was enqueued whose bad-vertex count no fold has read yet
-    uint64_t bad_last = 0, bad_total = 0;              // bad vertices of the last refit read / since the upload
-    bool bad_reported = true;                          // the last refit's bad vertices were reported by a synchronize (or there were none)
+    uint64_t bad_total = 0;                            // bad vertices since the upload
+    UpdateLane lane;                                   // (b_stage: peer copy of pos (+ nrm))
   } refit;
   // art_move_instances_device (art_move.hip): the plan is built on the first move after an upload (the upload drops it)
   struct MovePlan {
     bool ready = false;
-    DevBuf b_plan, b_work, b_stage;                    // MovePlanHost's arrays, one after the other | what the kernels write (MoveArgs) | contexts k > 0: peer copy of the matrices
+    DevBuf b_plan, b_work;                             // MovePlanHost's arrays, one after the other | what the kernels write (MoveArgs)
     MoveArgs args = MoveArgs();                        // everything but m12f
     std::vector<int> level_off; const int32_t* levels = nullptr;   // the instance tree's level L: levels[level_off[L] .. level_off[L + 1])
     bool small_entries = false;                        // few records per entry point: one wave each (launch_move_entry_boxes)
-    std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's move kernels: not yet folded / free for reuse
-    hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // as RefitPlan's
-    bool unread = false;                               // a move was enqueued whose counters no fold has read yet
-    uint64_t bad_last = 0;                             // bad matrices of the last move read
-    bool bad_reported = true;                          // ... were reported by a synchronize (or there were none)
+    UpdateLane lane;                                   // (b_stage: peer copy of the matrices)
   } move;
   int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
@@ -136,6 +138,44 @@ extern Ctx* g_cur;
 extern std::mutex g_mu;
 
 int fail(const std::string& msg);
+
+#define HIP_TRY(expr)                                                                       \
+  do {                                                                                      \
+    hipError_t _e = (expr);                                                                 \
+    if (_e != hipSuccess) return ::art::fail(std::string(#expr) + ": " + hipGetErrorString(_e));   \
+  } while (0)
+
+int use_dev(int k);                   // make device k's context the current one (g_ctx) and its GPU the current HIP device
+struct Dev0Guard { ~Dev0Guard() { g_cur = &g_devs[0]; if (g_devs[0].device >= 0) (void)hipSetDevice(g_devs[0].device); } };   // multi-device loops leave device 0 current on every exit path
+int ensure(DevBuf& b, size_t bytes);
+template <typename T>
+int upload(DevBuf& b, const std::vector<T>& v) {
+  b.release();
+  if (v.empty()) return 0;
+  HIP_TRY(hipMalloc(&b.p, v.size() * sizeof(T)));
+  b.bytes = v.size() * sizeof(T);
+  HIP_TRY(hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
+  return 0;
+}
+int check_device_ptr(const void* p, size_t bytes, const char* what);
+int check_tree_limits(int width, int64_t n_nodes, int64_t n_tris, bool flat, bool gpu_built, bool have_qnodes, int stack);
+struct GpuBvh;
+void free_tree(GpuBvh& g);                                             // a built tree nobody adopted (current device: the tree's)
+void adopt_tree(Ctx& c, GpuBvh& g, int width);                         // c's b_nodes / b_qnodes / b_tris become g's arrays (g gives them up)
+int pad_tri_records(DevBuf& dst, const float* tris, int n, hipStream_t s);   // dst = the 64-byte padded copy of n triangle records, enqueued on s
+// ---- device-side scene updates (art_update.cpp) ----
+// The stream a caller names (nullptr: the context stream; HIP's legacy handle: the null stream).  Where it is another stream, enter()
+// makes it wait for what the context stream holds and leave() makes the context stream wait for it.
+struct StreamOrder {
+  Ctx& c; hipStream_t cs, qs;
+  StreamOrder(Ctx& ctx, hipStream_t st);
+  bool other() const { return qs != cs; }
+  int enter(), leave();               // (leave() on every way out past enter(), also after a failed launch)
+};
+void release_updates(Ctx& c);         // the plans go with the scene (upload, rebuild); their events are kept for the next plan
+void destroy_updates(Ctx& c);         // shutdown
+void reset_update_info();             // the figures are cumulative since the last upload
+int sync_updates();                   // art_synchronize, current context, stream idle: fold the event pairs and counters, report a bad update once
 int ensure_device();
 int upload_scene(const ArtSceneDesc* d);
 int resize(int w, int h);

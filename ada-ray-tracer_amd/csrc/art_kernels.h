@@ -93,7 +93,7 @@ void launch_query_pack(hipStream_t st, const QueryArgs& Q);
 void launch_query_finalize(hipStream_t st, const DevScene& S, const QueryArgs& Q);
 void launch_query_occluded(hipStream_t st, const QueryArgs& Q);
 
-// refit of the CLOSEST mesh's tree in place (art_refit.hip, art_api.cpp art_refit_device)
+// refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex
 struct RefitArgs {
   const float* pos3f; const float* nrm3f;      // the caller's new vertex data (nrm3f nullptr: keep the normals)
@@ -108,7 +108,7 @@ struct RefitArgs {
 void launch_refit_tris(hipStream_t st, const RefitArgs& R);
 void launch_refit_level(hipStream_t st, const RefitArgs& R, const int32_t* level_nodes, int n);
 
-// a new tree from moved vertices and the cost figure of the tree in HBM (art_rebuild.hip, art_api.cpp art_rebuild_device / art_get_tree_cost)
+// a new tree from moved vertices and the cost figure of the tree in HBM (art_rebuild.hip, art_update.cpp art_rebuild_device / art_get_tree_cost)
 struct GatherArgs {
   const float* pos3f; const int32_t* idx;      // the caller's vertex positions, the mesh's index triples
   int64_t nverts; int32_t n_prims;
@@ -119,7 +119,7 @@ void launch_gather_tri9(hipStream_t st, const GatherArgs& G);
 // sums4 (zeroed by the caller): half areas of the inner child slots | of the leaf slots | of the leaf slots x triangle count | of the root's union
 void launch_tree_cost(hipStream_t st, const float* nodes, int n_nodes, int width, double* sums4);
 
-// the instances of an instanced scene move (art_move.hip, art_api.cpp art_move_instances_device).  Everything but m12f is the library's:
+// the instances of an instanced scene move (art_move.hip, art_update.cpp art_move_instances_device).  Everything but m12f is the library's:
 // the scene's arrays in HBM and the plan (art_instanced_build.h MovePlanHost) next to them.
 struct MoveArgs {
   const float* m12f;                           // the caller's matrices: 12 floats per instance

@@ -9,21 +9,23 @@
 //   k_move_pads_inst    one lane per instance: the upload's bound 8 * 2^-24 * (sum_j |minv_rj| * 3 E + |minv_r3|), maximised over the rows,
 //                       folded into needed[mesh].
 //   k_move_pads_mesh    one lane per mesh: repad = needed > current, current = max(current, needed).  Pads only grow.
-//   k_move_repad        one lane per node of the meshes' trees; a lane whose mesh is not re-padded returns at once.  The others do what
-//                       k_refit_level<4> does with inflate_abs = current[mesh].  The records never move, so the tight box below every
-//                       node is a constant of the plan and the whole forest is one launch, not one per level.  The entry words of the
-//                       merged quantised array are absolute and stay as stored: only planes and header are rewritten.
+//   k_move_repad        one lane per node of the meshes' trees; a lane whose mesh is not re-padded returns at once.  The others run
+//                       refit_node (art_refit_node.h: the rules of a node refit are stated there) with inflate_abs = current[mesh].  The
+//                       records never move, so the tight box below every node is a constant of the plan and the whole forest is one
+//                       launch, not one per level, and no tight union is written.  The entry words of the merged quantised array are
+//                       absolute and stay as stored: only planes and header are rewritten.
 //   k_move_entry_boxes  one workgroup per entry point: the three corners of every record below it through world_box's arithmetic
 //                       (binary64 products and sums, the four-term pad, one rounding) -- the upload's tight box -- and its proxy record.
-//   k_move_tlas_level   one launch per level of the instance tree, deepest first: a leaf child's box is its proxies' box under the
-//                       builder's pad rule, an inner child's the tight box below; quantised again, instance markers kept.
+//   k_move_tlas_level   one launch per level of the instance tree, deepest first: refit_node with a leaf child's box taken from its
+//                       proxies' entry points under the builder's pad rule, an inner child's from the tight box below; instance markers kept.
 //
 // A bad matrix (an element not finite, a determinant failing invert_3x4's test, or a reach beyond kMoveMaxReach) gives every entry
-// point of its instance an empty box, which the instance tree refit treats as art_refit.hip treats a box with a bad vertex.
+// point of its instance an empty box, which refit_node treats as it treats a box with a bad vertex.
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
 #include "art_kernels.h"
+#include "art_refit_node.h"
 
 namespace art {
 
@@ -115,24 +117,6 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_pads_mesh(const MoveArgs M)
   if (rp) { M.pad_cur[m] = nf; atomicAdd(&M.state[3], 1ull); }
 }
 
-// nd: a 4-wide packet whose good children carry padded boxes, bad[j]: children to be written as empty boxes.  Quantises, keeps the entry
-// words already stored in *dst (absolute offsets, instance markers), and writes the packet and the quantised node.
-__device__ __forceinline__ void move_store_node(float* nd, const bool bad[4], float4* np, QNode* dst) {
-  int32_t keep[4];
-#pragma unroll
-  for (int j = 0; j < 4; ++j) { keep[j] = __float_as_int(nd[4 * j + 3]); if (bad[j]) nd[4 * j + 3] = __int_as_float(-1); }   // hidden from quantise_node
-  QNode q;
-  quantise_node(nd, q);
-#pragma unroll
-  for (int j = 0; j < 4; ++j) {
-    if (bad[j]) { nd[4 * j + 3] = __int_as_float(keep[j]); q.rec[j].c0 = 0x00ffffffu; q.rec[j].c1 = 0u; }   // lo = 255, hi = 0
-    q.rec[j].entry = dst->rec[j].entry;
-  }
-  *dst = q;
-#pragma unroll
-  for (int k = 0; k < 8; ++k) np[k] = make_float4(nd[4 * k], nd[4 * k + 1], nd[4 * k + 2], nd[4 * k + 3]);
-}
-
 __global__ __launch_bounds__(kMoveBlock) void k_move_repad(const MoveArgs M) {
   const int g = blockIdx.x * kMoveBlock + threadIdx.x;
   if (g >= M.n_blas_nodes) return;
@@ -141,33 +125,12 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_repad(const MoveArgs M) {
   const int32_t nb = M.mesh_base[3 * mi], tb = M.mesh_base[3 * mi + 1], qb = M.mesh_base[3 * mi + 2];
   if (tb < 0) return;
   const float pad_abs = M.pad_cur[mi];
-  constexpr int W = 4;
-  float4* const np = reinterpret_cast<float4*>(M.blas_nodes + (size_t)g * 32);
-  float nd[32];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { const float4 v = np[k]; nd[4 * k] = v.x; nd[4 * k + 1] = v.y; nd[4 * k + 2] = v.z; nd[4 * k + 3] = v.w; }
-  bool bad[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    bad[j] = false;
-    const int32_t ref = __float_as_int(nd[4 * j + 3]), cnt = __float_as_int(nd[4 * W + 4 * j + 3]);
-    if (ref < 0) continue;
-    float l[3], h[3];
-    if (cnt > 0) {
-      l[0] = l[1] = l[2] = INFINITY; h[0] = h[1] = h[2] = -INFINITY;
-      for (int r = 0; r < cnt && r < kMaxLeafTris; ++r) {
-        const float* tr = M.blas_tris + (size_t)kTriFloats * (size_t)(tb + ref + r);
-        for (int q = 0; q < 9; ++q) { const float v = tr[q]; l[q % 3] = fminf(l[q % 3], v); h[q % 3] = fmaxf(h[q % 3], v); }
-      }
-    } else {
-      const float* b = M.blas_tight + 6 * (size_t)(nb + ref);
-      l[0] = b[0]; l[1] = b[1]; l[2] = b[2]; h[0] = b[3]; h[1] = b[4]; h[2] = b[5];
-    }
-    float lo[3], hi[3];
-    pad_child_box(l, h, M.mesh_pad_rel, pad_abs, lo, hi);
-    for (int a = 0; a < 3; ++a) { nd[4 * j + a] = lo[a]; nd[4 * W + 4 * j + a] = hi[a]; }
-  }
-  move_store_node(nd, bad, np, M.qnodes + (size_t)qb + (size_t)(g - nb));
+  refit_node<4, QEntries::kKeep>(M.blas_nodes + (size_t)g * 32, M.qnodes + (size_t)qb + (size_t)(g - nb), nullptr, M.mesh_pad_rel, pad_abs,
+                                 [&](int, int32_t ref, int32_t cnt, float l[3], float h[3]) {
+    if (cnt > 0) (void)records_box(M.blas_tris + (size_t)kTriFloats * (size_t)(tb + ref), cnt, l, h);      // (the records never move: always good)
+    else (void)stored_box(M.blas_tight + 6 * (size_t)(nb + ref), l, h);
+    return true;
+  });
 }
 
 template <int B>
@@ -217,42 +180,17 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_tlas_level(const MoveArgs M
   const int t = blockIdx.x * kMoveBlock + threadIdx.x;
   if (t >= n) return;
   const int node = level[t];
-  constexpr int W = 4;
-  float4* const np = reinterpret_cast<float4*>(M.tlas_nodes + (size_t)node * 32);
-  float nd[32];
-#pragma unroll
-  for (int k = 0; k < 8; ++k) { const float4 v = np[k]; nd[4 * k] = v.x; nd[4 * k + 1] = v.y; nd[4 * k + 2] = v.z; nd[4 * k + 3] = v.w; }
-  float tl[3] = {INFINITY, INFINITY, INFINITY}, th[3] = {-INFINITY, -INFINITY, -INFINITY};
-  bool bad[W];
-#pragma unroll
-  for (int j = 0; j < W; ++j) {
-    bad[j] = false;
-    const int32_t ref = __float_as_int(nd[4 * j + 3]), cnt = __float_as_int(nd[4 * W + 4 * j + 3]);
-    if (ref < 0) continue;
-    float l[3] = {INFINITY, INFINITY, INFINITY}, h[3] = {-INFINITY, -INFINITY, -INFINITY};
-    if (cnt > 0) {
-      for (int r = 0; r < cnt && r < kMaxLeafTris; ++r) {                   // the proxies of the leaf: each names its entry point (an empty box adds nothing)
-        const int32_t ent = __float_as_int(M.tlas_tris[(size_t)kTriFloats * (size_t)(ref + r) + 9]);
-        const float* b = M.ent_box + 6 * (size_t)ent;
-        for (int a = 0; a < 3; ++a) { l[a] = fminf(l[a], b[a]); h[a] = fmaxf(h[a], b[3 + a]); }
-      }
-    } else {
-      const float* b = M.tlas_tight + 6 * (size_t)ref;
-      for (int a = 0; a < 3; ++a) { l[a] = b[a]; h[a] = b[3 + a]; }
+  refit_node<4, QEntries::kKeep>(M.tlas_nodes + (size_t)node * 32, M.qnodes + node, M.tlas_tight + 6 * (size_t)node, M.tlas_pad_rel, M.tlas_pad_abs,
+                                 [&](int, int32_t ref, int32_t cnt, float l[3], float h[3]) {
+    if (cnt <= 0) return stored_box(M.tlas_tight + 6 * (size_t)ref, l, h);
+    l[0] = l[1] = l[2] = INFINITY; h[0] = h[1] = h[2] = -INFINITY;
+    for (int r = 0; r < cnt && r < kMaxLeafTris; ++r) {                     // the proxies of the leaf: each names its entry point (an empty box adds nothing)
+      const int32_t ent = __float_as_int(M.tlas_tris[(size_t)kTriFloats * (size_t)(ref + r) + 9]);
+      const float* b = M.ent_box + 6 * (size_t)ent;
+      for (int a = 0; a < 3; ++a) { l[a] = fminf(l[a], b[a]); h[a] = fmaxf(h[a], b[3 + a]); }
     }
-    bad[j] = !(l[0] <= h[0]);                                               // nothing good below
-    if (bad[j]) {
-      for (int a = 0; a < 3; ++a) { nd[4 * j + a] = INFINITY; nd[4 * W + 4 * j + a] = INFINITY; }
-      continue;
-    }
-    for (int a = 0; a < 3; ++a) { tl[a] = fminf(tl[a], l[a]); th[a] = fmaxf(th[a], h[a]); }
-    float lo[3], hi[3];
-    pad_child_box(l, h, M.tlas_pad_rel, M.tlas_pad_abs, lo, hi);
-    for (int a = 0; a < 3; ++a) { nd[4 * j + a] = lo[a]; nd[4 * W + 4 * j + a] = hi[a]; }
-  }
-  float* const tb = M.tlas_tight + 6 * (size_t)node;
-  tb[0] = tl[0]; tb[1] = tl[1]; tb[2] = tl[2]; tb[3] = th[0]; tb[4] = th[1]; tb[5] = th[2];
-  move_store_node(nd, bad, np, M.qnodes + node);
+    return l[0] <= h[0];                                                    // false: nothing good below
+  });
 }
 
 static dim3 move_grid(int n) { return dim3((unsigned)((n + kMoveBlock - 1) / kMoveBlock)); }

@@ -1,0 +1,555 @@
+// art_update.cpp -- the device-side scene updates of the C ABI (include/art_hip.h): art_refit_device (art_refit.hip), art_rebuild_device
+// (art_rebuild.hip + the GPU builders), art_move_instances_device (art_move.hip) and art_get_tree_cost.  What the kinds share is written
+// once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
+// lane of timing events and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
+// Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
+// out; the context stream is ordered after the update also when a launch failed; device 0 is current on every exit path.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "art_api_internal.h"
+#include "art_lbvh.h"
+
+namespace art {
+
+static ArtRefitInfo g_refit_info = ArtRefitInfo();         // art_get_refit_info: cumulative since the last upload
+static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
+static ArtMoveInfo g_move_info = ArtMoveInfo();            // art_get_move_info: the same
+void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); }
+// ---- the caller's stream ----------------------------------------------------------------------------------------------------------
+StreamOrder::StreamOrder(Ctx& ctx, hipStream_t st) : c(ctx), cs(ctx.stream), qs(st == nullptr ? ctx.stream : (st == hipStreamLegacy ? nullptr : st)) {}
+int StreamOrder::enter() {
+  if (!other()) return 0;
+  for (hipEvent_t& e : c.q_ev) if (!e) HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+  HIP_TRY(hipEventRecord(c.q_ev[0], cs));
+  HIP_TRY(hipStreamWaitEvent(qs, c.q_ev[0], 0));
+  return 0;
+}
+int StreamOrder::leave() {              // what was enqueued stays ordered before the context stream's next work
+  if (!other()) return 0;
+  HIP_TRY(hipEventRecord(c.q_ev[1], qs));
+  HIP_TRY(hipStreamWaitEvent(cs, c.q_ev[1], 0));
+  return 0;
+}
+
+// ---- the lane of one kind of update in one context --------------------------------------------------------------------------------
+// the current context's part of a new plan: contexts k > 0 stage the caller's data, device 0 signals when that data is ready
+static int plan_lane(UpdateLane& L, size_t stage_bytes) {
+  if (g_cur != &g_devs[0]) {
+    if (ensure(L.b_stage, stage_bytes)) return 1;
+    if (!L.done_ev) HIP_TRY(hipEventCreateWithFlags(&L.done_ev, hipEventDisableTiming));
+  } else if (g_ndev > 1 && !L.ready_ev) HIP_TRY(hipEventCreateWithFlags(&L.ready_ev, hipEventDisableTiming));
+  return 0;
+}
+
+// Completed event pairs -> *ms_sum (nullptr: not wanted), the pairs back to the free list.  wait: every pair is waited for; else pairs still
+// in flight stay listed, so that a host that updates every frame and never synchronises keeps a list as long as the updates in flight.
+static int fold_lane(UpdateLane& L, bool wait, double* ms_sum) {
+  size_t kept = 0; int rc = 0;
+  for (size_t i = 0; i + 1 < L.ev.size(); i += 2) {
+    float ms = 0.0f;
+    hipError_t e = rc ? hipErrorNotReady : (wait ? hipEventSynchronize(L.ev[i + 1]) : hipEventQuery(L.ev[i + 1]));
+    if (e == hipSuccess) e = hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]);
+    if (e == hipSuccess) { if (ms_sum) *ms_sum += ms; L.ev_free.push_back(L.ev[i]); L.ev_free.push_back(L.ev[i + 1]); continue; }
+    if (wait && !rc) rc = fail(std::string("update event pair: ") + hipGetErrorString(e));
+    L.ev[kept] = L.ev[i]; L.ev[kept + 1] = L.ev[i + 1]; kept += 2;
+  }
+  L.ev.resize(kept);
+  (void)hipGetLastError();                                                 // (hipErrorNotReady of a pair still in flight)
+  return rc;
+}
+
+// A timed update on stream s: start() takes an event pair from the free list (or creates one), records its first event and marks the
+// lane unread; the second event is recorded when the timer leaves scope, on every way out.
+struct LaneTimer {
+  hipEvent_t end = nullptr; hipStream_t s = nullptr;
+  int start(UpdateLane& L, hipStream_t stream) {
+    hipEvent_t e0 = nullptr, e1 = nullptr;
+    if (L.ev_free.size() >= 2) { e1 = L.ev_free.back(); L.ev_free.pop_back(); e0 = L.ev_free.back(); L.ev_free.pop_back(); }
+    else {
+      HIP_TRY(hipEventCreate(&e0));
+      if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
+    }
+    if (hipEventRecord(e0, stream) != hipSuccess) { L.ev_free.push_back(e0); L.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
+    L.ev.push_back(e0); L.ev.push_back(e1);
+    end = e1; s = stream; L.unread = true;
+    return 0;
+  }
+  ~LaneTimer() { if (end) (void)hipEventRecord(end, s); }
+};
+
+static void release_lane(UpdateLane& L) {
+  L.b_stage.release();
+  L.ev_free.insert(L.ev_free.end(), L.ev.begin(), L.ev.end()); L.ev.clear();
+  L.unread = false; L.bad_last = 0; L.bad_reported = true;
+}
+static void destroy_lane(UpdateLane& L) {
+  release_lane(L);
+  for (hipEvent_t e : L.ev_free) (void)hipEventDestroy(e);
+  for (hipEvent_t e : {L.ready_ev, L.done_ev}) if (e) (void)hipEventDestroy(e);
+  L.ev_free.clear(); L.ready_ev = L.done_ev = nullptr;
+}
+
+// reported once per bad update, like a lost path; the boxes stay empty until a good update or an upload
+static int report_bad(UpdateLane& L, const char* head, const char* tail) {
+  if (L.bad_reported) return 0;
+  L.bad_reported = true;
+  return fail(head + std::to_string(L.bad_last) + tail);
+}
+
+// ---- one update on every context --------------------------------------------------------------------------------------------------
+// The driver of refit and move, after the kind's own refusals.  Every check comes before the first launch: the caller's buffers (srcs),
+// then every context's plan (plan(), with that context current).  Device 0 runs `work` on the caller's stream, ordered against its context
+// stream; every other context waits for the caller's stream, copies the sources from device 0 into its lane's stage (one after the other; a
+// null source keeps its place), runs `work` on its own stream, and the caller's stream waits for it -- so the caller may overwrite its
+// buffers after whatever it enqueues next.  mark() notes on the host that the scene changes.
+struct PeerSrc { const void* p; size_t bytes; const char* what; };
+template <typename Lane, typename Plan, typename Mark, typename Work>
+static int run_update(const std::string& call, hipStream_t st, Lane lane, const std::vector<PeerSrc>& srcs, Plan plan, Mark mark, Work work) {
+  Ctx& c0 = g_devs[0];
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  std::vector<const void*> at;
+  for (const PeerSrc& x : srcs) { if (x.p && check_device_ptr(x.p, x.bytes, x.what)) return 1; at.push_back(x.p); }
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || plan()) return 1; }
+  if (use_dev(0)) return 1;
+  StreamOrder order(c0, st);
+  if (order.enter()) return 1;
+  mark();
+  const hipStream_t qs = order.qs;
+  int rc = 0;
+  if (g_ndev > 1 && hipEventRecord(lane(c0).ready_ev, qs) != hipSuccess) rc = fail(call + ": hipEventRecord failed");
+  if (!rc) rc = work(at.data(), qs);
+  for (int k = 1; k < g_ndev && !rc; ++k) {
+    if (use_dev(k)) { rc = 1; break; }
+    Ctx& c = g_ctx;
+    UpdateLane& L = lane(c);
+    bool ok = hipStreamWaitEvent(c.stream, lane(c0).ready_ev, 0) == hipSuccess;
+    char* stage = (char*)L.b_stage.p;
+    for (size_t i = 0; i < srcs.size(); stage += srcs[i].bytes, ++i) {
+      at[i] = srcs[i].p ? stage : nullptr;
+      if (ok && srcs[i].p) ok = hipMemcpyPeerAsync(stage, c.device, srcs[i].p, c0.device, srcs[i].bytes, c.stream) == hipSuccess;
+    }
+    if (!ok) { rc = fail(call + ": copy to device " + std::to_string(c.device) + " failed"); break; }
+    rc = work(at.data(), c.stream);
+    if (hipEventRecord(L.done_ev, c.stream) != hipSuccess || hipStreamWaitEvent(qs, L.done_ev, 0) != hipSuccess) rc = rc ? rc : fail(call + ": event ordering failed");
+  }
+  if (use_dev(0) || order.leave()) return 1;          // (also after a failure)
+  return rc;
+}
+
+// the info getters: cumulative since the upload; they wait for every context's stream (an update on another stream is ordered before it)
+template <typename Info, typename Fold>
+static int get_info(Info* out, const char* null_msg, const Info& info, Fold fold) {
+  if (!out) return fail(null_msg);
+  Dev0Guard guard;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (!g_ctx.device_ready) continue;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+    if (fold()) return 1;
+  }
+  *out = info;
+  return 0;
+}
+
+// ---- what refit and rebuild share -------------------------------------------------------------------------------------------------
+struct MeshCall { const char *name, *noun, *done; };
+static const MeshCall kRefitCall = {"art_refit_device", "refit", "refitted"}, kRebuildCall = {"art_rebuild_device", "rebuild", "rebuilt"};
+// the refusals both open with
+static int check_mesh_update(const MeshCall& call, const float* pos, int64_t nverts) {
+  const Ctx& c0 = g_devs[0]; const std::string name = call.name;
+  if (!c0.scene_ready) return fail(name + ": no scene uploaded");
+  const HostScene& hs = c0.host_scene;
+  if (c0.scene.n_inst > 0) return fail(name + ": the scene is instanced (n_instances > 0); only the tree of a flat CLOSEST mesh is " + call.done);
+  if (hs.m_nverts == 0) return fail(name + ": the scene has no ART_MESH_CLOSEST mesh");
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, whose host copy of the tree a " + call.noun + " would leave stale");
+  if (nverts != hs.m_nverts) return fail(name + ": nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.m_nverts));
+  if (!pos) return fail(name + ": null pos3f");
+  return 0;
+}
+
+// the tree in HBM changes: the host copies of it (art_export_bvh's cache, a host-built tree) and of the positions are stale
+static void drop_stale_host_copies(HostScene& hs) {
+  std::vector<float>().swap(hs.bvh.nodes); std::vector<float>().swap(hs.bvh.tris); std::vector<uint32_t>().swap(hs.bvh.qnodes);
+  std::vector<float>().swap(hs.m_pos);
+}
+
+// ---- moving geometry (art_refit_device, art_refit.hip) ----------------------------------------------------------------------------
+// The plan of the current context: its tree's inner nodes grouped by depth (read back from HBM once: the GPU builders leave the tree
+// there only, and every builder orders its nodes differently), the mesh's index triples, the tight-box scratch and the counters.
+static int build_refit_plan(const HostScene& hs) {
+  Ctx& c = g_ctx;
+  Ctx::RefitPlan& R = c.refit;
+  const auto t0 = std::chrono::steady_clock::now();
+  const int W = c.scene.node_width, NF = node_floats(W), N = c.scene.n_nodes;
+  if (N < 1 || !c.b_nodes.p) return fail("art_refit_device: the scene has no tree");
+  std::vector<float> nodes((size_t)N * NF);
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> order;
+  order.reserve((size_t)N);
+  order.push_back(0);
+  R.level_off.assign(1, 0);
+  for (size_t b = 0; b < order.size();) {                       // breadth first: level L = order[level_off[L] .. level_off[L + 1])
+    const size_t e = order.size();
+    for (size_t i = b; i < e; ++i) {
+      const float* nd = &nodes[(size_t)order[i] * NF];
+      for (int j = 0; j < W; ++j) {
+        int32_t ref, cnt;
+        std::memcpy(&ref, nd + 4 * j + 3, 4); std::memcpy(&cnt, nd + 4 * W + 4 * j + 3, 4);
+        if (ref < 0) continue;
+        if (cnt > 0) {
+          if (cnt > kMaxLeafTris || (int64_t)ref + cnt > (int64_t)c.scene.n_tris) return fail("art_refit_device: internal: a leaf outside the triangle records");
+          continue;
+        }
+        if (ref >= N || order.size() >= (size_t)N) return fail("art_refit_device: internal: the uploaded nodes do not form a tree");
+        order.push_back(ref);
+      }
+    }
+    R.level_off.push_back((int)e);
+    b = e;
+  }
+  if (order.size() != (size_t)N) return fail("art_refit_device: internal: unreachable nodes in the uploaded tree");
+  if (upload(R.b_idx, hs.m_idx) || upload(R.b_levels, order) || ensure(R.b_tight, (size_t)N * 6 * sizeof(float)) || ensure(R.b_bad, 2 * sizeof(unsigned long long)))
+    return 1;
+  HIP_TRY(hipMemset(R.b_bad.p, 0, 2 * sizeof(unsigned long long)));
+  if (plan_lane(R.lane, 2 * 12 * (size_t)hs.m_nverts)) return 1;
+  g_refit_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  R.ready = true;
+  return 0;
+}
+
+// the current context's refit on stream s, from positions (and normals) in this context's device memory
+static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hipStream_t s) {
+  Ctx& c = g_ctx;
+  Ctx::RefitPlan& P = c.refit;
+  RefitArgs A;
+  std::memset(&A, 0, sizeof A);
+  A.pos3f = pos; A.nrm3f = nrm; A.idx = (const int32_t*)P.b_idx.p;
+  A.nverts = hs.m_nverts; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.n_recs = c.scene.n_tris;
+  A.tris = (float*)c.b_tris.p; A.qtris = (float*)c.b_qtris.p; A.m_shade = (float*)c.b_m_shade.p;
+  A.bad = (unsigned long long*)P.b_bad.p;
+  A.nodes = (float*)c.b_nodes.p; A.qnodes = (c.scene.node_width == 4) ? (QNode*)c.b_qnodes.p : nullptr;
+  A.tight = (float*)P.b_tight.p;
+  A.width = c.scene.node_width; A.inflate_rel = c.bvh_params.inflate_rel; A.inflate_abs = c.bvh_params.inflate_abs;
+  (void)fold_lane(P.lane, /*wait=*/false, &c == &g_devs[0] ? &g_refit_info.refit_ms : nullptr);
+  LaneTimer timer;
+  if (timer.start(P.lane, s)) return 1;
+  HIP_TRY(hipMemsetAsync(A.bad, 0, sizeof(unsigned long long), s));      // [0]: this refit's bad vertices ([1] counts since the upload)
+  launch_refit_tris(s, A);
+  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                 // deepest level first
+    launch_refit_level(s, A, (const int32_t*)P.b_levels.p + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(std::string("art_refit_device: kernel launch failed: ") + hipGetErrorString(e));
+  return 0;
+}
+
+// The current context's event pairs of one kind (all of them: its stream is idle, and an update on another stream is ordered before the
+// context stream's later work), then the kind's counters where an update has not been read yet: read(words) -> this update's bad items.
+template <int N, typename Read>
+static int fold_kind(UpdateLane& L, double& ms_sum, const void* counters, Read read) {
+  const bool dev0 = (g_cur == &g_devs[0]);
+  if (fold_lane(L, /*wait=*/true, dev0 ? &ms_sum : nullptr)) return 1;
+  if (!L.unread || !counters) return 0;
+  unsigned long long w[N];
+  HIP_TRY(hipMemcpy(w, counters, sizeof w, hipMemcpyDeviceToHost));
+  L.unread = false;
+  L.bad_last = read(w, dev0); L.bad_reported = (L.bad_last == 0);
+  return 0;
+}
+static int fold_refit() {                   // b_bad: [0] this refit's bad vertices, [1] since the upload
+  Ctx::RefitPlan& R = g_ctx.refit;
+  return fold_kind<2>(R.lane, g_refit_info.refit_ms, R.b_bad.p, [&](const unsigned long long* w, bool dev0) { R.bad_total = w[1]; if (dev0) g_refit_info.bad_vertices = w[1]; return w[0]; });
+}
+
+int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
+  if (check_mesh_update(kRefitCall, pos, nverts)) return 1;
+  HostScene& hs = g_devs[0].host_scene;
+  const size_t bytes = 12 * (size_t)nverts;
+  return run_update(kRefitCall.name, st, [](Ctx& c) -> UpdateLane& { return c.refit.lane; }, {{pos, bytes, "pos3f"}, {nrm, bytes, "nrm3f"}},
+                    [&] { return !g_ctx.refit.ready && build_refit_plan(hs); },
+                    [&] { drop_stale_host_copies(hs); hs.refitted = true; if (nrm) hs.m_shade_stale = true; g_refit_info.refits += 1; },   // (art_trace_rays reads the shading records on the host)
+                    [&](const void* const* src, hipStream_t s) { return refit_one(hs, (const float*)src[0], (const float*)src[1], s); });
+}
+
+int get_refit_info(ArtRefitInfo* out) { return get_info(out, "null ArtRefitInfo", g_refit_info, fold_refit); }
+
+// ---- moving instances (art_move_instances_device, art_move.hip) -------------------------------------------------------------------
+// The plan of the current context, from the two-level build the upload kept: MovePlanHost's arrays in one buffer, the kernels' own
+// arrays in another, and MoveArgs pointing into both and into the scene's arrays.
+static int build_move_plan(const HostScene& hs) {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  const auto t0 = std::chrono::steady_clock::now();
+  MovePlanHost H;
+  std::string err;
+  if (!build_move_plan_host(hs.two, H, err)) return fail("art_move_instances_device: " + err);
+  const size_t n_entry = hs.two.entry.size(), n_inst = hs.two.inst.size(), nm = (size_t)H.n_mesh, n_tlas = (size_t)hs.two.tlas.n_nodes, n_blas = H.node_mesh.size();
+  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
+      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != hs.two.blas_tris.size() * 4)
+    return fail("art_move_instances_device: internal: the arrays in HBM are not the kept build's");
+  std::vector<uint8_t> img;                                                // every section 16-byte aligned
+  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (bytes) std::memcpy(&img[at], p, bytes); return at; };
+  const size_t o_roff = put(H.range_off.data(), H.range_off.size() * 4), o_rng = put(H.ranges.data(), H.ranges.size() * 4), o_prox = put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
+  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbox = put(H.mesh_box.data(), H.mesh_box.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
+  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_tight = put(H.blas_tight.data(), H.blas_tight.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
+  if (upload(P.b_plan, img)) return 1;
+  std::vector<uint8_t> work;
+  auto room = [&](size_t bytes) { const size_t at = work.size(); work.resize(at + ((bytes + 15) & ~(size_t)15), 0); return at; };
+  const size_t w_state = room(4 * 8), w_need = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
+  std::memcpy(&work[w_pad], H.pad_abs.data(), nm * 4);
+  if (upload(P.b_work, work)) return 1;
+  const char* pb = (const char*)P.b_plan.p; char* wb = (char*)P.b_work.p;
+  MoveArgs& A = P.args;
+  A = MoveArgs();
+  A.n_inst = (int32_t)n_inst; A.n_entry = (int32_t)n_entry; A.n_mesh = (int32_t)nm; A.n_blas_nodes = (int32_t)n_blas;
+  A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p;
+  A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
+  A.range_off = (const int32_t*)(pb + o_roff); A.ranges = (const int32_t*)(pb + o_rng); A.proxy_rec = (const int32_t*)(pb + o_prox); A.inst_mesh = (const int32_t*)(pb + o_imesh);
+  A.mesh_box = (const float*)(pb + o_mbox); A.mesh_base = (const int32_t*)(pb + o_mbase); A.node_mesh = (const int32_t*)(pb + o_nmesh); A.blas_tight = (const float*)(pb + o_tight);
+  A.state = (unsigned long long*)(wb + w_state); A.needed = (unsigned long long*)(wb + w_need); A.tlas_tight = (float*)(wb + w_tight); A.ent_box = (float*)(wb + w_box);
+  A.inst_ok = (int32_t*)(wb + w_ok); A.pad_cur = (float*)(wb + w_pad); A.repad = (int32_t*)(wb + w_repad);
+  A.extent = (double)hs.two.scene_extent; A.mesh_pad_rel = hs.two.mesh_pad_rel; A.mesh_pad_min = hs.two.mesh_pad_min;
+  const BvhBuildParams tp;                                                 // the instance tree builder's pad rule: the defaults, as build_two_level_host applied them
+  A.tlas_pad_rel = tp.inflate_rel; A.tlas_pad_abs = tp.inflate_abs;
+  P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off;
+  P.small_entries = H.records <= 64 * (int64_t)n_entry;
+  if (plan_lane(P.lane, 48 * n_inst)) return 1;
+  g_move_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  P.ready = true;
+  return 0;
+}
+
+// the current context's move on stream s, from matrices in this context's device memory
+static int move_one(const float* m12f, hipStream_t s) {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  MoveArgs A = P.args;
+  A.m12f = m12f;
+  (void)fold_lane(P.lane, /*wait=*/false, &c == &g_devs[0] ? &g_move_info.move_ms : nullptr);
+  LaneTimer timer;
+  if (timer.start(P.lane, s)) return 1;
+  launch_move_matrices(s, A);
+  launch_move_repad(s, A);
+  launch_move_entry_boxes(s, A, P.small_entries);
+  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                   // deepest level first
+    launch_move_tlas_level(s, A, P.levels + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(std::string("art_move_instances_device: kernel launch failed: ") + hipGetErrorString(e));
+  return 0;
+}
+
+static int fold_move() {                    // the counters k_move_matrices / k_move_pads_mesh keep
+  Ctx::MovePlan& P = g_ctx.move;
+  return fold_kind<4>(P.lane, g_move_info.move_ms, P.args.state, [&](const unsigned long long* w, bool dev0) { if (dev0) { g_move_info.bad_matrices = w[2]; g_move_info.repads = w[3]; } return w[1]; });
+}
+
+int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st) {
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail("art_move_instances_device: no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail("art_move_instances_device: the scene was committed through gcore_commit_scene, which keeps its own instances");
+  if (c0.scene.n_inst <= 0) return fail("art_move_instances_device: the scene is not instanced (n_instances = 0); art_refit_device moves the vertices of a flat mesh");
+  if (n_instances != (int64_t)c0.scene.n_inst) return fail("art_move_instances_device: n_instances " + std::to_string(n_instances) + " differs from the uploaded scene's " + std::to_string(c0.scene.n_inst));
+  if (!m12f) return fail("art_move_instances_device: null m12f");
+  return run_update("art_move_instances_device", st, [](Ctx& c) -> UpdateLane& { return c.move.lane; }, {{m12f, 48 * (size_t)n_instances, "m12f"}},
+                    [&] { return !g_ctx.move.ready && build_move_plan(hs); },
+                    [&] { hs.inst_stale = true; g_move_info.moves += 1; },                                      // (art_trace_rays reads the matrices on the host)
+                    [&](const void* const* src, hipStream_t s) { return move_one((const float*)src[0], s); });
+}
+
+int get_move_info(ArtMoveInfo* out) { return get_info(out, "null ArtMoveInfo", g_move_info, fold_move); }
+
+// ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
+// What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
+// anywhere leaves every context's scene as it was.
+struct PendingTree {
+  int device = -1; GpuBvh g; DevBuf qtris;
+  DevBuf idx;                                  // the mesh's index triples where no refit plan held them (or, after the commit, the plan's)
+  ~PendingTree() {
+    if (device >= 0) (void)hipSetDevice(device);
+    free_tree(g);
+    qtris.release(); idx.release();
+  }
+};
+
+// the current context's new tree on stream s, from positions in this context's device memory: gather, count the bad vertices, build,
+// check, pad.  Returns with s idle.  Nothing of the context's scene is touched.
+static int rebuild_one(const HostScene& hs, const BvhBuildParams& bp, const float* pos, hipStream_t s, PendingTree& out, float* gather_ms) {
+  Ctx& c = g_ctx;
+  const int32_t n_prims = (int32_t)(hs.m_idx.size() / 3);
+  DevBuf t9, bad;
+  struct Free { DevBuf &a, &b; ~Free() { a.release(); b.release(); } } fr{t9, bad};
+  out.device = c.device;
+  const int32_t* idx = (const int32_t*)c.refit.b_idx.p;                   // the refit plan keeps the index triples in HBM
+  if (!c.refit.ready || !idx) { if (upload(out.idx, hs.m_idx)) return 1; idx = (const int32_t*)out.idx.p; }
+  if (ensure(t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(bad, sizeof(unsigned long long))) return 1;
+  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
+  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
+  GatherArgs G;
+  G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)t9.p; G.bad = (unsigned long long*)bad.p;
+  HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
+  HIP_TRY(hipEventRecord(ev.a, s));
+  launch_gather_tri9(s, G);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.b, s));
+  unsigned long long n_bad = 0;
+  HIP_TRY(hipMemcpyAsync(&n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (gather_ms) HIP_TRY(hipEventElapsedTime(gather_ms, ev.a, ev.b));
+  if (n_bad) return fail("art_rebuild_device: " + std::to_string(n_bad) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
+  std::string err;
+  if (!build_bvh8_gpu((const float*)t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
+  if (check_tree_limits(bp.width, out.g.n_nodes, out.g.n_tris, true, true, out.g.qnodes != nullptr, out.g.max_stack)) return 1;
+  if (bp.width == 4 && pad_tri_records(out.qtris, out.g.tris, out.g.n_tris, s)) return 1;
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The current context takes its new tree (its streams are idle, its refit events are folded).  The one step that can fail, the copy
+// of the new header to d_scene, comes first: when it does (a lost device), the context's buffers are still the old ones.
+static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
+  Ctx& c = g_ctx;
+  {
+    DevScene s = c.scene;
+    s.nodes = t.g.nodes; s.tris = t.g.tris; s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
+    HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
+  }
+  if (!t.idx.p) { t.idx = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
+  release_updates(c);                                                     // the next refit plans against the new tree
+  c.bvh_params = g_devs[0].bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
+  adopt_tree(c, t.g, bp.width);
+  c.b_qtris.release();
+  c.b_qtris = t.qtris; t.qtris = DevBuf();                                // (owned by the context now)
+  DevScene& s = c.scene;
+  s.nodes = (const float*)c.b_nodes.p; s.tris = (const float*)c.b_tris.p;
+  s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
+  return 0;
+}
+
+// Every context builds into new buffers before any context's scene changes.
+int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  if (check_mesh_update(kRebuildCall, pos, nverts)) return 1;
+  Ctx& c0 = g_devs[0];
+  HostScene& hs = c0.host_scene;
+  BvhBuildParams bp = c0.bvh_params;
+  if (bp.spatial_alpha >= 0.0f) return fail("art_rebuild_device: option bvh_spatial_splits is set; reference splitting exists in the host builder only (art_upload_scene builds that tree)");
+  if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
+  if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const size_t bytes = 12 * (size_t)nverts;
+  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
+  const hipStream_t qs = StreamOrder(c0, st).qs;
+  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  }
+  if (use_dev(0)) return 1;
+  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
+  std::vector<PendingTree> built((size_t)g_ndev);
+  std::vector<DevBuf> stage((size_t)g_ndev);                              // contexts k > 0: peer copy of pos (+ nrm)
+  struct FreeStage { std::vector<DevBuf>& v; ~FreeStage() { for (size_t k = 0; k < v.size(); ++k) { if (v[k].p && g_devs[k].device >= 0) (void)hipSetDevice(g_devs[k].device); v[k].release(); } } } fs{stage};
+  float gather_ms = 0.0f;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    Ctx& c = g_ctx;
+    const float* p = pos;
+    if (k > 0) {
+      if (ensure(stage[(size_t)k], nrm ? 2 * bytes : bytes)) return 1;
+      float* sp = (float*)stage[(size_t)k].p;
+      if (hipMemcpyPeer(sp, c.device, pos, c0.device, bytes) != hipSuccess || (nrm && hipMemcpyPeer(sp + 3 * (size_t)nverts, c.device, nrm, c0.device, bytes) != hipSuccess))
+        return fail("art_rebuild_device: copy to device " + std::to_string(c.device) + " failed");
+      p = sp;
+    }
+    if (rebuild_one(hs, bp, p, k == 0 ? qs : c.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
+  }
+  // everything else that can fail without a lost device comes before the first swap: the refit events and counters of every context
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_refit()) return 1; }
+  // ---- commit: from here on the scene changes.  No step below allocates or waits for anything but its own launch; a failure here
+  // means the device is lost, and is the one case in which contexts may end up with different trees.
+  const double build_ms = built[0].g.build_ms;
+  const int32_t n_nodes = built[0].g.n_nodes, n_tris = built[0].g.n_tris, max_stack = built[0].g.max_stack;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k) || commit_tree(bp, built[(size_t)k])) return 1;
+    if (k > 0) continue;
+    hs.hdr.n_nodes = n_nodes; hs.hdr.n_tris = n_tris; hs.hdr.node_width = bp.width;
+    hs.bvh.width = bp.width; hs.bvh.n_nodes = n_nodes; hs.bvh.n_tris = n_tris; hs.bvh.max_stack = max_stack;
+    hs.bvh_build_ms = build_ms; hs.gpu_built = true; hs.refitted = false;
+    drop_stale_host_copies(hs);
+  }
+  for (int k = 0; k < g_ndev && nrm; ++k) {                               // the shading records: k_refit_tris' normals branch, no triangle records (n_recs = 0)
+    if (use_dev(k)) return 1;
+    Ctx& c = g_ctx;
+    const hipStream_t s = (k == 0) ? qs : c.stream;
+    const float* n = (k == 0) ? nrm : (const float*)stage[(size_t)k].p + 3 * (size_t)nverts;
+    RefitArgs A;
+    std::memset(&A, 0, sizeof A);
+    A.nrm3f = n; A.idx = (const int32_t*)built[(size_t)k].idx.p; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.m_shade = (float*)c.b_m_shade.p;
+    hs.m_shade_stale = true;                                              // (art_trace_rays reads the shading records on the host)
+    launch_refit_tris(s, A);
+    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("art_rebuild_device: rewriting the shading records failed");
+  }
+  g_rebuild_info.rebuilds += 1; g_rebuild_info.gather_ms += gather_ms; g_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
+  g_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int get_rebuild_info(ArtRebuildInfo* out) { if (!out) return fail("null ArtRebuildInfo"); *out = g_rebuild_info; return 0; }
+
+// device 0's tree as it lies in HBM (a refit on another stream is ordered before the context stream's later work)
+int get_tree_cost(ArtTreeCost* out) {
+  if (!out) return fail("null ArtTreeCost");
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail("art_get_tree_cost: no scene uploaded");
+  if (c.scene.n_inst > 0) return fail("art_get_tree_cost: the scene is instanced (n_instances > 0); the figure is defined for the tree of a flat CLOSEST mesh");
+  if (c.scene.n_nodes < 1 || !c.b_nodes.p) return fail("art_get_tree_cost: the scene has no tree (no ART_MESH_CLOSEST mesh)");
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  DevBuf sums;
+  struct Free { DevBuf& b; ~Free() { b.release(); } } fr{sums};
+  if (ensure(sums, 4 * sizeof(double))) return 1;
+  double h[4] = {0.0, 0.0, 0.0, 0.0};
+  HIP_TRY(hipMemsetAsync(sums.p, 0, sizeof h, c.stream));
+  launch_tree_cost(c.stream, (const float*)c.b_nodes.p, c.scene.n_nodes, c.scene.node_width, (double*)sums.p);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(h, sums.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  out->root_area = h[3];
+  const bool any = h[3] > 0.0;                                            // (no usable child box under the root: no ray enters the tree)
+  out->node_visits = 1.0 + (any ? h[0] / h[3] : 0.0);
+  out->leaf_visits = any ? h[1] / h[3] : 0.0;
+  out->tri_tests = any ? h[2] / h[3] : 0.0;
+  return 0;
+}
+
+// ---- what art_api.cpp calls ---------------------------------------------------------------------------------------------------------
+void release_updates(Ctx& c) {
+  Ctx::RefitPlan& R = c.refit;
+  R.b_idx.release(); R.b_levels.release(); R.b_tight.release(); R.b_bad.release();
+  R.level_off.clear(); R.ready = false; R.bad_total = 0; release_lane(R.lane);
+  Ctx::MovePlan& P = c.move;
+  P.b_plan.release(); P.b_work.release();
+  P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs(); P.ready = false; release_lane(P.lane);
+}
+
+void destroy_updates(Ctx& c) { release_updates(c); destroy_lane(c.refit.lane); destroy_lane(c.move.lane); }
+
+int sync_updates() {
+  Ctx& c = g_ctx;
+  if (fold_refit()) return 1;
+  if (report_bad(c.refit.lane, "art_refit_device: ", " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes "
+                 "holding them are empty (no ray enters them) until a good refit or art_upload_scene")) return 1;
+  if (fold_move()) return 1;
+  return report_bad(c.move.lane, "art_move_instances_device: ", " instance matrix(es) with an element that is not finite, without an inverse, or "
+                    "reaching beyond 1e18; their instances are empty (no ray enters them) until a good move or art_upload_scene");
+}
+
+}  // namespace art

@@ -316,6 +316,63 @@ def test_refusals(art, backend):
     assert got[1] == want[1] and np.array_equal(bits(got[0]), bits(want[0]))
 
 
+def _many_moves(art, be, n=200):
+    """Placement A uploaded, then n moves back to back on a side stream with nothing waited for in between -- alternately to A's and to
+    B's matrices, the last one to B's -- and ONE synchronize.  Returns ArtMoveInfo's figures and the picture."""
+    A, B = placed(0), placed(1)
+    be.upload_scene(A)
+    g = [gpu(mats(A)), gpu(mats(B))]
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        for k in range(n):
+            be.move_instances_torch(g[k % 2], check=False)
+    be.synchronize()
+    mi = be.move_info()
+    return dict(moves=int(mi.moves), move_ms=float(mi.move_ms), bad_matrices=int(mi.bad_matrices)), render(be, mis(art))
+
+
+def _check_many_moves(info, same, n=200):
+    print("many moves:", info)
+    assert info["moves"] == n
+    assert info["move_ms"] > 0.0 and np.isfinite(info["move_ms"]) and info["bad_matrices"] == 0
+    assert same
+
+
+def test_many_moves_in_flight(art, backend):
+    """A host that moves every frame and never synchronises: the figures and the picture come out as if each move had been waited for."""
+    want = fresh(art, backend, "B", placed(1))
+    info, got = _many_moves(art, backend)
+    _check_many_moves(info, got[1] == want[1] and got[2] == 0 and np.array_equal(bits(got[0]), bits(want[0])))
+
+
+MANY_SCRIPT = r'''
+import json, sys
+import numpy as np
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import __graft_entry__ as ge
+art = ge.load_package()
+import test_gpu_move_instances as T
+be = art.Backend(0)
+be.upload_scene(T.placed(1))
+want = T.render(be, T.mis(art))
+be.shutdown()
+be = art.Backend(devices=[0, 0])
+info, got = T._many_moves(art, be)
+be.shutdown()
+same = bool(got[1] == want[1] and got[2] == 0 and np.array_equal(T.bits(got[0]), T.bits(want[0])))
+print("RESULT " + json.dumps(dict(info=info, same=same)))
+'''
+
+
+def test_many_moves_in_flight_on_two_contexts(art):
+    """the same through the fan-out to a second context on the same GPU (a child process: the library is a process-wide singleton)"""
+    r = subprocess.run([sys.executable, "-c", MANY_SCRIPT, art.ROOT], capture_output=True, text=True, timeout=900)
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+    assert r.returncode == 0 and line, r.stdout[-3000:] + r.stderr[-3000:]
+    out = json.loads(line[0][7:])
+    _check_many_moves(out["info"], out["same"])
+
+
 SCRIPT = r'''
 import json, sys
 import numpy as np

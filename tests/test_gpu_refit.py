@@ -282,6 +282,66 @@ def test_contexts_on_one_gpu_are_all_refitted(art):
     assert out["refits_1"] == 1 and out["refits_3"] == 1
 
 
+def _many_refits(art, be, width, n=200):
+    """The synthetic mesh uploaded at P, then n refits back to back on a side stream with nothing waited for in between -- alternately
+    to a deformed mesh and to P, the last one at P -- and ONE synchronize.  Returns ArtRefitInfo's figures and whether the exported tree
+    equals the fresh upload's."""
+    sd = _scene("synthetic")
+    pos, nrm, _, _ = _mesh(sd)
+    p2, _ = _deform("synthetic", pos, nrm)
+    be.set_option("bvh_width", width)
+    be.upload_scene(sd)
+    n0, t0, _ = _export(be)
+    g = _gpu(p2, pos)
+    torch.cuda.synchronize()
+    with torch.cuda.stream(torch.cuda.Stream()):
+        for k in range(n):
+            be.refit_torch(g[k % 2], check=False)
+    be.synchronize()
+    ri = be.refit_info()
+    n1, t1, _ = _export(be)
+    return dict(refits=int(ri.refits), refit_ms=float(ri.refit_ms), bad_vertices=int(ri.bad_vertices),
+                nodes_equal=bool(np.array_equal(n1, n0)), tris_equal=bool(np.array_equal(t1, t0)))
+
+
+def _check_many_refits(out, n=200):
+    print("many refits:", out)
+    assert out["refits"] == n
+    assert out["refit_ms"] > 0.0 and np.isfinite(out["refit_ms"])
+    assert out["bad_vertices"] == 0
+    assert out["tris_equal"] and out["nodes_equal"]
+
+
+@pytest.mark.parametrize("width", [4, 8])
+def test_many_refits_in_flight_fold_as_one_by_one(art, backend, options, width):
+    """A host that refits every frame and never synchronises: every call folds the event pairs that have completed, and the figures
+    and the tree come out as if each refit had been waited for."""
+    _check_many_refits(_many_refits(art, backend, width))
+
+
+MANY_SCRIPT = r'''
+import json, sys
+sys.path.insert(0, sys.argv[1]); sys.path.insert(0, sys.argv[1] + "/tests")
+import __graft_entry__ as ge
+art = ge.load_package()
+import test_gpu_refit as T
+be = art.Backend(devices=[0, 0])
+out = {str(w): T._many_refits(art, be, w) for w in (4, 8)}
+be.shutdown()
+print("RESULT " + json.dumps(out))
+'''
+
+
+def test_many_refits_in_flight_on_two_contexts(art):
+    """the same through the fan-out to a second context on the same GPU (a child process: the library is a process-wide singleton)"""
+    r = subprocess.run([sys.executable, "-c", MANY_SCRIPT, art.ROOT], capture_output=True, text=True, timeout=900)
+    line = [ln for ln in r.stdout.splitlines() if ln.startswith("RESULT ")]
+    assert r.returncode == 0 and line, r.stdout[-3000:] + r.stderr[-3000:]
+    out = json.loads(line[0][7:])
+    for w in ("4", "8"):
+        _check_many_refits(out[w])
+
+
 def test_refusals_and_bad_vertices(art, backend):
     from ada_ray_tracer_amd import scenes
     L = backend.lib
