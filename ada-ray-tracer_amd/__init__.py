@@ -127,6 +127,10 @@ class ArtMoveInfo(C.Structure):
     _fields_ = [("moves", C.c_uint64), ("move_ms", C.c_double), ("plan_ms", C.c_double), ("bad_matrices", C.c_uint64), ("repads", C.c_uint64)]
 
 
+class ArtMeshRefitInfo(C.Structure):
+    _fields_ = [("refits", C.c_uint64), ("refit_ms", C.c_double), ("plan_ms", C.c_double), ("bad_vertices", C.c_uint64), ("repads", C.c_uint64)]
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -137,6 +141,7 @@ EXPORTED_SYMBOLS = [
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
+    "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -183,6 +188,8 @@ def load_library():
     L.art_get_tree_cost.argtypes = [C.POINTER(ArtTreeCost)]
     L.art_move_instances_device.argtypes = [C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_move_info.argtypes = [C.POINTER(ArtMoveInfo)]
+    L.art_refit_mesh_device.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
+    L.art_get_mesh_refit_info.argtypes = [C.POINTER(ArtMeshRefitInfo)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
@@ -539,6 +546,31 @@ class Backend:
         mi = ArtMoveInfo()
         _check(self.lib.art_get_move_info(C.byref(mi)))
         return mi
+
+    def refit_mesh_torch(self, mesh, pos, nrm=None, check=True):
+        """Deform mesh number `mesh` of an instanced scene (art_refit_mesh_device): pos, nrm float32 [nverts, 3] tensors on the library's
+        GPU, object space, in the vertex order of that uploaded mesh; nrm None keeps the normals.  Enqueued on torch.cuda.current_stream()
+        without waiting for it: work enqueued before sees the old shape, work enqueued after the new.  The picture is the one of
+        upload_scene with that mesh's vertices replaced, at the matrices in force; the trees keep their topology.  check=True raises
+        ValueError before any launch when a coordinate is not finite or beyond 1e18 in magnitude (or a normal is not finite); that check
+        costs ONE host synchronisation with the stream.  check=False skips it: boxes and entry points holding a bad vertex are then
+        emptied on the GPU and the next synchronize fails with the count."""
+        torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
+        if check and n:
+            with torch.cuda.stream(stream):
+                bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
+                badn = torch.zeros_like(bad) if q is None else (~torch.isfinite(q)).any(dim=1).sum()
+                counts = torch.stack([bad, badn]).tolist()                     # the one host synchronisation
+            if counts[0] or counts[1]:
+                raise ValueError("refit_mesh_torch: %d vertex position(s) not finite or beyond 1e18 in magnitude, %d normal(s) not finite" % tuple(counts))
+        _check(self.lib.art_refit_mesh_device(int(mesh), p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+
+    def mesh_refit_info(self):
+        """ArtMeshRefitInfo: refits, refit_ms (GPU time of device 0's kernels), plan_ms, bad_vertices, repads (meshes whose boxes a mesh
+        refit had to widen) -- cumulative since the upload (waits)"""
+        ri = ArtMeshRefitInfo()
+        _check(self.lib.art_get_mesh_refit_info(C.byref(ri)))
+        return ri
 
     def bvh_info(self):
         info = ArtBvhInfo()

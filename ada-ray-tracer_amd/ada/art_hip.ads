@@ -140,6 +140,26 @@ package Art_Hip is
                            kernel : int; stats : System.Address) return int;
   pragma Import (C, art_trace_rays, "art_trace_rays");
 
+  --  Deforming mesh number `mesh` (an index into Art_Scene_Desc.meshes) of an uploaded instanced scene: pos3f / nrm3f are DEVICE memory
+  --  of the library's GPU, 3 * nverts C floats in the vertex order of that mesh, object space; nrm3f = Null_Address keeps the normals;
+  --  hip_stream = Null_Address is the library's stream.  Stream-ordered; the picture is the one of art_upload_scene with that mesh's
+  --  vertices replaced, at the matrices in force (include/art_hip.h).
+  function art_refit_mesh_device (mesh : int; pos3f, nrm3f : System.Address; nverts : Interfaces.Integer_64;
+                                  hip_stream : System.Address) return int;
+  pragma Import (C, art_refit_mesh_device, "art_refit_mesh_device");
+
+  type Art_Mesh_Refit_Info is record   --  include/art_hip.h ArtMeshRefitInfo, 40 bytes; cumulative since art_upload_scene
+    refits       : Unsigned_64;
+    refit_ms     : double;
+    plan_ms      : double;
+    bad_vertices : Unsigned_64;
+    repads       : Unsigned_64;
+  end record;
+  pragma Convention (C, Art_Mesh_Refit_Info);
+
+  function art_get_mesh_refit_info (info : access Art_Mesh_Refit_Info) return int;   --  waits for the refits enqueued so far
+  pragma Import (C, art_get_mesh_refit_info, "art_get_mesh_refit_info");
+
   function art_last_error return Interfaces.C.Strings.chars_ptr;
   pragma Import (C, art_last_error, "art_last_error");
 

@@ -7,7 +7,7 @@
 //            -> finish (inside-out radiance fold) -> accumulate (reference summation order)
 //   then resolve (gamma, clamp, pack) when the caller asks for the LDR image.
 //
-// The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_get_tree_cost): art_update.cpp.
+// The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_refit_mesh_device, art_get_tree_cost): art_update.cpp.
 // There is no CPU fallback: every entry point that needs the GPU fails with art_last_error() set when
 // HIP reports no usable device.
 #include <hip/hip_runtime.h>
@@ -1221,6 +1221,13 @@ int art_move_instances_device(const float* m12f, int64_t n_instances, void* hip_
 }
 
 int art_get_move_info(ArtMoveInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_move_info(out); }
+
+int art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return refit_mesh_device(mesh, pos3f, nrm3f, nverts, (hipStream_t)hip_stream);
+}
+
+int art_get_mesh_refit_info(ArtMeshRefitInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_mesh_refit_info(out); }
 
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
   std::lock_guard<std::mutex> lk(g_mu);

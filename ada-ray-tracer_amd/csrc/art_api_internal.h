@@ -59,14 +59,22 @@ struct Ctx {
     uint64_t bad_total = 0;                            // bad vertices since the upload
     UpdateLane lane;                                   // (b_stage: peer copy of pos (+ nrm))
   } refit;
-  // art_move_instances_device (art_move.hip): the plan is built on the first move after an upload (the upload drops it)
+  // art_move_instances_device and art_refit_mesh_device (art_move.hip) share one plan: built by whichever of the two is called first
+  // after an upload (the upload drops it), before anything is changed, from the host's copy of the build -- which a mesh refit then leaves
+  // stale, so the plan is never built again before the next upload
   struct MovePlan {
     bool ready = false;
-    DevBuf b_plan, b_work;                             // MovePlanHost's arrays, one after the other | what the kernels write (MoveArgs)
-    MoveArgs args = MoveArgs();                        // everything but m12f
+    DevBuf b_plan, b_work;                             // MovePlanHost's constant arrays and the meshes' index triples, one after the other | what the kernels write (MoveArgs)
+    MoveArgs args = MoveArgs();                        // everything but m12f, m_cur_out, bad_total and repads: the call sets those
     std::vector<int> level_off; const int32_t* levels = nullptr;   // the instance tree's level L: levels[level_off[L] .. level_off[L + 1])
     bool small_entries = false;                        // few records per entry point: one wave each (launch_move_entry_boxes)
-    UpdateLane lane;                                   // (b_stage: peer copy of the matrices)
+    UpdateLane lane;                                   // the moves' (b_stage: peer copy of the matrices)
+    // per mesh of ArtSceneDesc::meshes, for a mesh refit: its slices of the records (tri_base < 0: no instance shows it), its index triples
+    // in HBM, and its tree's levels [level_first, level_end) of blas_level_off
+    struct Mesh { int32_t tri_base = -1, n_recs = 0, shade_base = 0, n_prims = 0; int64_t nverts = 0; const int32_t* idx = nullptr; int level_first = 0, level_end = 0; };
+    std::vector<Mesh> meshes;
+    std::vector<int> blas_level_off; const int32_t* blas_levels = nullptr;   // level k of the meshes' trees: blas_levels[blas_level_off[k] .. blas_level_off[k + 1]), nodes of blas_nodes
+    UpdateLane refit_lane;                             // the mesh refits' (b_stage: peer copy of pos (+ nrm))
   } move;
   int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
@@ -189,6 +197,8 @@ int get_rebuild_info(ArtRebuildInfo* out);
 int get_tree_cost(ArtTreeCost* out);
 int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st);
 int get_move_info(ArtMoveInfo* out);
+int refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
+int get_mesh_refit_info(ArtMeshRefitInfo* out);
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 
 }  // namespace art

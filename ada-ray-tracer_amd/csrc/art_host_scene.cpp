@@ -107,6 +107,14 @@ bool flatten_scene(const ArtSceneDesc& d, const BvhBuildParams& bp, HostScene& o
       D.root_entry = E.root_entry; D.qroot = E.qroot; D.inst = E.inst;
     }
     for (int i = 0; i < d.n_instances; ++i) total += out.two.inst[(size_t)i].n_tris;
+    std::vector<uint8_t> shown((size_t)d.n_meshes, 0);
+    for (int i = 0; i < d.n_instances; ++i) shown[(size_t)d.instances[i].mesh] = 1;
+    out.mesh_idx_off.push_back(0);                                    // (out is a fresh HostScene, as for materials and lights: mesh_idx, mesh_idx_off and mesh_nverts start empty)
+    for (int mi = 0; mi < d.n_meshes; ++mi) {
+      const ArtMesh& m = d.meshes[mi];
+      if (shown[(size_t)mi]) out.mesh_idx.insert(out.mesh_idx.end(), m.idx, m.idx + 3 * (size_t)m.ntris);
+      out.mesh_idx_off.push_back((int64_t)out.mesh_idx.size()); out.mesh_nverts.push_back(m.nverts);
+    }
     if (total >= (1ll << 31)) { err = "scene: too many instanced triangles"; return false; }
     h.n_inst = d.n_instances; h.n_entry = (int32_t)out.two.entry.size(); h.inst_shift = shift; h.n_tris = (int32_t)total; h.n_nodes = out.two.tlas.n_nodes; h.node_width = 4;
     out.bvh.width = 4; out.bvh.max_stack = std::max(out.two.tlas.max_stack + 3 + out.two.blas_max_stack, 8);      // instance tree + the "leave" marker over two entries of saved world-space state + a mesh's tree, on one stack

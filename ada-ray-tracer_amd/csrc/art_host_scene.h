@@ -31,7 +31,11 @@ struct HostScene {
   bool tree_in_hbm_only() const { return gpu_built || refitted; }
   double bvh_build_ms = 0.0;
   // instanced scene (ArtSceneDesc::n_instances > 0): m_shade then holds the MESHES' records (object-space normals), one block per mesh
+  // (`two` is the build as uploaded: art_refit_mesh_device leaves its records and boxes stale, and nothing reads them after the update plan is built)
   TwoLevelHost two; std::vector<DevInstance> inst;
+  // what art_refit_mesh_device gathers through, per mesh of ArtSceneDesc::meshes: the vertex count, and the index triples of every mesh an
+  // instance shows, mesh m's at mesh_idx[mesh_idx_off[m] .. mesh_idx_off[m + 1]) (copied to HBM with the update plan)
+  std::vector<int32_t> mesh_idx; std::vector<int64_t> mesh_idx_off; std::vector<int32_t> mesh_nverts;
   DevScene hdr;               // scalar part; pointer members are filled by the owner (host or device addresses)
 };
 

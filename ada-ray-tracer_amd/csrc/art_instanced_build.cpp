@@ -337,38 +337,40 @@ bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& e
       }
     }
   }
-  // the meshes' nodes by depth, their mesh, and the tight box below each of them (deepest level first)
+  // every mesh's nodes by depth inside that mesh (a mesh refit walks one mesh's levels), their mesh, and the tight box below each of them
+  // (deepest level first)
   P.node_mesh.assign((size_t)n_blas, -1); P.blas_tight.assign(6 * (size_t)n_blas, 0.0f);
+  P.blas_level_off.assign(1, 0); P.mesh_level_first.assign(1, 0);
   {
-    std::vector<int32_t> cur, next, blas_levels;                             // the meshes' nodes by depth inside their mesh, all meshes together
-    std::vector<int> blas_level_off;
-    for (size_t mi = 0; mi < nm; ++mi) { cur.push_back(P.mesh_base[3 * mi]); P.node_mesh[(size_t)P.mesh_base[3 * mi]] = (int32_t)mi; }
-    blas_level_off.assign(1, 0);
-    while (!cur.empty()) {
-      next.clear();
-      for (const int32_t g : cur) {
-        const int32_t mi = P.node_mesh[(size_t)g];
-        const float* nd = &T.blas_nodes[(size_t)g * NF];
-        for (int j = 0; j < W; ++j) {
-          const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
-          if (ref < 0) continue;
-          if (cnt > 0) {
-            if (P.mesh_base[3 * (size_t)mi + 1] >= 0 && (cnt > kMaxLeafTris || (int64_t)ref + cnt > mesh_recs[(size_t)mi])) { err = "move plan: a leaf outside its mesh's records"; return false; }
-            continue;
+    std::vector<int32_t> cur, next;
+    for (size_t mi = 0; mi < nm; ++mi) {
+      cur.assign(1, P.mesh_base[3 * mi]); P.node_mesh[(size_t)P.mesh_base[3 * mi]] = (int32_t)mi;
+      while (!cur.empty()) {
+        next.clear();
+        for (const int32_t g : cur) {
+          const float* nd = &T.blas_nodes[(size_t)g * NF];
+          for (int j = 0; j < W; ++j) {
+            const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+            if (ref < 0) continue;
+            if (cnt > 0) {
+              if (P.mesh_base[3 * mi + 1] >= 0 && (cnt > kMaxLeafTris || (int64_t)ref + cnt > mesh_recs[mi])) { err = "move plan: a leaf outside its mesh's records"; return false; }
+              continue;
+            }
+            const int64_t c = (int64_t)P.mesh_base[3 * mi] + ref;
+            if (ref >= mesh_nodes[mi] || P.node_mesh[(size_t)c] >= 0) { err = "move plan: a mesh's nodes do not form a tree"; return false; }
+            P.node_mesh[(size_t)c] = (int32_t)mi; next.push_back((int32_t)c);
           }
-          const int64_t c = (int64_t)P.mesh_base[3 * (size_t)mi] + ref;
-          if (ref >= mesh_nodes[(size_t)mi] || P.node_mesh[(size_t)c] >= 0) { err = "move plan: a mesh's nodes do not form a tree"; return false; }
-          P.node_mesh[(size_t)c] = mi; next.push_back((int32_t)c);
         }
+        P.blas_levels.insert(P.blas_levels.end(), cur.begin(), cur.end());
+        P.blas_level_off.push_back((int)P.blas_levels.size());
+        cur.swap(next);
       }
-      blas_levels.insert(blas_levels.end(), cur.begin(), cur.end());
-      blas_level_off.push_back((int)blas_levels.size());
-      cur.swap(next);
+      P.mesh_level_first.push_back((int)P.blas_level_off.size() - 1);
     }
-    if ((int64_t)blas_levels.size() != n_blas) { err = "move plan: unreachable nodes in a mesh's tree"; return false; }
-    for (int L = (int)blas_level_off.size() - 2; L >= 0; --L)
-      for (int k = blas_level_off[(size_t)L]; k < blas_level_off[(size_t)L + 1]; ++k) {
-        const int32_t g = blas_levels[(size_t)k], mi = P.node_mesh[(size_t)g];
+    if ((int64_t)P.blas_levels.size() != n_blas) { err = "move plan: unreachable nodes in a mesh's tree"; return false; }
+    for (int L = (int)P.blas_level_off.size() - 2; L >= 0; --L)          // (a mesh's levels lie one after the other: deepest first inside every mesh)
+      for (int k = P.blas_level_off[(size_t)L]; k < P.blas_level_off[(size_t)L + 1]; ++k) {
+        const int32_t g = P.blas_levels[(size_t)k], mi = P.node_mesh[(size_t)g];
         const float* nd = &T.blas_nodes[(size_t)g * NF];
         float* b = &P.blas_tight[6 * (size_t)g];
         for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[a + 3] = -INFINITY; }

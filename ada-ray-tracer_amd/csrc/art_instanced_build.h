@@ -49,17 +49,21 @@ struct TwoLevelHost {
 bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vector<InstIn>& insts, TwoLevelHost& out, std::string& err,
                           bool two_sided = true, float pad_rel = -1.0f, float pad_abs = -1.0f, int open_factor = 1, float scene_extent = 0.0f);
 
-// ---- what art_move_instances_device (art_move.hip) needs besides the arrays in HBM, from a one-sided build: built once per upload
+// ---- what art_move_instances_device and art_refit_mesh_device (art_move.hip) need besides the arrays in HBM, from a one-sided build:
+// built once per upload, before either call has changed anything (a mesh refit leaves blas_tris and blas_nodes of the build stale)
 struct MovePlanHost {
   int32_t n_mesh = 0;
   std::vector<int32_t> range_off, ranges;   // entry point e: the triangle records below it, (first record in blas_tris, count) pairs ranges[2k], ranges[2k + 1], k in [range_off[e], range_off[e + 1])
   std::vector<int32_t> proxy_rec;           // entry point e: its proxy record in tlas.tris
   std::vector<int32_t> inst_mesh;           // instance i: its mesh
-  std::vector<float> mesh_box;              // 6 per mesh: the object-space box of its records (zeros: a mesh nobody shows)
+  std::vector<float> mesh_box;              // 6 per mesh: the object-space box of its records (zeros: a mesh nobody shows); in HBM a mesh refit keeps it up to date
   std::vector<int32_t> mesh_base;           // 3 per mesh: first node in blas_nodes, first record in blas_tris (-1: a mesh nobody shows), first node in qnodes
   std::vector<int32_t> tlas_levels; std::vector<int> tlas_level_off;   // the instance tree's nodes, level L = tlas_levels[tlas_level_off[L] .. tlas_level_off[L + 1]), root first
   std::vector<int32_t> node_mesh;           // per node of blas_nodes: its mesh
-  std::vector<float> blas_tight;            // 6 per node of blas_nodes: the tight box of the records below it (they never move: computed here, once)
+  std::vector<float> blas_tight;            // 6 per node of blas_nodes: the tight box of the records below it (in HBM a mesh refit keeps it up to date)
+  // the meshes' nodes (indices into blas_nodes) by depth inside their mesh, root first: level k = blas_levels[blas_level_off[k] .. blas_level_off[k + 1]),
+  // and mesh m's levels are k in [mesh_level_first[m], mesh_level_first[m + 1])
+  std::vector<int32_t> blas_levels; std::vector<int> blas_level_off, mesh_level_first;
   std::vector<float> pad_abs;               // per mesh: the pad its boxes carry (mesh_pad_abs to begin with)
   int64_t records = 0;                      // sum over the entry points of the records below them
 };

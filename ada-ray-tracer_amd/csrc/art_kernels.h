@@ -119,31 +119,46 @@ void launch_gather_tri9(hipStream_t st, const GatherArgs& G);
 // sums4 (zeroed by the caller): half areas of the inner child slots | of the leaf slots | of the leaf slots x triangle count | of the root's union
 void launch_tree_cost(hipStream_t st, const float* nodes, int n_nodes, int width, double* sums4);
 
-// the instances of an instanced scene move (art_move.hip, art_update.cpp art_move_instances_device).  Everything but m12f is the library's:
-// the scene's arrays in HBM and the plan (art_instanced_build.h MovePlanHost) next to them.
+// an instanced scene changes in HBM (art_move.hip): its instances take new matrices (art_update.cpp art_move_instances_device), or one
+// of its meshes new vertices (art_refit_mesh_device).  Everything but m12f is the library's: the scene's arrays in HBM and the plan
+// (art_instanced_build.h MovePlanHost) next to them.  Both calls end in the same pipeline (launch_move_matrices .. launch_move_tlas_level).
 struct MoveArgs {
-  const float* m12f;                           // the caller's matrices: 12 floats per instance
+  const float* m12f;                           // the matrices the pipeline runs at, 12 floats per instance: a move's are the caller's, a mesh refit's are m_cur
   int32_t n_inst, n_entry, n_mesh, n_blas_nodes;
+  float* m_cur_out;                            // where the pipeline keeps m12f: a move's m_cur; nullptr for a mesh refit, whose m12f IS m_cur (no kernel reads the array it is writing)
+  unsigned long long* bad_total;               // a move counts its bad matrices since the upload here (state + 2); nullptr for a mesh refit, which brings no matrices
+  unsigned long long* repads;                  // the meshes this update re-pads are counted here: state + 3 for a move, state + 6 for a mesh refit
   DevInstance* inst;                           // the instance table, one record per entry point
   float* tlas_nodes; float* tlas_tris;         // the instance tree and its proxy records
-  float* blas_nodes; const float* blas_tris;   // the meshes' trees and their (unchanged) object-space records
+  float* blas_nodes; const float* blas_tris;   // the meshes' trees and their object-space records (a mesh refit rewrites a mesh's slice before the pipeline runs)
   QNode* qnodes;                               // the merged quantised array: the instance tree first, then every mesh's tree
   const int32_t* range_off; const int32_t* ranges; const int32_t* proxy_rec; const int32_t* inst_mesh;
-  const float* mesh_box; const int32_t* mesh_base; const int32_t* node_mesh; const float* blas_tight;
+  const int32_t* mesh_base; const int32_t* node_mesh;
+  // state the kernels maintain (the host's copies in TwoLevelHost are stale from the first mesh refit on)
+  float* mesh_box;                             // 6 per mesh: the object-space box of its good records
+  float* blas_tight;                           // 6 per node of blas_nodes: the tight box of the good records below it (lo > hi: none)
+  float* m_cur;                                // 12 per instance: the matrices in force (the uploaded ones, or the last accepted move's)
   float* tlas_tight;                           // 6 floats per node of the instance tree: the tight box below it
-  float* ent_box;                              // 6 floats per entry point: its world box (lo > hi: a bad matrix's, empty)
+  float* ent_box;                              // 6 floats per entry point: its world box (lo > hi: empty -- a bad matrix, or a bad vertex among its records)
   int32_t* inst_ok;                            // per instance: 1 = a good matrix
-  unsigned long long* state;                   // [0] the bits of E (binary64, >= 0), [1] bad matrices of this move, [2] since the upload, [3] meshes re-padded since the upload
+  unsigned long long* state;                   // [0] the bits of E (binary64, >= 0), [1] bad matrices of this move, [2] since the upload, [3] meshes re-padded by moves since the upload,
+                                               // [4] bad vertices of this mesh refit, [5] since the upload, [6] meshes re-padded by mesh refits since the upload,
+                                               // [7] bad vertices the meshes hold now (the sum of mesh_bad)
+  unsigned long long* mesh_bad;                // per mesh: the bad vertices its last refit left among its records (0: none, or never refitted)
   unsigned long long* needed;                  // per mesh: the bits of the pad this placement asks for (binary64, >= 0)
-  float* pad_cur; int32_t* repad;              // per mesh: the pad its boxes carry; 1 = this move widens them
+  float* pad_cur; int32_t* repad;              // per mesh: the pad its boxes carry; 1 = this update widens them
   double extent;                               // the scene's extent without the instances (TwoLevelHost::scene_extent)
   float mesh_pad_rel, mesh_pad_min;            // the meshes' relative pad and the floor of their absolute pad
   float tlas_pad_rel, tlas_pad_abs;            // the instance tree builder's pad rule
 };
+constexpr int kMoveStateWords = 8;
 constexpr double kMoveMaxReach = 1.0e18;       // an instance reaching further out than this (kRefitMaxCoord) has a bad matrix
 void launch_move_matrices(hipStream_t st, const MoveArgs& M);                  // begin + matrices + pads
 void launch_move_repad(hipStream_t st, const MoveArgs& M);
 void launch_move_entry_boxes(hipStream_t st, const MoveArgs& M, bool small);   // small: few records per entry point, one wave each
 void launch_move_tlas_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n);
+// a mesh refit, after launch_refit_tris on the mesh's slices: one level of that mesh's tree (nodes of blas_nodes), then its object-space box
+void launch_refit_mesh_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n);
+void launch_refit_mesh_box(hipStream_t st, const MoveArgs& M, int mesh);
 
 }  // namespace art

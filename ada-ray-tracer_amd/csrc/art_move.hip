@@ -1,26 +1,42 @@
-// art_move.hip -- gfx950 kernels of art_move_instances_device: the instances of an instanced scene take new object -> world matrices.
-// Topology, entry points and the meshes' records stay as built; matrices and boxes are rewritten, in this order (one launch each, every
-// launch reads only what earlier launches wrote: gfx950's per-XCD L2s are not coherent within a launch):
+// art_move.hip -- gfx950 kernels of the device-side updates of an instanced scene.  art_move_instances_device: the instances take new
+// object -> world matrices.  Topology, entry points and the meshes' records stay as built; matrices and boxes are rewritten, in this
+// order (one launch each, every launch reads only what earlier launches wrote: gfx950's per-XCD L2s are not coherent within a launch):
 //
 //   k_move_begin        E = the scene's extent without the instances, this move's bad count = 0, every mesh's needed pad = 0.
 //   k_move_matrices     one lane per entry-point record: DevInstance::m, and minv in invert_3x4's arithmetic (art_instanced_build.cpp:
 //                       binary64, rounded once -- the bytes an upload writes).  The first n_inst lanes (one per instance) count the bad
-//                       matrices and raise E to the instance's reach (atomicMax on the bits of a non-negative binary64).
+//                       matrices, raise E to the instance's reach (atomicMax on the bits of a non-negative binary64) and, for a move,
+//                       keep the matrix in m_cur (m_cur_out).  The matrices are read from m12f -- the caller's for a move, m_cur for a mesh
+//                       refit, which passes no m_cur_out: the kernel never reads the array it is writing.
 //   k_move_pads_inst    one lane per instance: the upload's bound 8 * 2^-24 * (sum_j |minv_rj| * 3 E + |minv_r3|), maximised over the rows,
 //                       folded into needed[mesh].
 //   k_move_pads_mesh    one lane per mesh: repad = needed > current, current = max(current, needed).  Pads only grow.
 //   k_move_repad        one lane per node of the meshes' trees; a lane whose mesh is not re-padded returns at once.  The others run
 //                       refit_node (art_refit_node.h: the rules of a node refit are stated there) with inflate_abs = current[mesh].  The
-//                       records never move, so the tight box below every node is a constant of the plan and the whole forest is one
-//                       launch, not one per level, and no tight union is written.  The entry words of the merged quantised array are
-//                       absolute and stay as stored: only planes and header are rewritten.
+//                       tight box below every node is state of the plan that earlier launches left (blas_tight), so the whole forest
+//                       is one launch, not one per level, and no tight union is written.  The entry words of the merged quantised array
+//                       are absolute and stay as stored: only planes and header are rewritten.
 //   k_move_entry_boxes  one workgroup per entry point: the three corners of every record below it through world_box's arithmetic
 //                       (binary64 products and sums, the four-term pad, one rounding) -- the upload's tight box -- and its proxy record.
+//                       A record with a bad coordinate (a bad mesh refit left it) never reaches that arithmetic: its entry point gets
+//                       the empty box.
 //   k_move_tlas_level   one launch per level of the instance tree, deepest first: refit_node with a leaf child's box taken from its
 //                       proxies' entry points under the builder's pad rule, an inner child's from the tight box below; instance markers kept.
 //
 // A bad matrix (an element not finite, a determinant failing invert_3x4's test, or a reach beyond kMoveMaxReach) gives every entry
 // point of its instance an empty box, which refit_node treats as it treats a box with a bad vertex.
+//
+// art_refit_mesh_device: one mesh takes new vertices.  k_refit_tris (art_refit.hip) rewrites the mesh's slices of the records, then
+//
+//   k_refit_mesh_level  one launch per level of THAT mesh's tree, deepest first, one lane per node: refit_node with inflate_abs =
+//                       current[mesh], a leaf child's box from its records, an inner child's from blas_tight; the node's tight union
+//                       goes to blas_tight.  (k_move_repad is the same node refit without the tight union.)
+//   k_refit_mesh_box    mesh_box[mesh] = the tight box stored for the mesh's root; an empty one (every record bad) keeps the previous box.
+//                       mesh_bad[mesh] = the bad vertices k_refit_tris counted, and their sum over the meshes: what art_synchronize reports
+//                       is what the meshes hold now, so a good refit of ANOTHER mesh does not hide a mesh that is still bad.
+//
+// and the pipeline above runs at the matrices in force: E depends on mesh_box and every mesh's pad on E, so a mesh that grows can widen
+// another mesh's pad, and every entry point's box depends on the records below it.
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
@@ -81,9 +97,10 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_matrices(const MoveArgs M) 
     }
     for (int k = 0; k < 12; ++k) { D->m[k] = m[k]; D->minv[k] = inv ? minv[k] : 0.0f; }
     first = (e < M.n_inst);
-    if (first) {
+    if (first) {                                                           // (record e < n_inst is instance e)
       M.inst_ok[e] = ok ? 1 : 0;
-      if (!ok) { atomicAdd(&M.state[1], 1ull); atomicAdd(&M.state[2], 1ull); }
+      if (!ok) { atomicAdd(&M.state[1], 1ull); if (M.bad_total) atomicAdd(M.bad_total, 1ull); }
+      if (M.m_cur_out) for (int k = 0; k < 12; ++k) M.m_cur_out[12 * (size_t)e + k] = m[k];
     }
     if (!first || !ok) reach_max = 0.0;
   }
@@ -114,7 +131,18 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_pads_mesh(const MoveArgs M)
   const float nf = fmaxf(M.mesh_pad_min, (float)fmin(need, 1.0e30));
   const bool rp = nf > M.pad_cur[m];
   M.repad[m] = rp ? 1 : 0;
-  if (rp) { M.pad_cur[m] = nf; atomicAdd(&M.state[3], 1ull); }
+  if (rp) { M.pad_cur[m] = nf; atomicAdd(M.repads, 1ull); }
+}
+
+// node g of blas_nodes, a node of mesh mi's tree, under the pad the mesh carries now; tight_out: where its tight union goes (nullptr: not wanted)
+__device__ __forceinline__ void refit_mesh_node(const MoveArgs& M, int g, int mi, float* tight_out) {
+  const int32_t nb = M.mesh_base[3 * mi], tb = M.mesh_base[3 * mi + 1], qb = M.mesh_base[3 * mi + 2];
+  if (tb < 0) return;                                                      // (a mesh nobody shows)
+  const float pad_abs = M.pad_cur[mi];
+  refit_node<4, QEntries::kKeep>(M.blas_nodes + (size_t)g * 32, M.qnodes + (size_t)qb + (size_t)(g - nb), tight_out, M.mesh_pad_rel, pad_abs,
+                                 [&](int, int32_t ref, int32_t cnt, float l[3], float h[3]) {
+    return cnt > 0 ? records_box(M.blas_tris + (size_t)kTriFloats * (size_t)(tb + ref), cnt, l, h) : stored_box(M.blas_tight + 6 * (size_t)(nb + ref), l, h);
+  });
 }
 
 __global__ __launch_bounds__(kMoveBlock) void k_move_repad(const MoveArgs M) {
@@ -122,15 +150,23 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_repad(const MoveArgs M) {
   if (g >= M.n_blas_nodes) return;
   const int mi = M.node_mesh[g];
   if (!M.repad[mi]) return;
-  const int32_t nb = M.mesh_base[3 * mi], tb = M.mesh_base[3 * mi + 1], qb = M.mesh_base[3 * mi + 2];
-  if (tb < 0) return;
-  const float pad_abs = M.pad_cur[mi];
-  refit_node<4, QEntries::kKeep>(M.blas_nodes + (size_t)g * 32, M.qnodes + (size_t)qb + (size_t)(g - nb), nullptr, M.mesh_pad_rel, pad_abs,
-                                 [&](int, int32_t ref, int32_t cnt, float l[3], float h[3]) {
-    if (cnt > 0) (void)records_box(M.blas_tris + (size_t)kTriFloats * (size_t)(tb + ref), cnt, l, h);      // (the records never move: always good)
-    else (void)stored_box(M.blas_tight + 6 * (size_t)(nb + ref), l, h);
-    return true;
-  });
+  refit_mesh_node(M, g, mi, nullptr);
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_refit_mesh_level(const MoveArgs M, const int32_t* __restrict__ level, int n) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (t >= n) return;
+  const int g = level[t];
+  refit_mesh_node(M, g, M.node_mesh[g], M.blas_tight + 6 * (size_t)g);
+}
+
+__global__ void k_refit_mesh_box(const MoveArgs M, int mesh) {
+  const float* t = M.blas_tight + 6 * (size_t)M.mesh_base[3 * mesh];       // the mesh's root
+  if (threadIdx.x < 6 && t[0] <= t[3]) M.mesh_box[6 * (size_t)mesh + threadIdx.x] = t[threadIdx.x];
+  unsigned long long held = 0ull;                                          // this refit's count replaces the mesh's; the other meshes keep theirs
+  for (int m = threadIdx.x; m < M.n_mesh; m += 64) held += (m == mesh) ? M.state[4] : M.mesh_bad[m];
+  for (int off = 32; off > 0; off >>= 1) held += __shfl_down(held, off);   // (one wave: launch_refit_mesh_box)
+  if (threadIdx.x == 0) { M.mesh_bad[mesh] = M.state[4]; M.state[7] = held; }
 }
 
 template <int B>
@@ -145,10 +181,12 @@ __global__ __launch_bounds__(B) void k_move_entry_boxes(const MoveArgs M) {
   double Mx[12];
   for (int k = 0; k < 12; ++k) Mx[k] = (double)D->m[k];
   double lo[3] = {1e300, 1e300, 1e300}, hi[3] = {-1e300, -1e300, -1e300}, mag[3] = {0.0, 0.0, 0.0};
+  bool bad = false;
   for (int k = M.range_off[e]; k < M.range_off[e + 1]; ++k) {
     const int32_t first = M.ranges[2 * k], n3 = 3 * M.ranges[2 * k + 1];
     for (int c = tid; c < n3; c += B) {
       const float* p = M.blas_tris + (size_t)kTriFloats * (size_t)(first + c / 3) + 3 * (c % 3);
+      if (!(coord_ok(p[0]) && coord_ok(p[1]) && coord_ok(p[2]))) { bad = true; continue; }      // (a bad vertex of a mesh refit: kept out of the arithmetic below)
       const double x = p[0], y = p[1], z = p[2];
       for (int r = 0; r < 3; ++r) {                                        // world_box of art_instanced_build.cpp
         const double a = Mx[4 * r] * x, b = Mx[4 * r + 1] * y, cc = Mx[4 * r + 2] * z, w = a + b + cc + Mx[4 * r + 3];
@@ -156,6 +194,10 @@ __global__ __launch_bounds__(B) void k_move_entry_boxes(const MoveArgs M) {
         mag[r] = fmax(mag[r], fabs(a) + fabs(b) + fabs(cc) + fabs(Mx[4 * r + 3]));
       }
     }
+  }
+  if (__syncthreads_or(bad ? 1 : 0)) {                                     // (every lane of the workgroup arrives here)
+    if (tid == 0) { box[0] = box[1] = box[2] = INFINITY; box[3] = box[4] = box[5] = -INFINITY; }
+    return;
   }
   __shared__ double red[(B / 64) * 9];
   for (int r = 0; r < 3; ++r) { lo[r] = wave_min(lo[r]); hi[r] = wave_max(hi[r]); mag[r] = wave_max(mag[r]); }
@@ -214,6 +256,15 @@ void launch_move_entry_boxes(hipStream_t st, const MoveArgs& M, bool small) {
 void launch_move_tlas_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n) {
   if (n <= 0) return;
   hipLaunchKernelGGL(k_move_tlas_level, move_grid(n), dim3(kMoveBlock), 0, st, M, level_nodes, n);
+}
+
+void launch_refit_mesh_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_refit_mesh_level, move_grid(n), dim3(kMoveBlock), 0, st, M, level_nodes, n);
+}
+
+void launch_refit_mesh_box(hipStream_t st, const MoveArgs& M, int mesh) {
+  hipLaunchKernelGGL(k_refit_mesh_box, dim3(1), dim3(64), 0, st, M, mesh);
 }
 
 }  // namespace art

@@ -1,5 +1,5 @@
 // art_update.cpp -- the device-side scene updates of the C ABI (include/art_hip.h): art_refit_device (art_refit.hip), art_rebuild_device
-// (art_rebuild.hip + the GPU builders), art_move_instances_device (art_move.hip) and art_get_tree_cost.  What the kinds share is written
+// (art_rebuild.hip + the GPU builders), art_move_instances_device and art_refit_mesh_device (art_move.hip) and art_get_tree_cost.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
 // lane of timing events and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
@@ -19,7 +19,8 @@ namespace art {
 static ArtRefitInfo g_refit_info = ArtRefitInfo();         // art_get_refit_info: cumulative since the last upload
 static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
 static ArtMoveInfo g_move_info = ArtMoveInfo();            // art_get_move_info: the same
-void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); }
+static ArtMeshRefitInfo g_mesh_refit_info = ArtMeshRefitInfo();   // art_get_mesh_refit_info: the same
+void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); g_mesh_refit_info = ArtMeshRefitInfo(); }
 // ---- the caller's stream ----------------------------------------------------------------------------------------------------------
 StreamOrder::StreamOrder(Ctx& ctx, hipStream_t st) : c(ctx), cs(ctx.stream), qs(st == nullptr ? ctx.stream : (st == hipStreamLegacy ? nullptr : st)) {}
 int StreamOrder::enter() {
@@ -279,30 +280,38 @@ int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t
 
 int get_refit_info(ArtRefitInfo* out) { return get_info(out, "null ArtRefitInfo", g_refit_info, fold_refit); }
 
-// ---- moving instances (art_move_instances_device, art_move.hip) -------------------------------------------------------------------
-// The plan of the current context, from the two-level build the upload kept: MovePlanHost's arrays in one buffer, the kernels' own
-// arrays in another, and MoveArgs pointing into both and into the scene's arrays.
-static int build_move_plan(const HostScene& hs) {
+// ---- an instanced scene changes (art_move_instances_device, art_refit_mesh_device, art_move.hip) ----------------------------------
+// The plan of the current context, from the two-level build the upload kept and before either call has changed anything: MovePlanHost's
+// constant arrays and the meshes' index triples in one buffer, what the kernels maintain in another (the tight boxes, the meshes' boxes
+// and pads, the matrices in force), and MoveArgs pointing into both and into the scene's arrays.  `call` builds it; its info takes the time.
+static int build_move_plan(const HostScene& hs, const std::string& call, double& plan_ms) {
   Ctx& c = g_ctx;
   Ctx::MovePlan& P = c.move;
   const auto t0 = std::chrono::steady_clock::now();
   MovePlanHost H;
   std::string err;
-  if (!build_move_plan_host(hs.two, H, err)) return fail("art_move_instances_device: " + err);
+  if (!build_move_plan_host(hs.two, H, err)) return fail(call + ": " + err);
   const size_t n_entry = hs.two.entry.size(), n_inst = hs.two.inst.size(), nm = (size_t)H.n_mesh, n_tlas = (size_t)hs.two.tlas.n_nodes, n_blas = H.node_mesh.size();
   if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
       c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != hs.two.blas_tris.size() * 4)
-    return fail("art_move_instances_device: internal: the arrays in HBM are not the kept build's");
+    return fail(call + ": internal: the arrays in HBM are not the kept build's");
+  if (hs.inst.size() != n_entry || hs.mesh_nverts.size() != nm || hs.mesh_idx_off.size() != nm + 1 || c.b_qtris.bytes != hs.two.blas_tris.size() / kTriFloats * (size_t)kQTriBytes)
+    return fail(call + ": internal: the host scene is not the kept build's");
   std::vector<uint8_t> img;                                                // every section 16-byte aligned
   auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (bytes) std::memcpy(&img[at], p, bytes); return at; };
   const size_t o_roff = put(H.range_off.data(), H.range_off.size() * 4), o_rng = put(H.ranges.data(), H.ranges.size() * 4), o_prox = put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
-  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbox = put(H.mesh_box.data(), H.mesh_box.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
-  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_tight = put(H.blas_tight.data(), H.blas_tight.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
+  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
+  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
+  const size_t o_blev = put(H.blas_levels.data(), H.blas_levels.size() * 4), o_idx = put(hs.mesh_idx.data(), hs.mesh_idx.size() * 4);
   if (upload(P.b_plan, img)) return 1;
   std::vector<uint8_t> work;
   auto room = [&](size_t bytes) { const size_t at = work.size(); work.resize(at + ((bytes + 15) & ~(size_t)15), 0); return at; };
-  const size_t w_state = room(4 * 8), w_need = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
+  const size_t w_state = room(kMoveStateWords * 8), w_need = room(nm * 8), w_mbad = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
+  const size_t w_mbox = room(nm * 24), w_btight = room(n_blas * 24), w_mcur = room(n_inst * 48);
   std::memcpy(&work[w_pad], H.pad_abs.data(), nm * 4);
+  std::memcpy(&work[w_mbox], H.mesh_box.data(), nm * 24);
+  std::memcpy(&work[w_btight], H.blas_tight.data(), n_blas * 24);
+  for (size_t i = 0; i < n_inst; ++i) std::memcpy(&work[w_mcur + 48 * i], hs.inst[i].m, 48);      // (record i < n_inst is instance i; no move has been accepted yet)
   if (upload(P.b_work, work)) return 1;
   const char* pb = (const char*)P.b_plan.p; char* wb = (char*)P.b_work.p;
   MoveArgs& A = P.args;
@@ -311,18 +320,43 @@ static int build_move_plan(const HostScene& hs) {
   A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p;
   A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
   A.range_off = (const int32_t*)(pb + o_roff); A.ranges = (const int32_t*)(pb + o_rng); A.proxy_rec = (const int32_t*)(pb + o_prox); A.inst_mesh = (const int32_t*)(pb + o_imesh);
-  A.mesh_box = (const float*)(pb + o_mbox); A.mesh_base = (const int32_t*)(pb + o_mbase); A.node_mesh = (const int32_t*)(pb + o_nmesh); A.blas_tight = (const float*)(pb + o_tight);
-  A.state = (unsigned long long*)(wb + w_state); A.needed = (unsigned long long*)(wb + w_need); A.tlas_tight = (float*)(wb + w_tight); A.ent_box = (float*)(wb + w_box);
+  A.mesh_base = (const int32_t*)(pb + o_mbase); A.node_mesh = (const int32_t*)(pb + o_nmesh);
+  A.mesh_box = (float*)(wb + w_mbox); A.blas_tight = (float*)(wb + w_btight); A.m_cur = (float*)(wb + w_mcur);
+  A.state = (unsigned long long*)(wb + w_state); A.needed = (unsigned long long*)(wb + w_need); A.mesh_bad = (unsigned long long*)(wb + w_mbad); A.tlas_tight = (float*)(wb + w_tight); A.ent_box = (float*)(wb + w_box);
   A.inst_ok = (int32_t*)(wb + w_ok); A.pad_cur = (float*)(wb + w_pad); A.repad = (int32_t*)(wb + w_repad);
   A.extent = (double)hs.two.scene_extent; A.mesh_pad_rel = hs.two.mesh_pad_rel; A.mesh_pad_min = hs.two.mesh_pad_min;
   const BvhBuildParams tp;                                                 // the instance tree builder's pad rule: the defaults, as build_two_level_host applied them
   A.tlas_pad_rel = tp.inflate_rel; A.tlas_pad_abs = tp.inflate_abs;
   P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off;
   P.small_entries = H.records <= 64 * (int64_t)n_entry;
-  if (plan_lane(P.lane, 48 * n_inst)) return 1;
-  g_move_info.plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  P.blas_levels = (const int32_t*)(pb + o_blev); P.blas_level_off = H.blas_level_off;
+  P.meshes.assign(nm, Ctx::MovePlan::Mesh());
+  int64_t max_verts = 0;
+  for (size_t mi = 0; mi < nm; ++mi) {
+    Ctx::MovePlan::Mesh& m = P.meshes[mi];
+    m.nverts = hs.mesh_nverts[mi]; m.level_first = H.mesh_level_first[mi]; m.level_end = H.mesh_level_first[mi + 1];
+    m.n_prims = (int32_t)((hs.mesh_idx_off[mi + 1] - hs.mesh_idx_off[mi]) / 3);
+    m.idx = (const int32_t*)(pb + o_idx) + hs.mesh_idx_off[mi];
+    max_verts = std::max(max_verts, m.nverts);
+  }
+  for (size_t i = 0; i < n_inst; ++i) {                                    // (build_move_plan_host checked every instance's slice)
+    Ctx::MovePlan::Mesh& m = P.meshes[(size_t)hs.two.inst[i].mesh];
+    m.tri_base = hs.two.inst[i].tri_base; m.n_recs = hs.two.inst[i].n_tris; m.shade_base = hs.inst[i].shade_base;
+    if (m.n_prims < 1 || (size_t)(m.shade_base + m.n_prims) * kTriShadeFloats * 4 > c.b_m_shade.bytes) return fail(call + ": internal: a mesh's shading records lie outside the array");
+  }
+  if (plan_lane(P.lane, 48 * n_inst) || plan_lane(P.refit_lane, 2 * 12 * (size_t)max_verts)) return 1;
+  plan_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
   P.ready = true;
   return 0;
+}
+
+// matrices, pads, re-pad, entry-point boxes, the instance tree: what a move and a mesh refit both end in
+static void launch_move_pipeline(const Ctx::MovePlan& P, const MoveArgs& A, hipStream_t s) {
+  launch_move_matrices(s, A);
+  launch_move_repad(s, A);
+  launch_move_entry_boxes(s, A, P.small_entries);
+  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                   // deepest level first
+    launch_move_tlas_level(s, A, P.levels + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
 }
 
 // the current context's move on stream s, from matrices in this context's device memory
@@ -330,15 +364,11 @@ static int move_one(const float* m12f, hipStream_t s) {
   Ctx& c = g_ctx;
   Ctx::MovePlan& P = c.move;
   MoveArgs A = P.args;
-  A.m12f = m12f;
+  A.m12f = m12f; A.m_cur_out = A.m_cur; A.bad_total = A.state + 2; A.repads = A.state + 3;
   (void)fold_lane(P.lane, /*wait=*/false, &c == &g_devs[0] ? &g_move_info.move_ms : nullptr);
   LaneTimer timer;
   if (timer.start(P.lane, s)) return 1;
-  launch_move_matrices(s, A);
-  launch_move_repad(s, A);
-  launch_move_entry_boxes(s, A, P.small_entries);
-  for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                   // deepest level first
-    launch_move_tlas_level(s, A, P.levels + P.level_off[(size_t)L], P.level_off[(size_t)L + 1] - P.level_off[(size_t)L]);
+  launch_move_pipeline(P, A, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(std::string("art_move_instances_device: kernel launch failed: ") + hipGetErrorString(e));
   return 0;
@@ -358,12 +388,67 @@ int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st
   if (n_instances != (int64_t)c0.scene.n_inst) return fail("art_move_instances_device: n_instances " + std::to_string(n_instances) + " differs from the uploaded scene's " + std::to_string(c0.scene.n_inst));
   if (!m12f) return fail("art_move_instances_device: null m12f");
   return run_update("art_move_instances_device", st, [](Ctx& c) -> UpdateLane& { return c.move.lane; }, {{m12f, 48 * (size_t)n_instances, "m12f"}},
-                    [&] { return !g_ctx.move.ready && build_move_plan(hs); },
+                    [&] { return !g_ctx.move.ready && build_move_plan(hs, "art_move_instances_device", g_move_info.plan_ms); },
                     [&] { hs.inst_stale = true; g_move_info.moves += 1; },                                      // (art_trace_rays reads the matrices on the host)
                     [&](const void* const* src, hipStream_t s) { return move_one((const float*)src[0], s); });
 }
 
 int get_move_info(ArtMoveInfo* out) { return get_info(out, "null ArtMoveInfo", g_move_info, fold_move); }
+
+// ---- deforming a mesh of an instanced scene (art_refit_mesh_device, art_refit.hip + art_move.hip) ---------------------------------
+// the current context's mesh refit on stream s, from positions (and normals) in this context's device memory
+static int refit_mesh_one(int32_t mesh, const float* pos, const float* nrm, hipStream_t s) {
+  Ctx& c = g_ctx;
+  Ctx::MovePlan& P = c.move;
+  const Ctx::MovePlan::Mesh& m = P.meshes[(size_t)mesh];
+  MoveArgs A = P.args;
+  A.m12f = A.m_cur; A.m_cur_out = nullptr; A.bad_total = nullptr; A.repads = A.state + 6;
+  RefitArgs R;                                                             // k_refit_tris on the mesh's slices of the records, their padded copy and the shading records
+  std::memset(&R, 0, sizeof R);
+  R.pos3f = pos; R.nrm3f = nrm; R.idx = m.idx;
+  R.nverts = m.nverts; R.n_prims = m.n_prims; R.n_recs = m.n_recs;
+  R.tris = (float*)c.b_blas_tris.p + (size_t)kTriFloats * (size_t)m.tri_base; R.qtris = (float*)c.b_qtris.p + (size_t)(kQTriBytes / 4) * (size_t)m.tri_base;
+  R.m_shade = (float*)c.b_m_shade.p + (size_t)kTriShadeFloats * (size_t)m.shade_base;
+  R.bad = A.state + 4;                                                     // state[4]: this refit's bad vertices, state[5]: since the upload
+  (void)fold_lane(P.refit_lane, /*wait=*/false, &c == &g_devs[0] ? &g_mesh_refit_info.refit_ms : nullptr);
+  LaneTimer timer;
+  if (timer.start(P.refit_lane, s)) return 1;
+  HIP_TRY(hipMemsetAsync(R.bad, 0, sizeof(unsigned long long), s));
+  launch_refit_tris(s, R);
+  for (int L = m.level_end - 1; L >= m.level_first; --L)                   // the mesh's tree, deepest level first
+    launch_refit_mesh_level(s, A, P.blas_levels + P.blas_level_off[(size_t)L], P.blas_level_off[(size_t)L + 1] - P.blas_level_off[(size_t)L]);
+  launch_refit_mesh_box(s, A, mesh);
+  launch_move_pipeline(P, A, s);                                           // at the matrices in force
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(std::string("art_refit_mesh_device: kernel launch failed: ") + hipGetErrorString(e));
+  return 0;
+}
+
+static int fold_mesh_refit() {              // the counters k_refit_tris / k_refit_mesh_box / k_move_pads_mesh keep for the mesh refits; reported: the bad vertices the meshes hold now
+  Ctx::MovePlan& P = g_ctx.move;
+  return fold_kind<kMoveStateWords>(P.refit_lane, g_mesh_refit_info.refit_ms, P.args.state, [&](const unsigned long long* w, bool dev0) { if (dev0) { g_mesh_refit_info.bad_vertices = w[5]; g_mesh_refit_info.repads = w[6]; } return w[7]; });
+}
+
+int refit_mesh_device(int32_t mesh, const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
+  Ctx& c0 = g_devs[0];
+  const std::string name = "art_refit_mesh_device";
+  if (!c0.scene_ready) return fail(name + ": no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which keeps its own meshes");
+  if (c0.scene.n_inst <= 0) return fail(name + ": the scene is not instanced (n_instances = 0); art_refit_device moves the vertices of a flat mesh");
+  const int64_t n_mesh = (int64_t)hs.mesh_nverts.size();
+  if (mesh < 0 || mesh >= n_mesh) return fail(name + ": mesh " + std::to_string(mesh) + " is out of range (the scene has " + std::to_string(n_mesh) + " meshes)");
+  if (hs.mesh_idx_off[(size_t)mesh + 1] == hs.mesh_idx_off[(size_t)mesh]) return fail(name + ": no instance shows mesh " + std::to_string(mesh));
+  if (nverts != (int64_t)hs.mesh_nverts[(size_t)mesh]) return fail(name + ": nverts " + std::to_string(nverts) + " differs from the uploaded mesh's " + std::to_string(hs.mesh_nverts[(size_t)mesh]));
+  if (!pos) return fail(name + ": null pos3f");
+  const size_t bytes = 12 * (size_t)nverts;
+  return run_update(name, st, [](Ctx& c) -> UpdateLane& { return c.move.refit_lane; }, {{pos, bytes, "pos3f"}, {nrm, bytes, "nrm3f"}},
+                    [&] { return !g_ctx.move.ready && build_move_plan(hs, name, g_mesh_refit_info.plan_ms); },
+                    [&] { if (nrm) hs.m_shade_stale = true; g_mesh_refit_info.refits += 1; },                     // (art_trace_rays reads the shading records on the host; the instance table keeps its bytes)
+                    [&](const void* const* src, hipStream_t s) { return refit_mesh_one(mesh, (const float*)src[0], (const float*)src[1], s); });
+}
+
+int get_mesh_refit_info(ArtMeshRefitInfo* out) { return get_info(out, "null ArtMeshRefitInfo", g_mesh_refit_info, fold_mesh_refit); }
 
 // ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
 // What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
@@ -538,9 +623,10 @@ void release_updates(Ctx& c) {
   Ctx::MovePlan& P = c.move;
   P.b_plan.release(); P.b_work.release();
   P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs(); P.ready = false; release_lane(P.lane);
+  P.meshes.clear(); P.blas_level_off.clear(); P.blas_levels = nullptr; release_lane(P.refit_lane);
 }
 
-void destroy_updates(Ctx& c) { release_updates(c); destroy_lane(c.refit.lane); destroy_lane(c.move.lane); }
+void destroy_updates(Ctx& c) { release_updates(c); destroy_lane(c.refit.lane); destroy_lane(c.move.lane); destroy_lane(c.move.refit_lane); }
 
 int sync_updates() {
   Ctx& c = g_ctx;
@@ -548,8 +634,11 @@ int sync_updates() {
   if (report_bad(c.refit.lane, "art_refit_device: ", " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes "
                  "holding them are empty (no ray enters them) until a good refit or art_upload_scene")) return 1;
   if (fold_move()) return 1;
-  return report_bad(c.move.lane, "art_move_instances_device: ", " instance matrix(es) with an element that is not finite, without an inverse, or "
-                    "reaching beyond 1e18; their instances are empty (no ray enters them) until a good move or art_upload_scene");
+  if (report_bad(c.move.lane, "art_move_instances_device: ", " instance matrix(es) with an element that is not finite, without an inverse, or "
+                 "reaching beyond 1e18; their instances are empty (no ray enters them) until a good move or art_upload_scene")) return 1;
+  if (fold_mesh_refit()) return 1;
+  return report_bad(c.move.refit_lane, "art_refit_mesh_device: ", " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the boxes and the entry "
+                    "points holding them are empty (no ray enters them) until a good refit of their mesh or art_upload_scene");
 }
 
 }  // namespace art

@@ -291,6 +291,35 @@ int  art_move_instances_device(const float* m12f, int64_t n_instances, void* hip
 typedef struct ArtMoveInfo { uint64_t moves; double move_ms; double plan_ms; uint64_t bad_matrices; uint64_t repads; } ArtMoveInfo;
 int  art_get_move_info(ArtMoveInfo* out);   /* cumulative since art_upload_scene; waits for the moves enqueued so far */
 
+/* Deforming a mesh of an instanced scene.  mesh indexes ArtSceneDesc::meshes of the uploaded instanced scene;
+ * pos3f / nrm3f: device memory of the library's device, 3*nverts floats in the vertex order of that ArtMesh, in object space; nrm3f ==
+ * NULL keeps the normals.  Indices, material ids, which mesh an instance shows and the matrices stay.  Kernels rewrite the mesh's
+ * triangle records, their padded copy and (with nrm3f) its shading records, refit the mesh's tree level by level (its topology and leaf
+ * order stay; the entry points stay where the build opened them), and then bring everything that depends on where the triangles are up
+ * to date at the matrices in force (the uploaded ones, or the last accepted move's): the absolute pads of the meshes' boxes -- the
+ * scene's extent follows the mesh's box, so a mesh that grows can widen another mesh's pad; pads only grow, as for a move -- the world
+ * box and proxy record of every entry point, and the instance tree's boxes.  Picture, ray count and hit records are those of
+ * art_upload_scene of the same scene with that mesh's vertices replaced, at the matrices in force, bit for bit.  Stream-ordered
+ * exactly as art_refit_device and art_move_instances_device are: work enqueued before the call sees the old shape, work enqueued after
+ * it the new one; the host waits only where the plan the call shares with art_move_instances_device is first built (the first of the
+ * two calls after an upload).  Under art_init_devices every context is updated, the others from a peer copy of pos3f / nrm3f.  Refused
+ * before anything is launched: no scene, a scene that is not instanced (art_refit_device moves a flat mesh), a scene committed through
+ * gcore_commit_scene, mesh out of range, a mesh no instance shows, nverts other than that mesh's uploaded count, null pos3f, host memory
+ * or another device's memory.  A vertex with a coordinate that is not finite or beyond 1e18 in magnitude is a bad vertex, counted as
+ * art_refit_device counts them: the boxes holding it and every entry point with it among its records are empty (no ray enters them) and
+ * the next art_synchronize fails with the count; a later good refit of the mesh or an upload clears that state.  The count is kept per
+ * mesh: art_synchronize after a mesh refit reports the bad vertices of all meshes that still hold some, so a good refit of another mesh
+ * does not hide them.  The placement test of art_move_instances_device runs again against the mesh's new box: an instance that the
+ * grown mesh takes beyond 1e18 (coordinate times matrix) is emptied like a bad matrix's instance until a refit or a move brings it back
+ * within reach, and nothing reports it -- the one case in which the picture is not the upload's.  After a large deformation
+ * the trees cost more to walk than the ones a fresh art_upload_scene builds; art_get_tree_cost is not defined for an instanced scene. */
+int  art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream);
+/* refits = calls accepted, refit_ms = HIP events around device 0's kernels of the call, plan_ms = host time of building the plans (where
+ * this call built them), bad_vertices = bad vertices counted on device 0 over all mesh refits, repads = meshes whose boxes a mesh refit
+ * re-padded, over all mesh refits. */
+typedef struct ArtMeshRefitInfo { uint64_t refits; double refit_ms; double plan_ms; uint64_t bad_vertices; uint64_t repads; } ArtMeshRefitInfo;
+int  art_get_mesh_refit_info(ArtMeshRefitInfo* out);   /* cumulative since art_upload_scene; waits like art_get_move_info */
+
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 int  art_get_stats(ArtStats* out);
 /* The wavefront stages around the trace kernel (device 0, cumulative since art_resize; cooperative schedule): GPU time per kind of
