@@ -131,6 +131,46 @@ class ArtMeshRefitInfo(C.Structure):
     _fields_ = [("refits", C.c_uint64), ("refit_ms", C.c_double), ("plan_ms", C.c_double), ("bad_vertices", C.c_uint64), ("repads", C.c_uint64)]
 
 
+class ArtTwoLevelInfo(C.Structure):
+    _fields_ = [("n_inst", C.c_int32), ("n_entry", C.c_int32), ("n_mesh", C.c_int32), ("n_tlas_nodes", C.c_int32), ("n_blas_nodes", C.c_int32),
+                ("n_records", C.c_int32), ("inst_shift", C.c_int32), ("updated", C.c_int32),
+                ("mesh_pad_rel", C.c_float), ("mesh_pad_min", C.c_float), ("scene_extent", C.c_float), ("tlas_pad_rel", C.c_float),
+                ("tlas_pad_abs", C.c_float), ("reserved_", C.c_int32)]
+
+
+TWO_LEVEL_ARRAYS = ("inst", "tlas_nodes", "tlas_tris", "blas_nodes", "blas_tris", "qnodes", "mesh_pad", "mesh_box", "mesh_base", "node_mesh")
+
+
+class ArtTwoLevelBuffers(C.Structure):
+    _fields_ = [(name, C.c_void_p) for name in TWO_LEVEL_ARRAYS] + [("cap", C.c_int64 * 10)]
+
+
+def two_level_arrays(call):
+    """call(info pointer, buffers pointer or None) -> rc is art_export_two_level or a function with its arguments: the sizes first, then
+    the arrays.  Returns (dict of numpy arrays and of the info's scalars, rc): rc != 0 means the call failed and the dict is None."""
+    info = ArtTwoLevelInfo()
+    rc = call(C.byref(info), None)
+    if rc:
+        return None, rc
+    i = info
+    shapes = dict(inst=((i.n_entry, 32), np.uint32), tlas_nodes=((i.n_tlas_nodes, 32), np.float32), tlas_tris=((i.n_entry, 12), np.float32),
+                  blas_nodes=((i.n_blas_nodes, 32), np.float32), blas_tris=((i.n_records, 12), np.float32),
+                  qnodes=((i.n_tlas_nodes + i.n_blas_nodes, 16), np.uint32), mesh_pad=((i.n_mesh,), np.float32), mesh_box=((i.n_mesh, 6), np.float32),
+                  mesh_base=((i.n_mesh, 3), np.int32), node_mesh=((i.n_blas_nodes,), np.int32))
+    out = {name: np.zeros(*shapes[name]) for name in TWO_LEVEL_ARRAYS}
+    buf = ArtTwoLevelBuffers()
+    for k, name in enumerate(TWO_LEVEL_ARRAYS):
+        setattr(buf, name, out[name].ctypes.data); buf.cap[k] = out[name].size
+    rc = call(C.byref(info), C.byref(buf))
+    if rc:
+        return None, rc
+    for name in ("n_inst", "inst_shift", "updated"):
+        out[name] = int(getattr(info, name))
+    for name in ("mesh_pad_rel", "mesh_pad_min", "scene_extent", "tlas_pad_rel", "tlas_pad_abs"):
+        out[name] = np.float32(getattr(info, name))
+    return out, 0
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -142,7 +182,7 @@ EXPORTED_SYMBOLS = [
     "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
-    "art_export_bvh", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
+    "art_export_bvh", "art_export_two_level", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
 ]
@@ -191,6 +231,7 @@ def load_library():
     L.art_refit_mesh_device.argtypes = [C.c_int32, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_mesh_refit_info.argtypes = [C.POINTER(ArtMeshRefitInfo)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
+    L.art_export_two_level.argtypes = [C.POINTER(ArtTwoLevelInfo), C.POINTER(ArtTwoLevelBuffers)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
     L.art_get_reduce_info.argtypes = [C.POINTER(ArtReduceInfo)]
     L.art_get_stage_stats.argtypes = [C.POINTER(ArtStageStats)]
@@ -583,6 +624,16 @@ class Backend:
         nodes = np.zeros(info.n_nodes * 8 * info.node_width, np.float32); tris = np.zeros(info.n_tris * 12, np.float32)
         _check(self.lib.art_export_bvh(_fp(nodes), nodes.size, _fp(tris), tris.size, C.byref(info)))
         return nodes, tris, info
+
+    def export_two_level(self):
+        """The two-level tree of the uploaded instanced scene as it lies in device 0's HBM (art_export_two_level; waits): a dict of numpy
+        arrays -- inst [n_entry, 32] uint32 (DevInstance words), tlas_nodes [., 32], tlas_tris [n_entry, 12], blas_nodes [., 32], blas_tris
+        [., 12] float32, qnodes [., 16] uint32 (the instance tree's nodes first), mesh_pad [n_mesh], mesh_box [n_mesh, 6] float32, mesh_base
+        [n_mesh, 3], node_mesh int32 -- and the scalars n_inst, inst_shift, updated, mesh_pad_rel, mesh_pad_min, scene_extent, tlas_pad_rel,
+        tlas_pad_abs."""
+        out, rc = two_level_arrays(self.lib.art_export_two_level)
+        _check(rc)
+        return out
 
     def stats(self):
         st = ArtStats()

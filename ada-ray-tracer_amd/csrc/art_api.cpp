@@ -1229,11 +1229,13 @@ int art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, 
 
 int art_get_mesh_refit_info(ArtMeshRefitInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_mesh_refit_info(out); }
 
+int art_export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) { std::lock_guard<std::mutex> lk(g_mu); return export_two_level(info, buf); }
+
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (!g_ctx.scene_ready) return fail("no scene uploaded");
   Bvh8& b = g_ctx.host_scene.bvh;
-  if (g_ctx.scene.n_inst > 0 && (nodes || tris)) return fail("art_export_bvh: an instanced scene has a two-level tree; only its sizes are reported (ArtBvhInfo)");
+  if (g_ctx.scene.n_inst > 0 && (nodes || tris)) return fail("art_export_bvh: an instanced scene has a two-level tree; only its sizes are reported here (ArtBvhInfo); art_export_two_level exports its arrays");
   if (g_ctx.host_scene.tree_in_hbm_only() && b.nodes.empty() && (nodes || tris)) {     // a GPU-built or refitted tree is fetched on first request
     HIP_TRY(hipStreamSynchronize(g_ctx.stream));                                         // (a refit on another stream is ordered before it)
     b.nodes.resize((size_t)b.n_nodes * node_floats(b.width)); b.tris.resize((size_t)b.n_tris * kTriFloats);

@@ -199,6 +199,7 @@ int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st
 int get_move_info(ArtMoveInfo* out);
 int refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_mesh_refit_info(ArtMeshRefitInfo* out);
+int export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf);   // device 0's two-level scene as it lies in HBM (caller holds g_mu)
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 
 }  // namespace art

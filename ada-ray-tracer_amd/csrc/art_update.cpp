@@ -1,5 +1,6 @@
 // art_update.cpp -- the device-side scene updates of the C ABI (include/art_hip.h): art_refit_device (art_refit.hip), art_rebuild_device
-// (art_rebuild.hip + the GPU builders), art_move_instances_device and art_refit_mesh_device (art_move.hip) and art_get_tree_cost.  What the kinds share is written
+// (art_rebuild.hip + the GPU builders), art_move_instances_device and art_refit_mesh_device (art_move.hip), art_get_tree_cost and the
+// diagnostic art_export_two_level.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
 // lane of timing events and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
@@ -449,6 +450,61 @@ int refit_mesh_device(int32_t mesh, const float* pos, const float* nrm, int64_t 
 }
 
 int get_mesh_refit_info(ArtMeshRefitInfo* out) { return get_info(out, "null ArtMeshRefitInfo", g_mesh_refit_info, fold_mesh_refit); }
+
+// ---- the two-level scene as it lies in HBM (art_export_two_level) -------------------------------------------------------------------
+// Device 0's arrays, copied after its stream has drained (an update on another stream is ordered before the context stream's later
+// work).  The per-mesh values: the plan's working buffer once an update has built the plan, the build's before that.
+int export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) {
+  const std::string name = "art_export_two_level";
+  if (!info) return fail(name + ": null ArtTwoLevelInfo");
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail(name + ": no scene uploaded");
+  const HostScene& hs = c.host_scene;
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which keeps its own two-level tree");
+  if (c.scene.n_inst <= 0) return fail(name + ": the scene is not instanced (n_instances = 0); art_export_bvh exports the tree of a flat mesh");
+  const TwoLevelHost& T = hs.two;
+  const size_t n_entry = T.entry.size(), n_inst = T.inst.size(), nm = T.mesh_pad_abs.size(), n_tlas = (size_t)T.tlas.n_nodes;
+  const size_t n_blas = T.blas_nodes.size() / 32, n_rec = T.blas_tris.size() / kTriFloats;
+  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
+      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != n_rec * kTriBytes)
+    return fail(name + ": internal: the arrays in HBM are not the kept build's");
+  const Ctx::MovePlan& P = c.move;
+  std::memset(info, 0, sizeof *info);
+  info->n_inst = (int32_t)n_inst; info->n_entry = (int32_t)n_entry; info->n_mesh = (int32_t)nm; info->n_tlas_nodes = (int32_t)n_tlas;
+  info->n_blas_nodes = (int32_t)n_blas; info->n_records = (int32_t)n_rec; info->inst_shift = c.scene.inst_shift; info->updated = P.ready ? 1 : 0;
+  const BvhBuildParams tp;                                                 // (the instance tree builder's pad rule: build_move_plan)
+  info->mesh_pad_rel = T.mesh_pad_rel; info->mesh_pad_min = T.mesh_pad_min; info->scene_extent = T.scene_extent;
+  info->tlas_pad_rel = tp.inflate_rel; info->tlas_pad_abs = tp.inflate_abs;
+  if (!buf) return 0;
+  void* const dst[10] = {buf->inst, buf->tlas_nodes, buf->tlas_tris, buf->blas_nodes, buf->blas_tris, buf->qnodes, buf->mesh_pad, buf->mesh_box, buf->mesh_base, buf->node_mesh};
+  const size_t words[10] = {n_entry * 32, n_tlas * 32, n_entry * kTriFloats, n_blas * 32, n_rec * kTriFloats, (n_tlas + n_blas) * 16, nm, 6 * nm, 3 * nm, n_blas};
+  static const char* const what[10] = {"inst", "tlas_nodes", "tlas_tris", "blas_nodes", "blas_tris", "qnodes", "mesh_pad", "mesh_box", "mesh_base", "node_mesh"};
+  bool any = false;
+  for (int k = 0; k < 10; ++k) {
+    if (!dst[k]) continue;
+    any = true;
+    if (buf->cap[k] < (int64_t)words[k]) return fail(name + ": buffer " + what[k] + " too small (" + std::to_string(words[k]) + " words)");
+  }
+  if (!any) return 0;
+  MovePlanHost H;
+  if (!P.ready && (dst[6] || dst[7] || dst[8] || dst[9])) {
+    std::string err;
+    if (!build_move_plan_host(T, H, err)) return fail(name + ": " + err);
+  }
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  const void* const dev[6] = {c.b_inst.p, c.b_tlas_nodes.p, c.b_tlas_tris.p, c.b_blas_nodes.p, c.b_blas_tris.p, c.b_qnodes.p};
+  for (int k = 0; k < 6; ++k) if (dst[k] && words[k]) HIP_TRY(hipMemcpy(dst[k], dev[k], words[k] * 4, hipMemcpyDeviceToHost));
+  const void* const plan_dev[4] = {P.args.pad_cur, P.args.mesh_box, P.args.mesh_base, P.args.node_mesh};
+  const void* const plan_host[4] = {H.pad_abs.data(), H.mesh_box.data(), H.mesh_base.data(), H.node_mesh.data()};
+  for (int k = 0; k < 4; ++k) {
+    if (!dst[6 + k] || !words[6 + k]) continue;
+    if (P.ready) HIP_TRY(hipMemcpy(dst[6 + k], plan_dev[k], words[6 + k] * 4, hipMemcpyDeviceToHost));
+    else std::memcpy(dst[6 + k], plan_host[k], words[6 + k] * 4);
+  }
+  return 0;
+}
 
 // ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
 // What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails

@@ -321,6 +321,34 @@ typedef struct ArtMeshRefitInfo { uint64_t refits; double refit_ms; double plan_
 int  art_get_mesh_refit_info(ArtMeshRefitInfo* out);   /* cumulative since art_upload_scene; waits like art_get_move_info */
 
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
+
+/* Diagnostic: the two-level tree of an instanced scene as it lies in device 0's HBM right now -- what the trace kernels read, after
+ * whatever art_move_instances_device and art_refit_mesh_device have done to it (the host's copies of the build are stale from the first
+ * update on).  The call waits for the library's stream (an update enqueued on another stream is ordered before it, as for art_export_bvh
+ * after a refit), copies, launches nothing and changes nothing.  buf == NULL, or a NULL pointer in it: that array is not wanted (sizes
+ * only); cap[k] is the capacity of the k-th pointer of ArtTwoLevelBuffers in 32-bit words, a buffer that is too small fails the call.
+ *   inst        32 words per entry point: the DevInstance records (m, minv, node_base, tri_base, shade_base, root_entry, qroot, inst, 2 pad
+ *               words); the first n_inst are the instances
+ *   tlas_nodes  32 per node of the instance tree: its binary32 packets      tlas_tris   12 per entry point: the proxy records
+ *   blas_nodes  32 per node of the meshes' trees, one mesh after the other  blas_tris   12 per triangle record of the meshes
+ *   qnodes      16 per node: the merged quantised array, the instance tree's n_tlas_nodes first, then the meshes' n_blas_nodes
+ *   mesh_pad    1 per mesh: the absolute pad its boxes carry                mesh_box    6 per mesh: the object-space box of its good records
+ *   mesh_base   3 per mesh: first node in blas_nodes, first record in blas_tris (-1: no instance shows the mesh), first node in qnodes
+ *   node_mesh   1 per node of blas_nodes: its mesh
+ * Before the first update the per-mesh values are the build's, afterwards the ones the kernels maintain (`updated` = 1).  The info also
+ * carries the rules an update applies: the meshes' relative pad and the floor of their absolute pad, the scene's extent without the
+ * instances, and the instance tree's pad rule.  Refused: no scene, a scene committed through gcore_commit_scene, a flat scene
+ * (art_export_bvh exports that tree). */
+typedef struct ArtTwoLevelInfo {
+  int32_t n_inst, n_entry, n_mesh, n_tlas_nodes, n_blas_nodes, n_records, inst_shift, updated;
+  float   mesh_pad_rel, mesh_pad_min, scene_extent, tlas_pad_rel, tlas_pad_abs; int32_t reserved_;
+} ArtTwoLevelInfo;
+typedef struct ArtTwoLevelBuffers {
+  uint32_t* inst; float* tlas_nodes; float* tlas_tris; float* blas_nodes; float* blas_tris; uint32_t* qnodes;
+  float* mesh_pad; float* mesh_box; int32_t* mesh_base; int32_t* node_mesh;
+  int64_t cap[10];
+} ArtTwoLevelBuffers;
+int  art_export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf);
 int  art_get_stats(ArtStats* out);
 /* The wavefront stages around the trace kernel (device 0, cumulative since art_resize; cooperative schedule): GPU time per kind of
  * kernel (HIP events on the launch stream, like ArtStats::trace_ms) and the work items every bounce read and kept -- what bench.py's

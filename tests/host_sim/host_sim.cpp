@@ -203,3 +203,33 @@ extern "C" int hs_trace_instanced(const float* verts, int n_verts, const int* id
   }
   return 0;
 }
+
+// ---- the two-level build of an instanced scene (art_host_scene.cpp flatten_scene -> build_two_level_host, build_move_plan_host) in the
+// form art_export_two_level gives the arrays in HBM on the GPU box: what an upload writes, before any update
+extern "C" int hs_two_level(const ArtSceneDesc* sd, ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) {
+  HostScene hs; BvhBuildParams bp = g_bp;
+  if (!flatten_scene(*sd, bp, hs, g_err)) return 1;
+  if (hs.hdr.n_inst <= 0) { g_err = "hs_two_level: the scene is not instanced"; return 1; }
+  const TwoLevelHost& T = hs.two;
+  MovePlanHost H;
+  if (!build_move_plan_host(T, H, g_err)) return 1;
+  const size_t n_entry = T.entry.size(), nm = T.mesh_pad_abs.size(), n_tlas = (size_t)T.tlas.n_nodes, n_blas = T.blas_nodes.size() / 32, n_rec = T.blas_tris.size() / kTriFloats;
+  if (hs.inst.size() != n_entry || T.tlas.tris.size() != n_entry * kTriFloats) { g_err = "hs_two_level: internal: entry points and proxies differ"; return 1; }
+  std::memset(info, 0, sizeof *info);
+  info->n_inst = (int32_t)T.inst.size(); info->n_entry = (int32_t)n_entry; info->n_mesh = (int32_t)nm; info->n_tlas_nodes = (int32_t)n_tlas;
+  info->n_blas_nodes = (int32_t)n_blas; info->n_records = (int32_t)n_rec; info->inst_shift = hs.hdr.inst_shift;
+  const BvhBuildParams tp;
+  info->mesh_pad_rel = T.mesh_pad_rel; info->mesh_pad_min = T.mesh_pad_min; info->scene_extent = T.scene_extent;
+  info->tlas_pad_rel = tp.inflate_rel; info->tlas_pad_abs = tp.inflate_abs;
+  if (!buf) return 0;
+  void* const dst[10] = {buf->inst, buf->tlas_nodes, buf->tlas_tris, buf->blas_nodes, buf->blas_tris, buf->qnodes, buf->mesh_pad, buf->mesh_box, buf->mesh_base, buf->node_mesh};
+  const void* const src[10] = {hs.inst.data(), T.tlas.nodes.data(), T.tlas.tris.data(), T.blas_nodes.data(), T.blas_tris.data(), T.qnodes.data(),
+                               H.pad_abs.data(), H.mesh_box.data(), H.mesh_base.data(), H.node_mesh.data()};
+  const size_t words[10] = {n_entry * 32, n_tlas * 32, n_entry * kTriFloats, n_blas * 32, n_rec * kTriFloats, (n_tlas + n_blas) * 16, nm, 6 * nm, 3 * nm, n_blas};
+  for (int k = 0; k < 10; ++k) {
+    if (!dst[k]) continue;
+    if (buf->cap[k] < (long long)words[k]) { g_err = "hs_two_level: buffer too small"; return 2; }
+    std::memcpy(dst[k], src[k], words[k] * 4);
+  }
+  return 0;
+}

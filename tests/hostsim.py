@@ -94,6 +94,16 @@ def bvh(art, sd):
     return nodes, tris, dict(n_nodes=info[0], n_tris=info[1], max_stack=info[2], width=info[3])
 
 
+def two_level(art, sd):
+    """the two-level build of an instanced art.SceneDesc as an upload writes it, in the form of Backend.export_two_level()"""
+    L = lib(art)
+    L.hs_two_level.argtypes = [C.POINTER(art.ArtSceneDesc), C.POINTER(art.ArtTwoLevelInfo), C.POINTER(art.ArtTwoLevelBuffers)]
+    out, rc = art.two_level_arrays(lambda info, buf: L.hs_two_level(C.byref(sd.desc), info, buf))
+    if rc:
+        raise RuntimeError(L.hs_last_error().decode())
+    return out
+
+
 def set_bvh_param(art, name, value):
     """Builder parameter (art_bvh.h BvhBuildParams) for the following host-simulation builds."""
     L = lib(art)

@@ -58,9 +58,10 @@ def _grid(k, s, o):
     return (ks.astype(np.float64) + o.astype(np.float64)).astype(F)
 
 
-def quantise(lo, hi, good):
+def quantise(lo, hi, good, codes=False):
     """art_qnode.h for n nodes at once.  lo, hi: [n, W, 3] padded boxes, good: [n, W] slots that take part.  Returns the dequantised
-    planes (only entries under `good` mean anything) and the per-node origin and scale."""
+    planes (only entries under `good` mean anything) and the per-node origin and scale; with codes also the 8-bit plane numbers
+    (ql, qh: int64 [n, W, 3])."""
     n, W, _ = lo.shape
     g3 = good[:, :, None]
     with np.errstate(invalid="ignore", over="ignore"):
@@ -94,6 +95,8 @@ def quantise(lo, hi, good):
             rounds += 1
             assert rounds < 300, "the scale loop does not end"
         s3 = s[:, None, None]; o3 = np.broadcast_to(o[:, None, :], (n, W, 3))
+        if codes:
+            return _grid(ql, s3, o3), _grid(qh, s3, o3), o, s, ql, qh
         return _grid(ql, s3, o3), _grid(qh, s3, o3), o, s
 
 
