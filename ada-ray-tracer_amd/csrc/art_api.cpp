@@ -34,27 +34,16 @@ std::mutex g_mu;
 static ncclComm_t g_comms[kMaxDevices];
 static bool g_comms_ready = false;     // distinct GPUs: the framebuffer reduce goes through RCCL
 // events around every reduce on device 0's stream (art_get_reduce_info: the reduce's GPU time is part of the evidence of a multi-GPU run)
-static std::vector<hipEvent_t> g_reduce_events;
+static EventPairs g_reduce_pairs;     // (a host that downloads every frame re-uses one pair)
 static double g_reduce_ms = 0.0; static int g_reduces = 0, g_reduce_path = 0;
 static bool g_multi_api = false;       // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
-static std::vector<hipEvent_t> g_reduce_free;     // event pairs folded into g_reduce_ms, ready for the next reduce (a host that downloads every frame re-uses two events)
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
-  for (hipEvent_t e : g_reduce_events) (void)hipEventDestroy(e);
-  for (hipEvent_t e : g_reduce_free) (void)hipEventDestroy(e);
-  g_reduce_events.clear(); g_reduce_free.clear(); g_reduce_ms = 0.0; g_reduces = 0; g_reduce_path = 0;
+  g_reduce_pairs.release(); g_reduce_ms = 0.0; g_reduces = 0; g_reduce_path = 0;
   g_passes = g_passes_overlapped = 0;
 }
 // completed pairs -> g_reduce_ms (device 0 current, its stream idle)
-static void fold_reduce_events() {
-  for (size_t i = 0; i + 1 < g_reduce_events.size(); i += 2) {
-    float ms = 0.0f;
-    if (hipEventElapsedTime(&ms, g_reduce_events[i], g_reduce_events[i + 1]) == hipSuccess) g_reduce_ms += ms;
-    else (void)hipGetLastError();
-    g_reduce_free.push_back(g_reduce_events[i]); g_reduce_free.push_back(g_reduce_events[i + 1]);
-  }
-  g_reduce_events.clear();
-}
+static void fold_reduce_events() { (void)g_reduce_pairs.fold(/*wait=*/true, [](float ms, uint8_t) { g_reduce_ms += ms; }); }
 // multi-device mode: the host clock at which a device's stream reaches a point (hipLaunchHostFunc), so that the devices' pass times share
 // ONE clock -- HIP events of different devices cannot be compared
 static double host_ms() {
@@ -108,7 +97,7 @@ void DevBuf::release() {
   p = nullptr; bytes = 0;
 }
 
-// `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Ctx::paths_spread_mb: the driver
+// `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Options::paths_spread_mb: the driver
 // then maps the range in pieces no larger than a chunk, which is what the shade stage's forty streams want).  Every failure undoes what
 // was done and reports it; the caller falls back to hipMalloc.
 static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, int fail_at = -1) {      // fail_at: test option spread_fail_at -- chunk number whose creation is made to fail
@@ -163,10 +152,9 @@ int ensure_device() {
   c.arch = prop.gcnArchName;
   // LDS per CU: 160 KB on gfx950 (MI355X_MICROARCH.md); the runtime's own figure where it is larger than the per-workgroup 64 KB
   c.lds_per_cu = (c.arch.rfind("gfx950", 0) == 0) ? 160 * 1024 : std::max<int>(64 * 1024, (int)prop.maxSharedMemoryPerMultiProcessor);
-  c.arch = prop.gcnArchName;
   HIP_TRY(hipMalloc(&c.d_cursor, kCursorInts * sizeof(int)));   // [0] work cursor, [1] live-ray queue length, [2] overflow queue length, [32*k] cursor of queue segment k
-  HIP_TRY(hipMalloc(&c.d_counters, 16 * sizeof(unsigned long long)));
-  HIP_TRY(hipMemset(c.d_counters, 0, 16 * sizeof(unsigned long long)));
+  HIP_TRY(hipMalloc(&c.d_counters, kCounters * sizeof(unsigned long long)));
+  HIP_TRY(hipMemset(c.d_counters, 0, kCounters * sizeof(unsigned long long)));
   c.device_ready = true;
   return 0;
 }
@@ -234,7 +222,7 @@ int upload_scene(const ArtSceneDesc* d) {
   if (!d) return fail("art_upload_scene: null scene");
   std::string err;
   HostScene hs;
-  if (!flatten_scene(*d, g_devs[0].bvh_params, hs, err)) return fail(err);      // validation + host BVH build: once, no GPU needed
+  if (!flatten_scene(*d, g_devs[0].opt.bvh_params, hs, err)) return fail(err);      // validation + host BVH build: once, no GPU needed
   const std::vector<float> tri9 = std::move(hs.deferred_tri9);                    // option bvh_builder >= 1: every device builds its own tree
   hs.deferred_tri9.clear();
   Dev0Guard guard;
@@ -244,20 +232,20 @@ int upload_scene(const ArtSceneDesc* d) {
     Ctx& c = g_ctx;
     if (c.refit.ready || c.move.ready) HIP_TRY(hipStreamSynchronize(c.stream));  // (a refit or a move still in flight reads the plan)
     release_updates(c);
-    c.bvh_params = g_devs[0].bvh_params;
+    c.opt.bvh_params = g_devs[0].opt.bvh_params;
     if (ensure_device()) return 1;
     int dev_stack = hs.bvh.max_stack;
     if (!tri9.empty()) {
       DevBuf t9;
       if (upload(t9, tri9)) return 1;
       GpuBvh g;
-      const bool ok = build_bvh8_gpu((const float*)t9.p, (int)(tri9.size() / 9), c.bvh_params, c.stream, g, err);
+      const bool ok = build_bvh8_gpu((const float*)t9.p, (int)(tri9.size() / 9), c.opt.bvh_params, c.stream, g, err);
       t9.release();
       if (!ok) { free_tree(g); return fail("GPU BVH build: " + err); }
-      adopt_tree(c, g, c.bvh_params.width);
+      adopt_tree(c, g, c.opt.bvh_params.width);
       dev_stack = g.max_stack;
       if (k == 0) {
-        hs.bvh.width = c.bvh_params.width;
+        hs.bvh.width = c.opt.bvh_params.width;
         hs.bvh.n_nodes = g.n_nodes; hs.bvh.n_tris = g.n_tris; hs.bvh.max_stack = g.max_stack;
         hs.bvh_build_ms = g.build_ms; hs.gpu_built = true;
       }
@@ -314,8 +302,8 @@ static int resize_one(int w, int h) {
   c.auto_phase = 0; c.auto_redo = 0; c.auto_gen += 1;    // (the batch size follows the frame: measure again)
   c.lost_reported = 0;                                   // (the device counters are zeroed below)
   if (c.d_items) HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream));
-  c.camera_rays = 0; c.camera_traced = 0;
-  HIP_TRY(hipMemsetAsync(c.d_counters, 0, 16 * sizeof(unsigned long long), c.stream));
+  c.camera_traced = 0;
+  HIP_TRY(hipMemsetAsync(c.d_counters, 0, kCounters * sizeof(unsigned long long), c.stream));
   return build_shard();
 }
 
@@ -371,7 +359,7 @@ static void carve(DevPaths q[2], int P, int depth, bool rec) {
       b.hit = (DevHit*)(h + HF_HIT * st); b.sh_t = h + HF_SHT * st;
       b.prev_pdf = h + HF_PDF * st; b.flags = (uint32_t*)(h + HF_FLAGS * st); b.sh_min_t = h + HF_SHMIN * st; b.slot_id = (const uint32_t*)(h + HF_SLOT * st);
       b.cand_r = b.cand_g = b.cand_b = nullptr;                                 // (dense fold records: the pending colour has no hot words)
-      b.shadow_rule = g_ctx.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
+      b.shadow_rule = g_ctx.opt.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
       continue;
     } else {
       b.hot = nullptr; b.stride = 0;
@@ -384,7 +372,7 @@ static void carve(DevPaths q[2], int P, int depth, bool rec) {
     b.prev_pdf = take(p); b.flags = (uint32_t*)take(p); b.sh_min_t = take(p);
     b.cand_r = take(p); b.cand_g = take(p); b.cand_b = take(p);
     b.slot_id = (const uint32_t*)take(p);
-    b.shadow_rule = g_ctx.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
+    b.shadow_rule = g_ctx.opt.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
   }
   DevPaths& a = q[0];
   a.e_r = take((depth + 1) * p); a.e_g = take((depth + 1) * p); a.e_b = take((depth + 1) * p);
@@ -404,12 +392,11 @@ static void carve(DevPaths q[2], int P, int depth, bool rec) {
 
 // LDS stack per ray: the tree's worst-case bound if 8 workgroups per CU (8 waves per SIMD) still fit in the CU's 160 KB, else the
 // largest size that does; then pushes are checked and the few rays that go deeper are finished by k_trace_overflow.
-static void stack_plan(int kernel, int& entries, bool& overflow) {
+static void stack_plan(int& entries, bool& overflow) {
   Ctx& c = g_ctx;
   const int per_block = c.lds_per_cu / 8, groups = 64 / c.scene.node_width;        // 8 workgroups of 4 waves per CU = 8 waves per SIMD
-  (void)kernel;
   int cap = per_block / (4 * groups * 8) - 3;     // entries per ray (+ 2 guard entries + the sink of masked pushes)
-  if (c.lds_stack_cap > 0) cap = c.lds_stack_cap;
+  if (c.opt.lds_stack_cap > 0) cap = c.opt.lds_stack_cap;
   cap = std::min(cap, 64 * 1024 / (4 * groups * 8) - 3);      // one workgroup's dynamic LDS stays within the 64 KB a launch may ask for by default
   entries = std::min(c.bvh_stack_bound, cap);
   overflow = c.bvh_stack_bound > entries;
@@ -417,22 +404,22 @@ static void stack_plan(int kernel, int& entries, bool& overflow) {
 
 static int coop_grid() {
   Ctx& c = g_ctx;
-  int entries; bool ovf; stack_plan(c.trace_kernel, entries, ovf);
-  if (c.opt_blocks_per_cu > 0) return c.num_cus * c.opt_blocks_per_cu;
+  int entries; bool ovf; stack_plan(entries, ovf);
+  if (c.opt.opt_blocks_per_cu > 0) return c.num_cus * c.opt.opt_blocks_per_cu;
   return c.num_cus * trace_coop_blocks_per_cu(entries, c.scene.node_width);
 }
 
 static void fill_trace_args(TraceArgs& a, const DevPaths& q, int n_rays) {
   Ctx& c = g_ctx;
-  a.n_rays = n_rays; a.width = c.scene.node_width; a.instanced = c.scene.n_inst > 0 ? (c.inst_coop ? 1 : 2) : 0;
+  a.n_rays = n_rays; a.width = c.scene.node_width; a.instanced = c.scene.n_inst > 0 ? (c.opt.inst_coop ? 1 : 2) : 0;
   a.inst = c.scene.inst; a.inst_shift = c.scene.inst_shift;
-  { int e; bool o; stack_plan(c.trace_kernel, e, o); a.stack_entries = e; a.stack_overflow = o ? 1 : 0; }
-  a.node_min = c.node_min ? c.node_min : (c.scene.n_inst > 0 ? 2 : 4); a.refill_min = c.refill_min; a.segments = c.queue_segments; a.chunk = c.ray_chunk;
+  { int e; bool o; stack_plan(e, o); a.stack_entries = e; a.stack_overflow = o ? 1 : 0; }
+  a.node_min = c.opt.node_min ? c.opt.node_min : (c.scene.n_inst > 0 ? 2 : 4); a.refill_min = c.opt.refill_min; a.segments = c.opt.queue_segments; a.chunk = c.opt.ray_chunk;
   a.ray_ox = q.ray_ox; a.ray_oy = q.ray_oy; a.ray_oz = q.ray_oz; a.ray_dx = q.ray_dx; a.ray_dy = q.ray_dy; a.ray_dz = q.ray_dz; a.ray_tfar = q.ray_tfar;
   a.hit = q.hit; a.sh_t = q.sh_t;
   a.nodes = c.scene.nodes; a.qnodes = (const uint32_t*)c.b_qnodes.p; a.tris = c.scene.tris; a.qtris = (const float*)c.b_qtris.p; a.n_tris = c.scene.n_tris;
-  a.sh_min = (c.shadow_anyhit && q.sh_min_t && n_rays > q.P) ? q.sh_min_t : nullptr; a.shadow_begin = q.P;
-  a.cursor = c.d_cursor; a.stats = c.d_counters + 3; a.live_rays = c.d_counters;
+  a.sh_min = (c.opt.shadow_anyhit && q.sh_min_t && n_rays > q.P) ? q.sh_min_t : nullptr; a.shadow_begin = q.P;
+  a.cursor = c.d_cursor; a.stats = c.d_counters + CNT_STATS; a.live_rays = c.d_counters + CNT_RAYS;
   a.queue = (int*)c.b_queue.p; a.queue_count = c.d_cursor + 1;
   a.rec = (float4*)c.b_queue.p;
   a.ovf_queue = (int*)c.b_ovf.p; a.ovf_count = c.d_cursor + 2;
@@ -440,48 +427,43 @@ static void fill_trace_args(TraceArgs& a, const DevPaths& q, int n_rays) {
   a.queue_fixed = -1; a.queue_items = nullptr; a.queue_mul = 1;
 }
 
-// one trace launch, bracketed by HIP events on the launch stream.  records != nullptr: the bank's rays are already trace records in item
-// order (DevPaths::rec, written by the stage that emitted them): no k_analytic pass, the queue is the record array itself.
+// One trace launch.  records != nullptr: the bank's rays are already trace records in item order (DevPaths::rec, written by the stage
+// that emitted them): no k_analytic pass, the queue is the record array itself.
 struct RecordQueue { int fixed; const int* items; int mul; };
-// event pairs around groups of launches on the launch stream: ev_begin(kind) ... ev_end()
-static int ev_begin(int kind, int trial = 0) {      // trial: 1 / 2 = a shade launch of the items-per-thread trial A / B (Ctx::opt_shade_per)
-  Ctx& c = g_ctx;
-  if (c.ev_pool.size() < c.ev_used + 2) {
-    hipEvent_t e0, e1;
-    HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
-    c.ev_pool.push_back(e0); c.ev_pool.push_back(e1);
-  }
-  if (c.ev_kind.size() < c.ev_pool.size() / 2) c.ev_kind.resize(c.ev_pool.size() / 2);
-  c.ev_kind[c.ev_used / 2] = (uint8_t)(kind | (trial << 4) | (trial ? (c.auto_gen & 3) << 6 : 0));
-  HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used], c.stream));
-  return 0;
-}
-static int ev_end() { Ctx& c = g_ctx; HIP_TRY(hipEventRecord(c.ev_pool[c.ev_used + 1], c.stream)); c.ev_used += 2; return 0; }
+// What a trace launch runs on and with.  The render passes and the debug pass take the first three from the context (pass_launch); the
+// ray queries name their own, so nothing ever has to change the context for the length of a call.
+struct TraceLaunch {
+  hipStream_t stream; int kernel; bool count_tests;      // kernel: TRACE_COOP or TRACE_SIMPLE
+  bool timed = true;                                     // an event pair (tag 0) around the trace kernel
+  const int* item_count = nullptr;
+  const RecordQueue* records = nullptr;
+  unsigned long long* live_rays = nullptr;               // where the launch counts the rays it issued (nullptr: d_counters[CNT_RAYS], ArtStats::rays)
+};
+static TraceLaunch pass_launch() { const Ctx& c = g_ctx; return {c.stream, c.opt.trace_kernel, c.opt.count_tests}; }
+// the tag of a stage_pairs pair.  trial: 1 / 2 = a shade launch of the items-per-thread trial A / B (Options::opt_shade_per)
+static uint8_t ev_tag(int kind, int trial = 0) { return (uint8_t)(kind | (trial << 4) | (trial ? (g_ctx.auto_gen & 3) << 6 : 0)); }
 
-// live_rays: where the launch counts the rays it issued (nullptr: d_counters[0], ArtStats::rays)
-static int trace(const DevPaths& q, int n_rays, bool timed = true, const int* item_count = nullptr, const RecordQueue* records = nullptr,
-                 unsigned long long* live_rays = nullptr) {
+static int trace(const DevPaths& q, int n_rays, const TraceLaunch& t) {
   Ctx& c = g_ctx;
-  const bool coop = (c.trace_kernel == TRACE_COOP);
+  const bool coop = (t.kernel == TRACE_COOP);
   if ((int64_t)n_rays > (1ll << 28)) return fail("internal: more than 2^28 rays in one trace launch (32-bit byte offsets of the 16-byte hit records)");
-  if (records && !coop) return fail("internal: trace records without the cooperative kernel");
-  if (coop && !records && ensure(c.b_queue, ((size_t)n_rays + kRecSlack) * kTraceRecBytes)) return 1;      // live-ray queue: one 64-byte trace record per queued ray (+ one chunk of slack for the chunk prefetch)
+  if (t.records && !coop) return fail("internal: trace records without the cooperative kernel");
+  if (coop && !t.records && ensure(c.b_queue, ((size_t)n_rays + kRecSlack) * kTraceRecBytes)) return 1;      // live-ray queue: one 64-byte trace record per queued ray (+ one chunk of slack for the chunk prefetch)
   TraceArgs a; fill_trace_args(a, q, n_rays);
-  a.item_count = item_count;
-  if (live_rays) a.live_rays = live_rays;
-  if (records) { a.rec = (float4*)q.rec; a.queue_fixed = records->fixed; a.queue_items = records->items; a.queue_mul = records->mul; }
+  a.item_count = t.item_count;
+  if (t.live_rays) a.live_rays = t.live_rays;
+  if (t.records) { a.rec = (float4*)q.rec; a.queue_fixed = t.records->fixed; a.queue_items = t.records->items; a.queue_mul = t.records->mul; }
   if (coop && a.stack_overflow && ensure(c.b_ovf, (size_t)n_rays * sizeof(int))) return 1;
   a.ovf_queue = (int*)c.b_ovf.p;
-  if (coop) {
-    HIP_TRY(hipMemsetAsync(c.d_cursor, 0, kCursorInts * sizeof(int), c.stream));
-  }
-  if (coop && !records) launch_analytic(c.stream, c.scene, a, c.count_tests);   // outside the trace-kernel event pair
-  if (timed && ev_begin(0)) return 1;
+  if (coop) HIP_TRY(hipMemsetAsync(c.d_cursor, 0, kCursorInts * sizeof(int), t.stream));
+  if (coop && !t.records) launch_analytic(t.stream, c.scene, a, t.count_tests);   // outside the trace-kernel event pair
+  EventPairs::Timer timer;
+  if (t.timed) HIP_TRY(c.stage_pairs.begin(timer, t.stream, ev_tag(0)));
   // a workgroup keeps 4 waves x (64 / width) rays in flight: a handful of rays (the legacy per-ray seam) gets a handful of workgroups
   const int rays_per_block = 4 * (64 / std::max(1, c.scene.node_width));
   const int grid = (int)std::min<int64_t>(coop_grid(), ((int64_t)n_rays + rays_per_block - 1) / rays_per_block);
-  launch_trace(c.stream, c.d_scene, a, c.trace_kernel, c.count_tests, std::max(1, grid));
-  if (timed && ev_end()) return 1;
+  launch_trace(t.stream, c.d_scene, a, t.kernel, t.count_tests, std::max(1, grid));
+  HIP_TRY(timer.end());
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -489,17 +471,13 @@ static int trace(const DevPaths& q, int n_rays, bool timed = true, const int* it
 // drain event pairs into stats (requires the stream to be idle)
 static int collect_timing() {
   Ctx& c = g_ctx;
-  for (size_t i = 0; i + 1 < c.ev_used; i += 2) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c.ev_pool[i], c.ev_pool[i + 1]));
-    const int tagged = (i / 2 < c.ev_kind.size()) ? c.ev_kind[i / 2] : 0;
+  HIP_TRY(c.stage_pairs.fold(/*wait=*/true, [&c](float ms, uint8_t tagged) {
     const int kind = tagged & 15, trial = (tagged >> 4) & 3, gen = tagged >> 6;
     if (kind == 0) { c.stats.trace_ms += ms; c.stats.trace_launches += 1; }
-    else if (kind == 1) { c.stage.shade_ms += ms; c.stage.shade_launches += 1; if ((trial == 1 || trial == 2) && gen == (c.auto_gen & 3)) c.auto_ms[trial - 1] += ms; }
+    else if (kind == 1) { c.stage.shade_ms += ms; c.stage.shade_launches += 1; if ((trial == 1 || trial == 2) && gen == (int)(c.auto_gen & 3)) c.auto_ms[trial - 1] += ms; }
     else if (kind == 2) c.stage.raygen_ms += ms;
     else c.stage.fold_ms += ms;
-  }
-  c.ev_used = 0;
+  }));
   if (c.auto_phase == 3) {         // both trial batches are done (the stream is idle): keep the faster setting from here on
     c.auto_per = (c.auto_ms[1] < c.auto_ms[0]) ? 2 : 4;
     c.auto_phase = 4;
@@ -510,12 +488,12 @@ static int collect_timing() {
     HIP_TRY(hipMemcpy(it, c.d_items, sizeof it, hipMemcpyDeviceToHost));
     for (int k = 0; k < 16; ++k) { c.stage.items_in[k] = it[k]; c.stage.items_out[k] = it[16 + k]; }
   }
-  unsigned long long cnt[16];
+  unsigned long long cnt[kCounters];
   HIP_TRY(hipMemcpy(cnt, c.d_counters, sizeof cnt, hipMemcpyDeviceToHost));
-  c.stats.node_phase_iters = cnt[8]; c.stats.leaf_phase_iters = cnt[9]; c.stats.wave_iters = cnt[10];
-  c.stats.rays = cnt[0];
-  c.stats.lost_paths = cnt[15];
-  c.stats.box_tests = cnt[3]; c.stats.tri_tests = cnt[4]; c.stats.node_visits = cnt[5]; c.stats.leaf_visits = cnt[6]; c.stats.traced_rays = cnt[7];
+  c.stats.node_phase_iters = cnt[CNT_NODE_ITERS]; c.stats.leaf_phase_iters = cnt[CNT_LEAF_ITERS]; c.stats.wave_iters = cnt[CNT_WAVE_ITERS];
+  c.stats.rays = cnt[CNT_RAYS];
+  c.stats.lost_paths = cnt[CNT_LOST];
+  c.stats.box_tests = cnt[CNT_STATS]; c.stats.tri_tests = cnt[CNT_STATS + 1]; c.stats.node_visits = cnt[CNT_STATS + 2]; c.stats.leaf_visits = cnt[CNT_STATS + 3]; c.stats.traced_rays = cnt[CNT_TRACED];
   return 0;
 }
 
@@ -538,7 +516,7 @@ static void make_frame(const ArtPassParams* p, DevFrame& f) {
   std::memcpy(f.background, p->background, 12);
   const float fov = kHalfPi;                                   // ray_tracer.adb:63  Pi/2.0
   f.cam_z = -(float)c.width / safe_tan(fov / 2.0f);            // ray_tracer.adb:67
-  f.skip_null_shadow = c.skip_null_shadow ? 1 : 0;
+  f.skip_null_shadow = c.opt.skip_null_shadow ? 1 : 0;
 }
 
 static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout);
@@ -561,7 +539,7 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   if (check_pass(p)) return 1;
   if (p->render_type == ART_RT_DEBUG || p->render_type == ART_RT_WHITTED) return fail("debug render types go through art_debug_hit_pass");
   if (p->render_type < ART_PT_STUPID || p->render_type > ART_PT_MIS) return fail("unknown render_type");
-  if (c.scene.n_inst > 0 && c.trace_kernel != TRACE_COOP) return fail("an instanced scene renders through the record schedule only (option trace_kernel = 0)");
+  if (c.scene.n_inst > 0 && c.opt.trace_kernel != TRACE_COOP) return fail("an instanced scene renders through the record schedule only (option trace_kernel = 0)");
   const int per = p->aa_on ? 4 : 1;
   if (spp_inout) c.spp = *spp_inout;
   if (p->aa_on && (c.spp % 4) != 0) return fail("with anti-aliasing on, spp must be a multiple of 4 (Generate4RayDirections order)");
@@ -572,7 +550,7 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   // pixel, sample and bounce), so when HBM is short (a shared GPU, a caller holding memory) the batch is halved until it fits.
   int pc = 0, sc = 0;
   if (npix > 0) {
-    int64_t cap = std::max<int64_t>(c.batch_paths, per);
+    int64_t cap = std::max<int64_t>(c.opt.batch_paths, per);
     // Two buffers belong to a batch: the path state and the live-ray queue (one 64-byte trace record for each of the up to 2 rays of a path).
     auto try_alloc = [&](size_t bytes, hipError_t& e) {          // true: the path state holds at least `bytes`
       DevBuf& b = c.b_paths;
@@ -581,7 +559,7 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
       release_paths(c);
       e = hipErrorOutOfMemory; c.paths_are_spread = false;
       // the default (-1): 64 MB chunks for a path state of a gigabyte or more -- where the mapping granularity decides the stage's rate
-      const int chunk_mb = c.paths_spread_mb > 0 ? c.paths_spread_mb : (c.paths_spread_mb < 0 && bytes >= ((size_t)1 << 30)) ? 64 : 0;
+      const int chunk_mb = c.opt.paths_spread_mb > 0 ? c.opt.paths_spread_mb : (c.opt.paths_spread_mb < 0 && bytes >= ((size_t)1 << 30)) ? 64 : 0;
       if (chunk_mb > 0) {
         const auto t0 = std::chrono::steady_clock::now();
         e = alloc_spread(b, bytes, (size_t)chunk_mb << 20, c.device, c.spread_fail_at);
@@ -595,7 +573,7 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
       b.p = nullptr; (void)hipGetLastError();
       return false;
     };
-    const bool rec_layout = (c.trace_kernel == TRACE_COOP);              // the cooperative schedule keeps its rays as trace records inside the path state
+    const bool rec_layout = (c.opt.trace_kernel == TRACE_COOP);              // the cooperative schedule keeps its rays as trace records inside the path state
     for (;;) {
       pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / per));
       sc = (int)std::min<int64_t>(S, std::max<int64_t>(per, (cap / pc) / per * per));
@@ -615,12 +593,10 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
       cap /= 2;
     }
   }
-  struct PassEvents {             // destroyed on every error return; handed to the context on success
-    hipEvent_t a = nullptr, b = nullptr;
-    ~PassEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-  } ev;
-  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-  HIP_TRY(hipEventRecord(ev.a, c.stream));
+  EventPairs::Timer pass_timer;
+  HIP_TRY(c.pass_pairs.begin(pass_timer, c.stream));
+  struct Uncounted { EventPairs::Timer& t; ~Uncounted() { t.cancel(); } } uncounted{pass_timer};      // a pass that fails midway never enters pass_ms
+  const TraceLaunch launch = pass_launch();
   Ctx::PassClock* clock = nullptr;
   if (g_multi_api) { clock = new Ctx::PassClock; c.pass_clock.push_back(clock); HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t0)); }
   if (npix > 0) {
@@ -630,12 +606,12 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
         const int sn = std::min(sc, S - s0);
         DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
         for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = (const uint32_t*)c.b_pixmap.p + px0; b.sample_base = (uint32_t)(c.spp + s0); }
-        carve(bank, bank[0].P, p->max_depth, c.trace_kernel == TRACE_COOP);
-        // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_api_internal.h Ctx::opt_shade_per).
+        carve(bank, bank[0].P, p->max_depth, c.opt.trace_kernel == TRACE_COOP);
+        // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_api_internal.h Options::opt_shade_per).
         // Nothing here waits for the GPU: a trial batch only tags its shade launches' event pairs, and the next call that synchronises
         // anyway reads them (collect_timing) -- Render_Pass releases all its workers before it waits for any (ray_tracer.adb:271-277).
-        int trial = 0, shade_per = c.opt_shade_per ? c.opt_shade_per : (c.auto_phase >= 4 ? c.auto_per : 4);
-        if (c.opt_shade_per == 0 && c.auto_phase < 3 && c.trace_kernel == TRACE_COOP) {
+        int trial = 0, shade_per = c.opt.opt_shade_per ? c.opt.opt_shade_per : (c.auto_phase >= 4 ? c.auto_per : 4);
+        if (c.opt.opt_shade_per == 0 && c.auto_phase < 3 && c.opt.trace_kernel == TRACE_COOP) {
           const int64_t Pb = (int64_t)pn * sn;
           if (c.auto_phase == 0) c.auto_phase = 1;                                      // the warm batch: 4 items per thread, not measured
           else if (c.auto_phase == 1) { trial = 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; c.auto_phase = 2; }
@@ -643,32 +619,29 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
           else if (++c.auto_redo > 3) { c.auto_per = 4; c.auto_phase = 4; }             // batch sizes keep changing: no trial, 4 items per thread
           else { trial = 1; c.auto_gen += 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; }    // a batch of another size: trial A again, on this size (new generation: the old trial's events no longer count)
         }
-        c.camera_rays += (uint64_t)bank[0].P;
         // Option camera_dedup: the batch's distinct camera rays -- one per (pixel, sample & 3), DevPaths::cam_dedup -- are generated and traced
         // once; bounce 0 still runs over all P slots and reads every slot's hit from its distinct ray.  The counting variant traces every
         // sample's camera ray: its contract is "equal to the oracle's walk".
-        const bool dedup = c.camera_dedup && !c.count_tests && c.trace_kernel == TRACE_COOP;
+        const bool dedup = c.opt.camera_dedup && !c.opt.count_tests && c.opt.trace_kernel == TRACE_COOP;
         // U distinct rays per pixel: 4 with AA on (a sample chunk is a whole number of Generate4RayDirections groups: sc and S are multiples of 4), 1 with AA off
         const int cam_u = p->aa_on ? 4 : 1;
         const int cam_n = dedup ? cam_u * pn : bank[0].P;      // camera rays this batch generates and traces
         c.camera_traced += (uint64_t)cam_n;
-        if (c.trace_kernel == TRACE_COOP) {
+        if (c.opt.trace_kernel == TRACE_COOP) {
           // Compacted work sets: raygen fills bank 0 (one item per slot); stage b shades the items of bank b & 1 and writes the survivors
           // densely into the other bank.  d_live[0] / d_live[32]: the banks' item counts.  Every stage leaves its rays as trace records in
           // its output bank (round 3), at positions given by the item index; the trace kernel reads them from there in item order.
           if (!c.d_live) HIP_TRY(hipMalloc(&c.d_live, 32 * 18 * sizeof(int)));          // d_live[32 k]: items of level k (the input set of bounce k), k = 1 .. max_depth <= 16
-          unsigned long long* const rays_b = c.count_tests ? c.d_counters + 7 : nullptr;          // the counting pass's ray count (stats[4])
+          unsigned long long* const rays_b = c.opt.count_tests ? c.d_counters + CNT_TRACED : nullptr;
           bank[0].rec_mode = REC_EXT;
           DevPaths q = bank[0];                            // identity layout for raygen
           q.slot_id = nullptr;
           q.cam_dedup = dedup ? cam_u : 0;
           DevPaths qgen = q; qgen.P = cam_n;               // raygen's slots: [0, cam_n) are the distinct rays (slot = (sample & 3 within the batch) * pn + pixel)
           if (!c.d_items) { HIP_TRY(hipMalloc(&c.d_items, 32 * sizeof(unsigned long long))); HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream)); }
-          if (ev_begin(2)) return 1;
-          launch_raygen(c.stream, F, c.scene, qgen);
-          if (ev_end()) return 1;
-          launch_bump(c.stream, c.d_counters, rays_b, (unsigned long long)q.P);      // ArtStats::rays: one camera query per sample (the reference's Find_Closest_Hit calls), however many were traced
-          { const RecordQueue rq = {cam_n, nullptr, 1}; if (trace(q, cam_n, true, nullptr, &rq)) return 1; }
+          { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(2))); launch_raygen(c.stream, F, c.scene, qgen); }
+          launch_bump(c.stream, c.d_counters + CNT_RAYS, rays_b, (unsigned long long)q.P);      // ArtStats::rays: one camera query per sample (the reference's Find_Closest_Hit calls), however many were traced
+          { const RecordQueue rq = {cam_n, nullptr, 1}; TraceLaunch t = launch; t.records = &rq; if (trace(q, cam_n, t)) return 1; }
           for (int b = 0; b < p->max_depth; ++b) {
             const int in = b & 1, out = in ^ 1;
             const DevPaths& qi = (b == 0) ? q : bank[in];
@@ -676,28 +649,29 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
             bank[out].rec_mode = (p->render_type == ART_PT_STUPID) ? REC_EXT : (last ? REC_SHADOW : REC_BOTH);
             int* const n_in = c.d_live + 32 * b; int* const n_out = c.d_live + 32 * (b + 1);      // per level: the fold walks them again
             HIP_TRY(hipMemsetAsync(n_out, 0, sizeof(int), c.stream));
-            if (ev_begin(1, trial)) return 1;
-            launch_shade_compact(c.stream, F, c.scene, qi, bank[out], b, b == 0 ? nullptr : n_in, n_out,
-                                 const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + 15, c.d_counters, rays_b, shade_per);
-            if (ev_end()) return 1;
-            if (b == 0 && c.inject_lost) { launch_bump(c.stream, c.d_counters + 15, nullptr, 1ull); c.inject_lost = 0; }      // test option: what a stage does when it loses a path
+            { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(1, trial)));
+              launch_shade_compact(c.stream, F, c.scene, qi, bank[out], b, b == 0 ? nullptr : n_in, n_out,
+                                   const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + CNT_LOST, c.d_counters + CNT_RAYS, rays_b, shade_per); }
+            if (b == 0 && c.inject_lost) { launch_bump(c.stream, c.d_counters + CNT_LOST, nullptr, 1ull); c.inject_lost = 0; }      // test option: what a stage does when it loses a path
             if (g_debug_live) {
               int n = -1; unsigned long long r0 = 0;
-              (void)hipStreamSynchronize(c.stream); (void)hipMemcpy(&n, n_out, 4, hipMemcpyDeviceToHost); (void)hipMemcpy(&r0, c.d_counters, 8, hipMemcpyDeviceToHost);
+              (void)hipStreamSynchronize(c.stream); (void)hipMemcpy(&n, n_out, 4, hipMemcpyDeviceToHost); (void)hipMemcpy(&r0, c.d_counters + CNT_RAYS, 8, hipMemcpyDeviceToHost);
               std::fprintf(stderr, "stage %d: items out %d of %d, rays so far %llu\n", b, n, q.P, r0);
             }
             if (!last || p->render_type != ART_PT_STUPID) {
               const RecordQueue rq = {-1, n_out, bank[out].rec_mode == REC_BOTH ? 2 : 1};
-              if (trace(bank[out], 2 * q.P, true, n_out, &rq)) return 1;
+              TraceLaunch t = launch; t.item_count = n_out; t.records = &rq;
+              if (trace(bank[out], 2 * q.P, t)) return 1;
             }
           }
           const int last = p->max_depth & 1;              // the bank the last stage wrote
-          if (ev_begin(3)) return 1;
+          EventPairs::Timer fold_timer;
+          HIP_TRY(c.stage_pairs.begin(fold_timer, c.stream, ev_tag(3)));
           launch_resolve_last(c.stream, bank[last], c.d_live + 32 * p->max_depth, p->max_depth - 1);
           if (bank[last].fold_dense) launch_fold_levels(c.stream, F, bank[last], p->max_depth, c.d_live);
           else launch_fold(c.stream, F, bank[last]);
           launch_accumulate(c.stream, F, q, sn, accum_ptr());
-          if (ev_end()) return 1;
+          HIP_TRY(fold_timer.end());
           launch_acc_items(c.stream, c.d_live, p->max_depth, q.P, c.d_items);
           c.stage.batches += 1;
         } else {                                          // one-ray-per-lane cross-check kernel: the plain schedule over all slots, in place
@@ -706,10 +680,10 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
           q.final_flags = q.flags;
           launch_raygen(c.stream, F, c.scene, q);
           for (int b = 0; b < p->max_depth; ++b) {
-            if (trace(q, b == 0 ? q.P : 2 * q.P)) return 1;
+            if (trace(q, b == 0 ? q.P : 2 * q.P, launch)) return 1;
             launch_shade(c.stream, F, c.scene, q, b);
           }
-          if (p->render_type != ART_PT_STUPID) { if (trace(q, 2 * q.P)) return 1; }
+          if (p->render_type != ART_PT_STUPID) { if (trace(q, 2 * q.P, launch)) return 1; }
           launch_finish(c.stream, F, q, p->max_depth - 1);
           launch_accumulate(c.stream, F, q, sn, accum_ptr());
         }
@@ -717,10 +691,8 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
       }
     }
   }
-  HIP_TRY(hipEventRecord(ev.b, c.stream));
+  HIP_TRY(pass_timer.end());
   if (clock) HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t1));
-  const hipEvent_t p0 = ev.a, p1 = ev.b; ev.a = ev.b = nullptr;
-  c.pass_events.push_back(p0); c.pass_events.push_back(p1);
   c.spp += S;
   c.stats.samples += (uint64_t)npix * S;
   if (spp_inout) *spp_inout = c.spp;
@@ -739,13 +711,7 @@ static int synchronize_one() {
   Ctx& c = g_ctx;
   if (!c.device_ready) return 0;
   HIP_TRY(hipStreamSynchronize(c.stream));
-  for (size_t i = 0; i + 1 < c.pass_events.size(); i += 2) {
-    float ms = 0.0f;
-    HIP_TRY(hipEventElapsedTime(&ms, c.pass_events[i], c.pass_events[i + 1]));
-    c.stats.pass_ms += ms;
-    (void)hipEventDestroy(c.pass_events[i]); (void)hipEventDestroy(c.pass_events[i + 1]);
-  }
-  c.pass_events.clear();
+  HIP_TRY(c.pass_pairs.fold(/*wait=*/true, [&c](float ms, uint8_t) { c.stats.pass_ms += ms; }));
   if (collect_timing()) return 1;
   if (sync_updates()) return 1;
   // a lost path is a wrong picture, not a statistic -- a stage that found a path without an output item, a ray its bank has no
@@ -772,17 +738,9 @@ static int reduce_accum(const float** out) {
   const size_t count = (size_t)c0.width * c0.height * 3;
   Dev0Guard guard;
   if (use_dev(0) || ensure(c0.b_reduced, count * 4)) return 1;
-  // a pair of events around the reduce: from the pool of folded pairs (synchronize() folds them) when there is one
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  if (g_reduce_free.size() >= 2) { ev1 = g_reduce_free.back(); g_reduce_free.pop_back(); ev0 = g_reduce_free.back(); g_reduce_free.pop_back(); }
-  else {
-    HIP_TRY(hipEventCreate(&ev0));
-    if (hipEventCreate(&ev1) != hipSuccess) { (void)hipEventDestroy(ev0); return fail("hipEventCreate failed"); }
-  }
-  if (hipEventRecord(ev0, c0.stream) != hipSuccess) { g_reduce_free.push_back(ev0); g_reduce_free.push_back(ev1); return fail("hipEventRecord failed"); }      // (a pair without a record must not reach the list)
-  g_reduce_events.push_back(ev0); g_reduce_events.push_back(ev1);
+  EventPairs::Timer timer;                   // around the reduce, ended on every way out (synchronize() folds the pairs)
+  HIP_TRY(g_reduce_pairs.begin(timer, c0.stream));
   g_reduces += 1; g_reduce_path = g_comms_ready ? 1 : 2;
-  struct Stop { hipEvent_t e; hipStream_t s; ~Stop() { (void)hipEventRecord(e, s); } } stop{ev1, c0.stream};       // recorded on every way out
   if (g_comms_ready) {
     if (ncclGroupStart() != ncclSuccess) return fail("ncclGroupStart failed");
     for (int k = 0; k < g_ndev; ++k) {
@@ -869,7 +827,7 @@ static int debug_pass_one(const ArtPassParams* p, float* accum_host, uint32_t* s
   if (ensure(c.b_ids, n * 12)) return 1;
   HIP_TRY(hipMemsetAsync(c.b_ids.p, 0xff, n * 12, c.stream));
   int32_t* d_pi = (int32_t*)c.b_ids.p; int32_t* d_mi = d_pi + n; int32_t* d_pt = d_mi + n;
-  const int pc = (int)std::min<int64_t>(npix, c.batch_paths);
+  const int pc = (int)std::min<int64_t>(npix, c.opt.batch_paths);
   if (npix > 0 && ensure_paths((size_t)pc, 1, false)) return 1;
   for (int px0 = 0; px0 < npix; px0 += pc) {
     const int pn = std::min(pc, npix - px0);
@@ -878,8 +836,7 @@ static int debug_pass_one(const ArtPassParams* p, float* accum_host, uint32_t* s
     DevPaths q = bank[0];
     q.P = pn; q.npix = pn; q.pixmap = (const uint32_t*)c.b_pixmap.p + px0; q.sample_base = 0; q.slot_id = nullptr; q.final_flags = q.flags;
     launch_raygen(c.stream, F, c.scene, q);
-    c.camera_rays += (uint64_t)pn;
-    if (trace(q, pn)) return 1;
+    if (trace(q, pn, pass_launch())) return 1;
     launch_debug(c.stream, F, c.scene, q, accum_ptr(), d_pi, d_mi, d_pt);
   }
   HIP_TRY(hipGetLastError());
@@ -915,15 +872,12 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
   float* d = (float*)c.b_rays.p;
   HIP_TRY(hipMemcpyAsync(d, soa.data(), 7 * N * 4, hipMemcpyHostToDevice, c.stream));
   HIP_TRY(hipMemsetAsync(d + 8 * N, 0xff, 4 * N * 4, c.stream));
-  if (st) HIP_TRY(hipMemsetAsync(c.d_counters + 3, 0, 8 * sizeof(unsigned long long), c.stream));
+  if (st) HIP_TRY(hipMemsetAsync(c.d_counters + CNT_STATS, 0, 8 * sizeof(unsigned long long), c.stream));
   DevPaths q; std::memset(&q, 0, sizeof q);
   q.ray_ox = d; q.ray_oy = d + N; q.ray_oz = d + 2 * N; q.ray_dx = d + 3 * N; q.ray_dy = d + 4 * N; q.ray_dz = d + 5 * N; q.ray_tfar = d + 6 * N;
   q.hit = (DevHit*)(d + 8 * N);                                      // 16-byte aligned: the buffer is, and 8 N floats precede it
-  const int saved_kernel = c.trace_kernel; const bool saved_count = c.count_tests;
-  c.trace_kernel = kernel; c.count_tests = (st != nullptr);
-  const int rc = trace(q, (int)n, /*timed=*/st != nullptr);       // without stats: no events, no counter read-back (the per-ray seam)
-  c.trace_kernel = saved_kernel; c.count_tests = saved_count;
-  if (rc) return 1;
+  const TraceLaunch launch = {c.stream, kernel, /*count_tests=*/st != nullptr, /*timed=*/st != nullptr};      // without stats: no events, no counter read-back (the per-ray seam)
+  if (trace(q, (int)n, launch)) return 1;
   std::vector<DevHit> hits(N);
   HIP_TRY(hipMemcpyAsync(hits.data(), d + 8 * N, N * sizeof(DevHit), hipMemcpyDeviceToHost, c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));
@@ -954,6 +908,27 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
     if (synchronize()) return 1;
     *st = c.stats;
   }
+  return 0;
+}
+
+// c's tree as it lies in HBM (c's GPU is current), after its stream has drained: a refit on another stream is ordered before that
+static int fetch_tree(Ctx& c, std::vector<float>& nodes, std::vector<float>& tris) {
+  const Bvh8& b = c.host_scene.bvh;
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  nodes.resize((size_t)b.n_nodes * node_floats(b.width)); tris.resize((size_t)b.n_tris * kTriFloats);
+  HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(tris.data(), c.b_tris.p, tris.size() * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+// the uploaded tree of device 0 as host arrays (the packets art_export_bvh returns; that call keeps what it fetches, this one does not); the caller holds g_mu
+int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris) {
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail("no scene uploaded");
+  const Bvh8& b = c.host_scene.bvh;
+  width = b.width; n_tris = b.n_tris;
+  if (c.host_scene.tree_in_hbm_only() && b.nodes.empty()) return use_dev(0) || fetch_tree(c, nodes, tris);
+  nodes = b.nodes; tris = b.tris;
   return 0;
 }
 
@@ -992,9 +967,9 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
     return 1;
   StreamOrder order(c, st);
   const hipStream_t qs = order.qs;
-  const size_t S = (size_t)std::min<int64_t>(n, c.query_slice);
+  const size_t S = (size_t)std::min<int64_t>(n, c.opt.query_slice);
   const bool coop = (kernel == TRACE_COOP);
-  int entries; bool ovf; stack_plan(kernel, entries, ovf);
+  int entries; bool ovf; stack_plan(entries, ovf);
   const size_t q_bytes = 256 + S * (8 * 4 + sizeof(DevHit));      // counter sink | 7 SoA floats + the shadow minimum | hit records
   const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
   if (grow) {                           // growing the scratch may wait: nothing enqueued may still use the old buffers
@@ -1009,8 +984,7 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
   unsigned long long* sink = (unsigned long long*)base;
   float* f = (float*)(base + 256);
   DevHit* dh = (DevHit*)(f + 8 * S);                                 // 16-byte aligned: 256 + 32 S bytes
-  const hipStream_t saved_stream = c.stream; const int saved_kernel = c.trace_kernel; const bool saved_count = c.count_tests;
-  c.stream = qs; c.trace_kernel = kernel; c.count_tests = false;
+  const TraceLaunch launch = {qs, kernel, /*count_tests=*/false, /*timed=*/false, nullptr, nullptr, /*live_rays=*/sink};
   int rc = 0;
   for (size_t s0 = 0; s0 < N && !rc; s0 += S) {
     const int m = (int)std::min(S, N - s0);
@@ -1023,46 +997,40 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
     DevPaths q; std::memset(&q, 0, sizeof q);
     q.ray_ox = Q.ox; q.ray_oy = Q.oy; q.ray_oz = Q.oz; q.ray_dx = Q.dx; q.ray_dy = Q.dy; q.ray_dz = Q.dz; q.ray_tfar = Q.tf; q.hit = dh;
     q.sh_min_t = Q.shm; q.P = 0;                                     // occlusion: every ray is a shadow ray (shadow_begin = 0)
-    rc = trace(q, m, /*timed=*/false, nullptr, nullptr, sink);
+    rc = trace(q, m, launch);
     if (rc) break;
     if (hits) launch_query_finalize(qs, c.scene, Q);
     else launch_query_occluded(qs, Q);
     if (hipGetLastError() != hipSuccess) rc = fail(std::string(name) + ": kernel launch failed");
   }
-  c.stream = saved_stream; c.trace_kernel = saved_kernel; c.count_tests = saved_count;
   if (order.leave()) return 1;          // (also after a failed launch)
   return rc;
 }
 
 void shutdown() {
-  if (g_devs[0].device_ready && !use_dev(0)) reset_reduce_info();
+  if (g_devs[0].device_ready && !use_dev(0)) { reset_reduce_info(); g_reduce_pairs.destroy(); }
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
   g_same_gpu = false; g_multi_api = false;
   for (int k = g_ndev - 1; k >= 0; --k) {
-  g_cur = &g_devs[k];
-  Ctx& c = g_ctx;
-  if (c.device_ready) {
-    if (c.device >= 0) (void)hipSetDevice(c.device);
-    (void)hipDeviceSynchronize();
-    DevBuf* bufs[] = {&c.b_spheres, &c.b_sphere_mat, &c.b_lights, &c.b_materials, &c.b_bf_pos, &c.b_bf_nrm, &c.b_bf_uv, &c.b_bf_idx,
-                      &c.b_nodes, &c.b_qnodes, &c.b_tris, &c.b_qtris, &c.b_m_shade, &c.b_accum, &c.b_screen, &c.b_stage,
-                      &c.b_pixmap, &c.b_paths, &c.b_rays, &c.b_ids, &c.b_queue, &c.b_ovf,
-                      &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query};
-    for (DevBuf* b : bufs) b->release();
-    if (c.d_cursor) (void)hipFree(c.d_cursor);
-    if (c.d_scene) (void)hipFree(c.d_scene);
-    if (c.d_counters) (void)hipFree(c.d_counters);
-    if (c.d_live) (void)hipFree(c.d_live);
-    if (c.d_items) (void)hipFree(c.d_items);
-    for (hipEvent_t e : c.ev_pool) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c.pass_events) (void)hipEventDestroy(e);
-    for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
-    destroy_updates(c);
-    for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
-    c.b_reduced.release();
-    if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
-  }
-  c = Ctx();
+    g_cur = &g_devs[k];
+    Ctx& c = g_ctx;
+    if (c.device_ready) {
+      if (c.device >= 0) (void)hipSetDevice(c.device);
+      (void)hipDeviceSynchronize();
+      DevBuf* bufs[] = {&c.b_spheres, &c.b_sphere_mat, &c.b_lights, &c.b_materials, &c.b_bf_pos, &c.b_bf_nrm, &c.b_bf_uv, &c.b_bf_idx,
+                        &c.b_nodes, &c.b_qnodes, &c.b_tris, &c.b_qtris, &c.b_m_shade, &c.b_accum, &c.b_screen, &c.b_stage,
+                        &c.b_pixmap, &c.b_paths, &c.b_rays, &c.b_ids, &c.b_queue, &c.b_ovf,
+                        &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query};
+      for (DevBuf* b : bufs) b->release();
+      for (void* p : {(void*)c.d_cursor, (void*)c.d_scene, (void*)c.d_counters, (void*)c.d_live, (void*)c.d_items}) if (p) (void)hipFree(p);
+      c.stage_pairs.destroy(); c.pass_pairs.destroy(); c.rebuild_pairs.destroy();
+      for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
+      destroy_updates(c);
+      for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
+      c.b_reduced.release();
+      if (c.own_stream) (void)hipStreamDestroy(c.own_stream);
+    }
+    c = Ctx();
   }
   g_ndev = 1; g_cur = &g_devs[0];
 }
@@ -1078,8 +1046,8 @@ int art_init(int device_ordinal) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (g_ctx.device_ready && device_ordinal >= 0 && device_ordinal != g_ctx.device) return fail("art_init: already bound to another device; call art_shutdown first");
   g_ctx.device = device_ordinal;
-  if (const char* e = getenv("ART_TRACE_KERNEL")) g_ctx.trace_kernel = (std::strcmp(e, "simple") == 0) ? TRACE_SIMPLE : TRACE_COOP;
-  if (const char* e = getenv("ART_BATCH_PATHS")) g_ctx.batch_paths = std::min<int64_t>(1ll << 27, std::max<int64_t>(1024, atoll(e)));
+  if (const char* e = getenv("ART_TRACE_KERNEL")) g_ctx.opt.trace_kernel = (std::strcmp(e, "simple") == 0) ? TRACE_SIMPLE : TRACE_COOP;
+  if (const char* e = getenv("ART_BATCH_PATHS")) g_ctx.opt.batch_paths = std::min<int64_t>(1ll << 27, std::max<int64_t>(1024, atoll(e)));
   return ensure_device();
 }
 
@@ -1102,15 +1070,13 @@ int art_init_devices(int32_t n, const int32_t* ordinals) {
     for (int i = 0; i < k; ++i) { if (ord[i] == ord[k]) distinct = false; else same = false; }
   }
   if (n > 1 && !distinct && !same) return fail("art_init_devices: the ordinals must be all different (one context per GPU) or all equal (rehearsal on one GPU)");
-  const Ctx opts = g_devs[0];                       // options set before initialisation apply to every device
+  const Options opts = g_devs[0].opt;               // options set before initialisation apply to every device
   Dev0Guard guard;
   g_ndev = n;
   for (int k = 0; k < n; ++k) {
     Ctx& c = g_devs[k];
     c = Ctx();
-    c.trace_kernel = opts.trace_kernel; c.batch_paths = opts.batch_paths; c.bvh_params = opts.bvh_params; c.node_min = opts.node_min; c.refill_min = opts.refill_min;
-    c.queue_segments = opts.queue_segments; c.ray_chunk = opts.ray_chunk; c.shadow_anyhit = opts.shadow_anyhit; c.skip_null_shadow = opts.skip_null_shadow; c.inst_coop = opts.inst_coop; c.opt_shade_per = opts.opt_shade_per; c.lds_stack_cap = opts.lds_stack_cap; c.paths_spread_mb = opts.paths_spread_mb;
-    c.opt_blocks_per_cu = opts.opt_blocks_per_cu; c.count_tests = opts.count_tests; c.query_slice = opts.query_slice; c.camera_dedup = opts.camera_dedup;
+    c.opt = opts;
     c.device = ord[k]; c.rank = k; c.nranks = n; c.tile = 32;
     if (use_dev(k) || ensure_device()) { shutdown(); return 1; }
     if (n > 1) {
@@ -1236,37 +1202,12 @@ int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap,
   if (!g_ctx.scene_ready) return fail("no scene uploaded");
   Bvh8& b = g_ctx.host_scene.bvh;
   if (g_ctx.scene.n_inst > 0 && (nodes || tris)) return fail("art_export_bvh: an instanced scene has a two-level tree; only its sizes are reported here (ArtBvhInfo); art_export_two_level exports its arrays");
-  if (g_ctx.host_scene.tree_in_hbm_only() && b.nodes.empty() && (nodes || tris)) {     // a GPU-built or refitted tree is fetched on first request
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));                                         // (a refit on another stream is ordered before it)
-    b.nodes.resize((size_t)b.n_nodes * node_floats(b.width)); b.tris.resize((size_t)b.n_tris * kTriFloats);
-    HIP_TRY(hipMemcpy(b.nodes.data(), g_ctx.b_nodes.p, b.nodes.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(b.tris.data(), g_ctx.b_tris.p, b.tris.size() * 4, hipMemcpyDeviceToHost));
-  }
+  if (g_ctx.host_scene.tree_in_hbm_only() && b.nodes.empty() && (nodes || tris) && fetch_tree(g_ctx, b.nodes, b.tris)) return 1;     // a GPU-built or refitted tree is fetched on first request, and kept
   if (info) { info->n_nodes = b.n_nodes; info->n_tris = b.n_tris; info->max_stack = b.max_stack; info->node_width = b.width; info->build_ms = g_ctx.host_scene.bvh_build_ms; }
   if (nodes) { if (node_cap < (int64_t)b.nodes.size()) return fail("art_export_bvh: node buffer too small"); std::memcpy(nodes, b.nodes.data(), b.nodes.size() * 4); }
   if (tris) { if (tri_cap < (int64_t)b.tris.size()) return fail("art_export_bvh: triangle buffer too small"); std::memcpy(tris, b.tris.data(), b.tris.size() * 4); }
   return 0;
 }
-
-}  // extern "C"
-namespace art {
-// the uploaded tree of device 0 as host arrays (the packets art_export_bvh returns); the caller holds g_mu
-int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris) {
-  Ctx& c = g_devs[0];
-  if (!c.scene_ready) return fail("no scene uploaded");
-  Bvh8& b = c.host_scene.bvh;
-  width = b.width; n_tris = b.n_tris;
-  if (c.host_scene.tree_in_hbm_only() && b.nodes.empty()) {
-    nodes.resize((size_t)b.n_nodes * node_floats(b.width)); tris.resize((size_t)b.n_tris * kTriFloats);
-    if (use_dev(0)) return 1;
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
-    HIP_TRY(hipMemcpy(tris.data(), c.b_tris.p, tris.size() * 4, hipMemcpyDeviceToHost));
-  } else { nodes = b.nodes; tris = b.tris; }
-  return 0;
-}
-}  // namespace art
-extern "C" {
 
 int art_get_reduce_info(ArtReduceInfo* out) {
   std::lock_guard<std::mutex> lk(g_mu);
@@ -1328,33 +1269,33 @@ int art_set_option(const char* name, int64_t value) {      // applies to every d
   return rc;
 }
 static int set_option_one(const std::string& n, int64_t value) {
-  if (n == "trace_kernel") { if (value != TRACE_COOP && value != TRACE_SIMPLE) return fail("trace_kernel: 0 (cooperative) or 1 (simple)"); g_ctx.trace_kernel = (int)value; }
-  else if (n == "queue_segments") { if (value != 1 && value != 2 && value != 4 && value != 8) return fail("queue_segments: 1, 2, 4 or 8"); g_ctx.queue_segments = (int)value; }
-  else if (n == "batch_paths") { if (value < 1024 || value > (1ll << 27)) return fail("batch_paths: 1024..2^27 (2 rays per path slot; the trace kernel addresses a ray's 16-byte hit record by a 32-bit byte offset)"); g_ctx.batch_paths = value; g_ctx.auto_phase = 0; g_ctx.auto_redo = 0; g_ctx.auto_gen += 1; }
-  else if (n == "paths_spread") { if (value < -1 || value > 65536) return fail("paths_spread: chunk size in MB, 0 = off (plain hipMalloc), -1 = automatic"); g_ctx.paths_spread_mb = (int)value; release_paths(g_ctx); }
+  if (n == "trace_kernel") { if (value != TRACE_COOP && value != TRACE_SIMPLE) return fail("trace_kernel: 0 (cooperative) or 1 (simple)"); g_ctx.opt.trace_kernel = (int)value; }
+  else if (n == "queue_segments") { if (value != 1 && value != 2 && value != 4 && value != 8) return fail("queue_segments: 1, 2, 4 or 8"); g_ctx.opt.queue_segments = (int)value; }
+  else if (n == "batch_paths") { if (value < 1024 || value > (1ll << 27)) return fail("batch_paths: 1024..2^27 (2 rays per path slot; the trace kernel addresses a ray's 16-byte hit record by a 32-bit byte offset)"); g_ctx.opt.batch_paths = value; g_ctx.auto_phase = 0; g_ctx.auto_redo = 0; g_ctx.auto_gen += 1; }
+  else if (n == "paths_spread") { if (value < -1 || value > 65536) return fail("paths_spread: chunk size in MB, 0 = off (plain hipMalloc), -1 = automatic"); g_ctx.opt.paths_spread_mb = (int)value; release_paths(g_ctx); }
   else if (n == "spread_fail_at") { g_ctx.spread_fail_at = (int)value; release_paths(g_ctx); }      // test option: creating chunk number `value` of the path state fails (-1: never)
   else if (n == "inject_lost") { g_ctx.inject_lost = value != 0; }      // test option: the next pass counts one lost path in its first batch
-  else if (n == "blocks_per_cu") { g_ctx.opt_blocks_per_cu = (int)value; g_ctx.blocks_per_cu = 0; }
-  else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.query_slice = value; }
-  else if (n == "count_tests") { g_ctx.count_tests = value != 0; }
-  else if (n == "camera_dedup") { if (value != 0 && value != 1) return fail("camera_dedup: 0 (every sample's camera ray is traced) or 1 (each distinct camera ray once per batch)"); g_ctx.camera_dedup = value != 0; }
-  else if (n == "shadow_anyhit") { g_ctx.shadow_anyhit = value != 0; }
-  else if (n == "skip_null_shadow") { g_ctx.skip_null_shadow = value != 0; }
-  else if (n == "inst_coop") { g_ctx.inst_coop = value != 0; }
-  else if (n == "shade_per") { if (value != 0 && value != 2 && value != 4) return fail("shade_per: 0 (measured), 2 or 4"); g_ctx.opt_shade_per = (int)value; }
-  else if (n == "ray_chunk") { if (value < 16 || value > 4096 || (value & 15)) return fail("ray_chunk: a multiple of 16, 16..4096"); g_ctx.ray_chunk = (int)value; }
-  else if (n == "refill_min") { if (value < 1 || value > 8) return fail("refill_min: 1..8"); g_ctx.refill_min = (int)value; }
-  else if (n == "node_min") { if (value < 0 || value > 8) return fail("node_min: 1..8, 0 = automatic"); g_ctx.node_min = (int)value; }
-  else if (n == "bvh_width") { if (value != 4 && value != 8) return fail("bvh_width: 4 or 8"); g_ctx.bvh_params.width = (int)value; }
-  else if (n == "lds_stack_cap") { if (value < 0 || value > kStackEntries) return fail("lds_stack_cap: 0 (automatic) .. 160"); g_ctx.lds_stack_cap = (int)value; }
-  else if (n == "bvh_max_leaf") { if (value < 0 || value > kMaxLeafTris) return fail("bvh_max_leaf: 1..8, 0 = defaults"); g_ctx.bvh_params.max_leaf = value ? (int)value : BvhBuildParams().max_leaf; g_ctx.bvh_params.gpu_max_leaf = (int)value; }
-  else if (n == "inst_open") { if (value < 0 || value > 4096) return fail("inst_open: 1 .. 4096 entry points per instance, 0 = chosen from the instances' overlap"); g_ctx.bvh_params.inst_open = (int)value; }
-  else if (n == "bvh_spatial_splits") { g_ctx.bvh_params.spatial_alpha = value ? 1.0e-5f : -1.0f; }   // host builder: SBVH reference splitting
-  else if (n == "bvh_builder") { if (value < 0 || value > 3) return fail("bvh_builder: 0 host SAH, 1 GPU LBVH, 2 GPU PLOC, 3 GPU SAH"); g_ctx.bvh_params.builder = (int)value; }
-  else if (n == "bvh_ploc_radius") { if (value < 1 || value > 64) return fail("bvh_ploc_radius: 1..64"); g_ctx.bvh_params.ploc_radius = (int)value; }
-  else if (n == "bvh_leaf_base_milli") { g_ctx.bvh_params.leaf_base = (float)value / 1000.0f; }
-  else if (n == "bvh_tri_cost_milli") { g_ctx.bvh_params.tri_cost = (float)value / 1000.0f; }
-  else if (n == "bvh_node_cost_milli") { g_ctx.bvh_params.node_cost = (float)value / 1000.0f; }
+  else if (n == "blocks_per_cu") { g_ctx.opt.opt_blocks_per_cu = (int)value; g_ctx.blocks_per_cu = 0; }
+  else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.opt.query_slice = value; }
+  else if (n == "count_tests") { g_ctx.opt.count_tests = value != 0; }
+  else if (n == "camera_dedup") { if (value != 0 && value != 1) return fail("camera_dedup: 0 (every sample's camera ray is traced) or 1 (each distinct camera ray once per batch)"); g_ctx.opt.camera_dedup = value != 0; }
+  else if (n == "shadow_anyhit") { g_ctx.opt.shadow_anyhit = value != 0; }
+  else if (n == "skip_null_shadow") { g_ctx.opt.skip_null_shadow = value != 0; }
+  else if (n == "inst_coop") { g_ctx.opt.inst_coop = value != 0; }
+  else if (n == "shade_per") { if (value != 0 && value != 2 && value != 4) return fail("shade_per: 0 (measured), 2 or 4"); g_ctx.opt.opt_shade_per = (int)value; }
+  else if (n == "ray_chunk") { if (value < 16 || value > 4096 || (value & 15)) return fail("ray_chunk: a multiple of 16, 16..4096"); g_ctx.opt.ray_chunk = (int)value; }
+  else if (n == "refill_min") { if (value < 1 || value > 8) return fail("refill_min: 1..8"); g_ctx.opt.refill_min = (int)value; }
+  else if (n == "node_min") { if (value < 0 || value > 8) return fail("node_min: 1..8, 0 = automatic"); g_ctx.opt.node_min = (int)value; }
+  else if (n == "bvh_width") { if (value != 4 && value != 8) return fail("bvh_width: 4 or 8"); g_ctx.opt.bvh_params.width = (int)value; }
+  else if (n == "lds_stack_cap") { if (value < 0 || value > kStackEntries) return fail("lds_stack_cap: 0 (automatic) .. 160"); g_ctx.opt.lds_stack_cap = (int)value; }
+  else if (n == "bvh_max_leaf") { if (value < 0 || value > kMaxLeafTris) return fail("bvh_max_leaf: 1..8, 0 = defaults"); g_ctx.opt.bvh_params.max_leaf = value ? (int)value : BvhBuildParams().max_leaf; g_ctx.opt.bvh_params.gpu_max_leaf = (int)value; }
+  else if (n == "inst_open") { if (value < 0 || value > 4096) return fail("inst_open: 1 .. 4096 entry points per instance, 0 = chosen from the instances' overlap"); g_ctx.opt.bvh_params.inst_open = (int)value; }
+  else if (n == "bvh_spatial_splits") { g_ctx.opt.bvh_params.spatial_alpha = value ? 1.0e-5f : -1.0f; }   // host builder: SBVH reference splitting
+  else if (n == "bvh_builder") { if (value < 0 || value > 3) return fail("bvh_builder: 0 host SAH, 1 GPU LBVH, 2 GPU PLOC, 3 GPU SAH"); g_ctx.opt.bvh_params.builder = (int)value; }
+  else if (n == "bvh_ploc_radius") { if (value < 1 || value > 64) return fail("bvh_ploc_radius: 1..64"); g_ctx.opt.bvh_params.ploc_radius = (int)value; }
+  else if (n == "bvh_leaf_base_milli") { g_ctx.opt.bvh_params.leaf_base = (float)value / 1000.0f; }
+  else if (n == "bvh_tri_cost_milli") { g_ctx.opt.bvh_params.tri_cost = (float)value / 1000.0f; }
+  else if (n == "bvh_node_cost_milli") { g_ctx.opt.bvh_params.node_cost = (float)value / 1000.0f; }
   else return fail("unknown option " + n);
   return 0;
 }

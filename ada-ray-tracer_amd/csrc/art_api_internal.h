@@ -6,6 +6,7 @@
 #include <string>
 #include <vector>
 #include "../../include/art_hip.h"
+#include "art_event_pairs.h"
 #include "art_host_scene.h"
 #include "art_kernels.h"
 
@@ -23,11 +24,56 @@ struct DevBuf {
 
 // What every kind of device-side scene update (art_update.cpp) keeps per context besides its own plan.
 struct UpdateLane {
-  std::vector<hipEvent_t> ev, ev_free;               // event pairs around this context's update kernels: not yet folded / free for reuse
+  EventPairs pairs;                                  // event pairs around this context's update kernels
   hipEvent_t ready_ev = nullptr, done_ev = nullptr;  // device 0: the caller's data is ready (contexts k > 0 wait for it); k > 0: this context's update is done
   DevBuf b_stage;                                    // contexts k > 0: peer copy of the caller's data
   bool unread = false;                               // an update was enqueued whose counters no fold has read yet
   uint64_t bad_last = 0; bool bad_reported = true;   // bad items (vertices, matrices) of the last update read; a synchronize reported them (or there were none)
+};
+
+// What art_set_option sets and art_init_devices hands to every context (derived state -- blocks_per_cu, auto_*, paths_are_spread -- is Ctx's).
+struct Options {
+  int trace_kernel = TRACE_COOP;
+  int64_t batch_paths = 128ll << 20;  // path slots per batch (328 B each at depth 8 -> up to 44 GB of the 288 GB HBM; buffers are sized to the frame,
+                                      // so a small render takes less): big batches keep late bounces wide (8M -> 32M: +7 %, -> 128M: +1.7 %)
+  int opt_blocks_per_cu = 0;
+  bool count_tests = false;
+  bool camera_dedup = true;      // each distinct camera ray of a batch is generated and traced once (DevPaths::cam_dedup); false: once per sample
+  int node_min = 0;              // the trace kernel leaves its node loop when fewer than 8 x node_min lanes still expand nodes.  0: 4 (the optimum on C4, profiles/r2_sensitivity.json);
+                                 // 2 for an instanced scene -- its groups also wait for instance entries, and leaving the loop for them less often is worth 6 % on I64 (profiles/r5_inst_sweep.py)
+  int refill_min = 2;            // idle ray groups of a wave take new rays when two of them are idle (1: at once; measured 0.5-1 % slower)
+  int queue_segments = 8;       // the live-ray queue is cut into this many contiguous segments, one per XCD (1 = a single cursor)
+  int ray_chunk = 48;            // trace records a wave claims per atomic (and prefetches): 16 -> 48 is worth 1 % on C4, 4 % on C3, 10 % on C5 (the claim stalls the wave)
+  bool shadow_anyhit = true;   // shadow rays use the visibility rule instead of a full closest-hit search (same decision)
+  bool skip_null_shadow = false;   // DevFrame::skip_null_shadow: shadow rays that cannot change the picture are not traced (fewer rays than the reference issues: off by default)
+  bool inst_coop = true;       // instanced scenes: the cooperative kernel crosses the instance boundary (k_trace_coop<.., INST>); false: k_trace_inst, one ray per lane (A/B, cross-check)
+  // Items per thread of k_shade_compact (256 x per items and one global atomic per workgroup): 4 or 2.  Neither wins everywhere (inside one
+  // process 2 is 5 % faster on C4, 3 % slower on C5, equal on S4: profiles/r6_shade/trial_check_*.txt; round 5's "+7 % / -10 %" of ab12 were
+  // mostly the mapping of the path state, which differed between its processes), so by default the library MEASURES -- without ever
+  // waiting for the GPU (round 6; until round 5 the trial blocked the host twice per trial batch, which serialised the devices of a
+  // multi-GPU process during their first two batches): after a scene upload or a resize batch 0 runs warm and unmeasured (code-object load,
+  // first touch of the path state), batch 1 with 4 items per thread, batch 2 with 2 -- their shade launches' event pairs carry the trial's
+  // tag -- and every batch after that with 4 until a synchronize (art_synchronize, art_get_stats, a download: calls that wait anyway) has
+  // read both trials' events; then the faster setting is kept.  Two trials only count when their batches had the same number of paths.
+  // The picture does not depend on it (the order of the items of a bank carries no meaning).  Option shade_per: 0 automatic, 2, 4.
+  int opt_shade_per = 0;
+  int lds_stack_cap = 0;        // force the LDS stack size (tests of the overflow path)
+  // HOW THE PATH STATE IS MAPPED decides the shade stage's rate (round 6, profiles/r6_bimodal).  The stage runs about forty concurrent streams
+  // through the 35-74 GB of path state.  As ONE hipMalloc it took 10.4 or 12.1 ms per batch on C3 (31.7 / 35.9 on C4, 22.2 / 26.0 on C5, 28.0 /
+  // 32.5 on S4) depending on the PROCESS -- same binary, same device addresses, same instructions, L2 hits, misses and fabric requests, 16 %
+  // more L1 -> L2 read latency -- and 15.0 as physically contiguous memory: the larger the pieces the driver maps the range in, the slower.
+  // paths_spread_mb: the path state as one address range over separately created physical chunks of that many MB (HIP virtual memory
+  // management, art_api.cpp alloc_spread): the fast mode in every process measured, 13-17 ms to set up, no extra memory; any failure falls
+  // back to hipMalloc.  -1 (default): 64 MB chunks when the path state is 1 GB or more; 0: plain hipMalloc; n > 0: n MB chunks always.
+  int paths_spread_mb = -1;
+  int64_t query_slice = 1ll << 24;             // rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
+  BvhBuildParams bvh_params;
+};
+
+enum Counter {           // the words of Ctx::d_counters, which the kernels bump through pointers the host hands them
+  CNT_RAYS = 0,          // rays issued by raygen and the shade stages (ArtStats::rays)
+  CNT_STATS = 3, CNT_TRACED = 7,      // [3..7]: box tests, triangle tests, node visits, leaf visits, rays of counting traces (TraceArgs::stats) | the last of them
+  CNT_NODE_ITERS = 8, CNT_LEAF_ITERS = 9, CNT_WAVE_ITERS = 10, CNT_LOST = 15, kCounters = 16      // the cooperative kernel's phase counters | paths lost by the wavefront stages (must stay 0)
 };
 
 struct Ctx {
@@ -39,10 +85,8 @@ struct Ctx {
   HostScene host_scene;
   DevScene scene;
   DevScene* d_scene = nullptr;                 // the same header in HBM (the trace kernels take it by pointer)
-  BvhBuildParams bvh_params;
   DevBuf b_spheres, b_sphere_mat, b_lights, b_materials, b_bf_pos, b_bf_nrm, b_bf_uv, b_bf_idx, b_nodes, b_qnodes, b_tris, b_qtris, b_m_shade;
   int bvh_stack_bound = 8;      // worst-case traversal stack of the uploaded tree
-  int lds_stack_cap = 0;        // option: force the LDS stack size (tests of the overflow path)
   // frame
   int width = 0, height = 0, spp = 0;
   int rank = 0, nranks = 1, tile = 32, npix_local = 0;
@@ -76,64 +120,30 @@ struct Ctx {
     std::vector<int> blas_level_off; const int32_t* blas_levels = nullptr;   // level k of the meshes' trees: blas_levels[blas_level_off[k] .. blas_level_off[k + 1]), nodes of blas_nodes
     UpdateLane refit_lane;                             // the mesh refits' (b_stage: peer copy of pos (+ nrm))
   } move;
-  int64_t query_slice = 1ll << 24;             // option query_slice: rays per slice of a query (112 B of scratch per ray: 1.9 GB at 2^24)
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
   float* ext_accum = nullptr;
   // work distribution / counters
   int* d_cursor = nullptr;
-  unsigned long long* d_counters = nullptr;   // [0] rays issued by shade, [3..7] box, tri, node, leaf, rays of counting traces
-  uint64_t camera_rays = 0;
+  unsigned long long* d_counters = nullptr;   // kCounters words, named by enum Counter
   uint64_t camera_traced = 0;     // camera rays the render passes generated and traced since art_resize (art_get_camera_rays_traced; host-side count)
-  // options
-  int trace_kernel = TRACE_COOP;
-  int64_t batch_paths = 128ll << 20;  // path slots per batch (328 B each at depth 8 -> up to 44 GB of the 288 GB HBM; buffers are sized to the frame,
-                                      // so a small render takes less): big batches keep late bounces wide (8M -> 32M: +7 %, -> 128M: +1.7 %)
-  int opt_blocks_per_cu = 0, blocks_per_cu = 0;
-  bool count_tests = false;
-  bool camera_dedup = true;      // each distinct camera ray of a batch is generated and traced once (DevPaths::cam_dedup); false: once per sample
-  int node_min = 0;              // the trace kernel leaves its node loop when fewer than 8 x node_min lanes still expand nodes.  0: 4 (the optimum on C4, profiles/r2_sensitivity.json);
-                                 // 2 for an instanced scene -- its groups also wait for instance entries, and leaving the loop for them less often is worth 6 % on I64 (profiles/r5_inst_sweep.py)
-  int refill_min = 2;            // idle ray groups of a wave take new rays when two of them are idle (1: at once; measured 0.5-1 % slower)
-  int queue_segments = 8;       // the live-ray queue is cut into this many contiguous segments, one per XCD (1 = a single cursor)
-  int ray_chunk = 48;            // trace records a wave claims per atomic (and prefetches): 16 -> 48 is worth 1 % on C4, 4 % on C3, 10 % on C5 (the claim stalls the wave)
-  bool shadow_anyhit = true;   // shadow rays use the visibility rule instead of a full closest-hit search (same decision)
-  // Items per thread of k_shade_compact (256 x per items and one global atomic per workgroup): 4 or 2.  Neither wins everywhere (inside one
-  // process 2 is 5 % faster on C4, 3 % slower on C5, equal on S4: profiles/r6_shade/trial_check_*.txt; round 5's "+7 % / -10 %" of ab12 were
-  // mostly the mapping of the path state, which differed between its processes), so by default the library MEASURES -- without ever
-  // waiting for the GPU (round 6; until round 5 the trial blocked the host twice per trial batch, which serialised the devices of a
-  // multi-GPU process during their first two batches): after a scene upload or a resize batch 0 runs warm and unmeasured (code-object load,
-  // first touch of the path state), batch 1 with 4 items per thread, batch 2 with 2 -- their shade launches' event pairs carry the trial's
-  // tag -- and every batch after that with 4 until a synchronize (art_synchronize, art_get_stats, a download: calls that wait anyway) has
-  // read both trials' events; then the faster setting is kept.  Two trials only count when their batches had the same number of paths.
-  // The picture does not depend on it (the order of the items of a bank carries no meaning).  Option shade_per: 0 automatic, 2, 4.
-  int opt_shade_per = 0, auto_per = 0, auto_phase = 0;      // auto_phase: 0 warm batch next, 1 trial A (4) next, 2 trial B (2) next, 3 both enqueued, 4 decided
+  Options opt; int blocks_per_cu = 0;
+  int auto_per = 0, auto_phase = 0;      // the items-per-thread trial (Options::opt_shade_per).  auto_phase: 0 warm batch next, 1 trial A (4) next, 2 trial B (2) next, 3 both enqueued, 4 decided
   double auto_ms[2] = {0.0, 0.0}; int64_t auto_P[2] = {0, 0}; int auto_redo = 0; unsigned auto_gen = 0;      // auto_gen: a trial's event pairs carry its generation (mod 4); a reset or a re-done trial starts a new one
-  uint64_t lost_reported = 0;    // lost paths (d_counters[15], cumulative) already reported by a synchronize: only synchronize_one advances it
+  uint64_t lost_reported = 0;    // lost paths (d_counters[CNT_LOST], cumulative) already reported by a synchronize: only synchronize_one advances it
+  // the two test options stay outside Options: art_init_devices has never carried them over to the contexts it creates
   int inject_lost = 0;           // test option: the next render pass bumps the self-check counter once in its first batch (tests/test_gpu_parity.py)
+  int spread_fail_at = -1; bool paths_are_spread = false;      // test option: the creation of this chunk is made to fail, so that the undo + hipMalloc fallback runs (tests/test_gpu_parity.py) | the path state is a spread mapping (Options::paths_spread_mb)
   // multi-device mode: host clock (steady_clock, ms since the process' first use) at which this device's stream reached the start / the end
   // of its passes -- hipLaunchHostFunc on the stream, so the devices' times share one clock (events of different devices cannot be compared)
   struct PassClock { double t0 = 0.0, t1 = 0.0; };
   std::vector<PassClock*> pass_clock;      // one per pass since the last art_get_reduce_info / resize (heap cells: the callbacks write into them)
   double busy_ms = 0.0, idle_ms = 0.0, start_skew_ms = 0.0;   // folded by art_get_reduce_info
-  // HOW THE PATH STATE IS MAPPED decides the shade stage's rate (round 6, profiles/r6_bimodal).  The stage runs about forty concurrent streams
-  // through the 35-74 GB of path state.  As ONE hipMalloc it took 10.4 or 12.1 ms per batch on C3 (31.7 / 35.9 on C4, 22.2 / 26.0 on C5, 28.0 /
-  // 32.5 on S4) depending on the PROCESS -- same binary, same device addresses, same instructions, L2 hits, misses and fabric requests, 16 %
-  // more L1 -> L2 read latency -- and 15.0 as physically contiguous memory: the larger the pieces the driver maps the range in, the slower.
-  // paths_spread_mb: the path state as one address range over separately created physical chunks of that many MB (HIP virtual memory
-  // management, art_api.cpp alloc_spread): the fast mode in every process measured, 13-17 ms to set up, no extra memory; any failure falls
-  // back to hipMalloc.  -1 (default): 64 MB chunks when the path state is 1 GB or more; 0: plain hipMalloc; n > 0: n MB chunks always.
-  int paths_spread_mb = -1; bool paths_are_spread = false;
-  int spread_fail_at = -1;       // test option: the creation of this chunk is made to fail, so that the undo + hipMalloc fallback runs (tests/test_gpu_parity.py)
-
-  bool skip_null_shadow = false;   // DevFrame::skip_null_shadow: shadow rays that cannot change the picture are not traced (fewer rays than the reference issues: off by default)
-  bool inst_coop = true;       // instanced scenes: the cooperative kernel crosses the instance boundary (k_trace_coop<.., INST>); false: k_trace_inst, one ray per lane (A/B, cross-check)
   // timing
-  std::vector<hipEvent_t> ev_pool; size_t ev_used = 0;
-  std::vector<uint8_t> ev_kind;                // per event pair: 0 trace kernel, 1 shade stage, 2 raygen, 3 fold group (art_get_stage_stats) | trial (1 / 2: A / B of the items-per-thread trial) << 4 | the trial's generation << 6
+  EventPairs stage_pairs;                      // around groups of launches; tag: 0 trace kernel, 1 shade stage, 2 raygen, 3 fold group (art_get_stage_stats) | trial (1 / 2: A / B of the items-per-thread trial) << 4 | the trial's generation << 6
   ArtStageStats stage = ArtStageStats();
   unsigned long long* d_items = nullptr;       // cumulative items_in[16] | items_out[16] (k_acc_items at the end of every batch)
-  std::vector<hipEvent_t> pass_events;
+  EventPairs pass_pairs, rebuild_pairs;        // around every render pass (ArtStats::pass_ms) | around the gather of art_rebuild_device
   ArtStats stats = ArtStats();
 };
 

@@ -2,7 +2,7 @@
 // (art_rebuild.hip + the GPU builders), art_move_instances_device and art_refit_mesh_device (art_move.hip), art_get_tree_cost and the
 // diagnostic art_export_two_level.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
-// lane of timing events and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
+// lane of timing event pairs (art_event_pairs.h) and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
 // out; the context stream is ordered after the update also when a launch failed; device 0 is current on every exit path.
 #include <hip/hip_runtime.h>
@@ -48,52 +48,32 @@ static int plan_lane(UpdateLane& L, size_t stage_bytes) {
   return 0;
 }
 
-// Completed event pairs -> *ms_sum (nullptr: not wanted), the pairs back to the free list.  wait: every pair is waited for; else pairs still
-// in flight stay listed, so that a host that updates every frame and never synchronises keeps a list as long as the updates in flight.
-static int fold_lane(UpdateLane& L, bool wait, double* ms_sum) {
-  size_t kept = 0; int rc = 0;
-  for (size_t i = 0; i + 1 < L.ev.size(); i += 2) {
-    float ms = 0.0f;
-    hipError_t e = rc ? hipErrorNotReady : (wait ? hipEventSynchronize(L.ev[i + 1]) : hipEventQuery(L.ev[i + 1]));
-    if (e == hipSuccess) e = hipEventElapsedTime(&ms, L.ev[i], L.ev[i + 1]);
-    if (e == hipSuccess) { if (ms_sum) *ms_sum += ms; L.ev_free.push_back(L.ev[i]); L.ev_free.push_back(L.ev[i + 1]); continue; }
-    if (wait && !rc) rc = fail(std::string("update event pair: ") + hipGetErrorString(e));
-    L.ev[kept] = L.ev[i]; L.ev[kept + 1] = L.ev[i + 1]; kept += 2;
-  }
-  L.ev.resize(kept);
-  (void)hipGetLastError();                                                 // (hipErrorNotReady of a pair still in flight)
-  return rc;
+// Completed event pairs -> ms_sum (device 0's; the other contexts' times are not reported).  wait: every pair is waited for; else pairs
+// still in flight stay listed, so that a host that updates every frame and never synchronises keeps a list as long as the updates in flight.
+static int fold_lane(UpdateLane& L, bool wait, double& ms_sum) {
+  const bool dev0 = (g_cur == &g_devs[0]);
+  const hipError_t e = L.pairs.fold(wait, [&ms_sum, dev0](float ms, uint8_t) { if (dev0) ms_sum += ms; });
+  return e == hipSuccess ? 0 : fail(std::string("update event pair: ") + hipGetErrorString(e));
 }
 
-// A timed update on stream s: start() takes an event pair from the free list (or creates one), records its first event and marks the
-// lane unread; the second event is recorded when the timer leaves scope, on every way out.
-struct LaneTimer {
-  hipEvent_t end = nullptr; hipStream_t s = nullptr;
-  int start(UpdateLane& L, hipStream_t stream) {
-    hipEvent_t e0 = nullptr, e1 = nullptr;
-    if (L.ev_free.size() >= 2) { e1 = L.ev_free.back(); L.ev_free.pop_back(); e0 = L.ev_free.back(); L.ev_free.pop_back(); }
-    else {
-      HIP_TRY(hipEventCreate(&e0));
-      if (hipEventCreate(&e1) != hipSuccess) { (void)hipEventDestroy(e0); return fail("hipEventCreate failed"); }
-    }
-    if (hipEventRecord(e0, stream) != hipSuccess) { L.ev_free.push_back(e0); L.ev_free.push_back(e1); return fail("hipEventRecord failed"); }
-    L.ev.push_back(e0); L.ev.push_back(e1);
-    end = e1; s = stream; L.unread = true;
-    return 0;
-  }
-  ~LaneTimer() { if (end) (void)hipEventRecord(end, s); }
-};
+// A timed update on stream s: the lane's completed pairs are folded, a new one ends when `timer` leaves scope; the lane is unread.
+static int start_lane(UpdateLane& L, hipStream_t s, double& ms_sum, EventPairs::Timer& timer) {
+  (void)fold_lane(L, /*wait=*/false, ms_sum);
+  HIP_TRY(L.pairs.begin(timer, s));
+  L.unread = true;
+  return 0;
+}
 
 static void release_lane(UpdateLane& L) {
   L.b_stage.release();
-  L.ev_free.insert(L.ev_free.end(), L.ev.begin(), L.ev.end()); L.ev.clear();
+  L.pairs.release();
   L.unread = false; L.bad_last = 0; L.bad_reported = true;
 }
 static void destroy_lane(UpdateLane& L) {
   release_lane(L);
-  for (hipEvent_t e : L.ev_free) (void)hipEventDestroy(e);
+  L.pairs.destroy();
   for (hipEvent_t e : {L.ready_ev, L.done_ev}) if (e) (void)hipEventDestroy(e);
-  L.ev_free.clear(); L.ready_ev = L.done_ev = nullptr;
+  L.ready_ev = L.done_ev = nullptr;
 }
 
 // reported once per bad update, like a lost path; the boxes stay empty until a good update or an upload
@@ -238,10 +218,9 @@ static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hi
   A.bad = (unsigned long long*)P.b_bad.p;
   A.nodes = (float*)c.b_nodes.p; A.qnodes = (c.scene.node_width == 4) ? (QNode*)c.b_qnodes.p : nullptr;
   A.tight = (float*)P.b_tight.p;
-  A.width = c.scene.node_width; A.inflate_rel = c.bvh_params.inflate_rel; A.inflate_abs = c.bvh_params.inflate_abs;
-  (void)fold_lane(P.lane, /*wait=*/false, &c == &g_devs[0] ? &g_refit_info.refit_ms : nullptr);
-  LaneTimer timer;
-  if (timer.start(P.lane, s)) return 1;
+  A.width = c.scene.node_width; A.inflate_rel = c.opt.bvh_params.inflate_rel; A.inflate_abs = c.opt.bvh_params.inflate_abs;
+  EventPairs::Timer timer;
+  if (start_lane(P.lane, s, g_refit_info.refit_ms, timer)) return 1;
   HIP_TRY(hipMemsetAsync(A.bad, 0, sizeof(unsigned long long), s));      // [0]: this refit's bad vertices ([1] counts since the upload)
   launch_refit_tris(s, A);
   for (int L = (int)P.level_off.size() - 2; L >= 0; --L)                 // deepest level first
@@ -256,7 +235,7 @@ static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hi
 template <int N, typename Read>
 static int fold_kind(UpdateLane& L, double& ms_sum, const void* counters, Read read) {
   const bool dev0 = (g_cur == &g_devs[0]);
-  if (fold_lane(L, /*wait=*/true, dev0 ? &ms_sum : nullptr)) return 1;
+  if (fold_lane(L, /*wait=*/true, ms_sum)) return 1;
   if (!L.unread || !counters) return 0;
   unsigned long long w[N];
   HIP_TRY(hipMemcpy(w, counters, sizeof w, hipMemcpyDeviceToHost));
@@ -366,9 +345,8 @@ static int move_one(const float* m12f, hipStream_t s) {
   Ctx::MovePlan& P = c.move;
   MoveArgs A = P.args;
   A.m12f = m12f; A.m_cur_out = A.m_cur; A.bad_total = A.state + 2; A.repads = A.state + 3;
-  (void)fold_lane(P.lane, /*wait=*/false, &c == &g_devs[0] ? &g_move_info.move_ms : nullptr);
-  LaneTimer timer;
-  if (timer.start(P.lane, s)) return 1;
+  EventPairs::Timer timer;
+  if (start_lane(P.lane, s, g_move_info.move_ms, timer)) return 1;
   launch_move_pipeline(P, A, s);
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(std::string("art_move_instances_device: kernel launch failed: ") + hipGetErrorString(e));
@@ -411,9 +389,8 @@ static int refit_mesh_one(int32_t mesh, const float* pos, const float* nrm, hipS
   R.tris = (float*)c.b_blas_tris.p + (size_t)kTriFloats * (size_t)m.tri_base; R.qtris = (float*)c.b_qtris.p + (size_t)(kQTriBytes / 4) * (size_t)m.tri_base;
   R.m_shade = (float*)c.b_m_shade.p + (size_t)kTriShadeFloats * (size_t)m.shade_base;
   R.bad = A.state + 4;                                                     // state[4]: this refit's bad vertices, state[5]: since the upload
-  (void)fold_lane(P.refit_lane, /*wait=*/false, &c == &g_devs[0] ? &g_mesh_refit_info.refit_ms : nullptr);
-  LaneTimer timer;
-  if (timer.start(P.refit_lane, s)) return 1;
+  EventPairs::Timer timer;
+  if (start_lane(P.refit_lane, s, g_mesh_refit_info.refit_ms, timer)) return 1;
   HIP_TRY(hipMemsetAsync(R.bad, 0, sizeof(unsigned long long), s));
   launch_refit_tris(s, R);
   for (int L = m.level_end - 1; L >= m.level_first; --L)                   // the mesh's tree, deepest level first
@@ -530,19 +507,18 @@ static int rebuild_one(const HostScene& hs, const BvhBuildParams& bp, const floa
   const int32_t* idx = (const int32_t*)c.refit.b_idx.p;                   // the refit plan keeps the index triples in HBM
   if (!c.refit.ready || !idx) { if (upload(out.idx, hs.m_idx)) return 1; idx = (const int32_t*)out.idx.p; }
   if (ensure(t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(bad, sizeof(unsigned long long))) return 1;
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
+  EventPairs::Timer timer;
   GatherArgs G;
   G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)t9.p; G.bad = (unsigned long long*)bad.p;
   HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-  HIP_TRY(hipEventRecord(ev.a, s));
+  HIP_TRY(c.rebuild_pairs.begin(timer, s));
   launch_gather_tri9(s, G);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev.b, s));
+  HIP_TRY(timer.end());
   unsigned long long n_bad = 0;
   HIP_TRY(hipMemcpyAsync(&n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
   HIP_TRY(hipStreamSynchronize(s));
-  if (gather_ms) HIP_TRY(hipEventElapsedTime(gather_ms, ev.a, ev.b));
+  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
   if (n_bad) return fail("art_rebuild_device: " + std::to_string(n_bad) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
   std::string err;
   if (!build_bvh8_gpu((const float*)t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
@@ -563,7 +539,7 @@ static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
   }
   if (!t.idx.p) { t.idx = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
   release_updates(c);                                                     // the next refit plans against the new tree
-  c.bvh_params = g_devs[0].bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
+  c.opt.bvh_params = g_devs[0].opt.bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
   adopt_tree(c, t.g, bp.width);
   c.b_qtris.release();
   c.b_qtris = t.qtris; t.qtris = DevBuf();                                // (owned by the context now)
@@ -579,7 +555,7 @@ int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream
   if (check_mesh_update(kRebuildCall, pos, nverts)) return 1;
   Ctx& c0 = g_devs[0];
   HostScene& hs = c0.host_scene;
-  BvhBuildParams bp = c0.bvh_params;
+  BvhBuildParams bp = c0.opt.bvh_params;
   if (bp.spatial_alpha >= 0.0f) return fail("art_rebuild_device: option bvh_spatial_splits is set; reference splitting exists in the host builder only (art_upload_scene builds that tree)");
   if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
   if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder

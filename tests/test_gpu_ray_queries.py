@@ -270,3 +270,46 @@ def test_bad_inputs_are_refused_before_any_launch(art, backend):
     assert L.art_trace_rays_device(og.data_ptr(), dg.data_ptr(), None, None, 1 << 31, raw.data_ptr(), art.TRACE_COOP, None) != 0
     # the library still answers afterwards
     _assert_same_bytes(backend.trace_rays_torch(og, dg).raw, _host_raw(backend.trace_rays(o, d)))
+
+
+def test_queries_between_passes_leave_the_context_alone(art, backend):
+    """Queries name their own stream and kernel; the context keeps its own.  Between two render passes: a sliced closest-hit query with the
+    one-ray-per-lane kernel on a side stream (1000 rays in slices of 256: four slices, the last one partial), an occlusion query, and a
+    query that is refused.  The second pass still renders on the context's stream with the context's kernel: the picture has the bits of
+    two passes without queries, the hits are those of the cooperative kernel, and only the passes' launches are timed."""
+    from ada_ray_tracer_amd import scenes
+    depth = 3
+    backend.upload_scene(scenes.mirror_scene())                       # 600 triangles behind the BVH, every material
+    o, d = _rays(1000, 71)
+    og, dg = _gpu(o, d)
+    p = art.Backend.pass_params(art.PT_MIS, True, depth, 1, seed=7)   # 4 samples per pass
+    backend.resize(64, 64)
+    spp = backend.render_pass_device(p, 0)
+    plain, _, _ = backend.render_pass(p, spp)
+    coop = backend.trace_rays_torch(og, dg, kernel=art.TRACE_COOP).raw.cpu().numpy()
+    assert (coop[:, 1] == 1).any() and (coop[:, 1] == 0).any()
+    torch.cuda.synchronize()
+
+    backend.resize(64, 64)
+    spp = backend.render_pass_device(p, 0)
+    s = torch.cuda.Stream()
+    L = backend.lib
+    backend.set_option("query_slice", 256)
+    try:
+        with torch.cuda.stream(s):
+            simple = backend.trace_rays_torch(og, dg, kernel=art.TRACE_SIMPLE)
+            occ = backend.occluded_torch(og, dg)
+        raw = torch.empty((1000, 11), dtype=torch.int32, device="cuda")
+        assert L.art_trace_rays_device(o.ctypes.data, dg.data_ptr(), None, None, 1000, raw.data_ptr(), art.TRACE_SIMPLE, s.cuda_stream) != 0
+        assert "origins is not device memory" in L.art_last_error().decode()
+    finally:
+        backend.set_option("query_slice", 1 << 24)
+    mixed, _, _ = backend.render_pass(p, spp)
+    s.synchronize()
+    assert np.array_equal(mixed.view(np.uint32), plain.view(np.uint32))
+    _assert_same_bytes(simple.raw, coop)
+    assert np.array_equal(occ.cpu().numpy(), coop[:, 1] != 0)
+    # one camera trace plus one trace per bounce, one shade per bounce, one batch per pass; the untimed query launches add nothing
+    st, stage = backend.stats(), backend.stage_stats()
+    assert st.trace_launches == 2 * (1 + depth), st.trace_launches
+    assert stage.shade_launches == 2 * depth and stage.batches == 2, (stage.shade_launches, stage.batches)
