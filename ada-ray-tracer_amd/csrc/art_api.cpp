@@ -575,8 +575,26 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
     };
     const bool rec_layout = (c.opt.trace_kernel == TRACE_COOP);              // the cooperative schedule keeps its rays as trace records inside the path state
     for (;;) {
-      pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / per));
-      sc = (int)std::min<int64_t>(S, std::max<int64_t>(per, (cap / pc) / per * per));
+      // Samples first needs room for all S samples of at least kMinPixelChunk pixels (or of the whole frame); with less, the shape is the
+      // pixels-first one of before.  The minimum is a compatibility rule, not a measured one: tests/test_gpu_camera_dedup.py
+      // (test_small_batches) pins the pixels-first plan at the smallest batch_paths (1024 paths, 8 samples: 256 pixels x 4 samples with
+      // AA on, 8 * W * H camera rays traced), where the plain rule "sc = S whenever batch_paths >= S" gives 128 pixels x 8 samples.  256 is
+      // that pinned pixel chunk.  Smaller chunks work (a last partial chunk is samples first at any size); nothing below 256 * S paths
+      // per batch has been timed either way.
+      constexpr int64_t kMinPixelChunk = 256;
+      if (cap / S >= std::min<int64_t>(npix, kMinPixelChunk)) {
+        // Samples first: a pixel chunk carries all S samples of the pass, so each distinct camera ray of the pass is generated and traced in
+        // exactly one batch (camera_dedup: U * pn rays per batch, U * npix per pass, however many pixel chunks there are).  The pixel map is
+        // dealt in 32 x 32 tiles: a chunk that does not cover the frame is a whole number of them.
+        sc = S;
+        pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / sc));
+        if (pc < npix && pc >= 1024) pc = pc / 1024 * 1024;
+      } else {
+        // too few path slots for 256 pixels with all their samples: pixels first, as many Generate4RayDirections groups per pixel as fit; the camera
+        // rays of a pixel chunk are then traced once per sample chunk
+        pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / per));
+        sc = (int)std::min<int64_t>(S, std::max<int64_t>(per, (cap / pc) / per * per));
+      }
       hipError_t e;
       if (try_alloc(path_floats((size_t)pc * sc, p->max_depth, rec_layout) * 4 + 256, e)) {
         if (g_debug_live) std::fprintf(stderr, "path state: %d pixels x %d samples per batch, %.2f GB\n", pc, sc, (double)g_ctx.b_paths.bytes / 1e9);
