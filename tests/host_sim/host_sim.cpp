@@ -9,6 +9,7 @@
 #include "../../ada-ray-tracer_amd/csrc/art_host_scene.h"
 #include "../../ada-ray-tracer_amd/csrc/art_shade.h"
 #include "../../ada-ray-tracer_amd/csrc/art_instanced_build.h"
+#include "../device_kat/kat_ops.h"
 
 using namespace art;
 
@@ -185,6 +186,19 @@ extern "C" void hs_kat_mat_eval(const ArtMaterial* m, const float l[3], const fl
   f3 b; float pdf;
   bsdf_eval(d, ld3(l), ld3(v), ld3(n), b, pdf);
   out4[0] = b.x; out4[1] = b.y; out4[2] = b.z; out4[3] = pdf;
+}
+
+// ---- the known-answer ops of tests/device_kat/kat_ops.h as batch calls: what tests/device_kat/device_kat.hip (dk_run) runs on the GPU, one
+// item per lane, runs here one item per loop turn -- the same per-item text, the other compiler.  Returns 0, or 1 with hs_last_error set.
+extern "C" int hs_kat_run(int op, long long n, const float* in, int in_floats_per_item, float* out, int out_floats_per_item,
+                          const void* params, int params_bytes) {
+  const kat::OpShape sh = kat::op_shape(op);
+  if (op < 0 || op >= kat::OP_COUNT || sh.in_words == 0) { g_err = "hs_kat_run: unknown op"; return 1; }
+  if (in_floats_per_item != sh.in_words || out_floats_per_item != sh.out_words) { g_err = "hs_kat_run: item sizes are not the op's"; return 1; }
+  if (params_bytes < sh.param_bytes || (sh.param_bytes > 0 && params == nullptr)) { g_err = "hs_kat_run: the op's parameter record is missing or short"; return 1; }
+  if (n < 0 || (n > 0 && (in == nullptr || out == nullptr))) { g_err = "hs_kat_run: bad item count or null array"; return 1; }
+  for (long long i = 0; i < n; ++i) kat::run_item(op, in + i * sh.in_words, out + i * sh.out_words, params);
+  return 0;
 }
 
 // ---- two-level (instanced) closest hit of the legacy seam, on the CPU: art_instanced_build.cpp + art_instanced.h, the code the GPU runs
