@@ -7,7 +7,7 @@
 //            -> finish (inside-out radiance fold) -> accumulate (reference summation order)
 //   then resolve (gamma, clamp, pack) when the caller asks for the LDR image.
 //
-// The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_refit_mesh_device, art_get_tree_cost): art_update.cpp.
+// The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_refit_mesh_device, art_rebuild_instance_tree_device, art_get_tree_cost): art_update.cpp.
 // There is no CPU fallback: every entry point that needs the GPU fails with art_last_error() set when
 // HIP reports no usable device.
 #include <hip/hip_runtime.h>
@@ -1212,6 +1212,15 @@ int art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, 
 }
 
 int art_get_mesh_refit_info(ArtMeshRefitInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_mesh_refit_info(out); }
+
+int art_rebuild_instance_tree_device(void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return rebuild_instance_tree_device((hipStream_t)hip_stream);
+}
+
+int art_get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_instance_rebuild_info(out); }
+
+int art_get_instance_tree_cost(ArtTreeCost* out) { std::lock_guard<std::mutex> lk(g_mu); return get_instance_tree_cost(out); }
 
 int art_export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) { std::lock_guard<std::mutex> lk(g_mu); return export_two_level(info, buf); }
 

@@ -161,4 +161,26 @@ void launch_move_tlas_level(hipStream_t st, const MoveArgs& M, const int32_t* le
 void launch_refit_mesh_level(hipStream_t st, const MoveArgs& M, const int32_t* level_nodes, int n);
 void launch_refit_mesh_box(hipStream_t st, const MoveArgs& M, int mesh);
 
+// a new instance tree from the proxy records in HBM (art_move.hip, art_update.cpp art_rebuild_instance_tree_device).  Nothing of the
+// scene is written: every kernel reads the scene's arrays and the builder's output and writes buffers the call allocated.
+struct InstRebuildArgs {
+  int32_t n_entry, n_blas_nodes;
+  int32_t n_tlas_old, n_tlas_new;              // nodes of the instance tree in force | of the new one
+  const int32_t* order;                        // the upload's proxy order: proxy i is entry point order[i]
+  // gather
+  const int32_t* proxy_rec; const float* tlas_tris;   // the plan's entry point -> proxy record, the proxy records in force
+  float* tri9;                                 // 9 floats per proxy, in the upload's order: what build_bvh_sah_gpu reads
+  unsigned long long* bad;                     // [0] proxies without a finite box, [1] leaves of the built tree the finish refused (both zeroed by the caller)
+  // finish: the builder's tree (breadth-first numbering, word 9 of a record = the input index) -> the host builder's numbering
+  const float* g_nodes; const float* g_tris; const QNode* g_qnodes;
+  const int32_t* node_map; const int32_t* rec_map;    // builder's node -> its number in the host builder's order | the same for the records
+  float* nodes_out; float* tris_out;           // the new instance tree's packets and proxy records (word 9 = the entry point)
+  // relocate
+  const QNode* qnodes_old; QNode* qnodes_out;  // the merged array in force | the new one: the finish writes its first n_tlas_new nodes, the relocation the meshes'
+  const DevInstance* inst_old; DevInstance* inst_out;
+};
+void launch_inst_gather(hipStream_t st, const InstRebuildArgs& R);
+void launch_inst_finish(hipStream_t st, const InstRebuildArgs& R);
+void launch_inst_relocate(hipStream_t st, const InstRebuildArgs& R);
+
 }  // namespace art

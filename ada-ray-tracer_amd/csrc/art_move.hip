@@ -37,6 +37,24 @@
 //
 // and the pipeline above runs at the matrices in force: E depends on mesh_box and every mesh's pad on E, so a mesh that grows can widen
 // another mesh's pad, and every entry point's box depends on the records below it.
+//
+// art_rebuild_instance_tree_device: the instance tree is built again from the proxy records in HBM.  The GPU binned-SAH builder
+// (art_sah.hip) does the building; around it
+//
+//   k_inst_gather       one lane per proxy in the upload's order: the entry point's box (corners 0 and 1 of its proxy record: the upload's
+//                       tight box, which a move or a mesh refit keeps up to date) as the 9-float triangle the upload feeds its builder.
+//                       A box that is not finite, inverted or beyond kRefitMaxCoord is counted; the host reads the count before the
+//                       builder starts.
+//   k_inst_finish       one lane per node of the built tree.  The builder numbers nodes breadth-first and records by reference position,
+//                       the host builder depth-first (art_bvh.cpp's collapse); the host has read the built tree's reference words back and
+//                       hands over both renumberings.  The lane writes its node's packet and quantised form at the host builder's number
+//                       with the references renumbered, every leaf's record at its new place with word 9 = the entry point (the builder
+//                       left the input index there), and the leaf's entry word as an instance marker.  A leaf that does not hold exactly
+//                       one record inside the array is counted and left empty (the host has refused that tree already: nothing is committed).
+//   k_inst_relocate     the meshes' quantised nodes behind the new instance tree: inner entry words move by the change in the instance
+//                       tree's node count, leaf words stay; and a copy of the instance table with every non-leaf qroot moved likewise.
+//
+// None of the three writes anything the scene in force reads: the driver swaps the new buffers in once every context has built.
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
@@ -235,6 +253,66 @@ __global__ __launch_bounds__(kMoveBlock) void k_move_tlas_level(const MoveArgs M
   });
 }
 
+// ---- art_rebuild_instance_tree_device ----------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMoveBlock) void k_inst_gather(const InstRebuildArgs R) {
+  const int i = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (i >= R.n_entry) return;
+  const float* p = R.tlas_tris + (size_t)kTriFloats * (size_t)R.proxy_rec[R.order[i]];      // (the host checked both index arrays)
+  const float lo[3] = {p[0], p[1], p[2]}, hi[3] = {p[3], p[4], p[5]};
+  bool ok = true;
+  for (int a = 0; a < 3; ++a) ok = ok && fabsf(lo[a]) <= kRefitMaxCoord && fabsf(hi[a]) <= kRefitMaxCoord && lo[a] <= hi[a];      // (false for NaN and +-inf)
+  if (!ok) atomicAdd(R.bad, 1ull);
+  float* t = R.tri9 + 9 * (size_t)i;                                       // ONE triangle whose corners span the box
+  t[0] = lo[0]; t[1] = lo[1]; t[2] = lo[2]; t[3] = hi[0]; t[4] = hi[1]; t[5] = hi[2]; t[6] = lo[0]; t[7] = hi[1]; t[8] = lo[2];
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_inst_finish(const InstRebuildArgs R) {
+  const int n = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (n >= R.n_tlas_new) return;
+  const int dst = R.node_map[n];                                           // (a permutation of the nodes: the host built it from the tree it checked)
+  const float* src = R.g_nodes + (size_t)n * 32;
+  float* out = R.nodes_out + (size_t)dst * 32;
+  QNode q = R.g_qnodes[n];
+  for (int j = 0; j < 4; ++j) {
+    int32_t ref = __float_as_int(src[4 * j + 3]);
+    const int32_t cnt = __float_as_int(src[16 + 4 * j + 3]);
+    if (ref >= 0 && cnt == 0) {
+      ref = (ref < R.n_tlas_new) ? R.node_map[ref] : 0;
+      q.rec[j].entry = (uint32_t)ref * (uint32_t)kQNodeBytes;
+    } else if (ref >= 0) {
+      const int32_t idx = (cnt == 1 && ref < R.n_entry) ? __float_as_int(R.g_tris[(size_t)kTriFloats * (size_t)ref + 9]) : -1;
+      if (idx < 0 || idx >= R.n_entry) { atomicAdd(R.bad + 1, 1ull); q.rec[j].entry = kQEntryEmpty; ref = -1; }
+      else {
+        const int32_t ent = R.order[idx], rec = R.rec_map[ref];
+        const float* ts = R.g_tris + (size_t)kTriFloats * (size_t)ref;
+        float* td = R.tris_out + (size_t)kTriFloats * (size_t)rec;
+        for (int k = 0; k < kTriFloats; ++k) td[k] = ts[k];
+        td[9] = __int_as_float(ent);
+        q.rec[j].entry = kQEntryLeaf | ((uint32_t)ent << 4) | kQCountInstance;
+        ref = rec;
+      }
+    }
+    for (int k = 0; k < 3; ++k) { out[4 * j + k] = src[4 * j + k]; out[16 + 4 * j + k] = src[16 + 4 * j + k]; }
+    out[4 * j + 3] = __int_as_float(ref); out[16 + 4 * j + 3] = src[16 + 4 * j + 3];
+  }
+  R.qnodes_out[dst] = q;
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_inst_relocate(const InstRebuildArgs R) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  const uint32_t shift = (uint32_t)(R.n_tlas_new - R.n_tlas_old) * (uint32_t)kQNodeBytes;      // (modulo 2^32: a smaller tree moves the words down)
+  if (t < R.n_blas_nodes) {
+    QNode q = R.qnodes_old[(size_t)R.n_tlas_old + (size_t)t];
+    for (int j = 0; j < 4; ++j) if (!(q.rec[j].entry & kQEntryLeaf)) q.rec[j].entry += shift;      // (an empty slot is a leaf of no records)
+    R.qnodes_out[(size_t)R.n_tlas_new + (size_t)t] = q;
+  }
+  if (t < R.n_entry) {
+    DevInstance d = R.inst_old[t];
+    if (!(d.qroot & kQEntryLeaf)) d.qroot += shift;
+    R.inst_out[t] = d;
+  }
+}
+
 static dim3 move_grid(int n) { return dim3((unsigned)((n + kMoveBlock - 1) / kMoveBlock)); }
 
 void launch_move_matrices(hipStream_t st, const MoveArgs& M) {
@@ -265,6 +343,18 @@ void launch_refit_mesh_level(hipStream_t st, const MoveArgs& M, const int32_t* l
 
 void launch_refit_mesh_box(hipStream_t st, const MoveArgs& M, int mesh) {
   hipLaunchKernelGGL(k_refit_mesh_box, dim3(1), dim3(64), 0, st, M, mesh);
+}
+
+void launch_inst_gather(hipStream_t st, const InstRebuildArgs& R) {
+  hipLaunchKernelGGL(k_inst_gather, move_grid(R.n_entry), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_inst_finish(hipStream_t st, const InstRebuildArgs& R) {
+  hipLaunchKernelGGL(k_inst_finish, move_grid(R.n_tlas_new), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_inst_relocate(hipStream_t st, const InstRebuildArgs& R) {
+  hipLaunchKernelGGL(k_inst_relocate, move_grid(R.n_blas_nodes > R.n_entry ? R.n_blas_nodes : R.n_entry), dim3(kMoveBlock), 0, st, R);
 }
 
 }  // namespace art

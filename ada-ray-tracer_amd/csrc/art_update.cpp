@@ -1,12 +1,13 @@
 // art_update.cpp -- the device-side scene updates of the C ABI (include/art_hip.h): art_refit_device (art_refit.hip), art_rebuild_device
-// (art_rebuild.hip + the GPU builders), art_move_instances_device and art_refit_mesh_device (art_move.hip), art_get_tree_cost and the
-// diagnostic art_export_two_level.  What the kinds share is written
+// (art_rebuild.hip + the GPU builders), art_move_instances_device, art_refit_mesh_device and art_rebuild_instance_tree_device
+// (art_move.hip), art_get_tree_cost, art_get_instance_tree_cost and the diagnostic art_export_two_level.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
 // lane of timing event pairs (art_event_pairs.h) and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
 // out; the context stream is ordered after the update also when a launch failed; device 0 is current on every exit path.
 #include <hip/hip_runtime.h>
 
+#include <algorithm>
 #include <chrono>
 #include <cstring>
 #include <string>
@@ -21,7 +22,8 @@ static ArtRefitInfo g_refit_info = ArtRefitInfo();         // art_get_refit_info
 static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_info: the same
 static ArtMoveInfo g_move_info = ArtMoveInfo();            // art_get_move_info: the same
 static ArtMeshRefitInfo g_mesh_refit_info = ArtMeshRefitInfo();   // art_get_mesh_refit_info: the same
-void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); g_mesh_refit_info = ArtMeshRefitInfo(); }
+static ArtInstanceRebuildInfo g_inst_rebuild_info = ArtInstanceRebuildInfo();   // art_get_instance_rebuild_info: the same
+void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); g_mesh_refit_info = ArtMeshRefitInfo(); g_inst_rebuild_info = ArtInstanceRebuildInfo(); }
 // ---- the caller's stream ----------------------------------------------------------------------------------------------------------
 StreamOrder::StreamOrder(Ctx& ctx, hipStream_t st) : c(ctx), cs(ctx.stream), qs(st == nullptr ? ctx.stream : (st == hipStreamLegacy ? nullptr : st)) {}
 int StreamOrder::enter() {
@@ -307,7 +309,7 @@ static int build_move_plan(const HostScene& hs, const std::string& call, double&
   A.extent = (double)hs.two.scene_extent; A.mesh_pad_rel = hs.two.mesh_pad_rel; A.mesh_pad_min = hs.two.mesh_pad_min;
   const BvhBuildParams tp;                                                 // the instance tree builder's pad rule: the defaults, as build_two_level_host applied them
   A.tlas_pad_rel = tp.inflate_rel; A.tlas_pad_abs = tp.inflate_abs;
-  P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off;
+  P.levels = (const int32_t*)(pb + o_lev); P.level_off = H.tlas_level_off; P.n_tlas = (int32_t)n_tlas;
   P.small_entries = H.records <= 64 * (int64_t)n_entry;
   P.blas_levels = (const int32_t*)(pb + o_blev); P.blas_level_off = H.blas_level_off;
   P.meshes.assign(nm, Ctx::MovePlan::Mesh());
@@ -621,13 +623,220 @@ int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream
 
 int get_rebuild_info(ArtRebuildInfo* out) { if (!out) return fail("null ArtRebuildInfo"); *out = g_rebuild_info; return 0; }
 
-// device 0's tree as it lies in HBM (a refit on another stream is ordered before the context stream's later work)
-int get_tree_cost(ArtTreeCost* out) {
-  if (!out) return fail("null ArtTreeCost");
-  Ctx& c = g_devs[0];
-  if (!c.scene_ready) return fail("art_get_tree_cost: no scene uploaded");
-  if (c.scene.n_inst > 0) return fail("art_get_tree_cost: the scene is instanced (n_instances > 0); the figure is defined for the tree of a flat CLOSEST mesh");
-  if (c.scene.n_nodes < 1 || !c.b_nodes.p) return fail("art_get_tree_cost: the scene has no tree (no ART_MESH_CLOSEST mesh)");
+// ---- a new instance tree from the proxy records in HBM (art_rebuild_instance_tree_device, art_move.hip + art_sah.hip) ---------------
+// What one context has built and not yet committed; whatever is still here when the call leaves is freed (PendingTree's rule).
+struct PendingInstTree {
+  int device = -1; GpuBvh g;
+  DevBuf nodes, tris, qnodes, inst;            // the new instance tree's packets and proxy records, the new merged node array, the new instance table
+  DevBuf plan;                                 // the plan's parts that follow the instance tree (Ctx::MovePlan::b_tlas)
+  size_t o_lev = 0, o_prox = 0, o_mbase = 0, o_tight = 0;
+  std::vector<int> level_off;
+  int32_t n_tlas = 0, max_stack = 0;
+  ~PendingInstTree() {
+    if (device >= 0) (void)hipSetDevice(device);
+    free_tree(g);
+    nodes.release(); tris.release(); qnodes.release(); inst.release(); plan.release();
+  }
+};
+
+// The built tree's packets and records as read back (the builder's numbering; word 9 of a record = the index of its proxy in `order`),
+// checked as build_move_plan_host checks a build -- every node reached exactly once, every entry point named by exactly one proxy -- and
+// re-planned: the host builder's numbering (art_bvh.cpp's collapse takes a node's slots in order, gives every leaf's records and every
+// inner child the next free number, and goes on with the child it numbered last), the levels in that numbering, and proxy_rec.
+static bool plan_built_tree(const std::vector<float>& nodes, const std::vector<float>& tris, const std::vector<int32_t>& order, std::vector<int32_t>& node_map,
+                            std::vector<int32_t>& rec_map, std::vector<int32_t>& levels, std::vector<int>& level_off, std::vector<int32_t>& proxy_rec, std::string& err) {
+  const int64_t N = (int64_t)(nodes.size() / 32), n_entry = (int64_t)order.size();
+  node_map.assign((size_t)N, -1); rec_map.assign((size_t)n_entry, -1); proxy_rec.assign((size_t)n_entry, -1);
+  auto words = [&](int32_t n, int j, int32_t& ref, int32_t& cnt) { std::memcpy(&ref, &nodes[(size_t)n * 32 + 4 * j + 3], 4); std::memcpy(&cnt, &nodes[(size_t)n * 32 + 16 + 4 * j + 3], 4); };
+  std::vector<int32_t> todo(1, 0);
+  int32_t next_node = 1, next_rec = 0;
+  node_map[0] = 0;
+  while (!todo.empty()) {
+    const int32_t n = todo.back(); todo.pop_back();
+    for (int j = 0; j < 4; ++j) {
+      int32_t ref, cnt;
+      words(n, j, ref, cnt);
+      if (ref < 0) continue;
+      if (cnt != 0) {
+        if (cnt != 1 || ref >= n_entry || rec_map[(size_t)ref] >= 0) { err = "the built instance tree has a leaf that is not one proxy of its own"; return false; }
+        int32_t idx;
+        std::memcpy(&idx, &tris[(size_t)ref * kTriFloats + 9], 4);
+        if (idx < 0 || idx >= n_entry || proxy_rec[(size_t)order[(size_t)idx]] >= 0) { err = "a proxy of the built instance tree names no entry point, or one twice"; return false; }
+        rec_map[(size_t)ref] = next_rec; proxy_rec[(size_t)order[(size_t)idx]] = next_rec; ++next_rec;
+        continue;
+      }
+      if (ref >= N || node_map[(size_t)ref] >= 0) { err = "the built instance tree's nodes do not form a tree"; return false; }
+      node_map[(size_t)ref] = next_node++; todo.push_back(ref);
+    }
+  }
+  if (next_node != N) { err = "unreachable nodes in the built instance tree"; return false; }
+  if (next_rec != n_entry) { err = "an entry point without a proxy in the built instance tree"; return false; }
+  std::vector<int32_t> cur(1, 0), next;                                    // (the builder's numbers; the levels hold the new ones)
+  levels.clear(); level_off.assign(1, 0);
+  while (!cur.empty()) {
+    next.clear();
+    for (const int32_t n : cur) {
+      levels.push_back(node_map[(size_t)n]);
+      for (int j = 0; j < 4; ++j) { int32_t ref, cnt; words(n, j, ref, cnt); if (ref >= 0 && cnt == 0) next.push_back(ref); }
+    }
+    level_off.push_back((int)levels.size());
+    cur.swap(next);
+  }
+  return true;
+}
+
+// the current context's new instance tree on stream s: gather, count the proxies without a box, build, read back, check and re-plan,
+// renumber, relocate.  Returns with s idle.  Nothing of the context's scene or plan is touched.
+static int rebuild_inst_one(const std::vector<int32_t>& order, hipStream_t s, PendingInstTree& out, float* gather_ms) {
+  const std::string name = "art_rebuild_instance_tree_device";
+  Ctx& c = g_ctx;
+  const Ctx::MovePlan& P = c.move;
+  const int32_t n_entry = P.args.n_entry, n_blas = P.args.n_blas_nodes, nm = P.args.n_mesh;
+  DevBuf t9, bad, d_order, d_maps;
+  struct Free { DevBuf &a, &b, &c, &d; ~Free() { a.release(); b.release(); c.release(); d.release(); } } fr{t9, bad, d_order, d_maps};
+  out.device = c.device;
+  if (upload(d_order, order) || ensure(t9, (size_t)n_entry * 9 * sizeof(float)) || ensure(bad, 2 * sizeof(unsigned long long))) return 1;
+  InstRebuildArgs R;
+  std::memset(&R, 0, sizeof R);
+  R.n_entry = n_entry; R.n_blas_nodes = n_blas; R.n_tlas_old = P.n_tlas;
+  R.order = (const int32_t*)d_order.p; R.proxy_rec = P.args.proxy_rec; R.tlas_tris = P.args.tlas_tris;
+  R.tri9 = (float*)t9.p; R.bad = (unsigned long long*)bad.p;
+  unsigned long long n_bad[2] = {0ull, 0ull};
+  {
+    EventPairs::Timer timer;
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof n_bad, s));
+    HIP_TRY(c.rebuild_pairs.begin(timer, s));
+    launch_inst_gather(s, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(timer.end());
+  }
+  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
+  if (n_bad[0]) return fail(name + ": " + std::to_string(n_bad[0]) + " entry point(s) without a finite world box; the tree was not rebuilt and the scene is unchanged");
+  BvhBuildParams tp; tp.width = 4; tp.max_leaf = 1;                        // what build_two_level_host gives the instance tree
+  std::string err;
+  if (!build_bvh_sah_gpu((const float*)t9.p, n_entry, tp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
+  const int32_t n_new = out.g.n_nodes;
+  if (!out.g.qnodes || n_new < 1 || out.g.n_tris != n_entry) return fail(name + ": internal: the GPU build returned no instance tree");
+  if (out.g.max_stack > kInstTopStack) return fail(name + ": instance tree stack bound " + std::to_string(out.g.max_stack) + " exceeds " + std::to_string(kInstTopStack));
+  if (((size_t)n_new + (size_t)n_blas) * kQNodeBytes >= (1ull << 31)) return fail(name + ": instanced scene too large for 31-bit node offsets");
+  std::vector<float> h_nodes((size_t)n_new * 32), h_tris((size_t)n_entry * kTriFloats);
+  HIP_TRY(hipMemcpy(h_nodes.data(), out.g.nodes, h_nodes.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(h_tris.data(), out.g.tris, h_tris.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> node_map, rec_map, levels, proxy_rec, mesh_base((size_t)3 * (size_t)nm);
+  if (!plan_built_tree(h_nodes, h_tris, order, node_map, rec_map, levels, out.level_off, proxy_rec, err)) return fail(name + ": internal: " + err);
+  HIP_TRY(hipMemcpy(mesh_base.data(), P.args.mesh_base, mesh_base.size() * 4, hipMemcpyDeviceToHost));
+  for (int32_t m = 0; m < nm; ++m) mesh_base[3 * (size_t)m + 2] += n_new - P.n_tlas;                       // (first node in qnodes)
+  std::vector<uint8_t> img;                                                // every section 16-byte aligned
+  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (p && bytes) std::memcpy(&img[at], p, bytes); return at; };
+  out.o_lev = put(levels.data(), levels.size() * 4); out.o_prox = put(proxy_rec.data(), proxy_rec.size() * 4); out.o_mbase = put(mesh_base.data(), mesh_base.size() * 4);
+  out.o_tight = put(nullptr, (size_t)n_new * 24);                          // (scratch: every level writes a node's tight box before the level above reads it)
+  node_map.insert(node_map.end(), rec_map.begin(), rec_map.end());
+  if (upload(out.plan, img) || upload(d_maps, node_map)) return 1;
+  if (ensure(out.nodes, (size_t)n_new * 128) || ensure(out.tris, (size_t)n_entry * kTriBytes) || ensure(out.qnodes, ((size_t)n_new + (size_t)n_blas) * kQNodeBytes) ||
+      ensure(out.inst, (size_t)n_entry * sizeof(DevInstance))) return 1;
+  R.n_tlas_new = n_new;
+  R.g_nodes = out.g.nodes; R.g_tris = out.g.tris; R.g_qnodes = (const QNode*)out.g.qnodes;
+  R.node_map = (const int32_t*)d_maps.p; R.rec_map = (const int32_t*)d_maps.p + n_new;
+  R.nodes_out = (float*)out.nodes.p; R.tris_out = (float*)out.tris.p;
+  R.qnodes_old = (const QNode*)c.b_qnodes.p; R.qnodes_out = (QNode*)out.qnodes.p;
+  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst.p;
+  launch_inst_finish(s, R);
+  launch_inst_relocate(s, R);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (n_bad[1]) return fail(name + ": internal: " + std::to_string(n_bad[1]) + " leaf(s) of the built instance tree refused");
+  free_tree(out.g);                                                        // (the renumbered copy is the tree)
+  out.n_tlas = n_new; out.max_stack = out.g.max_stack;
+  return 0;
+}
+
+// The current context takes its new instance tree (its streams are idle, its move events are folded).  The one step that can fail, the
+// copy of the new header to d_scene, comes first (commit_tree's rule).
+static int commit_inst_tree(const HostScene& hs, PendingInstTree& t) {
+  Ctx& c = g_ctx;
+  DevScene s = c.scene;
+  s.inst = (const DevInstance*)t.inst.p; s.tlas_nodes = (const float*)t.nodes.p; s.tlas_tris = (const float*)t.tris.p; s.n_nodes = t.n_tlas;
+  HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
+  c.scene = s;
+  Ctx::MovePlan& P = c.move;
+  DevBuf* const mine[5] = {&c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_qnodes, &P.b_tlas};
+  DevBuf* const built[5] = {&t.inst, &t.nodes, &t.tris, &t.qnodes, &t.plan};
+  for (int k = 0; k < 5; ++k) { mine[k]->release(); *mine[k] = *built[k]; *built[k] = DevBuf(); }      // (owned by the context now)
+  const char* pb = (const char*)P.b_tlas.p;
+  MoveArgs& A = P.args;
+  A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
+  A.proxy_rec = (const int32_t*)(pb + t.o_prox); A.mesh_base = (const int32_t*)(pb + t.o_mbase); A.tlas_tight = (float*)(pb + t.o_tight);
+  P.levels = (const int32_t*)(pb + t.o_lev); P.level_off = t.level_off; P.n_tlas = t.n_tlas;
+  c.bvh_stack_bound = std::max(8, t.max_stack + 3 + hs.two.blas_max_stack);      // (flatten_scene's bound: both trees and the "leave" marker on one stack)
+  c.blocks_per_cu = 0;   // re-query occupancy
+  return 0;
+}
+
+// Every context builds into new buffers, from its own proxy records, before any context's scene changes.
+int rebuild_instance_tree_device(hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string name = "art_rebuild_instance_tree_device";
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail(name + ": no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which keeps its own two-level tree");
+  if (c0.scene.n_inst <= 0) return fail(name + ": the scene is not instanced (n_instances = 0); art_rebuild_device builds the tree of a flat mesh");
+  const size_t n_entry = hs.two.entry.size();
+  if (n_entry < 2) return fail(name + ": an instance tree over fewer than two entry points has nothing to rebuild");
+  std::vector<int32_t> order(n_entry);                                    // the upload's proxy order: entry points by (instance, root_entry)
+  for (size_t e = 0; e < n_entry; ++e) order[e] = (int32_t)e;
+  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+    const TwoLevelHost::EntryPoint &x = hs.two.entry[(size_t)a], &y = hs.two.entry[(size_t)b];
+    return x.inst < y.inst || (x.inst == y.inst && x.root_entry < y.root_entry);
+  });
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const hipStream_t qs = StreamOrder(c0, st).qs;
+  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  }
+  if (use_dev(0)) return 1;
+  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
+  if (c0.move.ready) {                                                     // what the last update left in force (no plan: the upload's placement, which it checked)
+    unsigned long long w[kMoveStateWords];
+    HIP_TRY(hipMemcpy(w, c0.move.args.state, sizeof w, hipMemcpyDeviceToHost));
+    if (w[1] || w[7])
+      return fail(name + ": " + std::to_string(w[1]) + " bad instance matrix(es) and " + std::to_string(w[7]) + " bad vertex coordinate(s) are in force, " + std::to_string(w[1] + w[7]) +
+                  " in all: their entry points have no box to build over; a good art_move_instances_device or art_refit_mesh_device clears that state");
+  }
+  double plan_ms = 0.0;                                                    // (no update has run yet: the plan's time is this call's host time)
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || (!g_ctx.move.ready && build_move_plan(hs, name, plan_ms))) return 1; }
+  std::vector<PendingInstTree> built((size_t)g_ndev);
+  float gather_ms = 0.0f;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (rebuild_inst_one(order, k == 0 ? qs : g_ctx.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
+  }
+  // everything else that can fail without a lost device comes before the first swap: the update events and counters of every context
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_move() || fold_mesh_refit()) return 1; }
+  // ---- commit: from here on the scene changes (rebuild_device's rule: a failure below means the device is lost)
+  const double build_ms = built[0].g.build_ms;
+  const int32_t n_new = built[0].n_tlas, max_stack = built[0].max_stack, shift = n_new - hs.two.tlas.n_nodes;
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || commit_inst_tree(hs, built[(size_t)k])) return 1; }
+  // the host's copies: the sizes follow; the tree's arrays in hs.two have been stale since the first update, the table's qroot words go stale now
+  hs.two.tlas.n_nodes = n_new; hs.two.tlas.max_stack = max_stack;
+  for (int32_t& b : hs.two.qnode_base) b += shift;
+  hs.hdr.n_nodes = n_new; hs.bvh.n_nodes += shift; hs.bvh.max_stack = std::max(max_stack + 3 + hs.two.blas_max_stack, 8);
+  hs.inst_stale = true;
+  g_inst_rebuild_info.rebuilds += 1; g_inst_rebuild_info.gather_ms += gather_ms; g_inst_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
+  g_inst_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { if (!out) return fail("null ArtInstanceRebuildInfo"); *out = g_inst_rebuild_info; return 0; }
+
+// the cost figure of a tree of device 0 as it lies in HBM (an update on another stream is ordered before the context stream's later work)
+static int tree_cost_of(Ctx& c, const float* nodes, int n_nodes, int width, ArtTreeCost* out) {
   Dev0Guard guard;
   if (use_dev(0)) return 1;
   DevBuf sums;
@@ -635,7 +844,7 @@ int get_tree_cost(ArtTreeCost* out) {
   if (ensure(sums, 4 * sizeof(double))) return 1;
   double h[4] = {0.0, 0.0, 0.0, 0.0};
   HIP_TRY(hipMemsetAsync(sums.p, 0, sizeof h, c.stream));
-  launch_tree_cost(c.stream, (const float*)c.b_nodes.p, c.scene.n_nodes, c.scene.node_width, (double*)sums.p);
+  launch_tree_cost(c.stream, nodes, n_nodes, width, (double*)sums.p);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(h, sums.p, sizeof h, hipMemcpyDeviceToHost, c.stream));
   HIP_TRY(hipStreamSynchronize(c.stream));
@@ -647,13 +856,34 @@ int get_tree_cost(ArtTreeCost* out) {
   return 0;
 }
 
+int get_tree_cost(ArtTreeCost* out) {
+  if (!out) return fail("null ArtTreeCost");
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail("art_get_tree_cost: no scene uploaded");
+  if (c.scene.n_inst > 0) return fail("art_get_tree_cost: the scene is instanced (n_instances > 0); the figure is defined for the tree of a flat CLOSEST mesh");
+  if (c.scene.n_nodes < 1 || !c.b_nodes.p) return fail("art_get_tree_cost: the scene has no tree (no ART_MESH_CLOSEST mesh)");
+  return tree_cost_of(c, (const float*)c.b_nodes.p, c.scene.n_nodes, c.scene.node_width, out);
+}
+
+// the instance tree's packets: the same figure, a leaf slot being an entry point
+int get_instance_tree_cost(ArtTreeCost* out) {
+  if (!out) return fail("null ArtTreeCost");
+  Ctx& c = g_devs[0];
+  if (!c.scene_ready) return fail("art_get_instance_tree_cost: no scene uploaded");
+  if (c.host_scene.gcore_seam) return fail("art_get_instance_tree_cost: the scene was committed through gcore_commit_scene, which keeps its own two-level tree");
+  if (c.scene.n_inst <= 0) return fail("art_get_instance_tree_cost: the scene is not instanced (n_instances = 0); art_get_tree_cost has the figure of a flat mesh's tree");
+  const int n_tlas = c.host_scene.two.tlas.n_nodes;
+  if (n_tlas < 1 || c.b_tlas_nodes.bytes != (size_t)n_tlas * 128) return fail("art_get_instance_tree_cost: internal: the instance tree in HBM is not the kept build's");
+  return tree_cost_of(c, (const float*)c.b_tlas_nodes.p, n_tlas, 4, out);
+}
+
 // ---- what art_api.cpp calls ---------------------------------------------------------------------------------------------------------
 void release_updates(Ctx& c) {
   Ctx::RefitPlan& R = c.refit;
   R.b_idx.release(); R.b_levels.release(); R.b_tight.release(); R.b_bad.release();
   R.level_off.clear(); R.ready = false; R.bad_total = 0; release_lane(R.lane);
   Ctx::MovePlan& P = c.move;
-  P.b_plan.release(); P.b_work.release();
+  P.b_plan.release(); P.b_work.release(); P.b_tlas.release(); P.n_tlas = 0;
   P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs(); P.ready = false; release_lane(P.lane);
   P.meshes.clear(); P.blas_level_off.clear(); P.blas_levels = nullptr; release_lane(P.refit_lane);
 }

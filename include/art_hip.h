@@ -320,6 +320,35 @@ int  art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f,
 typedef struct ArtMeshRefitInfo { uint64_t refits; double refit_ms; double plan_ms; uint64_t bad_vertices; uint64_t repads; } ArtMeshRefitInfo;
 int  art_get_mesh_refit_info(ArtMeshRefitInfo* out);   /* cumulative since art_upload_scene; waits like art_get_move_info */
 
+/* A new instance tree for an instanced scene whose instances have moved: the other half of
+ * art_move_instances_device and art_refit_mesh_device, which keep the tree's topology.  The 4-wide tree over the entry points' world
+ * boxes is built again on the GPU from the proxy records as they lie in HBM at the call -- the upload's tight boxes at the placement
+ * of the last accepted move (or the upload's), mesh refits included -- by the GPU binned-SAH builder whatever "bvh_builder" says, with
+ * the parameters art_upload_scene gives the instance tree (width 4, one entry point per leaf, default costs and pads), the proxies fed
+ * in the upload's order (entry points by instance, then by where they enter the mesh's tree) and the nodes and records numbered as
+ * the host builder numbers them.  The entry points stay as built: the inst_open choice, the instance table, where every entry point
+ * enters its mesh and the numbering do not change, and nothing of the meshes is touched but the position of their quantised nodes --
+ * the merged node array holds the instance tree first, so a tree of another node count moves them, and every inner entry word and
+ * every entry point's node word moves with them.  With "inst_open" 1 the instance tree, its proxy records and its part of the node
+ * array are the ones art_upload_scene at the matrices in force builds, byte for byte; picture, ray count and hit records do not change
+ * in any case.  Ordering and failure as for art_rebuild_device: the call waits for what hip_stream (NULL: the library's stream) and the
+ * library's streams hold, returns when the new tree is committed, and a failure leaves every context as it was; under
+ * art_init_devices every context builds from its own proxy records before any context swaps.  A later move or mesh refit works
+ * against the new tree.  Refused before anything is launched: no scene, a flat scene (art_rebuild_device builds that tree), a scene
+ * committed through gcore_commit_scene, fewer than two entry points, and bad matrices or bad vertices in force (the message names the
+ * count; a good move or refit clears it). */
+int  art_rebuild_instance_tree_device(void* hip_stream);
+/* Cumulative since art_upload_scene: gather_ms = HIP events around device 0's proxy gather, build_ms = HIP events around device 0's
+ * builds, host_ms = host time inside the calls (all contexts, read-back, re-plan and commit included).  A failed call is not counted. */
+typedef struct ArtInstanceRebuildInfo { uint64_t rebuilds; double gather_ms, build_ms, host_ms; } ArtInstanceRebuildInfo;
+int  art_get_instance_rebuild_info(ArtInstanceRebuildInfo* out);   /* cumulative since art_upload_scene */
+/* art_get_tree_cost's figure for the instance tree in HBM, from its binary32 packets: root_area = A(union of the root's used child
+ * boxes), node_visits = 1 + sum over inner slots of A / root_area, leaf_visits = the expected number of entry points entered (sum over
+ * leaf slots), tri_tests = the same weighted by the leaf's count (equal to leaf_visits: one entry point per leaf).  Empty slots and slots
+ * a bad update emptied add nothing.  What a caller compares before and after art_rebuild_instance_tree_device; the library sets no
+ * policy.  Fails without a scene, on a flat scene and on a scene committed through gcore_commit_scene. */
+int  art_get_instance_tree_cost(ArtTreeCost* out);                 /* device 0; waits for the library's stream */
+
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 
 /* Diagnostic: the two-level tree of an instanced scene as it lies in device 0's HBM right now -- what the trace kernels read, after
