@@ -136,6 +136,10 @@ class ArtInstanceRebuildInfo(C.Structure):
     _fields_ = [("rebuilds", C.c_uint64), ("gather_ms", C.c_double), ("build_ms", C.c_double), ("host_ms", C.c_double)]
 
 
+class ArtMeshRebuildInfo(C.Structure):
+    _fields_ = [("rebuilds", C.c_uint64), ("gather_ms", C.c_double), ("build_ms", C.c_double), ("host_ms", C.c_double)]
+
+
 class ArtTwoLevelInfo(C.Structure):
     _fields_ = [("n_inst", C.c_int32), ("n_entry", C.c_int32), ("n_mesh", C.c_int32), ("n_tlas_nodes", C.c_int32), ("n_blas_nodes", C.c_int32),
                 ("n_records", C.c_int32), ("inst_shift", C.c_int32), ("updated", C.c_int32),
@@ -188,6 +192,7 @@ EXPORTED_SYMBOLS = [
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_rebuild_instance_tree_device", "art_get_instance_rebuild_info", "art_get_instance_tree_cost",
+    "art_rebuild_mesh_tree_device", "art_get_mesh_rebuild_info", "art_get_mesh_tree_cost",
     "art_export_bvh", "art_export_two_level", "art_get_stats", "art_get_stage_stats", "art_get_camera_rays_traced", "art_set_option", "art_last_error", "art_shutdown",
     "gcore_init_and_clear", "gcore_destroy", "gcore_add_mesh_3f", "gcore_instance_meshes", "gcore_commit_scene",
     "gcore_closest_hit", "gcore_closest_hit_n", "gcore_set_two_level", "gcore_set_single_ray_on_gpu",
@@ -239,6 +244,9 @@ def load_library():
     L.art_rebuild_instance_tree_device.argtypes = [C.c_void_p]
     L.art_get_instance_rebuild_info.argtypes = [C.POINTER(ArtInstanceRebuildInfo)]
     L.art_get_instance_tree_cost.argtypes = [C.POINTER(ArtTreeCost)]
+    L.art_rebuild_mesh_tree_device.argtypes = [C.c_int32, C.c_void_p]
+    L.art_get_mesh_rebuild_info.argtypes = [C.POINTER(ArtMeshRebuildInfo)]
+    L.art_get_mesh_tree_cost.argtypes = [C.c_int32, C.POINTER(ArtTreeCost)]
     L.art_export_bvh.argtypes = [f32p, C.c_int64, f32p, C.c_int64, C.POINTER(ArtBvhInfo)]
     L.art_export_two_level.argtypes = [C.POINTER(ArtTwoLevelInfo), C.POINTER(ArtTwoLevelBuffers)]
     L.art_get_stats.argtypes = [C.POINTER(ArtStats)]
@@ -622,20 +630,23 @@ class Backend:
         _check(self.lib.art_get_mesh_refit_info(C.byref(ri)))
         return ri
 
+    @staticmethod
+    def _rebuild_stream(stream):
+        """the stream a rebuild waits for: the caller's, else torch's current stream if torch is loaded and the GPU is in use, else the library's"""
+        if stream is not None:
+            return stream.cuda_stream or HIP_STREAM_LEGACY
+        torch = sys.modules.get("torch")
+        if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
+            return torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
+        return None
+
     def rebuild_instances(self, stream=None):
         """Build the instance tree of the uploaded instanced scene again, on the GPU, from the entry points' world boxes as the last
         move or mesh refit left them (art_rebuild_instance_tree_device): the entry points and the meshes stay, the tree over them is the
         one upload_scene would build at the matrices in force.  stream: a torch.cuda.Stream whose work runs first (None: torch's current
         stream if torch is loaded and the GPU is in use, else the library's).  Unlike a move the call returns only when the tree is
         committed.  Bad matrices or bad vertices in force fail the call with their count and leave the scene unchanged."""
-        handle = None
-        if stream is not None:
-            handle = stream.cuda_stream or HIP_STREAM_LEGACY
-        else:
-            torch = sys.modules.get("torch")
-            if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
-                handle = torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
-        _check(self.lib.art_rebuild_instance_tree_device(handle))
+        _check(self.lib.art_rebuild_instance_tree_device(self._rebuild_stream(stream)))
 
     def instance_rebuild_info(self):
         """ArtInstanceRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
@@ -649,6 +660,27 @@ class Backend:
         one's to decide when to call rebuild_instances."""
         tc = ArtTreeCost()
         _check(self.lib.art_get_instance_tree_cost(C.byref(tc)))
+        return tc
+
+    def rebuild_mesh(self, mesh, stream=None):
+        """Build the tree of mesh number `mesh` of the uploaded instanced scene again, on the GPU, from its triangle records as the
+        last refit_mesh_torch left them (art_rebuild_mesh_tree_device): the tree is the one upload_scene would build for the deformed
+        mesh at the pad in force; indices, shading, matrices, entry points and the instance tree stay, the meshes behind it move.
+        stream: as for rebuild_instances.  The call returns only when the tree is committed.  Bad matrices or bad vertices in force, and
+        an instance of the mesh that the build opened (inst_open), fail the call and leave the scene unchanged."""
+        _check(self.lib.art_rebuild_mesh_tree_device(int(mesh), self._rebuild_stream(stream)))
+
+    def mesh_rebuild_info(self):
+        """ArtMeshRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
+        ri = ArtMeshRebuildInfo()
+        _check(self.lib.art_get_mesh_rebuild_info(C.byref(ri)))
+        return ri
+
+    def mesh_tree_cost(self, mesh):
+        """ArtTreeCost of mesh number `mesh`'s tree in HBM, in object space (device 0; waits).  Compare the figure of a refitted tree with
+        the one at the last build to decide when to call rebuild_mesh."""
+        tc = ArtTreeCost()
+        _check(self.lib.art_get_mesh_tree_cost(int(mesh), C.byref(tc)))
         return tc
 
     def bvh_info(self):

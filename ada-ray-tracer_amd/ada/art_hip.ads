@@ -160,6 +160,31 @@ package Art_Hip is
   function art_get_mesh_refit_info (info : access Art_Mesh_Refit_Info) return int;   --  waits for the refits enqueued so far
   pragma Import (C, art_get_mesh_refit_info, "art_get_mesh_refit_info");
 
+  --  A new tree for mesh number `mesh` of an uploaded instanced scene, built on the GPU from that mesh's triangle records as the last
+  --  art_refit_mesh_device left them; returns when the tree is committed (include/art_hip.h).  art_get_mesh_tree_cost (include/art_hip.h)
+  --  has the figure to decide when.
+  function art_rebuild_mesh_tree_device (mesh : int; hip_stream : System.Address) return int;
+  pragma Import (C, art_rebuild_mesh_tree_device, "art_rebuild_mesh_tree_device");
+
+  type Art_Mesh_Rebuild_Info is record   --  include/art_hip.h ArtMeshRebuildInfo, 32 bytes; cumulative since art_upload_scene
+    rebuilds  : Unsigned_64;
+    gather_ms : double;
+    build_ms  : double;
+    host_ms   : double;
+  end record;
+  pragma Convention (C, Art_Mesh_Rebuild_Info);
+
+  function art_get_mesh_rebuild_info (info : access Art_Mesh_Rebuild_Info) return int;
+  pragma Import (C, art_get_mesh_rebuild_info, "art_get_mesh_rebuild_info");
+
+  type Art_Tree_Cost is record   --  include/art_hip.h ArtTreeCost, 32 bytes
+    root_area, node_visits, leaf_visits, tri_tests : double;
+  end record;
+  pragma Convention (C, Art_Tree_Cost);
+
+  function art_get_mesh_tree_cost (mesh : int; cost : access Art_Tree_Cost) return int;   --  device 0; waits for the library's stream
+  pragma Import (C, art_get_mesh_tree_cost, "art_get_mesh_tree_cost");
+
   function art_last_error return Interfaces.C.Strings.chars_ptr;
   pragma Import (C, art_last_error, "art_last_error");
 

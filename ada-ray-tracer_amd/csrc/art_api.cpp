@@ -1222,6 +1222,15 @@ int art_get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { std::lock_guard
 
 int art_get_instance_tree_cost(ArtTreeCost* out) { std::lock_guard<std::mutex> lk(g_mu); return get_instance_tree_cost(out); }
 
+int art_rebuild_mesh_tree_device(int32_t mesh, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  return rebuild_mesh_tree_device(mesh, (hipStream_t)hip_stream);
+}
+
+int art_get_mesh_rebuild_info(ArtMeshRebuildInfo* out) { std::lock_guard<std::mutex> lk(g_mu); return get_mesh_rebuild_info(out); }
+
+int art_get_mesh_tree_cost(int32_t mesh, ArtTreeCost* out) { std::lock_guard<std::mutex> lk(g_mu); return get_mesh_tree_cost(mesh, out); }
+
 int art_export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) { std::lock_guard<std::mutex> lk(g_mu); return export_two_level(info, buf); }
 
 int art_export_bvh(float* nodes, int64_t node_cap, float* tris, int64_t tri_cap, ArtBvhInfo* info) {

@@ -110,6 +110,7 @@ struct Ctx {
     bool ready = false;
     DevBuf b_plan, b_work;                             // MovePlanHost's constant arrays and the meshes' index triples, one after the other | what the kernels write (MoveArgs)
     DevBuf b_tlas;                                     // after art_rebuild_instance_tree_device: the plan's parts that follow the instance tree (its levels, proxy_rec, mesh_base, the tlas_tight scratch); args and levels point into it
+    DevBuf b_blas;                                     // after art_rebuild_mesh_tree_device: the plan's parts that follow the meshes' node layout (mesh_base, blas_levels, node_mesh, blas_tight); args and blas_levels point into it
     int32_t n_tlas = 0;                                // nodes of the instance tree the plan works against
     MoveArgs args = MoveArgs();                        // everything but m12f, m_cur_out, bad_total and repads: the call sets those
     std::vector<int> level_off; const int32_t* levels = nullptr;   // the instance tree's level L: levels[level_off[L] .. level_off[L + 1])
@@ -214,6 +215,9 @@ int get_mesh_refit_info(ArtMeshRefitInfo* out);
 int rebuild_instance_tree_device(hipStream_t st);
 int get_instance_rebuild_info(ArtInstanceRebuildInfo* out);
 int get_instance_tree_cost(ArtTreeCost* out);
+int rebuild_mesh_tree_device(int32_t mesh, hipStream_t st);
+int get_mesh_rebuild_info(ArtMeshRebuildInfo* out);
+int get_mesh_tree_cost(int32_t mesh, ArtTreeCost* out);
 int export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf);   // device 0's two-level scene as it lies in HBM (caller holds g_mu)
 int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& width, int& n_tris);   // device 0's tree as host arrays (caller holds g_mu)
 

@@ -96,7 +96,7 @@ bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vect
     // flattened upload, which art_upload_scene refuses for the same reason)
     if (b.max_stack > kStackEntries) { err = "mesh tree stack bound " + std::to_string(b.max_stack) + " exceeds " + std::to_string(kStackEntries); return false; }
     if (!two_sided) mesh_q.push_back(b.qnodes);
-    T.blas_max_stack = std::max(T.blas_max_stack, b.max_stack);
+    T.blas_max_stack = std::max(T.blas_max_stack, b.max_stack); T.mesh_max_stack.push_back(b.max_stack);
     node_base[mi] = (int32_t)(T.blas_nodes.size() / node_floats(4));
     tri_base[mi] = (int32_t)(T.blas_tris.size() / kTriFloats);
     ntris[mi] = b.n_tris;

@@ -27,6 +27,7 @@ struct TwoLevelHost {
   std::vector<EntryPoint> entry;
   int32_t open_factor = 1;              // entry points per instance asked of the build (the automatic choice, if that was left to it)
   int32_t blas_max_stack = 0;           // the largest worst-case traversal stack of the meshes' trees
+  std::vector<int32_t> mesh_max_stack;  // per mesh: its tree's bound (art_rebuild_mesh_tree_device replaces one of them; blas_max_stack follows their maximum)
   std::vector<float> mesh_pad_abs;      // per mesh: the absolute pad its tree's boxes were built with (>= the caller's; follows the mesh's instances)
   float scene_extent = 0.0f, mesh_pad_rel = 0.0f, mesh_pad_min = 0.0f;   // what the build was given: the caller's extent, the meshes' relative pad and the floor of their absolute pad (art_move_instances_device pads by the same rule)
   InstScene view() const {

@@ -183,4 +183,30 @@ void launch_inst_gather(hipStream_t st, const InstRebuildArgs& R);
 void launch_inst_finish(hipStream_t st, const InstRebuildArgs& R);
 void launch_inst_relocate(hipStream_t st, const InstRebuildArgs& R);
 
+// a new tree for one mesh of an instanced scene from its triangle records in HBM (art_move.hip, art_update.cpp
+// art_rebuild_mesh_tree_device).  Nothing of the scene is written: every kernel reads the scene's arrays and the builder's output and
+// writes buffers the call allocated.  A tree of another node count moves every mesh behind it by `delta` nodes.
+struct MeshRebuildArgs {
+  int32_t mesh, n_recs;                        // the mesh; its triangle records (one per triangle)
+  int32_t nb, tb, qb;                          // mesh_base of the mesh: first node in blas_nodes, first record in blas_tris, first node in qnodes
+  int32_t n_old, n_new, delta;                 // nodes of the mesh's tree in force | of the new one | n_new - n_old
+  int32_t n_tlas, n_blas_old, n_entry;         // nodes of the instance tree | of all the meshes' trees in force | entry points
+  // gather
+  const float* tris_old;                       // blas_tris in force
+  float* tri9;                                 // 9 floats per triangle, by its index in the mesh (word 9 of a record): what build_bvh_sah_gpu reads
+  unsigned long long* bad;                     // [0] records whose index is out of range or whose corners are not finite, [1] leaves of the built tree the finish refused (both zeroed by the caller)
+  // finish: the builder's tree (breadth-first numbering, mesh-relative entry words) -> the host builder's numbering inside the new arrays
+  const float* g_nodes; const float* g_tris; const QNode* g_qnodes;
+  const int32_t* node_map; const int32_t* rec_map;    // builder's node -> its number in the host builder's order | the same for the records
+  float* nodes_out; float* tris_out; float* qtris_out; QNode* qnodes_out;   // the new blas_nodes, blas_tris, padded copy and merged quantised array
+  int32_t* node_mesh_out; float* tight_out;    // the plan's per-node arrays over the new blas_nodes
+  // relocate
+  const float* nodes_old; const QNode* qnodes_old; const int32_t* node_mesh_old; const float* tight_old;
+  const DevInstance* inst_old; DevInstance* inst_out; const int32_t* inst_mesh;
+};
+void launch_mesh_gather(hipStream_t st, const MeshRebuildArgs& R);
+void launch_mesh_finish(hipStream_t st, const MeshRebuildArgs& R);
+void launch_mesh_relocate(hipStream_t st, const MeshRebuildArgs& R);
+void launch_mesh_tight_level(hipStream_t st, const MeshRebuildArgs& R, const int32_t* level_nodes, int n);   // after the finish, deepest level first: nodes of the new blas_nodes
+
 }  // namespace art

@@ -54,7 +54,22 @@
 //   k_inst_relocate     the meshes' quantised nodes behind the new instance tree: inner entry words move by the change in the instance
 //                       tree's node count, leaf words stay; and a copy of the instance table with every non-leaf qroot moved likewise.
 //
-// None of the three writes anything the scene in force reads: the driver swaps the new buffers in once every context has built.
+// art_rebuild_mesh_tree_device: one mesh's tree is built again from its triangle records in HBM, by the same builder; around it
+//
+//   k_mesh_gather       one lane per record of the mesh: its corners go to tri9 at the triangle's index in the mesh (word 9), the order an
+//                       upload feeds them in.  An index out of range or a corner that is not finite or beyond kRefitMaxCoord is counted;
+//                       the host reads the count before the builder starts.
+//   k_mesh_finish       one lane per 16-byte lane record: lane j of a node's four takes child slot j -- the packet's two rows and the
+//                       quantised record -- to the host builder's number inside the mesh's new slices, references renumbered, entry
+//                       words made absolute; lane q of a triangle record's four writes quarter q of the record at its new place and of
+//                       its 64-byte padded copy (quarter 3: the padding).  A leaf outside the records is counted and left empty (the host
+//                       has refused that tree already).
+//   k_mesh_relocate     one lane per 16 bytes of what the other meshes keep: their packets, their quantised nodes (and the instance
+//                       tree's), the instance table, and per node the plan's node_mesh and blas_tight.  A mesh behind the rebuilt one moves
+//                       by the change in its node count: its inner entry words, its instances' node_base and every qroot that names a node.
+//   k_mesh_tight_level  one launch per level of the new tree, deepest first: the tight box below every node, for the plan's blas_tight.
+//
+// None of these writes anything the scene in force reads: the driver swaps the new buffers in once every context has built.
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
@@ -313,6 +328,104 @@ __global__ __launch_bounds__(kMoveBlock) void k_inst_relocate(const InstRebuildA
   }
 }
 
+// ---- art_rebuild_mesh_tree_device --------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kMoveBlock) void k_mesh_gather(const MeshRebuildArgs R) {
+  const int i = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (i >= R.n_recs) return;
+  const float* p = R.tris_old + (size_t)kTriFloats * (size_t)(R.tb + i);
+  const int32_t prim = __float_as_int(p[9]);
+  bool ok = (uint32_t)prim < (uint32_t)R.n_recs;
+  for (int k = 0; k < 9; ++k) ok = ok && coord_ok(p[k]);
+  if (!ok) { atomicAdd(R.bad, 1ull); return; }
+  float* t = R.tri9 + 9 * (size_t)prim;
+  for (int k = 0; k < 9; ++k) t[k] = p[k];
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_mesh_finish(const MeshRebuildArgs R) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  const int i = t >> 2, j = t & 3;
+  if (i < R.n_new) {
+    const int dst = R.node_map[i];                                         // (a permutation of the nodes: the host built it from the tree it checked)
+    const float4* src = reinterpret_cast<const float4*>(R.g_nodes + (size_t)i * 32);
+    float4 lo = src[j], hi = src[4 + j];
+    uint4 q = reinterpret_cast<const uint4*>(R.g_qnodes + i)[j];
+    int32_t ref = __float_as_int(lo.w);
+    const int32_t cnt = __float_as_int(hi.w);
+    if (ref >= 0 && cnt == 0) {
+      ref = (ref < R.n_new) ? R.node_map[ref] : 0;
+      q.z = (uint32_t)(R.qb + ref) * (uint32_t)kQNodeBytes;
+    } else if (ref >= 0) {
+      if (cnt < 1 || cnt > 4 || ref > R.n_recs - cnt) { atomicAdd(R.bad + 1, 1ull); q.z = kQEntryEmpty; ref = -1; }
+      else {
+        ref = R.rec_map[ref];                                              // (a leaf's records stay one after the other, in the builder's order)
+        q.z = kQEntryLeaf | ((uint32_t)(R.tb + ref) * (uint32_t)kQTriBytes) | (uint32_t)cnt;
+      }
+    }
+    lo.w = __int_as_float(ref);
+    float4* out = reinterpret_cast<float4*>(R.nodes_out + (size_t)(R.nb + dst) * 32);
+    out[j] = lo; out[4 + j] = hi;
+    reinterpret_cast<uint4*>(R.qnodes_out + (size_t)R.qb + (size_t)dst)[j] = q;
+    if (j == 0) R.node_mesh_out[R.nb + dst] = R.mesh;
+  }
+  if (i < R.n_recs) {
+    const size_t rec = (size_t)R.tb + (size_t)R.rec_map[i];
+    const float4 v = (j < 3) ? reinterpret_cast<const float4*>(R.g_tris + (size_t)kTriFloats * (size_t)i)[j] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (j < 3) reinterpret_cast<float4*>(R.tris_out + (size_t)kTriFloats * rec)[j] = v;
+    reinterpret_cast<float4*>(R.qtris_out + (size_t)(kQTriBytes / 4) * rec)[j] = v;
+  }
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_mesh_relocate(const MeshRebuildArgs R) {
+  const int64_t t = (int64_t)blockIdx.x * kMoveBlock + threadIdx.x;
+  const int32_t first = R.nb, end = R.nb + R.n_old;                        // the rebuilt mesh's nodes in the arrays in force: not copied
+  const uint32_t shift = (uint32_t)R.delta * (uint32_t)kQNodeBytes;        // (modulo 2^32: a smaller tree moves the words down)
+  if (t < 8 * (int64_t)R.n_blas_old) {                                     // packets: mesh-relative references, copied as they are
+    const int64_t g = t >> 3;
+    if (g < first || g >= end) reinterpret_cast<uint4*>(R.nodes_out)[(g < first ? g : g + R.delta) * 8 + (t & 7)] = reinterpret_cast<const uint4*>(R.nodes_old)[t];
+  }
+  if (t < 4 * ((int64_t)R.n_tlas + R.n_blas_old)) {                        // quantised nodes: the instance tree's, then the meshes'
+    const int64_t n = t >> 2, g = n - R.n_tlas;
+    if (g < first || g >= end) {
+      uint4 q = reinterpret_cast<const uint4*>(R.qnodes_old)[t];
+      if (g >= end && !(q.z & kQEntryLeaf)) q.z += shift;                  // (an empty slot is a leaf of no records; record positions do not move)
+      reinterpret_cast<uint4*>(R.qnodes_out)[(g < first ? n : n + R.delta) * 4 + (t & 3)] = q;
+    }
+  }
+  if (t < 8 * (int64_t)R.n_entry) {                                        // the instance table: lane record 6 holds node_base, 7 qroot and inst
+    const int64_t e = t >> 3;
+    const int k = (int)(t & 7);
+    uint4 v = reinterpret_cast<const uint4*>(R.inst_old)[t];
+    if (k >= 6 && R.inst_mesh[R.inst_old[e].inst] > R.mesh) {
+      if (k == 6) v.x += (uint32_t)R.delta;
+      else if (!(v.x & kQEntryLeaf)) v.x += shift;
+    }
+    reinterpret_cast<uint4*>(R.inst_out)[t] = v;
+  }
+  if (t < R.n_blas_old && (t < first || t >= end)) {                       // the plan's per-node arrays
+    const int64_t d = t < first ? t : t + R.delta;
+    R.node_mesh_out[d] = R.node_mesh_old[t];
+    for (int k = 0; k < 6; ++k) R.tight_out[6 * d + k] = R.tight_old[6 * t + k];
+  }
+}
+
+__global__ __launch_bounds__(kMoveBlock) void k_mesh_tight_level(const MeshRebuildArgs R, const int32_t* __restrict__ level, int n) {
+  const int t = blockIdx.x * kMoveBlock + threadIdx.x;
+  if (t >= n) return;
+  const int g = level[t];
+  const float* nd = R.nodes_out + (size_t)g * 32;
+  float tl[3] = {INFINITY, INFINITY, INFINITY}, th[3] = {-INFINITY, -INFINITY, -INFINITY};
+  for (int j = 0; j < 4; ++j) {
+    const int32_t ref = __float_as_int(nd[4 * j + 3]), cnt = __float_as_int(nd[16 + 4 * j + 3]);
+    if (ref < 0) continue;
+    float l[3], h[3];
+    const bool ok = cnt > 0 ? records_box(R.tris_out + (size_t)kTriFloats * (size_t)(R.tb + ref), cnt, l, h) : stored_box(R.tight_out + 6 * (size_t)(R.nb + ref), l, h);
+    if (!ok) continue;                                                     // (the gather refused a bad record: every box is good)
+    for (int a = 0; a < 3; ++a) { tl[a] = fminf(tl[a], l[a]); th[a] = fmaxf(th[a], h[a]); }
+  }
+  float* o = R.tight_out + 6 * (size_t)g;
+  o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = th[0]; o[4] = th[1]; o[5] = th[2];
+}
+
 static dim3 move_grid(int n) { return dim3((unsigned)((n + kMoveBlock - 1) / kMoveBlock)); }
 
 void launch_move_matrices(hipStream_t st, const MoveArgs& M) {
@@ -355,6 +468,27 @@ void launch_inst_finish(hipStream_t st, const InstRebuildArgs& R) {
 
 void launch_inst_relocate(hipStream_t st, const InstRebuildArgs& R) {
   hipLaunchKernelGGL(k_inst_relocate, move_grid(R.n_blas_nodes > R.n_entry ? R.n_blas_nodes : R.n_entry), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_mesh_gather(hipStream_t st, const MeshRebuildArgs& R) {
+  hipLaunchKernelGGL(k_mesh_gather, move_grid(R.n_recs), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_mesh_finish(hipStream_t st, const MeshRebuildArgs& R) {
+  const int64_t lanes = 4 * (int64_t)(R.n_new > R.n_recs ? R.n_new : R.n_recs);
+  hipLaunchKernelGGL(k_mesh_finish, dim3((unsigned)((lanes + kMoveBlock - 1) / kMoveBlock)), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_mesh_relocate(hipStream_t st, const MeshRebuildArgs& R) {
+  int64_t lanes = 8 * (int64_t)R.n_blas_old;
+  if (4 * ((int64_t)R.n_tlas + R.n_blas_old) > lanes) lanes = 4 * ((int64_t)R.n_tlas + R.n_blas_old);
+  if (8 * (int64_t)R.n_entry > lanes) lanes = 8 * (int64_t)R.n_entry;
+  hipLaunchKernelGGL(k_mesh_relocate, dim3((unsigned)((lanes + kMoveBlock - 1) / kMoveBlock)), dim3(kMoveBlock), 0, st, R);
+}
+
+void launch_mesh_tight_level(hipStream_t st, const MeshRebuildArgs& R, const int32_t* level_nodes, int n) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(k_mesh_tight_level, move_grid(n), dim3(kMoveBlock), 0, st, R, level_nodes, n);
 }
 
 }  // namespace art

@@ -1,6 +1,6 @@
 // art_update.cpp -- the device-side scene updates of the C ABI (include/art_hip.h): art_refit_device (art_refit.hip), art_rebuild_device
-// (art_rebuild.hip + the GPU builders), art_move_instances_device, art_refit_mesh_device and art_rebuild_instance_tree_device
-// (art_move.hip), art_get_tree_cost, art_get_instance_tree_cost and the diagnostic art_export_two_level.  What the kinds share is written
+// (art_rebuild.hip + the GPU builders), art_move_instances_device, art_refit_mesh_device, art_rebuild_instance_tree_device and
+// art_rebuild_mesh_tree_device (art_move.hip), art_get_tree_cost, art_get_instance_tree_cost, art_get_mesh_tree_cost and the diagnostic art_export_two_level.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
 // lane of timing event pairs (art_event_pairs.h) and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
@@ -15,6 +15,7 @@
 
 #include "art_api_internal.h"
 #include "art_lbvh.h"
+#include "art_renumber.h"
 
 namespace art {
 
@@ -23,7 +24,8 @@ static ArtRebuildInfo g_rebuild_info = ArtRebuildInfo();   // art_get_rebuild_in
 static ArtMoveInfo g_move_info = ArtMoveInfo();            // art_get_move_info: the same
 static ArtMeshRefitInfo g_mesh_refit_info = ArtMeshRefitInfo();   // art_get_mesh_refit_info: the same
 static ArtInstanceRebuildInfo g_inst_rebuild_info = ArtInstanceRebuildInfo();   // art_get_instance_rebuild_info: the same
-void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); g_mesh_refit_info = ArtMeshRefitInfo(); g_inst_rebuild_info = ArtInstanceRebuildInfo(); }
+static ArtMeshRebuildInfo g_mesh_rebuild_info = ArtMeshRebuildInfo();           // art_get_mesh_rebuild_info: the same
+void reset_update_info() { g_refit_info = ArtRefitInfo(); g_rebuild_info = ArtRebuildInfo(); g_move_info = ArtMoveInfo(); g_mesh_refit_info = ArtMeshRefitInfo(); g_inst_rebuild_info = ArtInstanceRebuildInfo(); g_mesh_rebuild_info = ArtMeshRebuildInfo(); }
 // ---- the caller's stream ----------------------------------------------------------------------------------------------------------
 StreamOrder::StreamOrder(Ctx& ctx, hipStream_t st) : c(ctx), cs(ctx.stream), qs(st == nullptr ? ctx.stream : (st == hipStreamLegacy ? nullptr : st)) {}
 int StreamOrder::enter() {
@@ -641,46 +643,18 @@ struct PendingInstTree {
 
 // The built tree's packets and records as read back (the builder's numbering; word 9 of a record = the index of its proxy in `order`),
 // checked as build_move_plan_host checks a build -- every node reached exactly once, every entry point named by exactly one proxy -- and
-// re-planned: the host builder's numbering (art_bvh.cpp's collapse takes a node's slots in order, gives every leaf's records and every
-// inner child the next free number, and goes on with the child it numbered last), the levels in that numbering, and proxy_rec.
+// re-planned: the host builder's numbering and the levels in that numbering (renumber_built_tree, art_renumber.h, which states the rule
+// and serves a mesh's tree with its leaves of up to kMaxLeafTris records as well), and proxy_rec.
 static bool plan_built_tree(const std::vector<float>& nodes, const std::vector<float>& tris, const std::vector<int32_t>& order, std::vector<int32_t>& node_map,
                             std::vector<int32_t>& rec_map, std::vector<int32_t>& levels, std::vector<int>& level_off, std::vector<int32_t>& proxy_rec, std::string& err) {
   const int64_t N = (int64_t)(nodes.size() / 32), n_entry = (int64_t)order.size();
-  node_map.assign((size_t)N, -1); rec_map.assign((size_t)n_entry, -1); proxy_rec.assign((size_t)n_entry, -1);
-  auto words = [&](int32_t n, int j, int32_t& ref, int32_t& cnt) { std::memcpy(&ref, &nodes[(size_t)n * 32 + 4 * j + 3], 4); std::memcpy(&cnt, &nodes[(size_t)n * 32 + 16 + 4 * j + 3], 4); };
-  std::vector<int32_t> todo(1, 0);
-  int32_t next_node = 1, next_rec = 0;
-  node_map[0] = 0;
-  while (!todo.empty()) {
-    const int32_t n = todo.back(); todo.pop_back();
-    for (int j = 0; j < 4; ++j) {
-      int32_t ref, cnt;
-      words(n, j, ref, cnt);
-      if (ref < 0) continue;
-      if (cnt != 0) {
-        if (cnt != 1 || ref >= n_entry || rec_map[(size_t)ref] >= 0) { err = "the built instance tree has a leaf that is not one proxy of its own"; return false; }
-        int32_t idx;
-        std::memcpy(&idx, &tris[(size_t)ref * kTriFloats + 9], 4);
-        if (idx < 0 || idx >= n_entry || proxy_rec[(size_t)order[(size_t)idx]] >= 0) { err = "a proxy of the built instance tree names no entry point, or one twice"; return false; }
-        rec_map[(size_t)ref] = next_rec; proxy_rec[(size_t)order[(size_t)idx]] = next_rec; ++next_rec;
-        continue;
-      }
-      if (ref >= N || node_map[(size_t)ref] >= 0) { err = "the built instance tree's nodes do not form a tree"; return false; }
-      node_map[(size_t)ref] = next_node++; todo.push_back(ref);
-    }
-  }
-  if (next_node != N) { err = "unreachable nodes in the built instance tree"; return false; }
-  if (next_rec != n_entry) { err = "an entry point without a proxy in the built instance tree"; return false; }
-  std::vector<int32_t> cur(1, 0), next;                                    // (the builder's numbers; the levels hold the new ones)
-  levels.clear(); level_off.assign(1, 0);
-  while (!cur.empty()) {
-    next.clear();
-    for (const int32_t n : cur) {
-      levels.push_back(node_map[(size_t)n]);
-      for (int j = 0; j < 4; ++j) { int32_t ref, cnt; words(n, j, ref, cnt); if (ref >= 0 && cnt == 0) next.push_back(ref); }
-    }
-    level_off.push_back((int)levels.size());
-    cur.swap(next);
+  if (!renumber_built_tree(nodes.data(), N, n_entry, /*max_leaf=*/1, "instance tree", node_map, rec_map, levels, level_off, err)) return false;
+  proxy_rec.assign((size_t)n_entry, -1);
+  for (int64_t r = 0; r < n_entry; ++r) {
+    int32_t idx;
+    std::memcpy(&idx, &tris[(size_t)r * kTriFloats + 9], 4);
+    if (idx < 0 || idx >= n_entry || proxy_rec[(size_t)order[(size_t)idx]] >= 0) { err = "a proxy of the built instance tree names no entry point, or one twice"; return false; }
+    proxy_rec[(size_t)order[(size_t)idx]] = rec_map[(size_t)r];
   }
   return true;
 }
@@ -835,6 +809,232 @@ int rebuild_instance_tree_device(hipStream_t st) {
 
 int get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { if (!out) return fail("null ArtInstanceRebuildInfo"); *out = g_inst_rebuild_info; return 0; }
 
+// ---- a new tree for one mesh from its triangle records in HBM (art_rebuild_mesh_tree_device, art_move.hip + art_sah.hip) -------------
+// What one context has built and not yet committed; whatever is still here when the call leaves is freed (PendingTree's rule).
+struct PendingMeshTree {
+  int device = -1; GpuBvh g;
+  DevBuf nodes, tris, qtris, qnodes, inst;     // the new blas_nodes, blas_tris and padded copy, the new merged node array, the new instance table
+  DevBuf plan;                                 // the plan's parts that follow the meshes' node layout (Ctx::MovePlan::b_blas)
+  size_t o_mbase = 0, o_lev = 0, o_nmesh = 0, o_tight = 0;
+  std::vector<int> level_off;                  // the new blas_level_off
+  std::vector<int> mesh_level_first;           // per mesh, and one past the last: its levels in level_off
+  int32_t n_blas = 0, max_stack = 0;
+  ~PendingMeshTree() {
+    if (device >= 0) (void)hipSetDevice(device);
+    free_tree(g);
+    nodes.release(); tris.release(); qtris.release(); qnodes.release(); inst.release(); plan.release();
+  }
+};
+
+// the current context's new tree of mesh `mesh` on stream s: gather, count the bad records, build, read back, check and renumber, finish,
+// relocate, tight boxes.  Returns with s idle.  Nothing of the context's scene or plan is touched.
+static int rebuild_mesh_one(const HostScene& hs, int32_t mesh, hipStream_t s, PendingMeshTree& out, float* gather_ms) {
+  const std::string name = "art_rebuild_mesh_tree_device";
+  Ctx& c = g_ctx;
+  const Ctx::MovePlan& P = c.move;
+  const Ctx::MovePlan::Mesh& M = P.meshes[(size_t)mesh];
+  const int32_t nm = P.args.n_mesh, n_blas = P.args.n_blas_nodes, n_entry = P.args.n_entry, n_recs = M.n_recs;
+  DevBuf t9, bad, d_maps;
+  struct Free { DevBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } fr{t9, bad, d_maps};
+  out.device = c.device;
+  std::vector<int32_t> mesh_base((size_t)3 * (size_t)nm), old_levels((size_t)n_blas);
+  float pad = 0.0f;
+  HIP_TRY(hipMemcpy(mesh_base.data(), P.args.mesh_base, mesh_base.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(old_levels.data(), P.blas_levels, old_levels.size() * 4, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(&pad, P.args.pad_cur + mesh, 4, hipMemcpyDeviceToHost));   // the pad the mesh carries now: pads only grow, and the new boxes must not be tighter than a move has asked for
+  MeshRebuildArgs R;
+  std::memset(&R, 0, sizeof R);
+  R.mesh = mesh; R.n_recs = n_recs;
+  R.nb = mesh_base[3 * (size_t)mesh]; R.tb = mesh_base[3 * (size_t)mesh + 1]; R.qb = mesh_base[3 * (size_t)mesh + 2];
+  R.n_old = ((mesh + 1 < nm) ? mesh_base[3 * ((size_t)mesh + 1)] : n_blas) - R.nb;
+  R.n_tlas = P.n_tlas; R.n_blas_old = n_blas; R.n_entry = n_entry;
+  if (R.nb < 0 || R.n_old < 1 || R.nb + R.n_old > n_blas || R.tb != M.tri_base || R.qb != R.n_tlas + R.nb || n_recs != M.n_prims || c.b_blas_nodes.bytes != (size_t)n_blas * 128 ||
+      c.b_qnodes.bytes != ((size_t)R.n_tlas + (size_t)n_blas) * kQNodeBytes || (size_t)(R.tb + n_recs) * kTriBytes > c.b_blas_tris.bytes)
+    return fail(name + ": internal: the plan is not the layout in HBM");
+  if (ensure(t9, (size_t)n_recs * 9 * sizeof(float)) || ensure(bad, 2 * sizeof(unsigned long long))) return 1;
+  R.tris_old = (const float*)c.b_blas_tris.p; R.tri9 = (float*)t9.p; R.bad = (unsigned long long*)bad.p;
+  unsigned long long n_bad[2] = {0ull, 0ull};
+  {
+    EventPairs::Timer timer;
+    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof n_bad, s));
+    HIP_TRY(hipMemsetAsync(t9.p, 0, t9.bytes, s));                         // (an index named twice leaves a triangle unwritten: a defined input, which the checks below then refuse or not)
+    HIP_TRY(c.rebuild_pairs.begin(timer, s));
+    launch_mesh_gather(s, R);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(timer.end());
+  }
+  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
+  if (n_bad[0]) return fail(name + ": " + std::to_string(n_bad[0]) + " triangle record(s) of mesh " + std::to_string(mesh) + " with an index out of range or a corner that is not finite; the tree was not rebuilt and the scene is unchanged");
+  BvhBuildParams bp; bp.width = 4;                                         // what build_two_level_host gives a mesh of a one-sided build, at the pad in force
+  bp.inflate_rel = hs.two.mesh_pad_rel; bp.inflate_abs = pad;
+  std::string err;
+  if (!build_bvh_sah_gpu((const float*)t9.p, n_recs, bp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
+  const int32_t n_new = out.g.n_nodes;
+  if (!out.g.qnodes || n_new < 1 || out.g.n_tris != n_recs) return fail(name + ": internal: the GPU build returned no tree for the mesh");
+  if (out.g.max_stack > kStackEntries) return fail(name + ": mesh tree stack bound " + std::to_string(out.g.max_stack) + " exceeds " + std::to_string(kStackEntries));
+  const int64_t n_blas_new = (int64_t)n_blas - R.n_old + n_new;
+  if (((uint64_t)R.n_tlas + (uint64_t)n_blas_new) * kQNodeBytes >= (1ull << 31)) return fail(name + ": instanced scene too large for 31-bit node offsets");
+  std::vector<float> h_nodes((size_t)n_new * 32);
+  HIP_TRY(hipMemcpy(h_nodes.data(), out.g.nodes, h_nodes.size() * 4, hipMemcpyDeviceToHost));
+  std::vector<int32_t> node_map, rec_map, levels;
+  std::vector<int> level_off;
+  if (!renumber_built_tree(h_nodes.data(), n_new, n_recs, /*max_leaf=*/4, "mesh tree", node_map, rec_map, levels, level_off, err)) return fail(name + ": internal: " + err);
+  R.n_new = n_new; R.delta = n_new - R.n_old;
+  // the plan's parts that follow the node layout: mesh_base, and the level lists with this mesh's levels replaced and the meshes' behind it moved
+  for (int32_t k = mesh + 1; k < nm; ++k) { mesh_base[3 * (size_t)k] += R.delta; mesh_base[3 * (size_t)k + 2] += R.delta; }
+  std::vector<int32_t> new_levels;
+  new_levels.reserve((size_t)n_blas_new);
+  out.level_off.assign(1, 0); out.mesh_level_first.assign(1, 0);
+  for (int32_t k = 0; k < nm; ++k) {
+    if (k == mesh) {
+      for (size_t L = 0; L + 1 < level_off.size(); ++L) {
+        for (int i = level_off[L]; i < level_off[L + 1]; ++i) new_levels.push_back(R.nb + levels[(size_t)i]);
+        out.level_off.push_back((int)new_levels.size());
+      }
+    } else {
+      const Ctx::MovePlan::Mesh& K = P.meshes[(size_t)k];
+      for (int L = K.level_first; L < K.level_end; ++L) {
+        for (int i = P.blas_level_off[(size_t)L]; i < P.blas_level_off[(size_t)L + 1]; ++i) new_levels.push_back(old_levels[(size_t)i] + (k > mesh ? R.delta : 0));
+        out.level_off.push_back((int)new_levels.size());
+      }
+    }
+    out.mesh_level_first.push_back((int)out.level_off.size() - 1);
+  }
+  if ((int64_t)new_levels.size() != n_blas_new) return fail(name + ": internal: the plan's levels do not cover the meshes' nodes");
+  std::vector<uint8_t> img;                                                // every section 16-byte aligned
+  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (p && bytes) std::memcpy(&img[at], p, bytes); return at; };
+  out.o_mbase = put(mesh_base.data(), mesh_base.size() * 4); out.o_lev = put(new_levels.data(), new_levels.size() * 4);
+  out.o_nmesh = put(nullptr, (size_t)n_blas_new * 4); out.o_tight = put(nullptr, (size_t)n_blas_new * 24);      // (written by the finish, the relocation and the tight-box launches)
+  node_map.insert(node_map.end(), rec_map.begin(), rec_map.end());
+  if (upload(out.plan, img) || upload(d_maps, node_map)) return 1;
+  if (ensure(out.nodes, (size_t)n_blas_new * 128) || ensure(out.tris, c.b_blas_tris.bytes) || ensure(out.qtris, c.b_qtris.bytes) ||
+      ensure(out.qnodes, ((size_t)R.n_tlas + (size_t)n_blas_new) * kQNodeBytes) || ensure(out.inst, (size_t)n_entry * sizeof(DevInstance))) return 1;
+  char* pb = (char*)out.plan.p;
+  R.g_nodes = out.g.nodes; R.g_tris = out.g.tris; R.g_qnodes = (const QNode*)out.g.qnodes;
+  R.node_map = (const int32_t*)d_maps.p; R.rec_map = (const int32_t*)d_maps.p + n_new;
+  R.nodes_out = (float*)out.nodes.p; R.tris_out = (float*)out.tris.p; R.qtris_out = (float*)out.qtris.p; R.qnodes_out = (QNode*)out.qnodes.p;
+  R.node_mesh_out = (int32_t*)(pb + out.o_nmesh); R.tight_out = (float*)(pb + out.o_tight);
+  R.nodes_old = (const float*)c.b_blas_nodes.p; R.qnodes_old = (const QNode*)c.b_qnodes.p; R.node_mesh_old = P.args.node_mesh; R.tight_old = P.args.blas_tight;
+  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst.p; R.inst_mesh = P.args.inst_mesh;
+  // record positions do not move: the other meshes' records and padded copies are plain copies, the finish then writes this mesh's slices
+  HIP_TRY(hipMemcpyAsync(out.tris.p, c.b_blas_tris.p, c.b_blas_tris.bytes, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(out.qtris.p, c.b_qtris.p, c.b_qtris.bytes, hipMemcpyDeviceToDevice, s));
+  launch_mesh_finish(s, R);
+  launch_mesh_relocate(s, R);
+  const int32_t* d_levels = (const int32_t*)(pb + out.o_lev);
+  for (int L = out.mesh_level_first[(size_t)mesh + 1] - 1; L >= out.mesh_level_first[(size_t)mesh]; --L)      // deepest level first
+    launch_mesh_tight_level(s, R, d_levels + out.level_off[(size_t)L], out.level_off[(size_t)L + 1] - out.level_off[(size_t)L]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  if (n_bad[1]) return fail(name + ": internal: " + std::to_string(n_bad[1]) + " leaf(s) of the built mesh tree refused");
+  free_tree(out.g);                                                        // (the renumbered copy is the tree)
+  out.n_blas = (int32_t)n_blas_new; out.max_stack = out.g.max_stack;
+  return 0;
+}
+
+// The current context takes its mesh's new tree (its streams are idle, its update events are folded).  The one step that can fail, the
+// copy of the new header to d_scene, comes first (commit_tree's rule).  The plan keeps everything its kernels maintain in b_work.
+static int commit_mesh_tree(PendingMeshTree& t, int tlas_stack, int blas_stack) {
+  Ctx& c = g_ctx;
+  DevScene s = c.scene;
+  s.inst = (const DevInstance*)t.inst.p; s.blas_nodes = (const float*)t.nodes.p; s.blas_tris = (const float*)t.tris.p;
+  HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
+  c.scene = s;
+  Ctx::MovePlan& P = c.move;
+  DevBuf* const mine[6] = {&c.b_inst, &c.b_blas_nodes, &c.b_blas_tris, &c.b_qtris, &c.b_qnodes, &P.b_blas};
+  DevBuf* const built[6] = {&t.inst, &t.nodes, &t.tris, &t.qtris, &t.qnodes, &t.plan};
+  for (int k = 0; k < 6; ++k) { mine[k]->release(); *mine[k] = *built[k]; *built[k] = DevBuf(); }      // (owned by the context now)
+  const char* pb = (const char*)P.b_blas.p;
+  MoveArgs& A = P.args;
+  A.inst = (DevInstance*)c.b_inst.p; A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
+  A.n_blas_nodes = t.n_blas;
+  A.mesh_base = (const int32_t*)(pb + t.o_mbase); A.node_mesh = (const int32_t*)(pb + t.o_nmesh); A.blas_tight = (float*)(pb + t.o_tight);
+  P.blas_levels = (const int32_t*)(pb + t.o_lev); P.blas_level_off = t.level_off;
+  for (size_t k = 0; k < P.meshes.size(); ++k) { P.meshes[k].level_first = t.mesh_level_first[k]; P.meshes[k].level_end = t.mesh_level_first[k + 1]; }
+  c.bvh_stack_bound = std::max(8, tlas_stack + 3 + blas_stack);           // (flatten_scene's bound: both trees and the "leave" marker on one stack)
+  c.blocks_per_cu = 0;   // re-query occupancy
+  return 0;
+}
+
+// the refusals art_rebuild_mesh_tree_device and art_get_mesh_tree_cost share
+static int check_mesh_of_instanced(const std::string& name, int32_t mesh) {
+  const Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail(name + ": no scene uploaded");
+  const HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which keeps its own two-level tree");
+  if (c0.scene.n_inst <= 0) return fail(name + ": the scene is not instanced (n_instances = 0); " + (name == "art_get_mesh_tree_cost" ? "art_get_tree_cost has the figure of" : "art_rebuild_device builds the tree of") + " a flat mesh");
+  const int64_t n_mesh = (int64_t)hs.mesh_nverts.size();
+  if (mesh < 0 || mesh >= n_mesh || hs.mesh_idx_off.size() != (size_t)n_mesh + 1 || hs.two.qnode_base.size() != (size_t)n_mesh)
+    return fail(name + ": mesh " + std::to_string(mesh) + " is out of range (the scene has " + std::to_string(n_mesh) + " meshes)");
+  const int64_t n_tris = (hs.mesh_idx_off[(size_t)mesh + 1] - hs.mesh_idx_off[(size_t)mesh]) / 3;
+  if (n_tris == 0) return fail(name + ": no instance shows mesh " + std::to_string(mesh));
+  if (n_tris < 2) return fail(name + ": a mesh of fewer than two triangles has no GPU-built tree; art_refit_mesh_device moves it");
+  return 0;
+}
+
+// Every context builds into new buffers, from its own records, before any context's scene changes.
+int rebuild_mesh_tree_device(int32_t mesh, hipStream_t st) {
+  const auto t0 = std::chrono::steady_clock::now();
+  const std::string name = "art_rebuild_mesh_tree_device";
+  if (check_mesh_of_instanced(name, mesh)) return 1;
+  Ctx& c0 = g_devs[0];
+  HostScene& hs = c0.host_scene;
+  for (size_t e = 0; e < hs.two.entry.size(); ++e) {
+    const TwoLevelHost::EntryPoint& E = hs.two.entry[e];
+    if (hs.two.inst[(size_t)E.inst].mesh == mesh && E.root_entry != 0)
+      return fail(name + ": instance " + std::to_string(E.inst) + " of mesh " + std::to_string(mesh) + " was opened by the build (option inst_open): its entry points name subtrees of the "
+                  "tree in force, and opening it again would change the instance table and the instance tree; art_upload_scene rebuilds such a mesh");
+  }
+  Dev0Guard guard;
+  if (use_dev(0)) return 1;
+  const hipStream_t qs = StreamOrder(c0, st).qs;
+  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
+  }
+  if (use_dev(0)) return 1;
+  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
+  if (c0.move.ready) {                                                     // what the last update left in force (no plan: the upload's records, which it checked)
+    unsigned long long w[kMoveStateWords];
+    HIP_TRY(hipMemcpy(w, c0.move.args.state, sizeof w, hipMemcpyDeviceToHost));
+    if (w[1] || w[7])
+      return fail(name + ": " + std::to_string(w[1]) + " bad instance matrix(es) and " + std::to_string(w[7]) + " bad vertex coordinate(s) are in force, " + std::to_string(w[1] + w[7]) +
+                  " in all: their boxes are empty and the plan's boxes do not describe the records; a good art_move_instances_device or art_refit_mesh_device clears that state");
+  }
+  double plan_ms = 0.0;                                                    // (no update has run yet: the plan's time is this call's host time)
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || (!g_ctx.move.ready && build_move_plan(hs, name, plan_ms))) return 1; }
+  std::vector<PendingMeshTree> built((size_t)g_ndev);
+  float gather_ms = 0.0f;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    if (rebuild_mesh_one(hs, mesh, k == 0 ? qs : g_ctx.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
+  }
+  // everything else that can fail without a lost device comes before the first swap: the update events and counters of every context
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_move() || fold_mesh_refit()) return 1; }
+  // ---- commit: from here on the scene changes (rebuild_device's rule: a failure below means the device is lost)
+  const double build_ms = built[0].g.build_ms;
+  const int32_t n_blas_new = built[0].n_blas, n_blas_old = c0.move.args.n_blas_nodes, delta = n_blas_new - n_blas_old;
+  if (hs.two.mesh_max_stack.size() != hs.two.qnode_base.size()) hs.two.mesh_max_stack.assign(hs.two.qnode_base.size(), hs.two.blas_max_stack);
+  hs.two.mesh_max_stack[(size_t)mesh] = built[0].max_stack;
+  hs.two.blas_max_stack = *std::max_element(hs.two.mesh_max_stack.begin(), hs.two.mesh_max_stack.end());
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || commit_mesh_tree(built[(size_t)k], hs.two.tlas.max_stack, hs.two.blas_max_stack)) return 1; }
+  // the host's copies: the sizes follow; the trees' arrays in hs.two have been stale since the first update, the table's node_base and qroot words go stale now
+  for (size_t k = (size_t)mesh + 1; k < hs.two.qnode_base.size(); ++k) hs.two.qnode_base[k] += delta;
+  for (InstRec& r : hs.two.inst) if (r.mesh > mesh) r.node_base += delta;
+  hs.two.blas_nodes.resize((size_t)n_blas_new * 32, 0.0f); std::vector<uint32_t>().swap(hs.two.qnodes);
+  hs.bvh.n_nodes += delta; hs.bvh.max_stack = std::max(hs.two.tlas.max_stack + 3 + hs.two.blas_max_stack, 8);
+  hs.inst_stale = true;
+  g_mesh_rebuild_info.rebuilds += 1; g_mesh_rebuild_info.gather_ms += gather_ms; g_mesh_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
+  g_mesh_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+int get_mesh_rebuild_info(ArtMeshRebuildInfo* out) { if (!out) return fail("null ArtMeshRebuildInfo"); *out = g_mesh_rebuild_info; return 0; }
+
 // the cost figure of a tree of device 0 as it lies in HBM (an update on another stream is ordered before the context stream's later work)
 static int tree_cost_of(Ctx& c, const float* nodes, int n_nodes, int width, ArtTreeCost* out) {
   Dev0Guard guard;
@@ -877,13 +1077,25 @@ int get_instance_tree_cost(ArtTreeCost* out) {
   return tree_cost_of(c, (const float*)c.b_tlas_nodes.p, n_tlas, 4, out);
 }
 
+// one mesh's tree of an instanced scene: the same figure over its slice of blas_nodes, in object space
+int get_mesh_tree_cost(int32_t mesh, ArtTreeCost* out) {
+  if (!out) return fail("null ArtTreeCost");
+  if (check_mesh_of_instanced("art_get_mesh_tree_cost", mesh)) return 1;
+  Ctx& c = g_devs[0];
+  const TwoLevelHost& T = c.host_scene.two;
+  const int64_t n_blas = (int64_t)(c.b_blas_nodes.bytes / 128), nb = (int64_t)T.qnode_base[(size_t)mesh] - T.tlas.n_nodes;
+  const int64_t ne = ((size_t)mesh + 1 < T.qnode_base.size()) ? (int64_t)T.qnode_base[(size_t)mesh + 1] - T.tlas.n_nodes : n_blas;
+  if (nb < 0 || ne <= nb || ne > n_blas) return fail("art_get_mesh_tree_cost: internal: the meshes' trees in HBM are not the kept layout");
+  return tree_cost_of(c, (const float*)c.b_blas_nodes.p + (size_t)nb * 32, (int)(ne - nb), 4, out);
+}
+
 // ---- what art_api.cpp calls ---------------------------------------------------------------------------------------------------------
 void release_updates(Ctx& c) {
   Ctx::RefitPlan& R = c.refit;
   R.b_idx.release(); R.b_levels.release(); R.b_tight.release(); R.b_bad.release();
   R.level_off.clear(); R.ready = false; R.bad_total = 0; release_lane(R.lane);
   Ctx::MovePlan& P = c.move;
-  P.b_plan.release(); P.b_work.release(); P.b_tlas.release(); P.n_tlas = 0;
+  P.b_plan.release(); P.b_work.release(); P.b_tlas.release(); P.b_blas.release(); P.n_tlas = 0;
   P.level_off.clear(); P.levels = nullptr; P.args = MoveArgs(); P.ready = false; release_lane(P.lane);
   P.meshes.clear(); P.blas_level_off.clear(); P.blas_levels = nullptr; release_lane(P.refit_lane);
 }

@@ -312,7 +312,8 @@ int  art_get_move_info(ArtMoveInfo* out);   /* cumulative since art_upload_scene
  * does not hide them.  The placement test of art_move_instances_device runs again against the mesh's new box: an instance that the
  * grown mesh takes beyond 1e18 (coordinate times matrix) is emptied like a bad matrix's instance until a refit or a move brings it back
  * within reach, and nothing reports it -- the one case in which the picture is not the upload's.  After a large deformation
- * the trees cost more to walk than the ones a fresh art_upload_scene builds; art_get_tree_cost is not defined for an instanced scene. */
+ * the trees cost more to walk than the ones a fresh art_upload_scene builds: art_get_mesh_tree_cost has the figure of the mesh's tree and
+ * art_rebuild_mesh_tree_device builds it again. */
 int  art_refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream);
 /* refits = calls accepted, refit_ms = HIP events around device 0's kernels of the call, plan_ms = host time of building the plans (where
  * this call built them), bad_vertices = bad vertices counted on device 0 over all mesh refits, repads = meshes whose boxes a mesh refit
@@ -348,6 +349,38 @@ int  art_get_instance_rebuild_info(ArtInstanceRebuildInfo* out);   /* cumulative
  * a bad update emptied add nothing.  What a caller compares before and after art_rebuild_instance_tree_device; the library sets no
  * policy.  Fails without a scene, on a flat scene and on a scene committed through gcore_commit_scene. */
 int  art_get_instance_tree_cost(ArtTreeCost* out);                 /* device 0; waits for the library's stream */
+
+/* A new tree for one mesh of an instanced scene whose vertices have moved: the other half of
+ * art_refit_mesh_device, which keeps the tree's topology, and the counterpart of art_rebuild_instance_tree_device.  The call takes no
+ * vertices: mesh `mesh`'s 4-wide tree is built again on the GPU from that mesh's triangle records as they lie in HBM at the call --
+ * after whatever art_refit_mesh_device has written -- by the GPU binned-SAH builder whatever "bvh_builder" says, with the parameters
+ * art_upload_scene gives a mesh (width 4, default leaf size and costs, the scene's relative pad) and the absolute pad the mesh carries
+ * at the call (pads only grow: the build's, or what a later move or refit widened it to), the corners fed in the order of the
+ * triangles' indices in the mesh and the nodes and records numbered as the host builder numbers them.  Indices, material ids, shading
+ * records, matrices, the other meshes' records, the entry points and the instance tree are not touched; the mesh's records are
+ * reordered into the new leaves.  The meshes' trees lie one after the other, so a tree of another node count moves every mesh behind
+ * it: their nodes, their inner entry words, their instances' node_base and every entry point's node word move with them.  After
+ * art_refit_mesh_device + this call + art_rebuild_instance_tree_device the two-level scene is the one art_upload_scene of the deformed
+ * scene builds with "inst_open" 1, word for word, where the pad is the upload's; picture, ray count and hit records do not change in any
+ * case.  Ordering and failure as for art_rebuild_instance_tree_device: the call waits for what hip_stream (NULL: the library's stream)
+ * and the library's streams hold, returns when the new tree is committed, and a failure (the allocator, the builder, a stack bound
+ * above the trace kernels', the 31-bit node offsets, the check of the tree read back) leaves every context as it was; under
+ * art_init_devices every context builds from its own records before any context swaps.  A later move, mesh refit, instance-tree rebuild
+ * or mesh rebuild works against the new layout.  Refused before anything is launched: no scene, a flat scene (art_rebuild_device builds
+ * that tree), a scene committed through gcore_commit_scene, mesh out of range, a mesh no instance shows, a mesh of fewer than two
+ * triangles (art_refit_mesh_device moves it), bad matrices or bad vertices in force (the message names the counts; a good move or refit
+ * clears them), and an instance of this mesh that the build opened ("inst_open": its entry points name subtrees of the old tree; opened
+ * entry points of other meshes are relocated). */
+int  art_rebuild_mesh_tree_device(int32_t mesh, void* hip_stream);
+/* Cumulative since art_upload_scene: gather_ms = HIP events around device 0's record gather, build_ms = HIP events around device 0's
+ * builds, host_ms = host time inside the calls (all contexts, read-back, renumbering and commit included).  A failed call is not counted. */
+typedef struct ArtMeshRebuildInfo { uint64_t rebuilds; double gather_ms, build_ms, host_ms; } ArtMeshRebuildInfo;
+int  art_get_mesh_rebuild_info(ArtMeshRebuildInfo* out);   /* cumulative since art_upload_scene; a failed call is not counted */
+/* art_get_tree_cost's figure for the tree of mesh `mesh` of an instanced scene as it lies in HBM, in object space, from its binary32
+ * packets.  Empty slots and slots a bad refit emptied add nothing.  What a caller compares after art_refit_mesh_device to decide when to
+ * call art_rebuild_mesh_tree_device; the library sets no policy.  Refused as art_rebuild_mesh_tree_device refuses, but for bad state in
+ * force and opened instances, which do not concern the figure. */
+int  art_get_mesh_tree_cost(int32_t mesh, ArtTreeCost* out);   /* device 0; waits for the library's stream */
 
 int  art_export_bvh(float* nodes, int64_t node_floats_cap, float* tris, int64_t tri_floats_cap, ArtBvhInfo* info);
 
