@@ -107,6 +107,17 @@ class ArtHit(C.Structure):
                 ("mat_id", C.c_int32), ("mat", C.c_int32), ("normal", C.c_float * 3), ("u", C.c_float), ("v", C.c_float)]
 
 
+class ArtAovBuffers(C.Structure):
+    _fields_ = [("albedo3f", C.c_void_p), ("normal3f", C.c_void_p), ("depth", C.c_void_p), ("alpha", C.c_void_p),
+                ("prim_type", C.c_void_p), ("prim_index", C.c_void_p), ("mat", C.c_void_p)]
+
+
+# Backend.render_aovs_torch: plane -> (field of ArtAovBuffers, floats or ints per pixel, integer plane)
+AOV_PLANES = collections.OrderedDict([("albedo", ("albedo3f", 3, False)), ("normal", ("normal3f", 3, False)), ("depth", ("depth", 1, False)),
+                                      ("alpha", ("alpha", 1, False)), ("prim_type", ("prim_type", 1, True)), ("prim_index", ("prim_index", 1, True)),
+                                      ("mat", ("mat", 1, True))])
+
+
 class ArtBvhInfo(C.Structure):
     _fields_ = [("n_nodes", C.c_int32), ("n_tris", C.c_int32), ("max_stack", C.c_int32), ("node_width", C.c_int32),
                 ("build_ms", C.c_double)]
@@ -188,7 +199,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_refit_device", "art_get_refit_info",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_rebuild_instance_tree_device", "art_get_instance_rebuild_info", "art_get_instance_tree_cost",
@@ -232,6 +243,7 @@ def load_library():
     L.art_trace_rays.argtypes = [f32p, f32p, f32p, C.c_int64, C.POINTER(ArtHit), C.c_int32, C.POINTER(ArtStats)]
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -500,6 +512,29 @@ class Backend:
         out = torch.empty((n,), dtype=torch.bool, device=o.device)
         ptr = lambda x: None if x is None else x.data_ptr()
         _check(self.lib.art_occluded_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, out.data_ptr() if n else None, stream))
+        return out
+
+    def render_aovs_torch(self, params, want=tuple(AOV_PLANES)):
+        """First-hit feature buffers of the frame (art_render_aovs_device): a dict of torch tensors on the library's GPU, one per name in
+        `want` -- albedo, normal [H, W, 3] float32; depth, alpha [H, W] float32; prim_type, prim_index, mat [H, W] int32 -- allocated by
+        torch and enqueued on torch.cuda.current_stream() without waiting for it.  Of `params` only aa_on and background are read: with
+        aa_on a float plane is the mean of the pixel's four camera rays, the ids are those of ray 0.  An unknown name raises ValueError
+        before any call."""
+        want = tuple(want)
+        for name in want:
+            if name not in AOV_PLANES:
+                raise ValueError("render_aovs_torch: unknown plane %r (known: %s)" % (name, ", ".join(AOV_PLANES)))
+        import torch
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+        dev = torch.device("cuda", torch.cuda.current_device())
+        h, w = getattr(self, "height", 0), getattr(self, "width", 0)
+        out, buf = {}, ArtAovBuffers()
+        for name in want:
+            field, per, integer = AOV_PLANES[name]
+            out[name] = torch.empty((h, w, 3) if per == 3 else (h, w), dtype=torch.int32 if integer else torch.float32, device=dev)
+            setattr(buf, field, out[name].data_ptr() or None)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.lib.art_render_aovs_device(C.byref(params), C.byref(buf), stream or HIP_STREAM_LEGACY))
         return out
 
     def _vertex_tensors(self, pos, nrm):

@@ -140,6 +140,20 @@ package Art_Hip is
                            kernel : int; stats : System.Address) return int;
   pragma Import (C, art_trace_rays, "art_trace_rays");
 
+  --  First-hit feature buffers of the whole frame (include/art_hip.h ArtAovBuffers, 56 bytes): every component is DEVICE memory of the
+  --  library's GPU, row-major, or Null_Address = not wanted.  Of p only aa_on and background are read; hip_stream = Null_Address is the
+  --  library's stream.  Stream-ordered like the device ray queries; accum buffer, spp and the statistics are not touched.
+  type Art_Aov_Buffers is record
+    albedo3f, normal3f : System.Address;            --  3 C floats per pixel
+    depth, alpha       : System.Address;            --  1 C float per pixel
+    prim_type, prim_index, mat : System.Address;    --  1 int per pixel: Art_Hit's fields for the pixel's ray 0
+  end record;
+  pragma Convention (C, Art_Aov_Buffers);
+
+  function art_render_aovs_device (p : access constant Art_Pass_Params; buffers : access constant Art_Aov_Buffers;
+                                   hip_stream : System.Address) return int;
+  pragma Import (C, art_render_aovs_device, "art_render_aovs_device");
+
   --  Deforming mesh number `mesh` (an index into Art_Scene_Desc.meshes) of an uploaded instanced scene: pos3f / nrm3f are DEVICE memory
   --  of the library's GPU, 3 * nverts C floats in the vertex order of that mesh, object space; nrm3f = Null_Address keeps the normals;
   --  hip_stream = Null_Address is the library's stream.  Stream-ordered; the picture is the one of art_upload_scene with that mesh's

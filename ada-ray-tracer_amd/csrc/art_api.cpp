@@ -966,6 +966,22 @@ int check_device_ptr(const void* p, size_t bytes, const char* what) {
   return 0;
 }
 
+// The scratch of one slice of S rays: b_query = counter sink (256 B) | 7 SoA floats + the shadow minimum per ray | the hit records, and
+// what the trace launch needs of b_queue and b_ovf.  Growing it may wait: nothing enqueued may still use the old buffers.
+static int ensure_query_scratch(const StreamOrder& order, size_t S, bool coop) {
+  Ctx& c = g_ctx;
+  int entries; bool ovf; stack_plan(entries, ovf);
+  const size_t q_bytes = 256 + S * (8 * 4 + sizeof(DevHit));
+  const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
+  if (!grow) return 0;
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
+  if (ensure(c.b_query, q_bytes)) return 1;
+  if (coop && ensure(c.b_queue, (S + kRecSlack) * kTraceRecBytes)) return 1;
+  if (coop && ovf && ensure(c.b_ovf, S * sizeof(int))) return 1;
+  return 0;
+}
+
 // hits (closest hit) or occluded (occlusion): n rays in slices of query_slice, every launch on the stream `st` names (StreamOrder).
 // The scratch (b_query, b_queue, b_ovf) is shared with the render passes on the context stream: on another stream the query waits
 // for what the context stream holds, and the context stream waits for the query.
@@ -987,16 +1003,7 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
   const hipStream_t qs = order.qs;
   const size_t S = (size_t)std::min<int64_t>(n, c.opt.query_slice);
   const bool coop = (kernel == TRACE_COOP);
-  int entries; bool ovf; stack_plan(entries, ovf);
-  const size_t q_bytes = 256 + S * (8 * 4 + sizeof(DevHit));      // counter sink | 7 SoA floats + the shadow minimum | hit records
-  const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
-  if (grow) {                           // growing the scratch may wait: nothing enqueued may still use the old buffers
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    if (order.other()) HIP_TRY(hipStreamSynchronize(qs));
-    if (ensure(c.b_query, q_bytes)) return 1;
-    if (coop && ensure(c.b_queue, (S + kRecSlack) * kTraceRecBytes)) return 1;
-    if (coop && ovf && ensure(c.b_ovf, S * sizeof(int))) return 1;
-  }
+  if (ensure_query_scratch(order, S, coop)) return 1;
   if (order.enter()) return 1;
   char* base = (char*)c.b_query.p;
   unsigned long long* sink = (unsigned long long*)base;
@@ -1020,6 +1027,67 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
     if (hits) launch_query_finalize(qs, c.scene, Q);
     else launch_query_occluded(qs, Q);
     if (hipGetLastError() != hipSuccess) rc = fail(std::string(name) + ": kernel launch failed");
+  }
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
+// art_render_aovs_device: the whole frame's camera rays (k per pixel) in slices of whole pixels, k * pixels <= query_slice, through the
+// queries' scratch and stream order; per slice k_aov_raygen, the render loop's trace launch, k_aov_resolve.  Like a query it counts its
+// rays into the scratch's sink and takes no event pair: ArtStats and ArtStageStats do not see it.
+int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_render_aovs_device";
+  if (!p) return fail(name + ": null ArtPassParams");
+  if (!out) return fail(name + ": null ArtAovBuffers");
+  if (!out->albedo3f && !out->normal3f && !out->depth && !out->alpha && !out->prim_type && !out->prim_index && !out->mat) return fail(name + ": no plane is wanted (all seven pointers are null)");
+  if (!c.scene_ready) return fail(name + ": no scene uploaded");
+  if (c.host_scene.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which has no camera");
+  if (c.width <= 0) return fail(name + ": no viewport (art_resize)");
+  const int kernel = c.opt.trace_kernel;
+  if (c.scene.n_inst > 0 && kernel != TRACE_COOP) return fail(name + ": an instanced scene is traced through the record schedule only (option trace_kernel = 0)");
+  if (ensure_device()) return 1;
+  const int64_t npix = (int64_t)c.width * c.height;
+  const size_t N = (size_t)npix;
+  if ((out->albedo3f && check_device_ptr(out->albedo3f, 12 * N, "albedo3f")) || (out->normal3f && check_device_ptr(out->normal3f, 12 * N, "normal3f")) ||
+      (out->depth && check_device_ptr(out->depth, 4 * N, "depth")) || (out->alpha && check_device_ptr(out->alpha, 4 * N, "alpha")) ||
+      (out->prim_type && check_device_ptr(out->prim_type, 4 * N, "prim_type")) || (out->prim_index && check_device_ptr(out->prim_index, 4 * N, "prim_index")) ||
+      (out->mat && check_device_ptr(out->mat, 4 * N, "mat")))
+    return 1;
+  ArtPassParams pp = ArtPassParams();   // only aa_on and background are the caller's
+  pp.aa_on = p->aa_on; std::memcpy(pp.background, p->background, 12);
+  DevFrame F; make_frame(&pp, F);
+  const int k = F.aa_on ? 4 : 1;
+  const int64_t ns = std::min<int64_t>(npix, std::max<int64_t>(1, c.opt.query_slice / k));      // pixels per slice
+  const size_t S = (size_t)(ns * k);                                                            // its rays: at most 2^28 (query_slice), or k
+  StreamOrder order(c, st);
+  const hipStream_t qs = order.qs;
+  const bool coop = (kernel == TRACE_COOP);
+  if (ensure_query_scratch(order, S, coop)) return 1;
+  if (order.enter()) return 1;
+  char* base = (char*)c.b_query.p;
+  unsigned long long* sink = (unsigned long long*)base;
+  float* f = (float*)(base + 256);
+  DevHit* dh = (DevHit*)(f + 8 * S);
+  const TraceLaunch launch = {qs, kernel, /*count_tests=*/false, /*timed=*/false, nullptr, nullptr, /*live_rays=*/sink};
+  int rc = 0;
+  for (int64_t p0 = 0; p0 < npix && !rc; p0 += ns) {
+    const int n = (int)std::min<int64_t>(ns, npix - p0);
+    AovArgs A; std::memset(&A, 0, sizeof A);
+    A.n = n; A.k = k; A.pixel0 = (uint32_t)p0;
+    A.ox = f; A.oy = f + S; A.oz = f + 2 * S; A.dx = f + 3 * S; A.dy = f + 4 * S; A.dz = f + 5 * S; A.tf = f + 6 * S; A.hit = dh;
+    A.albedo = out->albedo3f ? out->albedo3f + 3 * p0 : nullptr; A.normal = out->normal3f ? out->normal3f + 3 * p0 : nullptr;
+    A.depth = out->depth ? out->depth + p0 : nullptr; A.alpha = out->alpha ? out->alpha + p0 : nullptr;
+    A.prim_type = out->prim_type ? out->prim_type + p0 : nullptr; A.prim_index = out->prim_index ? out->prim_index + p0 : nullptr;
+    A.mat = out->mat ? out->mat + p0 : nullptr;
+    launch_aov_raygen(qs, F, c.scene, A);
+    DevPaths q; std::memset(&q, 0, sizeof q);
+    q.ray_ox = A.ox; q.ray_oy = A.oy; q.ray_oz = A.oz; q.ray_dx = A.dx; q.ray_dy = A.dy; q.ray_dz = A.dz; q.ray_tfar = A.tf; q.hit = dh;
+    q.P = 0;                                                         // (no shadow minima: every ray is a closest-hit query)
+    rc = trace(q, k * n, launch);
+    if (rc) break;
+    launch_aov_resolve(qs, F, c.scene, A);
+    if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
   }
   if (order.leave()) return 1;          // (also after a failed launch)
   return rc;
@@ -1181,6 +1249,11 @@ int art_occluded_rays_device(const float* origins3f, const float* dirs3f, const 
   std::lock_guard<std::mutex> lk(g_mu);
   if (!occluded_out && n > 0) return fail("art_occluded_rays_device: null occluded_out");
   return query_rays(origins3f, dirs3f, tnear, tfar, n, nullptr, occluded_out, TRACE_COOP, (hipStream_t)hip_stream);
+}
+
+int art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return render_aovs(p, out, (hipStream_t)hip_stream);
 }
 
 int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {

@@ -202,6 +202,7 @@ int upload_scene(const ArtSceneDesc* d);
 int resize(int w, int h);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
+int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);

@@ -93,6 +93,21 @@ void launch_query_pack(hipStream_t st, const QueryArgs& Q);
 void launch_query_finalize(hipStream_t st, const DevScene& S, const QueryArgs& Q);
 void launch_query_occluded(hipStream_t st, const QueryArgs& Q);
 
+// first-hit feature buffers (art_aov.hip, art_api.cpp render_aovs): one slice of n whole pixels, k camera rays each, in the queries'
+// scratch.  Ray s of local pixel l lies at slot s * n + l (samples first, like a render batch).  The planes are the caller's, advanced
+// to the slice's first pixel; nullptr: not wanted.
+struct AovArgs {
+  int32_t n, k;                       // pixels of the slice | rays per pixel: 4 (anti-aliasing) or 1
+  uint32_t pixel0;                    // the slice's first pixel (y * width + x)
+  float *ox, *oy, *oz, *dx, *dy, *dz, *tf;  // SoA slots of the trace launch, k * n of each
+  DevHit* hit;
+  float* albedo; float* normal;       // 3 floats per pixel
+  float* depth; float* alpha;
+  int32_t* prim_type; int32_t* prim_index; int32_t* mat;
+};
+void launch_aov_raygen(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
+void launch_aov_resolve(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
+
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex
 struct RefitArgs {

@@ -191,6 +191,16 @@ ART_HD LightSample light_sample(L lp, float u1, float u2, f3 p) {
 // ---------------------------------------------------------------- materials
 struct BsdfSample { f3 color, dir; float pdf; bool specular; };
 
+// the albedo plane of art_render_aovs_device (include/art_hip.h): the colour the material multiplies reflected light by, white for
+// what only transmits or emits, black for the null material
+ART_HD f3 material_albedo(const DevMaterial& m) {
+  switch (m.type) {
+    case MAT_LAMBERT: case MAT_MIRROR: case MAT_PHONG: return mk3(m.p[0], m.p[1], m.p[2]);
+    case MAT_GLASS: case MAT_LIGHT: return mk3(1.0f, 1.0f, 1.0f);
+    default: return mk3(0.0f, 0.0f, 0.0f);
+  }
+}
+
 ART_HD float fresnel_unpolarised(float cos1, float eta_ext_in, float eta_int_in) {   // materials.adb:70-99
   float ext = eta_ext_in, in = eta_int_in;
   if (cos1 < 0.0f) { const float tmp = ext; ext = in; in = tmp; }

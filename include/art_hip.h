@@ -215,6 +215,40 @@ int  art_trace_rays_device(const float* origins3f, const float* dirs3f, const fl
 int  art_occluded_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n,
                               uint8_t* occluded_out, void* hip_stream);
 
+/* First-hit feature buffers of the frame: what a denoiser, a segmentation mask or a compositing step wants
+ * next to the radiance.  Every pointer of ArtAovBuffers is device memory of the library's device (device 0 under art_init_devices),
+ * row-major (pixel (x, y) at y*width + x) whatever p->layout says; NULL = that plane is not wanted and costs nothing.
+ * Frame and scope: the frame art_resize set, always the WHOLE frame on device 0 whatever art_set_shard or art_init_devices dealt, like
+ * the device ray queries.  Of p only aa_on and background are read; render_type, max_depth, vthreads, seed and layout are ignored.
+ * Rays: pixel q owns K camera rays, K = 4 with aa_on, else 1; ray s is the ray a render pass traces for sample s of q (the
+ * Generate4RayDirections offset of s through the camera matrix, from cam_pos, unbounded), traced by the render loop's own trace launch
+ * under the option "trace_kernel" as it stands -- the launch art_trace_rays_device uses, so spheres, the Cornell box, rect lights, the
+ * REFERENCE_BF mesh and the CLOSEST mesh (or the instances) are all seen.  With h_s the ArtHit art_trace_rays returns for ray s:
+ *   hit:   depth_s = h_s.t   normal_s = h_s.normal   albedo_s = albedo of materials[h_s.mat]   hit_s = 1
+ *   miss:  depth_s = 0       normal_s = (0, 0, 0)    albedo_s = p->background                  hit_s = 0
+ * Albedo of a material: LAMBERT, MIRROR, PHONG p[0..2]; GLASS and LIGHT (1, 1, 1); NULL (0, 0, 0).
+ * A float plane holds (((v_0 + v_1) + v_2) + v_3) * 0.25f in binary32, in that association, not contracted (K = 1: v_0); alpha is that
+ * mean of hit_s, the normal is not renormalised.  prim_type, prim_index and mat are those of h_0 (-1 on a miss; instanced scenes:
+ * prim_index = instance << shift | triangle, as the queries report it).
+ * The frame is traced in slices of whole pixels, K * pixels <= the option "query_slice" (at least one pixel), in the queries' scratch.
+ * Stream-ordered exactly as art_trace_rays_device: NULL = the library's stream, hipStreamLegacy = the null stream; the host waits only
+ * when the scratch has to grow; the call runs after everything the library has enqueued and before anything it enqueues later, so a
+ * refit, move or rebuild enqueued before it is seen.  It does not touch the accum buffer, spp, anything a later pass reads of the path
+ * state, ArtStageStats or ArtStats: like the device queries' rays, its rays are counted nowhere and its trace launch is not timed.
+ * Refused before anything is launched: null p or out, all seven pointers NULL, no scene, no art_resize, a scene committed through
+ * gcore_commit_scene (it has no camera), an instanced scene with the option "trace_kernel" 1 (as art_render_pass), and any given
+ * pointer that is host memory, another device's memory or too small for its plane. */
+typedef struct ArtAovBuffers {
+  float*   albedo3f;               /* 3 floats per pixel */
+  float*   normal3f;               /* 3 floats per pixel */
+  float*   depth;                  /* 1 */
+  float*   alpha;                  /* 1: share of the pixel's camera rays that hit anything */
+  int32_t* prim_type;              /* ArtHit::prim_type of ray 0, -1 miss */
+  int32_t* prim_index;             /* ArtHit::prim_index of ray 0 */
+  int32_t* mat;                    /* ArtHit::mat of ray 0 */
+} ArtAovBuffers;
+int  art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream);
+
 /* Moving geometry.  Moves the vertices of the scene's ART_MESH_CLOSEST mesh and refits its tree in place: same
  * topology, same leaf order, new boxes (the builders' padding rule, quantised again at width 4), for every builder and both widths.
  * pos3f: device memory, 3*nverts floats, in the vertex order of the ArtMesh.pos uploaded; nrm3f: the same for normals, or NULL = keep
