@@ -3,6 +3,7 @@
 // art_rebuild_mesh_tree_device (art_move.hip), art_get_tree_cost, art_get_instance_tree_cost, art_get_mesh_tree_cost and the diagnostic art_export_two_level.  What the kinds share is written
 // once, in the first half of this file: the ordering of the caller's stream against the context stream (StreamOrder), the per-context
 // lane of timing event pairs (art_event_pairs.h) and bad-item bookkeeping (UpdateLane), and the driver that runs an update on every context (run_update).
+// The three calls that replace a tree have a driver of their own (run_rebuild), which states the rule that makes them safe.
 // Invariants of every entry point: every check comes before the first launch; the end event of a timed update is recorded on every way
 // out; the context stream is ordered after the update also when a launch failed; device 0 is current on every exit path.
 #include <hip/hip_runtime.h>
@@ -10,7 +11,9 @@
 #include <algorithm>
 #include <chrono>
 #include <cstring>
+#include <initializer_list>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "art_api_internal.h"
@@ -265,6 +268,13 @@ int refit_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t
 int get_refit_info(ArtRefitInfo* out) { return get_info(out, "null ArtRefitInfo", g_refit_info, fold_refit); }
 
 // ---- an instanced scene changes (art_move_instances_device, art_refit_mesh_device, art_move.hip) ----------------------------------
+// The parts of a plan that are built on the host, as one buffer: every section is 16-byte aligned, a null source reserves zeroed scratch.
+struct PlanImage {
+  std::vector<uint8_t> img;
+  size_t put(const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (p && bytes) std::memcpy(&img[at], p, bytes); return at; }
+  int upload_to(DevBuf& b) const { return upload(b, img); }
+};
+
 // The plan of the current context, from the two-level build the upload kept and before either call has changed anything: MovePlanHost's
 // constant arrays and the meshes' index triples in one buffer, what the kernels maintain in another (the tight boxes, the meshes' boxes
 // and pads, the matrices in force), and MoveArgs pointing into both and into the scene's arrays.  `call` builds it; its info takes the time.
@@ -281,22 +291,17 @@ static int build_move_plan(const HostScene& hs, const std::string& call, double&
     return fail(call + ": internal: the arrays in HBM are not the kept build's");
   if (hs.inst.size() != n_entry || hs.mesh_nverts.size() != nm || hs.mesh_idx_off.size() != nm + 1 || c.b_qtris.bytes != hs.two.blas_tris.size() / kTriFloats * (size_t)kQTriBytes)
     return fail(call + ": internal: the host scene is not the kept build's");
-  std::vector<uint8_t> img;                                                // every section 16-byte aligned
-  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (bytes) std::memcpy(&img[at], p, bytes); return at; };
-  const size_t o_roff = put(H.range_off.data(), H.range_off.size() * 4), o_rng = put(H.ranges.data(), H.ranges.size() * 4), o_prox = put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
-  const size_t o_imesh = put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbase = put(H.mesh_base.data(), H.mesh_base.size() * 4);
-  const size_t o_nmesh = put(H.node_mesh.data(), H.node_mesh.size() * 4), o_lev = put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
-  const size_t o_blev = put(H.blas_levels.data(), H.blas_levels.size() * 4), o_idx = put(hs.mesh_idx.data(), hs.mesh_idx.size() * 4);
-  if (upload(P.b_plan, img)) return 1;
-  std::vector<uint8_t> work;
-  auto room = [&](size_t bytes) { const size_t at = work.size(); work.resize(at + ((bytes + 15) & ~(size_t)15), 0); return at; };
-  const size_t w_state = room(kMoveStateWords * 8), w_need = room(nm * 8), w_mbad = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = room(nm * 4), w_repad = room(nm * 4);
-  const size_t w_mbox = room(nm * 24), w_btight = room(n_blas * 24), w_mcur = room(n_inst * 48);
-  std::memcpy(&work[w_pad], H.pad_abs.data(), nm * 4);
-  std::memcpy(&work[w_mbox], H.mesh_box.data(), nm * 24);
-  std::memcpy(&work[w_btight], H.blas_tight.data(), n_blas * 24);
-  for (size_t i = 0; i < n_inst; ++i) std::memcpy(&work[w_mcur + 48 * i], hs.inst[i].m, 48);      // (record i < n_inst is instance i; no move has been accepted yet)
-  if (upload(P.b_work, work)) return 1;
+  PlanImage img, work;                                                     // the constant arrays | what the kernels maintain
+  const size_t o_roff = img.put(H.range_off.data(), H.range_off.size() * 4), o_rng = img.put(H.ranges.data(), H.ranges.size() * 4), o_prox = img.put(H.proxy_rec.data(), H.proxy_rec.size() * 4);
+  const size_t o_imesh = img.put(H.inst_mesh.data(), H.inst_mesh.size() * 4), o_mbase = img.put(H.mesh_base.data(), H.mesh_base.size() * 4);
+  const size_t o_nmesh = img.put(H.node_mesh.data(), H.node_mesh.size() * 4), o_lev = img.put(H.tlas_levels.data(), H.tlas_levels.size() * 4);
+  const size_t o_blev = img.put(H.blas_levels.data(), H.blas_levels.size() * 4), o_idx = img.put(hs.mesh_idx.data(), hs.mesh_idx.size() * 4);
+  if (img.upload_to(P.b_plan)) return 1;
+  auto room = [&](size_t bytes) { return work.put(nullptr, bytes); };
+  const size_t w_state = room(kMoveStateWords * 8), w_need = room(nm * 8), w_mbad = room(nm * 8), w_tight = room(n_tlas * 24), w_box = room(n_entry * 24), w_ok = room(n_inst * 4), w_pad = work.put(H.pad_abs.data(), nm * 4), w_repad = room(nm * 4);
+  const size_t w_mbox = work.put(H.mesh_box.data(), nm * 24), w_btight = work.put(H.blas_tight.data(), n_blas * 24), w_mcur = room(n_inst * 48);
+  for (size_t i = 0; i < n_inst; ++i) std::memcpy(&work.img[w_mcur + 48 * i], hs.inst[i].m, 48);      // (record i < n_inst is instance i; no move has been accepted yet)
+  if (work.upload_to(P.b_work)) return 1;
   const char* pb = (const char*)P.b_plan.p; char* wb = (char*)P.b_work.p;
   MoveArgs& A = P.args;
   A = MoveArgs();
@@ -487,17 +492,126 @@ int export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) {
   return 0;
 }
 
-// ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
-// What one context has built and not yet committed; whatever is still here when the call leaves is freed, so a rebuild that fails
-// anywhere leaves every context's scene as it was.
-struct PendingTree {
-  int device = -1; GpuBvh g; DevBuf qtris;
-  DevBuf idx;                                  // the mesh's index triples where no refit plan held them (or, after the commit, the plan's)
-  ~PendingTree() {
-    if (device >= 0) (void)hipSetDevice(device);
-    free_tree(g);
-    qtris.release(); idx.release();
+// ---- replacing a tree: what art_rebuild_device, art_rebuild_instance_tree_device and art_rebuild_mesh_tree_device share -------------
+// The rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built.
+// qs: the caller's stream as device 0 names it.  Device 0 is current afterwards.
+static int quiesce(hipStream_t st, hipStream_t& qs) {
+  Ctx& c0 = g_devs[0];
+  qs = StreamOrder(c0, st).qs;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
   }
+  if (use_dev(0)) return 1;
+  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
+  return 0;
+}
+
+// What the last update of an instanced scene left in force on device 0 (no plan: the upload's placement and records, which it checked).
+// why: what that state denies the call, and what clears it.
+static int refuse_bad_state(const std::string& name, const char* why) {
+  const Ctx::MovePlan& P = g_devs[0].move;
+  if (!P.ready) return 0;
+  unsigned long long w[kMoveStateWords];
+  HIP_TRY(hipMemcpy(w, P.args.state, sizeof w, hipMemcpyDeviceToHost));
+  if (!w[1] && !w[7]) return 0;
+  return fail(name + ": " + std::to_string(w[1]) + " bad instance matrix(es) and " + std::to_string(w[7]) + " bad vertex coordinate(s) are in force, " + std::to_string(w[1] + w[7]) + " in all: " + why);
+}
+
+// a build's counter words, once s is idle
+template <int N>
+static int read_counters(hipStream_t s, const unsigned long long* bad, unsigned long long (&w)[N]) {
+  HIP_TRY(hipMemcpyAsync(w, bad, sizeof w, hipMemcpyDeviceToHost, s));
+  HIP_TRY(hipStreamSynchronize(s));
+  return 0;
+}
+
+// The current context's gather on stream s: the counter words zeroed, `launch` between a pair of c.rebuild_pairs, the words read back
+// (s is idle then) and the pair's time given to *gather_ms where the caller asks for it.  zeroed: a buffer the gather must find zeroed.
+template <int N, typename Launch>
+static int timed_gather(hipStream_t s, unsigned long long* bad, unsigned long long (&w)[N], float* gather_ms, Launch launch, const DevBuf* zeroed = nullptr) {
+  Ctx& c = g_ctx;
+  EventPairs::Timer timer;
+  HIP_TRY(hipMemsetAsync(bad, 0, sizeof w, s));
+  if (zeroed) HIP_TRY(hipMemsetAsync(zeroed->p, 0, zeroed->bytes, s));
+  HIP_TRY(c.rebuild_pairs.begin(timer, s));
+  launch();
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(timer.end());
+  if (read_counters(s, bad, w)) return 1;
+  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
+  return 0;
+}
+
+// the scratch of one context's build in HBM, released on every way out of it
+struct BuildScratch { DevBuf t9, bad, order, maps; ~BuildScratch() { t9.release(); bad.release(); order.release(); maps.release(); } };
+
+// What one context has built and not yet committed: the builder's tree and the N buffers a kind names.  Whatever is still here when the
+// call leaves is freed, so a rebuild that fails anywhere leaves every context's scene as it was.
+template <int N>
+struct Pending {
+  int device = -1; GpuBvh g; DevBuf buf[N];
+  Pending() = default;
+  Pending(const Pending&) = delete;
+  ~Pending() { if (device >= 0) (void)hipSetDevice(device); free_tree(g); for (DevBuf& b : buf) b.release(); }
+};
+
+// built buffers become the current context's: {mine, built} pairs
+static void take_built(std::initializer_list<std::pair<DevBuf*, DevBuf*>> pairs) {
+  for (const std::pair<DevBuf*, DevBuf*>& mb : pairs) { mb.first->release(); *mb.first = *mb.second; *mb.second = DevBuf(); }      // (owned by the context now)
+}
+
+// The driver of the three calls, after the kind's own refusals (t0: the call's first line).  Every context builds into new buffers
+// before any context's scene changes: every check and allocation comes before the first swap, and a failure before it leaves every
+// context as it was.  A failure after it means a lost device, the one case in which contexts may end up with different trees.
+//   prepare(k)                       nothing is built yet: what the kind refuses in force, and context k's plan
+//   build(k, s, pending, gather_ms)  context k's new tree on s (context 0: the caller's stream, and the gather time that is reported);
+//                                    returns with s idle and has touched nothing of the context's scene or plan
+//   fold()                           whatever else can fail without a lost device: context k's events and counters of the kind
+//   before_commit(first)             what the commits take from the host
+//   commit(pending)                  context k takes its tree.  No step allocates or waits for anything but its own copy; the one that
+//                                    can fail, the copy of the new header to d_scene, comes first, while the buffers are the old ones
+//   after(built, qs)                 the host's copies follow, and what the kind still enqueues on the new tree
+// Context k is current in prepare, build, fold and commit.  A call is counted once all of it has succeeded.
+template <typename P, typename Info, typename Prepare, typename Build, typename Fold, typename Before, typename Commit, typename After>
+static int run_rebuild(std::chrono::steady_clock::time_point t0, hipStream_t st, Info& info, Prepare prepare, Build build, Fold fold, Before before_commit, Commit commit, After after) {
+  Dev0Guard guard;
+  hipStream_t qs = nullptr;
+  if (use_dev(0) || quiesce(st, qs)) return 1;
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || prepare(k)) return 1; }
+  std::vector<P> built((size_t)g_ndev);
+  float gather_ms = 0.0f;
+  for (int k = 0; k < g_ndev; ++k) {
+    if (use_dev(k)) return 1;
+    built[(size_t)k].device = g_ctx.device;
+    if (build(k, k == 0 ? qs : g_ctx.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
+  }
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold()) return 1; }
+  // ---- commit: from here on the scene changes
+  before_commit(built[0]);
+  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || commit(built[(size_t)k])) return 1; }
+  if (after(built, qs)) return 1;
+  info.rebuilds += 1; info.gather_ms += gather_ms; info.build_ms += built[0].g.build_ms;
+  info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+  return 0;
+}
+
+// the rebuild counts: cumulative since the upload, kept on the host (no stream is waited for)
+template <typename Info>
+static int get_rebuild_counts(Info* out, const char* null_msg, const Info& info) { if (!out) return fail(null_msg); *out = info; return 0; }
+
+// what both rebuilds of an instanced scene prepare and fold
+static int prepare_instanced(int k, const HostScene& hs, const std::string& name, const char* why) {
+  double plan_ms = 0.0;                                                    // (no update has run yet: the plan's time is this call's host time)
+  return (k == 0 && refuse_bad_state(name, why)) || (!g_ctx.move.ready && build_move_plan(hs, name, plan_ms));
+}
+static int fold_instanced() { return fold_move() || fold_mesh_refit(); }
+
+// ---- a new tree from device-resident vertices (art_rebuild_device, art_rebuild.hip) -----------------------------------------------
+struct PendingTree : Pending<3> {
+  DevBuf& qtris() { return buf[0]; }
+  DevBuf& idx() { return buf[1]; }             // the mesh's index triples where no refit plan held them (or, after the commit, the plan's)
+  DevBuf& stage() { return buf[2]; }           // contexts k > 0: peer copy of pos (+ nrm)
 };
 
 // the current context's new tree on stream s, from positions in this context's device memory: gather, count the bad vertices, build,
@@ -505,35 +619,24 @@ struct PendingTree {
 static int rebuild_one(const HostScene& hs, const BvhBuildParams& bp, const float* pos, hipStream_t s, PendingTree& out, float* gather_ms) {
   Ctx& c = g_ctx;
   const int32_t n_prims = (int32_t)(hs.m_idx.size() / 3);
-  DevBuf t9, bad;
-  struct Free { DevBuf &a, &b; ~Free() { a.release(); b.release(); } } fr{t9, bad};
-  out.device = c.device;
+  BuildScratch sc;
   const int32_t* idx = (const int32_t*)c.refit.b_idx.p;                   // the refit plan keeps the index triples in HBM
-  if (!c.refit.ready || !idx) { if (upload(out.idx, hs.m_idx)) return 1; idx = (const int32_t*)out.idx.p; }
-  if (ensure(t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(bad, sizeof(unsigned long long))) return 1;
-  EventPairs::Timer timer;
+  if (!c.refit.ready || !idx) { if (upload(out.idx(), hs.m_idx)) return 1; idx = (const int32_t*)out.idx().p; }
+  if (ensure(sc.t9, (size_t)n_prims * 9 * sizeof(float)) || ensure(sc.bad, sizeof(unsigned long long))) return 1;
   GatherArgs G;
-  G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)t9.p; G.bad = (unsigned long long*)bad.p;
-  HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof(unsigned long long), s));
-  HIP_TRY(c.rebuild_pairs.begin(timer, s));
-  launch_gather_tri9(s, G);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(timer.end());
-  unsigned long long n_bad = 0;
-  HIP_TRY(hipMemcpyAsync(&n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
-  if (n_bad) return fail("art_rebuild_device: " + std::to_string(n_bad) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
+  G.pos3f = pos; G.idx = idx; G.nverts = hs.m_nverts; G.n_prims = n_prims; G.tri9 = (float*)sc.t9.p; G.bad = (unsigned long long*)sc.bad.p;
+  unsigned long long n_bad[1];
+  if (timed_gather(s, G.bad, n_bad, gather_ms, [&] { launch_gather_tri9(s, G); })) return 1;
+  if (n_bad[0]) return fail("art_rebuild_device: " + std::to_string(n_bad[0]) + " vertex coordinate(s) not finite or beyond 1e18 in magnitude; the tree was not rebuilt and the scene is unchanged");
   std::string err;
-  if (!build_bvh8_gpu((const float*)t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
+  if (!build_bvh8_gpu((const float*)sc.t9.p, n_prims, bp, s, out.g, err)) return fail("art_rebuild_device: GPU BVH build: " + err);
   if (check_tree_limits(bp.width, out.g.n_nodes, out.g.n_tris, true, true, out.g.qnodes != nullptr, out.g.max_stack)) return 1;
-  if (bp.width == 4 && pad_tri_records(out.qtris, out.g.tris, out.g.n_tris, s)) return 1;
+  if (bp.width == 4 && pad_tri_records(out.qtris(), out.g.tris, out.g.n_tris, s)) return 1;
   HIP_TRY(hipStreamSynchronize(s));
   return 0;
 }
 
-// The current context takes its new tree (its streams are idle, its refit events are folded).  The one step that can fail, the copy
-// of the new header to d_scene, comes first: when it does (a lost device), the context's buffers are still the old ones.
+// the current context takes its new tree (its streams are idle, its refit events are folded)
 static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
   Ctx& c = g_ctx;
   {
@@ -541,19 +644,17 @@ static int commit_tree(const BvhBuildParams& bp, PendingTree& t) {
     s.nodes = t.g.nodes; s.tris = t.g.tris; s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
     HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
   }
-  if (!t.idx.p) { t.idx = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
+  if (!t.idx().p) { t.idx() = c.refit.b_idx; c.refit.b_idx = DevBuf(); }     // (kept for the shading records)
   release_updates(c);                                                     // the next refit plans against the new tree
   c.opt.bvh_params = g_devs[0].opt.bvh_params;                                    // (the options as they stand; bp may name builder 3 in place of 0)
   adopt_tree(c, t.g, bp.width);
-  c.b_qtris.release();
-  c.b_qtris = t.qtris; t.qtris = DevBuf();                                // (owned by the context now)
+  take_built({{&c.b_qtris, &t.qtris()}});
   DevScene& s = c.scene;
   s.nodes = (const float*)c.b_nodes.p; s.tris = (const float*)c.b_tris.p;
   s.n_nodes = t.g.n_nodes; s.n_tris = t.g.n_tris; s.node_width = bp.width;
   return 0;
 }
 
-// Every context builds into new buffers before any context's scene changes.
 int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream_t st) {
   const auto t0 = std::chrono::steady_clock::now();
   if (check_mesh_update(kRebuildCall, pos, nverts)) return 1;
@@ -563,82 +664,56 @@ int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream
   if (bp.spatial_alpha >= 0.0f) return fail("art_rebuild_device: option bvh_spatial_splits is set; reference splitting exists in the host builder only (art_upload_scene builds that tree)");
   if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
   if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
   const size_t bytes = 12 * (size_t)nverts;
-  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;
-  const hipStream_t qs = StreamOrder(c0, st).qs;
-  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  }
-  if (use_dev(0)) return 1;
-  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
-  std::vector<PendingTree> built((size_t)g_ndev);
-  std::vector<DevBuf> stage((size_t)g_ndev);                              // contexts k > 0: peer copy of pos (+ nrm)
-  struct FreeStage { std::vector<DevBuf>& v; ~FreeStage() { for (size_t k = 0; k < v.size(); ++k) { if (v[k].p && g_devs[k].device >= 0) (void)hipSetDevice(g_devs[k].device); v[k].release(); } } } fs{stage};
-  float gather_ms = 0.0f;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    Ctx& c = g_ctx;
-    const float* p = pos;
-    if (k > 0) {
-      if (ensure(stage[(size_t)k], nrm ? 2 * bytes : bytes)) return 1;
-      float* sp = (float*)stage[(size_t)k].p;
-      if (hipMemcpyPeer(sp, c.device, pos, c0.device, bytes) != hipSuccess || (nrm && hipMemcpyPeer(sp + 3 * (size_t)nverts, c.device, nrm, c0.device, bytes) != hipSuccess))
-        return fail("art_rebuild_device: copy to device " + std::to_string(c.device) + " failed");
-      p = sp;
-    }
-    if (rebuild_one(hs, bp, p, k == 0 ? qs : c.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
-  }
-  // everything else that can fail without a lost device comes before the first swap: the refit events and counters of every context
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_refit()) return 1; }
-  // ---- commit: from here on the scene changes.  No step below allocates or waits for anything but its own launch; a failure here
-  // means the device is lost, and is the one case in which contexts may end up with different trees.
-  const double build_ms = built[0].g.build_ms;
-  const int32_t n_nodes = built[0].g.n_nodes, n_tris = built[0].g.n_tris, max_stack = built[0].g.max_stack;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k) || commit_tree(bp, built[(size_t)k])) return 1;
-    if (k > 0) continue;
-    hs.hdr.n_nodes = n_nodes; hs.hdr.n_tris = n_tris; hs.hdr.node_width = bp.width;
-    hs.bvh.width = bp.width; hs.bvh.n_nodes = n_nodes; hs.bvh.n_tris = n_tris; hs.bvh.max_stack = max_stack;
-    hs.bvh_build_ms = build_ms; hs.gpu_built = true; hs.refitted = false;
-    drop_stale_host_copies(hs);
-  }
-  for (int k = 0; k < g_ndev && nrm; ++k) {                               // the shading records: k_refit_tris' normals branch, no triangle records (n_recs = 0)
-    if (use_dev(k)) return 1;
-    Ctx& c = g_ctx;
-    const hipStream_t s = (k == 0) ? qs : c.stream;
-    const float* n = (k == 0) ? nrm : (const float*)stage[(size_t)k].p + 3 * (size_t)nverts;
-    RefitArgs A;
-    std::memset(&A, 0, sizeof A);
-    A.nrm3f = n; A.idx = (const int32_t*)built[(size_t)k].idx.p; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.m_shade = (float*)c.b_m_shade.p;
-    hs.m_shade_stale = true;                                              // (art_trace_rays reads the shading records on the host)
-    launch_refit_tris(s, A);
-    if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("art_rebuild_device: rewriting the shading records failed");
-  }
-  g_rebuild_info.rebuilds += 1; g_rebuild_info.gather_ms += gather_ms; g_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
-  g_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
+  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;      // (against g_ctx: context 0, which every call leaves current)
+  return run_rebuild<PendingTree>(t0, st, g_rebuild_info,
+      [](int) { return 0; },
+      [&](int k, hipStream_t s, PendingTree& t, float* gather_ms) {
+        const float* p = pos;
+        if (k > 0) {
+          const int dev = g_ctx.device;
+          if (ensure(t.stage(), nrm ? 2 * bytes : bytes)) return 1;
+          float* sp = (float*)t.stage().p;
+          if (hipMemcpyPeer(sp, dev, pos, c0.device, bytes) != hipSuccess || (nrm && hipMemcpyPeer(sp + 3 * (size_t)nverts, dev, nrm, c0.device, bytes) != hipSuccess))
+            return fail("art_rebuild_device: copy to device " + std::to_string(dev) + " failed");
+          p = sp;
+        }
+        return rebuild_one(hs, bp, p, s, t, gather_ms);
+      },
+      fold_refit,
+      [](const PendingTree&) {},
+      [&](PendingTree& t) { return commit_tree(bp, t); },
+      [&](std::vector<PendingTree>& built, hipStream_t qs) {
+        const GpuBvh& g = built[0].g;
+        hs.hdr.n_nodes = g.n_nodes; hs.hdr.n_tris = g.n_tris; hs.hdr.node_width = bp.width;
+        hs.bvh.width = bp.width; hs.bvh.n_nodes = g.n_nodes; hs.bvh.n_tris = g.n_tris; hs.bvh.max_stack = g.max_stack;
+        hs.bvh_build_ms = g.build_ms; hs.gpu_built = true; hs.refitted = false;
+        drop_stale_host_copies(hs);
+        for (int k = 0; k < g_ndev && nrm; ++k) {                         // the shading records: k_refit_tris' normals branch, no triangle records (n_recs = 0)
+          if (use_dev(k)) return 1;
+          Ctx& c = g_ctx;
+          const hipStream_t s = (k == 0) ? qs : c.stream;
+          const float* n = (k == 0) ? nrm : (const float*)built[(size_t)k].stage().p + 3 * (size_t)nverts;
+          RefitArgs A;
+          std::memset(&A, 0, sizeof A);
+          A.nrm3f = n; A.idx = (const int32_t*)built[(size_t)k].idx().p; A.n_prims = (int32_t)(hs.m_idx.size() / 3); A.m_shade = (float*)c.b_m_shade.p;
+          hs.m_shade_stale = true;                                        // (art_trace_rays reads the shading records on the host)
+          launch_refit_tris(s, A);
+          if (hipGetLastError() != hipSuccess || hipStreamSynchronize(s) != hipSuccess) return fail("art_rebuild_device: rewriting the shading records failed");
+        }
+        return 0;
+      });
 }
 
-int get_rebuild_info(ArtRebuildInfo* out) { if (!out) return fail("null ArtRebuildInfo"); *out = g_rebuild_info; return 0; }
+int get_rebuild_info(ArtRebuildInfo* out) { return get_rebuild_counts(out, "null ArtRebuildInfo", g_rebuild_info); }
 
 // ---- a new instance tree from the proxy records in HBM (art_rebuild_instance_tree_device, art_move.hip + art_sah.hip) ---------------
-// What one context has built and not yet committed; whatever is still here when the call leaves is freed (PendingTree's rule).
-struct PendingInstTree {
-  int device = -1; GpuBvh g;
-  DevBuf nodes, tris, qnodes, inst;            // the new instance tree's packets and proxy records, the new merged node array, the new instance table
-  DevBuf plan;                                 // the plan's parts that follow the instance tree (Ctx::MovePlan::b_tlas)
+struct PendingInstTree : Pending<5> {
+  DevBuf& nodes() { return buf[0]; } DevBuf& tris() { return buf[1]; } DevBuf& qnodes() { return buf[2]; } DevBuf& inst() { return buf[3]; }      // the new instance tree's packets and proxy records, the new merged node array, the new instance table
+  DevBuf& plan() { return buf[4]; }            // the plan's parts that follow the instance tree (Ctx::MovePlan::b_tlas)
   size_t o_lev = 0, o_prox = 0, o_mbase = 0, o_tight = 0;
   std::vector<int> level_off;
   int32_t n_tlas = 0, max_stack = 0;
-  ~PendingInstTree() {
-    if (device >= 0) (void)hipSetDevice(device);
-    free_tree(g);
-    nodes.release(); tris.release(); qnodes.release(); inst.release(); plan.release();
-  }
 };
 
 // The built tree's packets and records as read back (the builder's numbering; word 9 of a record = the index of its proxy in `order`),
@@ -666,31 +741,19 @@ static int rebuild_inst_one(const std::vector<int32_t>& order, hipStream_t s, Pe
   Ctx& c = g_ctx;
   const Ctx::MovePlan& P = c.move;
   const int32_t n_entry = P.args.n_entry, n_blas = P.args.n_blas_nodes, nm = P.args.n_mesh;
-  DevBuf t9, bad, d_order, d_maps;
-  struct Free { DevBuf &a, &b, &c, &d; ~Free() { a.release(); b.release(); c.release(); d.release(); } } fr{t9, bad, d_order, d_maps};
-  out.device = c.device;
-  if (upload(d_order, order) || ensure(t9, (size_t)n_entry * 9 * sizeof(float)) || ensure(bad, 2 * sizeof(unsigned long long))) return 1;
+  BuildScratch sc;
+  if (upload(sc.order, order) || ensure(sc.t9, (size_t)n_entry * 9 * sizeof(float)) || ensure(sc.bad, 2 * sizeof(unsigned long long))) return 1;
   InstRebuildArgs R;
   std::memset(&R, 0, sizeof R);
   R.n_entry = n_entry; R.n_blas_nodes = n_blas; R.n_tlas_old = P.n_tlas;
-  R.order = (const int32_t*)d_order.p; R.proxy_rec = P.args.proxy_rec; R.tlas_tris = P.args.tlas_tris;
-  R.tri9 = (float*)t9.p; R.bad = (unsigned long long*)bad.p;
-  unsigned long long n_bad[2] = {0ull, 0ull};
-  {
-    EventPairs::Timer timer;
-    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof n_bad, s));
-    HIP_TRY(c.rebuild_pairs.begin(timer, s));
-    launch_inst_gather(s, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(timer.end());
-  }
-  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
+  R.order = (const int32_t*)sc.order.p; R.proxy_rec = P.args.proxy_rec; R.tlas_tris = P.args.tlas_tris;
+  R.tri9 = (float*)sc.t9.p; R.bad = (unsigned long long*)sc.bad.p;
+  unsigned long long n_bad[2];
+  if (timed_gather(s, R.bad, n_bad, gather_ms, [&] { launch_inst_gather(s, R); })) return 1;
   if (n_bad[0]) return fail(name + ": " + std::to_string(n_bad[0]) + " entry point(s) without a finite world box; the tree was not rebuilt and the scene is unchanged");
   BvhBuildParams tp; tp.width = 4; tp.max_leaf = 1;                        // what build_two_level_host gives the instance tree
   std::string err;
-  if (!build_bvh_sah_gpu((const float*)t9.p, n_entry, tp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
+  if (!build_bvh_sah_gpu((const float*)sc.t9.p, n_entry, tp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
   const int32_t n_new = out.g.n_nodes;
   if (!out.g.qnodes || n_new < 1 || out.g.n_tris != n_entry) return fail(name + ": internal: the GPU build returned no instance tree");
   if (out.g.max_stack > kInstTopStack) return fail(name + ": instance tree stack bound " + std::to_string(out.g.max_stack) + " exceeds " + std::to_string(kInstTopStack));
@@ -702,43 +765,38 @@ static int rebuild_inst_one(const std::vector<int32_t>& order, hipStream_t s, Pe
   if (!plan_built_tree(h_nodes, h_tris, order, node_map, rec_map, levels, out.level_off, proxy_rec, err)) return fail(name + ": internal: " + err);
   HIP_TRY(hipMemcpy(mesh_base.data(), P.args.mesh_base, mesh_base.size() * 4, hipMemcpyDeviceToHost));
   for (int32_t m = 0; m < nm; ++m) mesh_base[3 * (size_t)m + 2] += n_new - P.n_tlas;                       // (first node in qnodes)
-  std::vector<uint8_t> img;                                                // every section 16-byte aligned
-  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (p && bytes) std::memcpy(&img[at], p, bytes); return at; };
-  out.o_lev = put(levels.data(), levels.size() * 4); out.o_prox = put(proxy_rec.data(), proxy_rec.size() * 4); out.o_mbase = put(mesh_base.data(), mesh_base.size() * 4);
-  out.o_tight = put(nullptr, (size_t)n_new * 24);                          // (scratch: every level writes a node's tight box before the level above reads it)
+  PlanImage img;
+  out.o_lev = img.put(levels.data(), levels.size() * 4); out.o_prox = img.put(proxy_rec.data(), proxy_rec.size() * 4); out.o_mbase = img.put(mesh_base.data(), mesh_base.size() * 4);
+  out.o_tight = img.put(nullptr, (size_t)n_new * 24);                      // (scratch: every level writes a node's tight box before the level above reads it)
   node_map.insert(node_map.end(), rec_map.begin(), rec_map.end());
-  if (upload(out.plan, img) || upload(d_maps, node_map)) return 1;
-  if (ensure(out.nodes, (size_t)n_new * 128) || ensure(out.tris, (size_t)n_entry * kTriBytes) || ensure(out.qnodes, ((size_t)n_new + (size_t)n_blas) * kQNodeBytes) ||
-      ensure(out.inst, (size_t)n_entry * sizeof(DevInstance))) return 1;
+  if (img.upload_to(out.plan()) || upload(sc.maps, node_map)) return 1;
+  if (ensure(out.nodes(), (size_t)n_new * 128) || ensure(out.tris(), (size_t)n_entry * kTriBytes) || ensure(out.qnodes(), ((size_t)n_new + (size_t)n_blas) * kQNodeBytes) ||
+      ensure(out.inst(), (size_t)n_entry * sizeof(DevInstance))) return 1;
   R.n_tlas_new = n_new;
   R.g_nodes = out.g.nodes; R.g_tris = out.g.tris; R.g_qnodes = (const QNode*)out.g.qnodes;
-  R.node_map = (const int32_t*)d_maps.p; R.rec_map = (const int32_t*)d_maps.p + n_new;
-  R.nodes_out = (float*)out.nodes.p; R.tris_out = (float*)out.tris.p;
-  R.qnodes_old = (const QNode*)c.b_qnodes.p; R.qnodes_out = (QNode*)out.qnodes.p;
-  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst.p;
+  R.node_map = (const int32_t*)sc.maps.p; R.rec_map = (const int32_t*)sc.maps.p + n_new;
+  R.nodes_out = (float*)out.nodes().p; R.tris_out = (float*)out.tris().p;
+  R.qnodes_old = (const QNode*)c.b_qnodes.p; R.qnodes_out = (QNode*)out.qnodes().p;
+  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst().p;
   launch_inst_finish(s, R);
   launch_inst_relocate(s, R);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if (read_counters(s, R.bad, n_bad)) return 1;
   if (n_bad[1]) return fail(name + ": internal: " + std::to_string(n_bad[1]) + " leaf(s) of the built instance tree refused");
   free_tree(out.g);                                                        // (the renumbered copy is the tree)
   out.n_tlas = n_new; out.max_stack = out.g.max_stack;
   return 0;
 }
 
-// The current context takes its new instance tree (its streams are idle, its move events are folded).  The one step that can fail, the
-// copy of the new header to d_scene, comes first (commit_tree's rule).
+// the current context takes its new instance tree (its streams are idle, its move events are folded)
 static int commit_inst_tree(const HostScene& hs, PendingInstTree& t) {
   Ctx& c = g_ctx;
   DevScene s = c.scene;
-  s.inst = (const DevInstance*)t.inst.p; s.tlas_nodes = (const float*)t.nodes.p; s.tlas_tris = (const float*)t.tris.p; s.n_nodes = t.n_tlas;
+  s.inst = (const DevInstance*)t.inst().p; s.tlas_nodes = (const float*)t.nodes().p; s.tlas_tris = (const float*)t.tris().p; s.n_nodes = t.n_tlas;
   HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
   c.scene = s;
   Ctx::MovePlan& P = c.move;
-  DevBuf* const mine[5] = {&c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_qnodes, &P.b_tlas};
-  DevBuf* const built[5] = {&t.inst, &t.nodes, &t.tris, &t.qnodes, &t.plan};
-  for (int k = 0; k < 5; ++k) { mine[k]->release(); *mine[k] = *built[k]; *built[k] = DevBuf(); }      // (owned by the context now)
+  take_built({{&c.b_inst, &t.inst()}, {&c.b_tlas_nodes, &t.nodes()}, {&c.b_tlas_tris, &t.tris()}, {&c.b_qnodes, &t.qnodes()}, {&P.b_tlas, &t.plan()}});
   const char* pb = (const char*)P.b_tlas.p;
   MoveArgs& A = P.args;
   A.inst = (DevInstance*)c.b_inst.p; A.tlas_nodes = (float*)c.b_tlas_nodes.p; A.tlas_tris = (float*)c.b_tlas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
@@ -749,7 +807,7 @@ static int commit_inst_tree(const HostScene& hs, PendingInstTree& t) {
   return 0;
 }
 
-// Every context builds into new buffers, from its own proxy records, before any context's scene changes.
+// every context builds from its own proxy records
 int rebuild_instance_tree_device(hipStream_t st) {
   const auto t0 = std::chrono::steady_clock::now();
   const std::string name = "art_rebuild_instance_tree_device";
@@ -766,64 +824,33 @@ int rebuild_instance_tree_device(hipStream_t st) {
     const TwoLevelHost::EntryPoint &x = hs.two.entry[(size_t)a], &y = hs.two.entry[(size_t)b];
     return x.inst < y.inst || (x.inst == y.inst && x.root_entry < y.root_entry);
   });
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  const hipStream_t qs = StreamOrder(c0, st).qs;
-  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  }
-  if (use_dev(0)) return 1;
-  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
-  if (c0.move.ready) {                                                     // what the last update left in force (no plan: the upload's placement, which it checked)
-    unsigned long long w[kMoveStateWords];
-    HIP_TRY(hipMemcpy(w, c0.move.args.state, sizeof w, hipMemcpyDeviceToHost));
-    if (w[1] || w[7])
-      return fail(name + ": " + std::to_string(w[1]) + " bad instance matrix(es) and " + std::to_string(w[7]) + " bad vertex coordinate(s) are in force, " + std::to_string(w[1] + w[7]) +
-                  " in all: their entry points have no box to build over; a good art_move_instances_device or art_refit_mesh_device clears that state");
-  }
-  double plan_ms = 0.0;                                                    // (no update has run yet: the plan's time is this call's host time)
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || (!g_ctx.move.ready && build_move_plan(hs, name, plan_ms))) return 1; }
-  std::vector<PendingInstTree> built((size_t)g_ndev);
-  float gather_ms = 0.0f;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (rebuild_inst_one(order, k == 0 ? qs : g_ctx.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
-  }
-  // everything else that can fail without a lost device comes before the first swap: the update events and counters of every context
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_move() || fold_mesh_refit()) return 1; }
-  // ---- commit: from here on the scene changes (rebuild_device's rule: a failure below means the device is lost)
-  const double build_ms = built[0].g.build_ms;
-  const int32_t n_new = built[0].n_tlas, max_stack = built[0].max_stack, shift = n_new - hs.two.tlas.n_nodes;
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || commit_inst_tree(hs, built[(size_t)k])) return 1; }
-  // the host's copies: the sizes follow; the tree's arrays in hs.two have been stale since the first update, the table's qroot words go stale now
-  hs.two.tlas.n_nodes = n_new; hs.two.tlas.max_stack = max_stack;
-  for (int32_t& b : hs.two.qnode_base) b += shift;
-  hs.hdr.n_nodes = n_new; hs.bvh.n_nodes += shift; hs.bvh.max_stack = std::max(max_stack + 3 + hs.two.blas_max_stack, 8);
-  hs.inst_stale = true;
-  g_inst_rebuild_info.rebuilds += 1; g_inst_rebuild_info.gather_ms += gather_ms; g_inst_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
-  g_inst_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
+  return run_rebuild<PendingInstTree>(t0, st, g_inst_rebuild_info,
+      [&](int k) { return prepare_instanced(k, hs, name, "their entry points have no box to build over; a good art_move_instances_device or art_refit_mesh_device clears that state"); },
+      [&](int, hipStream_t s, PendingInstTree& t, float* gather_ms) { return rebuild_inst_one(order, s, t, gather_ms); },
+      fold_instanced,
+      [](const PendingInstTree&) {},
+      [&](PendingInstTree& t) { return commit_inst_tree(hs, t); },
+      [&](std::vector<PendingInstTree>& built, hipStream_t) {
+        // the host's copies: the sizes follow; the tree's arrays in hs.two have been stale since the first update, the table's qroot words go stale now
+        const int32_t n_new = built[0].n_tlas, max_stack = built[0].max_stack, shift = n_new - hs.two.tlas.n_nodes;
+        hs.two.tlas.n_nodes = n_new; hs.two.tlas.max_stack = max_stack;
+        for (int32_t& b : hs.two.qnode_base) b += shift;
+        hs.hdr.n_nodes = n_new; hs.bvh.n_nodes += shift; hs.bvh.max_stack = std::max(max_stack + 3 + hs.two.blas_max_stack, 8);
+        hs.inst_stale = true;
+        return 0;
+      });
 }
 
-int get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { if (!out) return fail("null ArtInstanceRebuildInfo"); *out = g_inst_rebuild_info; return 0; }
+int get_instance_rebuild_info(ArtInstanceRebuildInfo* out) { return get_rebuild_counts(out, "null ArtInstanceRebuildInfo", g_inst_rebuild_info); }
 
 // ---- a new tree for one mesh from its triangle records in HBM (art_rebuild_mesh_tree_device, art_move.hip + art_sah.hip) -------------
-// What one context has built and not yet committed; whatever is still here when the call leaves is freed (PendingTree's rule).
-struct PendingMeshTree {
-  int device = -1; GpuBvh g;
-  DevBuf nodes, tris, qtris, qnodes, inst;     // the new blas_nodes, blas_tris and padded copy, the new merged node array, the new instance table
-  DevBuf plan;                                 // the plan's parts that follow the meshes' node layout (Ctx::MovePlan::b_blas)
+struct PendingMeshTree : Pending<6> {
+  DevBuf& nodes() { return buf[0]; } DevBuf& tris() { return buf[1]; } DevBuf& qtris() { return buf[2]; } DevBuf& qnodes() { return buf[3]; } DevBuf& inst() { return buf[4]; }      // the new blas_nodes, blas_tris and padded copy, the new merged node array, the new instance table
+  DevBuf& plan() { return buf[5]; }            // the plan's parts that follow the meshes' node layout (Ctx::MovePlan::b_blas)
   size_t o_mbase = 0, o_lev = 0, o_nmesh = 0, o_tight = 0;
   std::vector<int> level_off;                  // the new blas_level_off
   std::vector<int> mesh_level_first;           // per mesh, and one past the last: its levels in level_off
   int32_t n_blas = 0, max_stack = 0;
-  ~PendingMeshTree() {
-    if (device >= 0) (void)hipSetDevice(device);
-    free_tree(g);
-    nodes.release(); tris.release(); qtris.release(); qnodes.release(); inst.release(); plan.release();
-  }
 };
 
 // the current context's new tree of mesh `mesh` on stream s: gather, count the bad records, build, read back, check and renumber, finish,
@@ -834,9 +861,7 @@ static int rebuild_mesh_one(const HostScene& hs, int32_t mesh, hipStream_t s, Pe
   const Ctx::MovePlan& P = c.move;
   const Ctx::MovePlan::Mesh& M = P.meshes[(size_t)mesh];
   const int32_t nm = P.args.n_mesh, n_blas = P.args.n_blas_nodes, n_entry = P.args.n_entry, n_recs = M.n_recs;
-  DevBuf t9, bad, d_maps;
-  struct Free { DevBuf &a, &b, &c; ~Free() { a.release(); b.release(); c.release(); } } fr{t9, bad, d_maps};
-  out.device = c.device;
+  BuildScratch sc;
   std::vector<int32_t> mesh_base((size_t)3 * (size_t)nm), old_levels((size_t)n_blas);
   float pad = 0.0f;
   HIP_TRY(hipMemcpy(mesh_base.data(), P.args.mesh_base, mesh_base.size() * 4, hipMemcpyDeviceToHost));
@@ -851,26 +876,15 @@ static int rebuild_mesh_one(const HostScene& hs, int32_t mesh, hipStream_t s, Pe
   if (R.nb < 0 || R.n_old < 1 || R.nb + R.n_old > n_blas || R.tb != M.tri_base || R.qb != R.n_tlas + R.nb || n_recs != M.n_prims || c.b_blas_nodes.bytes != (size_t)n_blas * 128 ||
       c.b_qnodes.bytes != ((size_t)R.n_tlas + (size_t)n_blas) * kQNodeBytes || (size_t)(R.tb + n_recs) * kTriBytes > c.b_blas_tris.bytes)
     return fail(name + ": internal: the plan is not the layout in HBM");
-  if (ensure(t9, (size_t)n_recs * 9 * sizeof(float)) || ensure(bad, 2 * sizeof(unsigned long long))) return 1;
-  R.tris_old = (const float*)c.b_blas_tris.p; R.tri9 = (float*)t9.p; R.bad = (unsigned long long*)bad.p;
-  unsigned long long n_bad[2] = {0ull, 0ull};
-  {
-    EventPairs::Timer timer;
-    HIP_TRY(hipMemsetAsync(bad.p, 0, sizeof n_bad, s));
-    HIP_TRY(hipMemsetAsync(t9.p, 0, t9.bytes, s));                         // (an index named twice leaves a triangle unwritten: a defined input, which the checks below then refuse or not)
-    HIP_TRY(c.rebuild_pairs.begin(timer, s));
-    launch_mesh_gather(s, R);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(timer.end());
-  }
-  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
-  HIP_TRY(c.rebuild_pairs.fold(/*wait=*/true, [gather_ms](float ms, uint8_t) { if (gather_ms) *gather_ms = ms; }));      // (the last pair is this gather's)
+  if (ensure(sc.t9, (size_t)n_recs * 9 * sizeof(float)) || ensure(sc.bad, 2 * sizeof(unsigned long long))) return 1;
+  R.tris_old = (const float*)c.b_blas_tris.p; R.tri9 = (float*)sc.t9.p; R.bad = (unsigned long long*)sc.bad.p;
+  unsigned long long n_bad[2];
+  if (timed_gather(s, R.bad, n_bad, gather_ms, [&] { launch_mesh_gather(s, R); }, &sc.t9)) return 1;      // (t9 zeroed: an index named twice leaves a triangle unwritten, a defined input, which the checks below then refuse or not)
   if (n_bad[0]) return fail(name + ": " + std::to_string(n_bad[0]) + " triangle record(s) of mesh " + std::to_string(mesh) + " with an index out of range or a corner that is not finite; the tree was not rebuilt and the scene is unchanged");
   BvhBuildParams bp; bp.width = 4;                                         // what build_two_level_host gives a mesh of a one-sided build, at the pad in force
   bp.inflate_rel = hs.two.mesh_pad_rel; bp.inflate_abs = pad;
   std::string err;
-  if (!build_bvh_sah_gpu((const float*)t9.p, n_recs, bp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
+  if (!build_bvh_sah_gpu((const float*)sc.t9.p, n_recs, bp, s, out.g, err)) return fail(name + ": GPU BVH build: " + err);
   const int32_t n_new = out.g.n_nodes;
   if (!out.g.qnodes || n_new < 1 || out.g.n_tris != n_recs) return fail(name + ": internal: the GPU build returned no tree for the mesh");
   if (out.g.max_stack > kStackEntries) return fail(name + ": mesh tree stack bound " + std::to_string(out.g.max_stack) + " exceeds " + std::to_string(kStackEntries));
@@ -903,50 +917,46 @@ static int rebuild_mesh_one(const HostScene& hs, int32_t mesh, hipStream_t s, Pe
     out.mesh_level_first.push_back((int)out.level_off.size() - 1);
   }
   if ((int64_t)new_levels.size() != n_blas_new) return fail(name + ": internal: the plan's levels do not cover the meshes' nodes");
-  std::vector<uint8_t> img;                                                // every section 16-byte aligned
-  auto put = [&](const void* p, size_t bytes) { const size_t at = img.size(); img.resize(at + ((bytes + 15) & ~(size_t)15), 0); if (p && bytes) std::memcpy(&img[at], p, bytes); return at; };
-  out.o_mbase = put(mesh_base.data(), mesh_base.size() * 4); out.o_lev = put(new_levels.data(), new_levels.size() * 4);
-  out.o_nmesh = put(nullptr, (size_t)n_blas_new * 4); out.o_tight = put(nullptr, (size_t)n_blas_new * 24);      // (written by the finish, the relocation and the tight-box launches)
+  PlanImage img;
+  out.o_mbase = img.put(mesh_base.data(), mesh_base.size() * 4); out.o_lev = img.put(new_levels.data(), new_levels.size() * 4);
+  out.o_nmesh = img.put(nullptr, (size_t)n_blas_new * 4); out.o_tight = img.put(nullptr, (size_t)n_blas_new * 24);      // (written by the finish, the relocation and the tight-box launches)
   node_map.insert(node_map.end(), rec_map.begin(), rec_map.end());
-  if (upload(out.plan, img) || upload(d_maps, node_map)) return 1;
-  if (ensure(out.nodes, (size_t)n_blas_new * 128) || ensure(out.tris, c.b_blas_tris.bytes) || ensure(out.qtris, c.b_qtris.bytes) ||
-      ensure(out.qnodes, ((size_t)R.n_tlas + (size_t)n_blas_new) * kQNodeBytes) || ensure(out.inst, (size_t)n_entry * sizeof(DevInstance))) return 1;
-  char* pb = (char*)out.plan.p;
+  if (img.upload_to(out.plan()) || upload(sc.maps, node_map)) return 1;
+  if (ensure(out.nodes(), (size_t)n_blas_new * 128) || ensure(out.tris(), c.b_blas_tris.bytes) || ensure(out.qtris(), c.b_qtris.bytes) ||
+      ensure(out.qnodes(), ((size_t)R.n_tlas + (size_t)n_blas_new) * kQNodeBytes) || ensure(out.inst(), (size_t)n_entry * sizeof(DevInstance))) return 1;
+  char* pb = (char*)out.plan().p;
   R.g_nodes = out.g.nodes; R.g_tris = out.g.tris; R.g_qnodes = (const QNode*)out.g.qnodes;
-  R.node_map = (const int32_t*)d_maps.p; R.rec_map = (const int32_t*)d_maps.p + n_new;
-  R.nodes_out = (float*)out.nodes.p; R.tris_out = (float*)out.tris.p; R.qtris_out = (float*)out.qtris.p; R.qnodes_out = (QNode*)out.qnodes.p;
+  R.node_map = (const int32_t*)sc.maps.p; R.rec_map = (const int32_t*)sc.maps.p + n_new;
+  R.nodes_out = (float*)out.nodes().p; R.tris_out = (float*)out.tris().p; R.qtris_out = (float*)out.qtris().p; R.qnodes_out = (QNode*)out.qnodes().p;
   R.node_mesh_out = (int32_t*)(pb + out.o_nmesh); R.tight_out = (float*)(pb + out.o_tight);
   R.nodes_old = (const float*)c.b_blas_nodes.p; R.qnodes_old = (const QNode*)c.b_qnodes.p; R.node_mesh_old = P.args.node_mesh; R.tight_old = P.args.blas_tight;
-  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst.p; R.inst_mesh = P.args.inst_mesh;
+  R.inst_old = (const DevInstance*)c.b_inst.p; R.inst_out = (DevInstance*)out.inst().p; R.inst_mesh = P.args.inst_mesh;
   // record positions do not move: the other meshes' records and padded copies are plain copies, the finish then writes this mesh's slices
-  HIP_TRY(hipMemcpyAsync(out.tris.p, c.b_blas_tris.p, c.b_blas_tris.bytes, hipMemcpyDeviceToDevice, s));
-  HIP_TRY(hipMemcpyAsync(out.qtris.p, c.b_qtris.p, c.b_qtris.bytes, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(out.tris().p, c.b_blas_tris.p, c.b_blas_tris.bytes, hipMemcpyDeviceToDevice, s));
+  HIP_TRY(hipMemcpyAsync(out.qtris().p, c.b_qtris.p, c.b_qtris.bytes, hipMemcpyDeviceToDevice, s));
   launch_mesh_finish(s, R);
   launch_mesh_relocate(s, R);
   const int32_t* d_levels = (const int32_t*)(pb + out.o_lev);
   for (int L = out.mesh_level_first[(size_t)mesh + 1] - 1; L >= out.mesh_level_first[(size_t)mesh]; --L)      // deepest level first
     launch_mesh_tight_level(s, R, d_levels + out.level_off[(size_t)L], out.level_off[(size_t)L + 1] - out.level_off[(size_t)L]);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(n_bad, bad.p, sizeof n_bad, hipMemcpyDeviceToHost, s));
-  HIP_TRY(hipStreamSynchronize(s));
+  if (read_counters(s, R.bad, n_bad)) return 1;
   if (n_bad[1]) return fail(name + ": internal: " + std::to_string(n_bad[1]) + " leaf(s) of the built mesh tree refused");
   free_tree(out.g);                                                        // (the renumbered copy is the tree)
   out.n_blas = (int32_t)n_blas_new; out.max_stack = out.g.max_stack;
   return 0;
 }
 
-// The current context takes its mesh's new tree (its streams are idle, its update events are folded).  The one step that can fail, the
-// copy of the new header to d_scene, comes first (commit_tree's rule).  The plan keeps everything its kernels maintain in b_work.
+// The current context takes its mesh's new tree (its streams are idle, its update events are folded).  The plan keeps everything its
+// kernels maintain in b_work.
 static int commit_mesh_tree(PendingMeshTree& t, int tlas_stack, int blas_stack) {
   Ctx& c = g_ctx;
   DevScene s = c.scene;
-  s.inst = (const DevInstance*)t.inst.p; s.blas_nodes = (const float*)t.nodes.p; s.blas_tris = (const float*)t.tris.p;
+  s.inst = (const DevInstance*)t.inst().p; s.blas_nodes = (const float*)t.nodes().p; s.blas_tris = (const float*)t.tris().p;
   HIP_TRY(hipMemcpy(c.d_scene, &s, sizeof(DevScene), hipMemcpyHostToDevice));
   c.scene = s;
   Ctx::MovePlan& P = c.move;
-  DevBuf* const mine[6] = {&c.b_inst, &c.b_blas_nodes, &c.b_blas_tris, &c.b_qtris, &c.b_qnodes, &P.b_blas};
-  DevBuf* const built[6] = {&t.inst, &t.nodes, &t.tris, &t.qtris, &t.qnodes, &t.plan};
-  for (int k = 0; k < 6; ++k) { mine[k]->release(); *mine[k] = *built[k]; *built[k] = DevBuf(); }      // (owned by the context now)
+  take_built({{&c.b_inst, &t.inst()}, {&c.b_blas_nodes, &t.nodes()}, {&c.b_blas_tris, &t.tris()}, {&c.b_qtris, &t.qtris()}, {&c.b_qnodes, &t.qnodes()}, {&P.b_blas, &t.plan()}});
   const char* pb = (const char*)P.b_blas.p;
   MoveArgs& A = P.args;
   A.inst = (DevInstance*)c.b_inst.p; A.blas_nodes = (float*)c.b_blas_nodes.p; A.blas_tris = (const float*)c.b_blas_tris.p; A.qnodes = (QNode*)c.b_qnodes.p;
@@ -975,7 +985,7 @@ static int check_mesh_of_instanced(const std::string& name, int32_t mesh) {
   return 0;
 }
 
-// Every context builds into new buffers, from its own records, before any context's scene changes.
+// every context builds from its own records
 int rebuild_mesh_tree_device(int32_t mesh, hipStream_t st) {
   const auto t0 = std::chrono::steady_clock::now();
   const std::string name = "art_rebuild_mesh_tree_device";
@@ -988,52 +998,30 @@ int rebuild_mesh_tree_device(int32_t mesh, hipStream_t st) {
       return fail(name + ": instance " + std::to_string(E.inst) + " of mesh " + std::to_string(mesh) + " was opened by the build (option inst_open): its entry points name subtrees of the "
                   "tree in force, and opening it again would change the instance table and the instance tree; art_upload_scene rebuilds such a mesh");
   }
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  const hipStream_t qs = StreamOrder(c0, st).qs;
-  // the rebuild waits for the host anyway: what the library's streams and the caller's stream hold is done before anything is built
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    HIP_TRY(hipStreamSynchronize(g_ctx.stream));
-  }
-  if (use_dev(0)) return 1;
-  if (qs != c0.stream) HIP_TRY(hipStreamSynchronize(qs));
-  if (c0.move.ready) {                                                     // what the last update left in force (no plan: the upload's records, which it checked)
-    unsigned long long w[kMoveStateWords];
-    HIP_TRY(hipMemcpy(w, c0.move.args.state, sizeof w, hipMemcpyDeviceToHost));
-    if (w[1] || w[7])
-      return fail(name + ": " + std::to_string(w[1]) + " bad instance matrix(es) and " + std::to_string(w[7]) + " bad vertex coordinate(s) are in force, " + std::to_string(w[1] + w[7]) +
-                  " in all: their boxes are empty and the plan's boxes do not describe the records; a good art_move_instances_device or art_refit_mesh_device clears that state");
-  }
-  double plan_ms = 0.0;                                                    // (no update has run yet: the plan's time is this call's host time)
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || (!g_ctx.move.ready && build_move_plan(hs, name, plan_ms))) return 1; }
-  std::vector<PendingMeshTree> built((size_t)g_ndev);
-  float gather_ms = 0.0f;
-  for (int k = 0; k < g_ndev; ++k) {
-    if (use_dev(k)) return 1;
-    if (rebuild_mesh_one(hs, mesh, k == 0 ? qs : g_ctx.stream, built[(size_t)k], k == 0 ? &gather_ms : nullptr)) return 1;
-  }
-  // everything else that can fail without a lost device comes before the first swap: the update events and counters of every context
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || fold_move() || fold_mesh_refit()) return 1; }
-  // ---- commit: from here on the scene changes (rebuild_device's rule: a failure below means the device is lost)
-  const double build_ms = built[0].g.build_ms;
-  const int32_t n_blas_new = built[0].n_blas, n_blas_old = c0.move.args.n_blas_nodes, delta = n_blas_new - n_blas_old;
-  if (hs.two.mesh_max_stack.size() != hs.two.qnode_base.size()) hs.two.mesh_max_stack.assign(hs.two.qnode_base.size(), hs.two.blas_max_stack);
-  hs.two.mesh_max_stack[(size_t)mesh] = built[0].max_stack;
-  hs.two.blas_max_stack = *std::max_element(hs.two.mesh_max_stack.begin(), hs.two.mesh_max_stack.end());
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || commit_mesh_tree(built[(size_t)k], hs.two.tlas.max_stack, hs.two.blas_max_stack)) return 1; }
-  // the host's copies: the sizes follow; the trees' arrays in hs.two have been stale since the first update, the table's node_base and qroot words go stale now
-  for (size_t k = (size_t)mesh + 1; k < hs.two.qnode_base.size(); ++k) hs.two.qnode_base[k] += delta;
-  for (InstRec& r : hs.two.inst) if (r.mesh > mesh) r.node_base += delta;
-  hs.two.blas_nodes.resize((size_t)n_blas_new * 32, 0.0f); std::vector<uint32_t>().swap(hs.two.qnodes);
-  hs.bvh.n_nodes += delta; hs.bvh.max_stack = std::max(hs.two.tlas.max_stack + 3 + hs.two.blas_max_stack, 8);
-  hs.inst_stale = true;
-  g_mesh_rebuild_info.rebuilds += 1; g_mesh_rebuild_info.gather_ms += gather_ms; g_mesh_rebuild_info.build_ms += build_ms;      // (a failed call is not counted)
-  g_mesh_rebuild_info.host_ms += std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-  return 0;
+  int32_t delta = 0;                                                       // the meshes' nodes: new count less old
+  return run_rebuild<PendingMeshTree>(t0, st, g_mesh_rebuild_info,
+      [&](int k) { return prepare_instanced(k, hs, name, "their boxes are empty and the plan's boxes do not describe the records; a good art_move_instances_device or art_refit_mesh_device clears that state"); },
+      [&](int, hipStream_t s, PendingMeshTree& t, float* gather_ms) { return rebuild_mesh_one(hs, mesh, s, t, gather_ms); },
+      fold_instanced,
+      [&](const PendingMeshTree& first) {
+        delta = first.n_blas - c0.move.args.n_blas_nodes;
+        if (hs.two.mesh_max_stack.size() != hs.two.qnode_base.size()) hs.two.mesh_max_stack.assign(hs.two.qnode_base.size(), hs.two.blas_max_stack);
+        hs.two.mesh_max_stack[(size_t)mesh] = first.max_stack;
+        hs.two.blas_max_stack = *std::max_element(hs.two.mesh_max_stack.begin(), hs.two.mesh_max_stack.end());
+      },
+      [&](PendingMeshTree& t) { return commit_mesh_tree(t, hs.two.tlas.max_stack, hs.two.blas_max_stack); },
+      [&](std::vector<PendingMeshTree>& built, hipStream_t) {
+        // the host's copies: the sizes follow; the trees' arrays in hs.two have been stale since the first update, the table's node_base and qroot words go stale now
+        for (size_t k = (size_t)mesh + 1; k < hs.two.qnode_base.size(); ++k) hs.two.qnode_base[k] += delta;
+        for (InstRec& r : hs.two.inst) if (r.mesh > mesh) r.node_base += delta;
+        hs.two.blas_nodes.resize((size_t)built[0].n_blas * 32, 0.0f); std::vector<uint32_t>().swap(hs.two.qnodes);
+        hs.bvh.n_nodes += delta; hs.bvh.max_stack = std::max(hs.two.tlas.max_stack + 3 + hs.two.blas_max_stack, 8);
+        hs.inst_stale = true;
+        return 0;
+      });
 }
 
-int get_mesh_rebuild_info(ArtMeshRebuildInfo* out) { if (!out) return fail("null ArtMeshRebuildInfo"); *out = g_mesh_rebuild_info; return 0; }
+int get_mesh_rebuild_info(ArtMeshRebuildInfo* out) { return get_rebuild_counts(out, "null ArtMeshRebuildInfo", g_mesh_rebuild_info); }
 
 // the cost figure of a tree of device 0 as it lies in HBM (an update on another stream is ordered before the context stream's later work)
 static int tree_cost_of(Ctx& c, const float* nodes, int n_nodes, int width, ArtTreeCost* out) {
