@@ -4,9 +4,10 @@
 // rtcCommitScene (embree_connect.cpp:241-244) -- the 1.1-1.4 s the host build takes for 1M triangles become a few milliseconds --
 // and it builds THE SAME TREE: every quantity a split decision depends on is a minimum, a maximum or an integer count over the SET of
 // references of a node (boxes, centroid bounds, bin populations), evaluated with the host's binary32 expressions in the host's order,
-// so the decisions do not depend on the order in which the references are visited.  (Only the fallbacks for degenerate inputs differ:
-// a node whose centroids all coincide, or one deeper than max_sah_depth, is cut in the middle of its current reference order instead
-// of by an nth_element on (centroid, triangle id).)
+// so the decisions do not depend on the order in which the references are visited.  The fallback for degenerate inputs -- a node whose
+// centroids all coincide, or one deeper than max_sah_depth -- is the host's too: the count / 2 references that come first by (centroid
+// on the widest axis of the node's box, triangle id), art_bvh.cpp's nth_element.  k_eval finds the first key of the right half by
+// bisection over the 64 bits of (centroid, id) and the partition compares with it (pos_key), so this is a property of the SET as well.
 //
 // Level by level over the binary tree, one host round trip per level (the sizes of the next level):
 //   k_bin_big    nodes with more than kChunk references: one workgroup per chunk of kChunk references bins them in LDS (3 axes x NB bins x
@@ -69,7 +70,8 @@ struct S4Sum { __host__ __device__ S4 operator()(const S4& x, const S4& y) const
 enum { DEC_LEAF = 0, DEC_SAH = 1, DEC_POS = 2 };
 struct Dec {                                                     // what k_eval decided for an active node
   int kind, axis, bin, nl;
-  float cb_lo, scale; int pad0, pad1;                            // binning of the split axis (big nodes: read by the partition kernels)
+  float cb_lo, scale;                                            // binning of the split axis (big nodes: read by the partition kernels)
+  uint32_t thr_hi, thr_lo;                                       // DEC_POS: the smallest pos_key of the right half (axis = the widest axis of the node's box)
   int lbox[6], rbox[6], lcb[6], rcb[6];                          // small nodes: the children's boxes and centroid bounds (encoded)
 };
 
@@ -94,6 +96,12 @@ __device__ __forceinline__ int bin_of(float lo, float hi, float cb_lo, float sca
 }
 
 __device__ __forceinline__ float sel3(int a, float x, float y, float z) { return (a == 0) ? x : (a == 1) ? y : z; }
+// The order of art_bvh.cpp:219 as one integer: centroid on axis a first (-0 counts as +0, as in the host's float comparison), then the
+// triangle id.  Ids are unique inside a node, so keys are.
+__device__ __forceinline__ uint64_t pos_key(const float4 lo, const float4 hi, int a) {
+  const float c = (0.5f * sel3(a, lo.x, lo.y, lo.z) + 0.5f * sel3(a, hi.x, hi.y, hi.z)) + 0.0f;
+  return ((uint64_t)((uint32_t)enc(c) ^ 0x80000000u) << 32) | (uint64_t)(uint32_t)__float_as_int(lo.w);
+}
 __device__ __forceinline__ int wave_min_i(int v) { for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o)); return v; }
 __device__ __forceinline__ int wave_max_i(int v) { for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o)); return v; }
 __device__ __forceinline__ void wave_sync() {
@@ -236,11 +244,25 @@ __global__ __launch_bounds__(256) void k_eval(const Args A, int m) {
   int nl = 0;
   if (kind == DEC_SAH) nl = lc[best_axis * nb + best_bin - 1];
   else if (kind == DEC_POS) nl = count / 2;
-  const int ax = (kind == DEC_SAH) ? best_axis : 0;
+  int ax = (kind == DEC_SAH) ? best_axis : 0;
+  uint64_t thr = 0;
+  if (kind == DEC_POS) {
+    // art_bvh.cpp:214-219: the widest axis of the node's box, and the nl references that come first by (centroid, id).  thr = the largest
+    // K with #{key < K} <= nl, bit by bit: the key that has exactly nl keys below it.  64 passes over the node's references, here only.
+    const float bl[3] = {dec(b0.x), dec(b0.y), dec(b0.z)}, bh[3] = {dec(b1.x), dec(b1.y), dec(b1.z)};
+    for (int k = 1; k < 3; ++k) if (bh[k] - bl[k] > bh[ax] - bl[ax]) ax = k;
+    for (int bit = 63; bit >= 0; --bit) {
+      const uint64_t t = thr | (1ull << bit);
+      int below = 0;
+      for (int k = lane; k < count; k += 64) below += (pos_key(A.rlo_in[first + k], A.rhi_in[first + k], ax) < t) ? 1 : 0;
+      for (int o = 32; o > 0; o >>= 1) below += __shfl_xor(below, o);
+      if (below <= nl) thr = t;
+    }
+  }
   const float s_cbl = sel3(ax, cbl[0], cbl[1], cbl[2]), s_scale = sel3(ax, scale[0], scale[1], scale[2]);
 
   Dec d;
-  d.kind = kind; d.axis = ax; d.bin = best_bin; d.nl = nl; d.cb_lo = s_cbl; d.scale = s_scale; d.pad0 = d.pad1 = 0;
+  d.kind = kind; d.axis = ax; d.bin = best_bin; d.nl = nl; d.cb_lo = s_cbl; d.scale = s_scale; d.thr_hi = (uint32_t)(thr >> 32); d.thr_lo = (uint32_t)thr;
   for (int k = 0; k < 6; ++k) { d.lbox[k] = d.lcb[k] = d.rbox[k] = d.rcb[k] = (k < 3) ? kEncPosInf : kEncNegInf; }
   if (kind != DEC_LEAF && !big) {
     // stable partition into the other buffer; the children's boxes and centroid bounds on the way
@@ -253,7 +275,7 @@ __global__ __launch_bounds__(256) void k_eval(const Args A, int m) {
       float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
       if (valid) { lo = A.rlo_in[first + k]; hi = A.rhi_in[first + k]; }
       const float l[3] = {lo.x, lo.y, lo.z}, h[3] = {hi.x, hi.y, hi.z};
-      const bool left = (kind == DEC_SAH) ? (bin_of(sel3(ax, lo.x, lo.y, lo.z), sel3(ax, hi.x, hi.y, hi.z), s_cbl, s_scale, nb) < best_bin) : (k < nl);
+      const bool left = (kind == DEC_SAH) ? (bin_of(sel3(ax, lo.x, lo.y, lo.z), sel3(ax, hi.x, hi.y, hi.z), s_cbl, s_scale, nb) < best_bin) : (pos_key(lo, hi, ax) < thr);
       const uint64_t ml = __builtin_amdgcn_ballot_w64(valid && left), mr = __builtin_amdgcn_ballot_w64(valid && !left);
       const uint64_t below = (1ull << lane) - 1ull;
       if (valid) {
@@ -321,8 +343,8 @@ __global__ __launch_bounds__(256) void k_commit(const Args A, int m) {
 }
 
 // ---- big nodes: stable partition, chunk by chunk ---------------------------------------------------------------------------------
-__device__ __forceinline__ bool goes_left(const Dec& d, int nb, const float4 lo, const float4 hi, int k) {
-  if (d.kind != DEC_SAH) return k < d.nl;
+__device__ __forceinline__ bool goes_left(const Dec& d, int nb, const float4 lo, const float4 hi) {
+  if (d.kind != DEC_SAH) return pos_key(lo, hi, d.axis) < (((uint64_t)d.thr_hi << 32) | (uint64_t)d.thr_lo);
   const float l = (d.axis == 0) ? lo.x : (d.axis == 1) ? lo.y : lo.z, h = (d.axis == 0) ? hi.x : (d.axis == 1) ? hi.y : hi.z;
   return bin_of(l, h, d.cb_lo, d.scale, nb) < d.bin;
 }
@@ -338,7 +360,7 @@ __global__ __launch_bounds__(256) void k_part_count(const Args A) {
   int n = 0;
   for (int r = 0; r < kRounds; ++r) {
     const int k = cd.y * kChunk + r * 256 + (int)threadIdx.x;
-    if (k < count && goes_left(d, A.P.nb, A.rlo_in[first + k], A.rhi_in[first + k], k)) ++n;
+    if (k < count && goes_left(d, A.P.nb, A.rlo_in[first + k], A.rhi_in[first + k])) ++n;
   }
   for (int o = 32; o > 0; o >>= 1) n += __shfl_xor(n, o);
   if ((threadIdx.x & 63) == 0) atomicAdd(&s_n, n);
@@ -365,7 +387,7 @@ __global__ __launch_bounds__(256) void k_part_write(const Args A) {
     const bool valid = k < count;
     float4 lo = make_float4(0.f, 0.f, 0.f, 0.f), hi = lo;
     if (valid) { lo = A.rlo_in[first + k]; hi = A.rhi_in[first + k]; }
-    const bool left = valid && goes_left(d, A.P.nb, lo, hi, k);
+    const bool left = valid && goes_left(d, A.P.nb, lo, hi);
     const uint64_t ml = __builtin_amdgcn_ballot_w64(left), mr = __builtin_amdgcn_ballot_w64(valid && !left);
     __syncthreads();                                                               // the previous round's counts have been read
     if (lane == 0) { s_wl[wave] = (int)__popcll(ml); s_wr[wave] = (int)__popcll(mr); }
