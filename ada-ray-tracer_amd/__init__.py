@@ -392,6 +392,7 @@ class Backend:
         else:
             arr = (C.c_int32 * len(devices))(*devices)
             _check(self.lib.art_init_devices(len(devices), arr))
+        self._accum_tensor = None                     # the tensor bind_accum holds while it is bound
 
     def reduce(self):
         _check(self.lib.art_reduce())
@@ -407,6 +408,9 @@ class Backend:
         _check(self.lib.art_upload_scene(C.byref(desc)))
 
     def resize(self, width, height):
+        t = self._accum_tensor
+        if t is not None and t.numel() < 3 * width * height:
+            raise ArtError("resize: the bound accum tensor holds %d elements, a %d x %d frame needs %d" % (t.numel(), width, height, 3 * width * height))
         self.width, self.height = width, height
         _check(self.lib.art_resize(width, height))
 
@@ -449,8 +453,28 @@ class Backend:
         _check(self.lib.art_download(_fp(accum), _up(screen), layout, spp))
         return accum, screen
 
-    def bind_accum(self, device_ptr):
-        _check(self.lib.art_bind_accum(device_ptr))
+    def bind_accum(self, accum):
+        """Render into caller-owned device memory (art_bind_accum; the contract is in include/art_hip.h): row-major float3, zeroed by the
+        next resize, added to by every pass.  accum: None (back to the library's buffer), an integer device address (the caller keeps
+        the memory alive and large enough), or a contiguous float32 torch tensor on the library's GPU.  A tensor is checked before any
+        C call, held here until the next bind_accum so that it cannot be collected while bound, and resize() refuses a frame it is
+        too small for."""
+        held = None
+        if accum is not None and not isinstance(accum, int):
+            torch = sys.modules.get("torch")
+            if torch is None or not isinstance(accum, torch.Tensor):
+                raise ArtError("bind_accum: None, an integer device address or a torch tensor is required, not %s" % type(accum).__name__)
+            if accum.device.type != "cuda":
+                raise ArtError("bind_accum: must be a GPU tensor on the library's device, not on %s" % accum.device)
+            if accum.dtype != torch.float32:
+                raise ArtError("bind_accum: dtype must be torch.float32, not %s" % accum.dtype)
+            if not accum.is_contiguous():
+                raise ArtError("bind_accum: the tensor must be contiguous (the library writes row-major float3 from its first element on)")
+            if accum.numel() == 0:
+                raise ArtError("bind_accum: the tensor is empty")
+            held, accum = accum, accum.data_ptr()
+        _check(self.lib.art_bind_accum(accum))         # (a refused pointer keeps the previous binding, and the tensor held for it)
+        self._accum_tensor = held
 
     def synchronize(self):
         _check(self.lib.art_synchronize())
@@ -747,6 +771,7 @@ class Backend:
 
     def shutdown(self):
         self.lib.art_shutdown()
+        self._accum_tensor = None
 
 
 class RayTracer:

@@ -275,7 +275,24 @@ static int build_shard() {
   Ctx& c = g_ctx;
   const std::vector<uint32_t> pm = build_pixmap(c.width, c.height, c.rank, c.nranks, c.tile);
   c.npix_local = (int)pm.size();
-  return upload(c.b_pixmap, pm);
+  // Stream-ordered through a pinned copy, and b_pixmap only ever grows: art_resize and art_set_shard return without waiting for the
+  // stream.  (Freeing and allocating b_pixmap on every call, as upload() does, made both wait until EVERY stream of the device was idle
+  // -- hipFree does -- so a caller's work queued on the stream held the host up: tests/test_gpu_bound_accum.py, the stream test.)
+  // The list is read by the passes that follow on the same stream; a pass before it has been waited for by its own call.
+  if (pm.empty()) return 0;
+  const size_t bytes = pm.size() * sizeof(uint32_t);
+  if (c.pixmap_copied) HIP_TRY(hipEventSynchronize(c.pixmap_copied));      // (the pinned copy's previous upload: it is about to be overwritten)
+  else HIP_TRY(hipEventCreateWithFlags(&c.pixmap_copied, hipEventDisableTiming));
+  if (c.pixmap_host_bytes < bytes) {
+    if (c.pixmap_host) { (void)hipHostFree(c.pixmap_host); c.pixmap_host = nullptr; c.pixmap_host_bytes = 0; }
+    HIP_TRY(hipHostMalloc((void**)&c.pixmap_host, bytes, hipHostMallocDefault));
+    c.pixmap_host_bytes = bytes;
+  }
+  if (ensure(c.b_pixmap, bytes)) return 1;
+  std::memcpy(c.pixmap_host, pm.data(), bytes);
+  HIP_TRY(hipMemcpyAsync(c.b_pixmap.p, c.pixmap_host, bytes, hipMemcpyHostToDevice, c.stream));
+  HIP_TRY(hipEventRecord(c.pixmap_copied, c.stream));
+  return 0;
 }
 
 static int resize_one(int w, int h);
@@ -1111,6 +1128,8 @@ void shutdown() {
       for (void* p : {(void*)c.d_cursor, (void*)c.d_scene, (void*)c.d_counters, (void*)c.d_live, (void*)c.d_items}) if (p) (void)hipFree(p);
       c.stage_pairs.destroy(); c.pass_pairs.destroy(); c.rebuild_pairs.destroy();
       for (hipEvent_t e : c.q_ev) if (e) (void)hipEventDestroy(e);
+      if (c.pixmap_copied) (void)hipEventDestroy(c.pixmap_copied);
+      if (c.pixmap_host) (void)hipHostFree(c.pixmap_host);
       destroy_updates(c);
       for (Ctx::PassClock* pc : c.pass_clock) delete pc;      // (after hipDeviceSynchronize: no callback is pending)
       c.b_reduced.release();
@@ -1213,7 +1232,14 @@ int art_debug_hit_pass(const ArtPassParams* p, float* accum_host, uint32_t* scre
   return debug_pass(p, accum_host, screen_host, prim_index, mat_id, prim_type);
 }
 
-int art_bind_accum(void* device_accum_rowmajor) { std::lock_guard<std::mutex> lk(g_mu); SINGLE_DEVICE_ONLY("art_bind_accum"); g_ctx.ext_accum = (float*)device_accum_rowmajor; return 0; }
+int art_bind_accum(void* device_accum_rowmajor) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  SINGLE_DEVICE_ONLY("art_bind_accum");
+  // (the frame may not be known yet, so only the kind of memory and its device are checked: a refused pointer leaves the binding as it was)
+  if (device_accum_rowmajor && (ensure_device() || check_device_ptr(device_accum_rowmajor, 0, "art_bind_accum: device_accum_rowmajor"))) return 1;
+  g_ctx.ext_accum = (float*)device_accum_rowmajor;
+  return 0;
+}
 void* art_accum_device(void) {          // device 0; in multi-device mode the reduced framebuffer (valid after a reduce: art_reduce / art_download)
   std::lock_guard<std::mutex> lk(g_mu);
   return (g_ndev > 1) ? g_devs[0].b_reduced.p : (void*)accum_ptr();

@@ -126,6 +126,8 @@ struct Ctx {
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
   float* ext_accum = nullptr;
+  // the rank's pixel list on its way to b_pixmap (build_shard): a pinned copy, and the event behind its last stream-ordered upload
+  uint32_t* pixmap_host = nullptr; size_t pixmap_host_bytes = 0; hipEvent_t pixmap_copied = nullptr;
   // work distribution / counters
   int* d_cursor = nullptr;
   unsigned long long* d_counters = nullptr;   // kCounters words, named by enum Counter

@@ -174,7 +174,12 @@ typedef struct ArtReduceInfo {
   int32_t passes, passes_overlapped;
 } ArtReduceInfo;
 int  art_get_reduce_info(ArtReduceInfo* out);
-int  art_set_stream(void* hip_stream);                   /* hipStream_t; NULL = default stream */
+/* The stream every later call enqueues on (hipStream_t; NULL = the null stream): art_resize's clears, the whole of a render pass, the
+ * read-backs and the device-side updates.  The call itself enqueues nothing and waits for nothing, so work already queued on the stream
+ * being left is NOT ordered before work on the new one.  Only art_resize, art_set_shard and the device-side updates (refit, move, rebuild) leave any,
+ * since art_render_pass, art_debug_hit_pass and art_download wait at their end: a caller that switches streams after one of those calls
+ * art_synchronize first.  Work the CALLER queued on the stream before a library call runs before what that call enqueues. */
+int  art_set_stream(void* hip_stream);
 int  art_upload_scene(const ArtSceneDesc* scene);        /* Scene.Init: flatten + BVH build + copy to HBM */
 int  art_resize(int32_t width, int32_t height);          /* Resize_Viewport (ray_tracer.adb:297-320): zero accum, spp := 0 */
 int  art_set_shard(int32_t rank, int32_t nranks, int32_t tile);   /* pixel tiles (tile x tile) dealt along diagonals over the ranks */
@@ -187,8 +192,17 @@ int  art_render_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen
 int  art_debug_hit_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host,
                         int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 
-/* device-resident variants for the multi-GPU harness: accumulate into caller-owned HBM (row-major float3),
- * e.g. a buffer that is then reduced over xGMI with RCCL. */
+/* device-resident variants for the multi-GPU harness: accumulate into caller-owned HBM, e.g. a buffer that is then reduced over xGMI
+ * with RCCL.  The binding: the buffer is width*height float3, ROW-MAJOR (pixel (x, y) at floats 3*(y*width + x) ..) whatever p->layout
+ * says -- the layout only shapes what the host read-backs hand out.  It must be device memory of the library's device: anything else is
+ * refused ("... is not device memory"), nothing is launched and the previous binding stays.  It is not touched at bind time and its
+ * size cannot be checked then (the frame may come later): the caller keeps it at least width*height*12 bytes and alive until it is
+ * unbound.  art_resize zeroes its first width*height*12 bytes on the library's stream (art_set_stream); every art_render_pass adds its
+ * samples into the pixels this rank owns (art_set_shard) and leaves every other pixel as it is, i.e. +0.0f since the resize;
+ * art_debug_hit_pass WRITES the debug image into it; art_download and the host pointers of a pass read from it.  art_accum_device()
+ * returns it while it is bound, else the library's own buffer (multi-device mode: the reduced frame on device 0).
+ * NULL unbinds: the library's own buffer is used again -- it holds what it held before the binding, so call art_resize -- and the
+ * caller's buffer is never touched again. */
 int  art_bind_accum(void* device_accum_rowmajor);        /* NULL: back to the internal buffer */
 void* art_accum_device(void);
 int  art_download(float* accum_host, uint32_t* screen_host, int32_t layout, int32_t spp);

@@ -39,6 +39,14 @@ for name, devs in (("one", None), ("init_devices_1", [0]), ("three_contexts", [0
             be.set_shard(0, 2, 32); out[name + "_set_shard_refused"] = False
         except art.ArtError:
             out[name + "_set_shard_refused"] = True
+        try:
+            be.bind_accum(be.lib.art_accum_device()); out[name + "_bind_accum_refused"] = False      # (device memory: only the mode refuses it)
+        except art.ArtError:
+            out[name + "_bind_accum_refused"] = True
+        try:
+            be.set_stream(None); out[name + "_set_stream_refused"] = False
+        except art.ArtError:
+            out[name + "_set_stream_refused"] = True
     be.shutdown()
 ref, rspp, cnt = orc.render(conv.OracleScene(sd).scene, orc.make_params(100, 72, orc.PT_MIS, True, 8, 2, seed=5), passes=2)
 base = imgs["one"]
@@ -88,7 +96,9 @@ def test_n_contexts_in_one_process_give_the_single_device_image(art):
     assert out.pop("enqueue") == {"passes": 3, "overlapped": 3, "busy_positive": True, "idle_nonnegative": True, "one_device_never_idle": True,
                                   "skew_below_busy": True, "first_device_skew_zero": True}, ms
     assert out == {"oracle_equal": True, "one": True, "init_devices_1": True, "three_contexts": True, "eight_contexts": True,
-                   "three_contexts_set_shard_refused": True, "eight_contexts_set_shard_refused": True, "instanced_three_contexts": True}, out
+                   "three_contexts_set_shard_refused": True, "eight_contexts_set_shard_refused": True, "instanced_three_contexts": True,
+                   "three_contexts_bind_accum_refused": True, "eight_contexts_bind_accum_refused": True,
+                   "three_contexts_set_stream_refused": True, "eight_contexts_set_stream_refused": True}, out
 
 
 def test_rccl_calls_of_the_n_device_path_run_on_one_device(art):

@@ -326,7 +326,10 @@ def test_bench_scale_tree_is_sound_and_hits_equal_brute_force(art, backend, conf
 
 
 def test_pixel_tile_shards_sum_to_the_full_frame(art, backend, cornell):
-    """8(e): interleaved pixel tiles, one owner per pixel -> the sum over ranks is bit-identical to 1 GPU."""
+    """8(e): interleaved pixel tiles, one owner per pixel -> the sum over ranks is bit-identical to 1 GPU.  Per rank: exact zeros outside
+    the pixels the header's rule gives it (tests/pixmap_ref.py), the full frame's bits inside."""
+    import pixmap_ref
+    assert (3, 16, (96, 64)) in pixmap_ref.SHARD_CASES       # (tests/test_pixmap.py holds the reference to be a partition there)
     cs, sd = cornell
     backend.upload_scene(sd)
     p = art.Backend.pass_params(art.PT_MIS, True, 8, 1, seed=5)
@@ -338,7 +341,9 @@ def test_pixel_tile_shards_sum_to_the_full_frame(art, backend, cornell):
         backend.set_shard(r, 3, 16)
         backend.resize(96, 64)
         part, _, _ = backend.render_pass(p, 0)
-        assert np.count_nonzero(part.any(-1)) <= part.shape[0] * part.shape[1]
+        mask = pixmap_ref.owner_mask(96, 64, r, 3, 16)
+        assert mask.any() and not bits(part)[~mask].any(), "rank %d: a pixel it does not own is not 0x00000000" % r
+        assert np.array_equal(bits(part)[mask], bits(full)[mask]), "rank %d: its own pixels differ from the full frame's" % r
         total += part
     backend.set_shard(0, 1, 32)
     assert np.array_equal(bits(total), bits(full))
