@@ -112,6 +112,11 @@ class ArtAovBuffers(C.Structure):
                 ("prim_type", C.c_void_p), ("prim_index", C.c_void_p), ("mat", C.c_void_p)]
 
 
+class ArtDenoiseParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("normal_log2", C.c_int32), ("variant", C.c_int32), ("scale", C.c_float), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
+
+
 # Backend.render_aovs_torch: plane -> (field of ArtAovBuffers, floats or ints per pixel, integer plane)
 AOV_PLANES = collections.OrderedDict([("albedo", ("albedo3f", 3, False)), ("normal", ("normal3f", 3, False)), ("depth", ("depth", 1, False)),
                                       ("alpha", ("alpha", 1, False)), ("prim_type", ("prim_type", 1, True)), ("prim_index", ("prim_index", 1, True)),
@@ -199,7 +204,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_refit_device", "art_get_refit_info",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_rebuild_instance_tree_device", "art_get_instance_rebuild_info", "art_get_instance_tree_cost",
@@ -244,6 +249,7 @@ def load_library():
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
+    L.art_denoise_device.argtypes = [C.POINTER(ArtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -559,6 +565,48 @@ class Backend:
             setattr(buf, field, out[name].data_ptr() or None)
         stream = torch.cuda.current_stream(dev).cuda_stream
         _check(self.lib.art_render_aovs_device(C.byref(params), C.byref(buf), stream or HIP_STREAM_LEGACY))
+        return out
+
+    def denoise_torch(self, color, albedo=None, normal=None, depth=None, iterations=5, scale=1.0, sigma_color=4.0, sigma_depth=1.0,
+                      normal_log2=7, demodulate=True, out=None, variant=0, **other_planes):
+        """Edge-avoiding a-trous filter of `color` guided by the feature buffers (art_denoise_device; include/art_hip.h states the
+        arithmetic).  color, albedo, normal: float32 [H, W, 3]; depth: float32 [H, W]; all contiguous and on one GPU, the library's; a
+        guide that is None is not used.  Returns `out`, float32 [H, W, 3] on the same device (torch.empty when None; `out is color`
+        filters in place).  Enqueued on torch.cuda.current_stream() without waiting for it.  Every tensor is checked before any C
+        call.  A tensor bound with bind_accum is accepted as it is (scale = 1 / spp), and so is the dict of render_aovs_torch as
+        keyword arguments: its planes that the filter does not read (alpha, prim_type, prim_index, mat) are ignored.  The defaults
+        of iterations, the sigmas and normal_log2 are starting values taken from the literature (Dammertz et al. 2010, SVGF), not
+        tuned on this renderer."""
+        for name in other_planes:
+            if name not in AOV_PLANES:
+                raise TypeError("denoise_torch: unexpected keyword argument %r" % name)
+        torch = sys.modules.get("torch")
+        planes = (("color", color, 3), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3))
+        if torch is None or not isinstance(color, torch.Tensor):
+            raise ArtError("denoise_torch: color: a torch tensor is required, not %s" % type(color).__name__)
+        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
+            raise ArtError("denoise_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
+        h, w = int(color.shape[0]), int(color.shape[1])
+        for name, x, per in planes:
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise ArtError("denoise_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
+            if x.dtype != torch.float32:
+                raise ArtError("denoise_torch: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
+            if tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
+                raise ArtError("denoise_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
+            if not x.is_contiguous():
+                raise ArtError("denoise_torch: %s: the tensor must be contiguous" % name)
+            if x.device.type != "cuda" or x.device != color.device:
+                raise ArtError("denoise_torch: %s: must be a GPU tensor on %s, not on %s"
+                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=color.device)
+        p = ArtDenoiseParams(w, h, int(iterations), 1 if demodulate else 0, int(normal_log2), int(variant), float(scale), float(sigma_color), float(sigma_depth))
+        ptr = lambda x: None if x is None else x.data_ptr()
+        stream = torch.cuda.current_stream(color.device).cuda_stream
+        _check(self.lib.art_denoise_device(C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth), ptr(out), stream or HIP_STREAM_LEGACY))
         return out
 
     def _vertex_tensors(self, pos, nrm):

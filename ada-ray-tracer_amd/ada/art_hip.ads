@@ -154,6 +154,25 @@ package Art_Hip is
                                    hip_stream : System.Address) return int;
   pragma Import (C, art_render_aovs_device, "art_render_aovs_device");
 
+  --  Edge-avoiding a-trous denoiser over device planes (include/art_hip.h ArtDenoiseParams, 36 bytes, states the arithmetic): color3f,
+  --  albedo3f, normal3f (3 C floats per pixel) and depth (1) are DEVICE memory of the library's GPU, row-major; the three guides may be
+  --  Null_Address; out3f may be color3f.  Needs no scene and no viewport; hip_stream = Null_Address is the library's stream.
+  type Art_Denoise_Params is record
+    width, height : int;
+    iterations    : int;     --  1 .. 8
+    demodulate    : int;
+    normal_log2   : int;     --  0 .. 10
+    variant       : int;     --  0 .. 2
+    scale         : C_float;
+    sigma_color   : C_float;
+    sigma_depth   : C_float;
+  end record;
+  pragma Convention (C, Art_Denoise_Params);
+
+  function art_denoise_device (p : access constant Art_Denoise_Params; color3f, albedo3f, normal3f, depth, out3f : System.Address;
+                               hip_stream : System.Address) return int;
+  pragma Import (C, art_denoise_device, "art_denoise_device");
+
   --  Deforming mesh number `mesh` (an index into Art_Scene_Desc.meshes) of an uploaded instanced scene: pos3f / nrm3f are DEVICE memory
   --  of the library's GPU, 3 * nverts C floats in the vertex order of that mesh, object space; nrm3f = Null_Address keeps the normals;
   --  hip_stream = Null_Address is the library's stream.  Stream-ordered; the picture is the one of art_upload_scene with that mesh's

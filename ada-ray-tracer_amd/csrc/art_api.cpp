@@ -15,6 +15,7 @@
 
 #include <algorithm>
 #include <chrono>
+#include <cmath>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -1110,6 +1111,47 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
   return rc;
 }
 
+// art_denoise_device: the a-trous filter of art_denoise.h over the caller's planes, in a scratch of its own (b_denoise: two images, the
+// guide records and the depth gradients, 56 bytes per pixel) and the queries' stream order.  It needs no scene and no viewport and takes
+// no event pair: ArtStats and ArtStageStats do not see it.
+int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st) {
+  const std::string name = "art_denoise_device";
+  if (!p) return fail(name + ": null ArtDenoiseParams");
+  if (!color3f || !out3f) return fail(name + ": null color3f or out3f");
+  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return fail(name + ": width and height must be at least 1 and width * height at most 2^28");
+  if (p->iterations < 1 || p->iterations > 8) return fail(name + ": iterations must be 1 .. 8");
+  if (p->normal_log2 < 0 || p->normal_log2 > 10) return fail(name + ": normal_log2 must be 0 .. 10");
+  if (p->variant < 0 || p->variant > 2) return fail(name + ": variant must be 0 .. 2");
+  if (!std::isfinite(p->scale)) return fail(name + ": scale is not finite");
+  if (std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return fail(name + ": a sigma is NaN");
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)p->width * (size_t)p->height;
+  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || (albedo3f && check_device_ptr(albedo3f, 12 * N, "albedo3f")) ||
+      (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) || (depth && check_device_ptr(depth, 4 * N, "depth")))
+    return 1;
+  StreamOrder order(c, st);
+  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2));
+  if (c.b_denoise.bytes < bytes) {        // growing it may wait: nothing enqueued may still use the old scratch
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
+    if (ensure(c.b_denoise, bytes)) return 1;
+  }
+  if (order.enter()) return 1;
+  DenoiseArgs A; std::memset(&A, 0, sizeof A);
+  A.P.W = p->width; A.P.H = p->height; A.P.normal_log2 = p->normal_log2; A.P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
+  A.P.has_normal = normal3f ? 1 : 0; A.P.has_depth = depth ? 1 : 0;
+  A.P.scale = p->scale; A.P.sigma_color = p->sigma_color; A.P.sigma_depth = p->sigma_depth;
+  A.n = (int32_t)N; A.color = color3f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f;
+  dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
+  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N);
+  launch_denoise(order.qs, A, p->iterations);      // (variant: one kernel exists, every tap from global memory; 0, 1 and 2 all select it)
+  int rc = 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) { reset_reduce_info(); g_reduce_pairs.destroy(); }
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -1123,7 +1165,7 @@ void shutdown() {
       DevBuf* bufs[] = {&c.b_spheres, &c.b_sphere_mat, &c.b_lights, &c.b_materials, &c.b_bf_pos, &c.b_bf_nrm, &c.b_bf_uv, &c.b_bf_idx,
                         &c.b_nodes, &c.b_qnodes, &c.b_tris, &c.b_qtris, &c.b_m_shade, &c.b_accum, &c.b_screen, &c.b_stage,
                         &c.b_pixmap, &c.b_paths, &c.b_rays, &c.b_ids, &c.b_queue, &c.b_ovf,
-                        &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query};
+                        &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query, &c.b_denoise};
       for (DevBuf* b : bufs) b->release();
       for (void* p : {(void*)c.d_cursor, (void*)c.d_scene, (void*)c.d_counters, (void*)c.d_live, (void*)c.d_items}) if (p) (void)hipFree(p);
       c.stage_pairs.destroy(); c.pass_pairs.destroy(); c.rebuild_pairs.destroy();
@@ -1280,6 +1322,11 @@ int art_occluded_rays_device(const float* origins3f, const float* dirs3f, const 
 int art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return render_aovs(p, out, (hipStream_t)hip_stream);
+}
+
+int art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return denoise_device(p, color3f, albedo3f, normal3f, depth, out3f, (hipStream_t)hip_stream);
 }
 
 int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {

@@ -93,6 +93,7 @@ struct Ctx {
   DevBuf b_inst, b_tlas_nodes, b_tlas_tris, b_blas_nodes, b_blas_tris;      // instanced scene (DevScene::n_inst > 0)
   DevBuf b_accum, b_screen, b_stage, b_pixmap, b_paths, b_rays, b_ids, b_queue, b_ovf;
   DevBuf b_query;                              // device-resident ray queries: SoA rays + shadow minima + hit records of one slice, and a counter sink
+  DevBuf b_denoise;                            // art_denoise_device: its working images, guide records and depth gradients (art_denoise.h)
   hipEvent_t q_ev[2] = {nullptr, nullptr};     // ... their ordering with the context stream when they run on another stream (library -> query, query -> library)
   // art_refit_device (art_refit.hip): the plan is built on the first refit after an upload (the upload drops it); per context, because
   // the GPU builders may number the nodes differently on every device
@@ -205,6 +206,7 @@ int resize(int w, int h);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);
+int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st);
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);

@@ -4,6 +4,7 @@
 #include "art_shade.h"
 #include "art_qnode.h"
 #include "art_instanced.h"
+#include "art_denoise.h"
 
 namespace art {
 
@@ -107,6 +108,17 @@ struct AovArgs {
 };
 void launch_aov_raygen(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
 void launch_aov_resolve(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
+
+// art_denoise_device (art_denoise.hip, art_api.cpp denoise_device): the caller's planes (albedo / normal / depth nullptr: not given; out
+// may be color) and the library's scratch records of art_denoise.h, n = W * H of each
+struct DenoiseArgs {
+  dn::Params P;
+  int32_t n;
+  const float* color; const float* albedo; const float* normal; const float* depth;
+  float* out;
+  dn::Rec4* image[2]; dn::Rec4* guide; dn::Rec2* grad;
+};
+void launch_denoise(hipStream_t st, const DenoiseArgs& A, int iterations);      // the pack kernel and `iterations` filter launches
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex

@@ -263,6 +263,62 @@ typedef struct ArtAovBuffers {
 } ArtAovBuffers;
 int  art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream);
 
+/* Edge-avoiding a-trous wavelet denoiser (Dammertz et al. 2010, with the depth-gradient and normal-power edge stops of SVGF), guided by
+ * the feature buffers above.  Every pointer is device memory of the library's device (device 0 under
+ * art_init_devices), row-major, float3 / float per pixel: the layout of art_bind_accum and ArtAovBuffers.  albedo3f, normal3f and depth
+ * may each be NULL: that term is then 1, and without albedo there is no demodulation.  out3f may equal color3f (filtering in place); any
+ * other overlap is the caller's error.  The call needs an initialised device only, no scene and no viewport; width and height are the
+ * image's own.  It does not touch the accum buffer, spp, ArtStats, ArtStageStats, the path state or the queries' scratch: its scratch is
+ * its own (56 bytes per pixel).
+ * Stream-ordered exactly as art_render_aovs_device: NULL = the library's stream, hipStreamLegacy = the null stream; the call runs after
+ * everything the library has enqueued and before anything it enqueues later; the host waits only when the denoiser's scratch has to grow.
+ * Refused before anything is launched, with art_last_error set: null p, color3f or out3f; width or height < 1 or width * height > 2^28;
+ * iterations outside 1..8; normal_log2 outside 0..10; variant outside 0..2; a scale that is not finite; a sigma that is NaN; any given
+ * pointer that is host memory, another device's memory or too small for its plane.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_denoise.h is its one definition, compiled for the GPU and for the host).  All operations are
+ * binary32, not contracted, in the order written, except where binary64 is named; channel-wise where a colour is meant.  amax(a, b) =
+ * (a >= b) ? a : b.  z = depth, n = normal3f, W = width, H = height.
+ * Preparation, once per call and pixel:
+ *   c_0 = scale * color.   With demodulation (demodulate != 0 and albedo3f given): a = amax(albedo, 1e-3f), c_0 = c_0 / a.
+ *   gx = 0.5f * (z(x1, y) - z(x0, y)) with x1 = min(x + 1, W - 1), x0 = max(x - 1, 0); gy likewise in y.
+ *   A pixel is BAD IN COLOUR (at iteration i) when a channel of c_i is not finite; BAD IN GUIDES when a given normal component or its
+ *   given depth is not finite (albedo does not count).
+ * Iteration i = 0 .. iterations - 1, s = 1 << i, centre p = (x, y): acc = 0, wsum = 0; the taps (dx, dy) run with dy = -2..2 outer and
+ * dx = -2..2 inner, q = p + s * (dx, dy), and each tap that is not skipped adds, in that order,  acc += w * c_i(q);  wsum += w.
+ *   h = k[|dx|] * k[|dy|], k = {0.375f, 0.25f, 0.0625f}.
+ *   A tap is skipped when q is outside the image, bad in colour or bad in guides -- the centre tap (dx = dy = 0) too, so a centre that is
+ *   bad in colour or in guides does not count itself.  A centre tap that is not skipped has w = h, with no edge terms.  Every other tap:
+ *     wn = amax(dot(n_p, n_q), 0.0f), dot = (px * qx + py * qy) + pz * qz, then wn = wn * wn, normal_log2 times.  No normals: wn = 1.
+ *     xz = fabsf(z_p - z_q) / (sigma_depth * (fabsf(gx_p * (float)(s * dx)) + fabsf(gy_p * (float)(s * dy))) + (1e-3f * z_p + 1e-6f)).
+ *          No depth, or sigma_depth <= 0: xz = 0.
+ *     lum(c) = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  xc = fabsf(lum(c_i(p)) - lum(c_i(q))) / (sigma_color * 2^-i)  (2^-i exact).
+ *          xc = 0 when sigma_color <= 0 or the centre is bad in colour.
+ *     t = -((double)xz + (double)xc);   e = 0.0f when t < -200, else (float)exp_small(t) when t <= 0, else NaN (t is NaN -- a centre bad
+ *          in guides, a NaN gradient -- or positive, which only a negative depth can produce).
+ *     w = (h * wn) * e;  a w that is NaN skips the tap.
+ *     exp_small(t), binary64 throughout: v = t * 0x1.71547652b82fep+0; k = (int)(v + (v >= 0 ? 0.5 : -0.5)) (truncation);
+ *          r = (t - k * 0x1.62e42fee00000p-1) - k * 0x1.a39ef35793c76p-33; q = C13, then q = q * r + C_j for j = 12 .. 0 (Horner), with
+ *          C13 .. C0 = 0x1.6124613a86d09p-33, 0x1.1eed8eff8d898p-29, 0x1.ae64567f544e4p-26, 0x1.27e4fb7789f5cp-22, 0x1.71de3a556c734p-19,
+ *          0x1.a01a01a01a01ap-16, 0x1.a01a01a01a01ap-13, 0x1.6c16c16c16c17p-10, 0x1.1111111111111p-7, 0x1.5555555555555p-5,
+ *          0x1.5555555555555p-3, 0.5, 1.0, 1.0; the result is q * 2^k (csrc/art_math.h m1::exp_small).
+ *   c_{i+1}(p) = acc / wsum when wsum > 0, else c_i(p) unchanged (every tap was skipped: the pixel keeps its value, NaN included).
+ * After the last iteration: out = c * a with demodulation, else c.
+ * So a non-finite colour pixel is never read as a tap and is replaced by its neighbours' weighted mean in the first iteration that
+ * reaches a good one.  Quality is not part of the contract; the sigmas' useful range depends on the renderer's units. */
+typedef struct ArtDenoiseParams {
+  int32_t width, height;     /* the image's own size, row-major; independent of art_resize */
+  int32_t iterations;        /* 1..8; iteration i (from 0) uses tap spacing s = 1 << i */
+  int32_t demodulate;        /* 1 and albedo given: filter colour / max(albedo, 1e-3f), multiply back at the end */
+  int32_t normal_log2;       /* 0..10: normal weight = max(0, n_p . n_q) squared this many times (7 = power 128) */
+  int32_t variant;           /* 0 automatic, 1 direct loads, 2 LDS tile: tests and A/B only.  One kernel exists (direct loads): all three select it */
+  float   scale;             /* colour is multiplied by this first (1/spp for an accum buffer) */
+  float   sigma_color;       /* <= 0: no colour term */
+  float   sigma_depth;       /* <= 0: no depth term */
+} ArtDenoiseParams;
+int  art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth,
+                        float* out3f, void* hip_stream);
+
 /* Moving geometry.  Moves the vertices of the scene's ART_MESH_CLOSEST mesh and refits its tree in place: same
  * topology, same leaf order, new boxes (the builders' padding rule, quantised again at width 4), for every builder and both widths.
  * pos3f: device memory, 3*nverts floats, in the vertex order of the ArtMesh.pos uploaded; nrm3f: the same for normals, or NULL = keep
