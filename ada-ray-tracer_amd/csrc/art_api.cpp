@@ -7,6 +7,7 @@
 //            -> finish (inside-out radiance fold) -> accumulate (reference summation order)
 //   then resolve (gamma, clamp, pack) when the caller asks for the LDR image.
 //
+// The path state, the trace launch and that schedule itself: art_render.cpp (batch shape and shade trial: art_pass_plan.h).
 // The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_refit_mesh_device, art_rebuild_instance_tree_device, art_get_tree_cost): art_update.cpp.
 // There is no CPU fallback: every entry point that needs the GPU fails with art_last_error() set when
 // HIP reports no usable device.
@@ -37,7 +38,7 @@ static bool g_comms_ready = false;     // distinct GPUs: the framebuffer reduce 
 // events around every reduce on device 0's stream (art_get_reduce_info: the reduce's GPU time is part of the evidence of a multi-GPU run)
 static EventPairs g_reduce_pairs;     // (a host that downloads every frame re-uses one pair)
 static double g_reduce_ms = 0.0; static int g_reduces = 0, g_reduce_path = 0;
-static bool g_multi_api = false;       // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
+bool g_multi_api = false;              // the process came up through art_init_devices: passes carry host-clock marks (art_get_reduce_info), also with n = 1
 static int g_passes = 0, g_passes_overlapped = 0;  // multi-device passes folded so far / those in which every device had started before any had finished
 static void reset_reduce_info() {
   g_reduce_pairs.release(); g_reduce_ms = 0.0; g_reduces = 0; g_reduce_path = 0;
@@ -51,7 +52,7 @@ static double host_ms() {
   static const std::chrono::steady_clock::time_point t0 = std::chrono::steady_clock::now();
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
 }
-static void clock_cb(void* p) { *(double*)p = host_ms(); }
+void clock_cb(void* p) { *(double*)p = host_ms(); }
 // every device's passes (all idle) -> busy / idle / start skew per device.  Pass i of every device is one Render_Pass: idle = the slowest
 // device's end - this device's end (what an uneven tile deal costs), start skew = this device's start - the first device's start (what a
 // host that enqueues device after device costs), overlapped = every device had started before any had finished.
@@ -68,8 +69,7 @@ static void fold_pass_clocks() {
   for (int k = 0; k < g_ndev; ++k) { for (Ctx::PassClock* pc : g_devs[k].pass_clock) delete pc; g_devs[k].pass_clock.clear(); }
 }
 static bool g_same_gpu = false;        // rehearsal: several contexts on ONE physical GPU, the reduce is a local sum (no collective possible)
-static const bool g_debug_live = getenv("ART_DEBUG_LIVE") != nullptr;   // development aid: work-set sizes per stage on stderr (syncs the stream); read once
-static const bool g_debug_addr = getenv("ART_DEBUG_ADDR") != nullptr;   // development aid: device addresses of the path state per batch layout on stderr (profiles/r6_bimodal)
+const bool g_debug_addr = getenv("ART_DEBUG_ADDR") != nullptr;   // development aid: device addresses of the path state per batch layout on stderr (profiles/r6_bimodal)
 static thread_local std::string t_err;
 static std::string g_err;
 
@@ -101,7 +101,7 @@ void DevBuf::release() {
 // `bytes` of device memory as ONE address range over separately created physical chunks of `chunk` bytes (Options::paths_spread_mb: the driver
 // then maps the range in pieces no larger than a chunk, which is what the shade stage's forty streams want).  Every failure undoes what
 // was done and reports it; the caller falls back to hipMalloc.
-static hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, int fail_at = -1) {      // fail_at: test option spread_fail_at -- chunk number whose creation is made to fail
+hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, int fail_at) {      // fail_at: test option spread_fail_at -- chunk number whose creation is made to fail
   hipMemAllocationProp prop; std::memset(&prop, 0, sizeof prop);
   prop.type = hipMemAllocationTypePinned; prop.location.type = hipMemLocationTypeDevice; prop.location.id = device;
   size_t gran = 0;
@@ -265,14 +265,14 @@ int upload_scene(const ArtSceneDesc* d) {
     c.bvh_stack_bound = std::max(8, dev_stack);
     c.blocks_per_cu = 0;   // re-query occupancy
     c.scene_ready = true;
-    c.auto_phase = 0; c.auto_redo = 0; c.auto_gen += 1;  // a new scene: the shade stage measures its items-per-thread choice again
+    c.trial.reset();     // a new scene: the shade stage measures its items-per-thread choice again
   }
   g_devs[0].host_scene = std::move(hs);
   return 0;
 }
 
 // ------------------------------------------------------------------------------------------------
-static int build_shard() {
+int build_shard() {
   Ctx& c = g_ctx;
   const std::vector<uint32_t> pm = build_pixmap(c.width, c.height, c.rank, c.nranks, c.tile);
   c.npix_local = (int)pm.size();
@@ -296,15 +296,6 @@ static int build_shard() {
   return 0;
 }
 
-static int resize_one(int w, int h);
-int resize(int w, int h) {
-  if (w <= 0 || h <= 0 || (int64_t)w * h > (1ll << 30)) return fail("art_resize: bad size");
-  Dev0Guard guard;
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || resize_one(w, h)) return 1; }
-  for (int k = 0; k < g_ndev; ++k) { Ctx& c = g_devs[k]; c.busy_ms = c.idle_ms = c.start_skew_ms = 0.0; for (Ctx::PassClock* pc : c.pass_clock) delete pc; c.pass_clock.clear(); }
-  if (g_devs[0].device_ready && !use_dev(0)) reset_reduce_info();
-  return 0;
-}
 static int resize_one(int w, int h) {
   Ctx& c = g_ctx;
   if (ensure_device()) return 1;
@@ -317,172 +308,18 @@ static int resize_one(int w, int h) {
   c.spp = 0;
   c.stats = ArtStats();
   c.stage = ArtStageStats();
-  c.auto_phase = 0; c.auto_redo = 0; c.auto_gen += 1;    // (the batch size follows the frame: measure again)
+  c.trial.reset();                                       // (the batch size follows the frame: measure again)
   c.lost_reported = 0;                                   // (the device counters are zeroed below)
   if (c.d_items) HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream));
   c.camera_traced = 0;
   HIP_TRY(hipMemsetAsync(c.d_counters, 0, kCounters * sizeof(unsigned long long), c.stream));
   return build_shard();
 }
-
-static float* accum_ptr() { return g_ctx.ext_accum ? g_ctx.ext_accum : (float*)g_ctx.b_accum.p; }
-static int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host, int layout, int spp);
-
-// Path arrays for P slots and `depth` fold levels, carved out of one allocation.  Hot state exists in TWO banks: every bounce reads one
-// and writes the survivors densely into the other (k_shade_compact); cold state (fold stack, terminal value, per-sample radiance, final
-// flags) is indexed by slot.  Hot state per item, record layout (round 3, the cooperative schedule): the trace records of its two rays
-// (2 x 64 B; the next stage reads the extension ray from there), their hit records (2 x 16 B), prev pdf, flags, shadow epsilon, pending
-// explicit colour, item -> slot map, and the extension ray once more as six SoA words for the next stage: 21 words per bank + 32 words of
-// records in one array shared by the banks.  Plain layout (one-ray-per-lane schedule, debug pass): rays as SoA arrays, 29 words.
-constexpr size_t kRecSlack = 4096;       // records past the last one the trace kernel's chunk prefetch may touch
-// (record schedule: 6 ray words, ONE 16-byte hit record + the shadow ray's result word, 7 per-path words)
-static size_t hot_stride(size_t P) { return (P + 63) & ~(size_t)63; }
-static size_t hot_floats(size_t P, bool rec) { return rec ? (size_t)kHotFields * hot_stride(P) + 64 : (14 + 8 + 7) * P; }
-// (the trace records are not double-banked: a bank's records are dead once its rays are traced, and the next stage reads none of them)
-// cold state: e (depth + 1 levels: dense fold records keep e_k at level k + 1) and w (depth levels) x 3, child (depth levels), term, rad, final flags
-static size_t path_floats(size_t P, int depth, bool rec) { return 2 * hot_floats(P, rec) + (rec ? 32 * P + kRecSlack * 16 + 16 : 0) + (7 * (size_t)depth + 3 + 3 + 3 + 1) * P + 64; }
-
-// Every release of the path state goes through here.  hipFree waits for the device, but unmapping a spread path state (alloc_spread) does
-// not, and work queued on the context's stream may still use it.
-static void release_paths(Ctx& c) {
-  if (c.b_paths.reserved) (void)hipStreamSynchronize(c.stream);
-  c.b_paths.release();
-}
-static int ensure_paths(size_t P, int depth, bool rec) {
-  const size_t bytes = path_floats(P, depth, rec) * 4 + 256;
-  if (g_ctx.b_paths.bytes < bytes) release_paths(g_ctx);
-  return ensure(g_ctx.b_paths, bytes);
-}
-
-// q[0], q[1]: the two banks (slot_id = their own map); both share the cold arrays.  An identity-layout user takes q[0] with slot_id = nullptr
-// and final_flags = flags.
-static void carve(DevPaths q[2], int P, int depth, bool rec) {
-  float* const f0 = (float*)g_ctx.b_paths.p;
-  float* f = f0; const size_t p = (size_t)P;
-  auto take = [&](size_t n) { float* r = f; f += n; return r; };
-  auto align = [&](size_t floats) { f += (floats - ((size_t)(f - f0) & (floats - 1))) & (floats - 1); };
-  Rec4* records = nullptr;
-  if (rec) { align(16); records = (Rec4*)take(32 * p + kRecSlack * 16); }       // 64-byte records, ONE array for both banks
-  for (int k = 0; k < 2; ++k) {
-    DevPaths& b = q[k];
-    if (rec) {
-      // the bank as ONE block (art_scene.h HotField); the pointer fields name its pieces for the kernels that take them one by one
-      b.rec = records;
-      align(64);
-      const size_t st = hot_stride(p);
-      float* const h = take((size_t)kHotFields * st);
-      b.hot = h; b.stride = (int32_t)st;
-      b.ray_ox = h + HF_OX * st; b.ray_oy = h + HF_OY * st; b.ray_oz = h + HF_OZ * st; b.ray_dx = h + HF_DX * st; b.ray_dy = h + HF_DY * st; b.ray_dz = h + HF_DZ * st;
-      b.ray_tfar = nullptr;
-      b.hit = (DevHit*)(h + HF_HIT * st); b.sh_t = h + HF_SHT * st;
-      b.prev_pdf = h + HF_PDF * st; b.flags = (uint32_t*)(h + HF_FLAGS * st); b.sh_min_t = h + HF_SHMIN * st; b.slot_id = (const uint32_t*)(h + HF_SLOT * st);
-      b.cand_r = b.cand_g = b.cand_b = nullptr;                                 // (dense fold records: the pending colour has no hot words)
-      b.shadow_rule = g_ctx.opt.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
-      continue;
-    } else {
-      b.hot = nullptr; b.stride = 0;
-      b.rec = nullptr; b.rec_mode = REC_NONE;
-      b.ray_ox = take(2 * p); b.ray_oy = take(2 * p); b.ray_oz = take(2 * p);
-      b.ray_dx = take(2 * p); b.ray_dy = take(2 * p); b.ray_dz = take(2 * p); b.ray_tfar = take(2 * p);
-    }
-    align(4);                                                                   // 16-byte hit records
-    b.hit = (DevHit*)take(8 * p); b.sh_t = nullptr;
-    b.prev_pdf = take(p); b.flags = (uint32_t*)take(p); b.sh_min_t = take(p);
-    b.cand_r = take(p); b.cand_g = take(p); b.cand_b = take(p);
-    b.slot_id = (const uint32_t*)take(p);
-    b.shadow_rule = g_ctx.opt.shadow_anyhit ? 1 : 0; b.has_bvh = g_ctx.scene.n_tris > 0 ? 1 : 0;
-  }
-  DevPaths& a = q[0];
-  a.e_r = take((depth + 1) * p); a.e_g = take((depth + 1) * p); a.e_b = take((depth + 1) * p);
-  a.w_r = take(depth * p); a.w_g = take(depth * p); a.w_b = take(depth * p);
-  a.child = (int32_t*)take(depth * p);
-  a.cold = rec ? a.e_r : nullptr; a.depth = depth;       // (the seven takes above are consecutive: ONE block, art_scene.h DevPaths::cold)
-  a.fold_dense = rec ? 1 : 0;                   // the compacted (record) schedule keeps dense fold records; the plain one folds by slot
-  a.synth0 = rec ? 1 : 0;                       // ... and lets bounce 0 recompute the camera ray instead of reading it back (nothing else reads raygen's bank)
-  a.term_r = take(p); a.term_g = take(p); a.term_b = take(p);
-  a.rad_r = take(p); a.rad_g = take(p); a.rad_b = take(p);
-  a.final_flags = (uint32_t*)take(p);
-  DevPaths& c = q[1];
-  c.e_r = a.e_r; c.e_g = a.e_g; c.e_b = a.e_b; c.w_r = a.w_r; c.w_g = a.w_g; c.w_b = a.w_b;
-  c.term_r = a.term_r; c.term_g = a.term_g; c.term_b = a.term_b; c.rad_r = a.rad_r; c.rad_g = a.rad_g; c.rad_b = a.rad_b;
-  c.final_flags = a.final_flags; c.child = a.child; c.fold_dense = a.fold_dense; c.synth0 = a.synth0; c.cold = a.cold; c.depth = a.depth;
-}
-
-// LDS stack per ray: the tree's worst-case bound if 8 workgroups per CU (8 waves per SIMD) still fit in the CU's 160 KB, else the
-// largest size that does; then pushes are checked and the few rays that go deeper are finished by k_trace_overflow.
-static void stack_plan(int& entries, bool& overflow) {
-  Ctx& c = g_ctx;
-  const int per_block = c.lds_per_cu / 8, groups = 64 / c.scene.node_width;        // 8 workgroups of 4 waves per CU = 8 waves per SIMD
-  int cap = per_block / (4 * groups * 8) - 3;     // entries per ray (+ 2 guard entries + the sink of masked pushes)
-  if (c.opt.lds_stack_cap > 0) cap = c.opt.lds_stack_cap;
-  cap = std::min(cap, 64 * 1024 / (4 * groups * 8) - 3);      // one workgroup's dynamic LDS stays within the 64 KB a launch may ask for by default
-  entries = std::min(c.bvh_stack_bound, cap);
-  overflow = c.bvh_stack_bound > entries;
-}
-
-static int coop_grid() {
-  Ctx& c = g_ctx;
-  int entries; bool ovf; stack_plan(entries, ovf);
-  if (c.opt.opt_blocks_per_cu > 0) return c.num_cus * c.opt.opt_blocks_per_cu;
-  return c.num_cus * trace_coop_blocks_per_cu(entries, c.scene.node_width);
-}
-
-static void fill_trace_args(TraceArgs& a, const DevPaths& q, int n_rays) {
-  Ctx& c = g_ctx;
-  a.n_rays = n_rays; a.width = c.scene.node_width; a.instanced = c.scene.n_inst > 0 ? (c.opt.inst_coop ? 1 : 2) : 0;
-  a.inst = c.scene.inst; a.inst_shift = c.scene.inst_shift;
-  { int e; bool o; stack_plan(e, o); a.stack_entries = e; a.stack_overflow = o ? 1 : 0; }
-  a.node_min = c.opt.node_min ? c.opt.node_min : (c.scene.n_inst > 0 ? 2 : 4); a.refill_min = c.opt.refill_min; a.segments = c.opt.queue_segments; a.chunk = c.opt.ray_chunk;
-  a.ray_ox = q.ray_ox; a.ray_oy = q.ray_oy; a.ray_oz = q.ray_oz; a.ray_dx = q.ray_dx; a.ray_dy = q.ray_dy; a.ray_dz = q.ray_dz; a.ray_tfar = q.ray_tfar;
-  a.hit = q.hit; a.sh_t = q.sh_t;
-  a.nodes = c.scene.nodes; a.qnodes = (const uint32_t*)c.b_qnodes.p; a.tris = c.scene.tris; a.qtris = (const float*)c.b_qtris.p; a.n_tris = c.scene.n_tris;
-  a.sh_min = (c.opt.shadow_anyhit && q.sh_min_t && n_rays > q.P) ? q.sh_min_t : nullptr; a.shadow_begin = q.P;
-  a.cursor = c.d_cursor; a.stats = c.d_counters + CNT_STATS; a.live_rays = c.d_counters + CNT_RAYS;
-  a.queue = (int*)c.b_queue.p; a.queue_count = c.d_cursor + 1;
-  a.rec = (float4*)c.b_queue.p;
-  a.ovf_queue = (int*)c.b_ovf.p; a.ovf_count = c.d_cursor + 2;
-  a.item_count = nullptr;
-  a.queue_fixed = -1; a.queue_items = nullptr; a.queue_mul = 1;
-}
-
-// One trace launch.  records != nullptr: the bank's rays are already trace records in item order (DevPaths::rec, written by the stage
-// that emitted them): no k_analytic pass, the queue is the record array itself.
-struct RecordQueue { int fixed; const int* items; int mul; };
-// What a trace launch runs on and with.  The render passes and the debug pass take the first three from the context (pass_launch); the
-// ray queries name their own, so nothing ever has to change the context for the length of a call.
-struct TraceLaunch {
-  hipStream_t stream; int kernel; bool count_tests;      // kernel: TRACE_COOP or TRACE_SIMPLE
-  bool timed = true;                                     // an event pair (tag 0) around the trace kernel
-  const int* item_count = nullptr;
-  const RecordQueue* records = nullptr;
-  unsigned long long* live_rays = nullptr;               // where the launch counts the rays it issued (nullptr: d_counters[CNT_RAYS], ArtStats::rays)
-};
-static TraceLaunch pass_launch() { const Ctx& c = g_ctx; return {c.stream, c.opt.trace_kernel, c.opt.count_tests}; }
-// the tag of a stage_pairs pair.  trial: 1 / 2 = a shade launch of the items-per-thread trial A / B (Options::opt_shade_per)
-static uint8_t ev_tag(int kind, int trial = 0) { return (uint8_t)(kind | (trial << 4) | (trial ? (g_ctx.auto_gen & 3) << 6 : 0)); }
-
-static int trace(const DevPaths& q, int n_rays, const TraceLaunch& t) {
-  Ctx& c = g_ctx;
-  const bool coop = (t.kernel == TRACE_COOP);
-  if ((int64_t)n_rays > (1ll << 28)) return fail("internal: more than 2^28 rays in one trace launch (32-bit byte offsets of the 16-byte hit records)");
-  if (t.records && !coop) return fail("internal: trace records without the cooperative kernel");
-  if (coop && !t.records && ensure(c.b_queue, ((size_t)n_rays + kRecSlack) * kTraceRecBytes)) return 1;      // live-ray queue: one 64-byte trace record per queued ray (+ one chunk of slack for the chunk prefetch)
-  TraceArgs a; fill_trace_args(a, q, n_rays);
-  a.item_count = t.item_count;
-  if (t.live_rays) a.live_rays = t.live_rays;
-  if (t.records) { a.rec = (float4*)q.rec; a.queue_fixed = t.records->fixed; a.queue_items = t.records->items; a.queue_mul = t.records->mul; }
-  if (coop && a.stack_overflow && ensure(c.b_ovf, (size_t)n_rays * sizeof(int))) return 1;
-  a.ovf_queue = (int*)c.b_ovf.p;
-  if (coop) HIP_TRY(hipMemsetAsync(c.d_cursor, 0, kCursorInts * sizeof(int), t.stream));
-  if (coop && !t.records) launch_analytic(t.stream, c.scene, a, t.count_tests);   // outside the trace-kernel event pair
-  EventPairs::Timer timer;
-  if (t.timed) HIP_TRY(c.stage_pairs.begin(timer, t.stream, ev_tag(0)));
-  // a workgroup keeps 4 waves x (64 / width) rays in flight: a handful of rays (the legacy per-ray seam) gets a handful of workgroups
-  const int rays_per_block = 4 * (64 / std::max(1, c.scene.node_width));
-  const int grid = (int)std::min<int64_t>(coop_grid(), ((int64_t)n_rays + rays_per_block - 1) / rays_per_block);
-  launch_trace(t.stream, c.d_scene, a, t.kernel, t.count_tests, std::max(1, grid));
-  HIP_TRY(timer.end());
-  HIP_TRY(hipGetLastError());
+int resize(int w, int h) {
+  if (w <= 0 || h <= 0 || (int64_t)w * h > (1ll << 30)) return fail("art_resize: bad size");
+  if (each_device(/*stop_at_failure=*/true, [&](int) { return resize_one(w, h); })) return 1;
+  for (int k = 0; k < g_ndev; ++k) { Ctx& c = g_devs[k]; c.busy_ms = c.idle_ms = c.start_skew_ms = 0.0; for (Ctx::PassClock* pc : c.pass_clock) delete pc; c.pass_clock.clear(); }
+  if (g_devs[0].device_ready && !use_dev(0)) reset_reduce_info();
   return 0;
 }
 
@@ -490,17 +327,14 @@ static int trace(const DevPaths& q, int n_rays, const TraceLaunch& t) {
 static int collect_timing() {
   Ctx& c = g_ctx;
   HIP_TRY(c.stage_pairs.fold(/*wait=*/true, [&c](float ms, uint8_t tagged) {
-    const int kind = tagged & 15, trial = (tagged >> 4) & 3, gen = tagged >> 6;
-    if (kind == 0) { c.stats.trace_ms += ms; c.stats.trace_launches += 1; }
-    else if (kind == 1) { c.stage.shade_ms += ms; c.stage.shade_launches += 1; if ((trial == 1 || trial == 2) && gen == (int)(c.auto_gen & 3)) c.auto_ms[trial - 1] += ms; }
-    else if (kind == 2) c.stage.raygen_ms += ms;
+    const ShadeTrial::Tag tag = ShadeTrial::decode(tagged);
+    if (tag.kind == 0) { c.stats.trace_ms += ms; c.stats.trace_launches += 1; }
+    else if (tag.kind == 1) { c.stage.shade_ms += ms; c.stage.shade_launches += 1; c.trial.add(tag.trial, tag.gen, ms); }
+    else if (tag.kind == 2) c.stage.raygen_ms += ms;
     else c.stage.fold_ms += ms;
   }));
-  if (c.auto_phase == 3) {         // both trial batches are done (the stream is idle): keep the faster setting from here on
-    c.auto_per = (c.auto_ms[1] < c.auto_ms[0]) ? 2 : 4;
-    c.auto_phase = 4;
-    if (g_debug_addr) std::fprintf(stderr, "ART_DEBUG_ADDR shade_per trial: 4 items per thread %.3f ms, 2 items per thread %.3f ms per batch of %lld paths -> %d\n", c.auto_ms[0], c.auto_ms[1], (long long)c.auto_P[0], c.auto_per);
-  }
+  // both trial batches are done (the stream is idle): the faster setting is kept from here on
+  if (c.trial.decide() && g_debug_addr) std::fprintf(stderr, "ART_DEBUG_ADDR shade_per trial: 4 items per thread %.3f ms, 2 items per thread %.3f ms per batch of %lld paths -> %d\n", c.trial.ms[0], c.trial.ms[1], (long long)c.trial.P[0], c.trial.per);
   if (c.d_items) {
     unsigned long long it[32];
     HIP_TRY(hipMemcpy(it, c.d_items, sizeof it, hipMemcpyDeviceToHost));
@@ -515,235 +349,7 @@ static int collect_timing() {
   return 0;
 }
 
-static int check_pass(const ArtPassParams* p) {
-  Ctx& c = g_ctx;
-  if (!p) return fail("null ArtPassParams");
-  if (!c.scene_ready) return fail("no scene uploaded (art_upload_scene)");
-  if (c.width <= 0) return fail("no viewport (art_resize)");
-  if (p->max_depth < 1 || p->max_depth > 16) return fail("max_depth must be 1..16");
-  if (p->vthreads < 1) return fail("vthreads must be >= 1");
-  if (p->layout != ART_LAYOUT_ADA_XY && p->layout != ART_LAYOUT_ROW_MAJOR) return fail("unknown layout");
-  return 0;
-}
-
-static void make_frame(const ArtPassParams* p, DevFrame& f) {
-  Ctx& c = g_ctx;
-  f.width = c.width; f.height = c.height;
-  f.render_type = p->render_type; f.aa_on = p->aa_on ? 1 : 0; f.max_depth = p->max_depth;
-  f.seed_lo = (uint32_t)p->seed; f.seed_hi = (uint32_t)(p->seed >> 32);
-  std::memcpy(f.background, p->background, 12);
-  const float fov = kHalfPi;                                   // ray_tracer.adb:63  Pi/2.0
-  f.cam_z = -(float)c.width / safe_tan(fov / 2.0f);            // ray_tracer.adb:67
-  f.skip_null_shadow = c.opt.skip_null_shadow ? 1 : 0;
-}
-
-static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout);
-// One Render_Pass on every device of the process: each GPU renders the pixel tiles it owns into its own accum buffer, asynchronously on
-// its own stream (the host only enqueues: ~100 calls per device and pass).  The buffers meet in reduce_accum() when somebody asks
-// for the image.
-int render_pass_device(const ArtPassParams* p, int32_t* spp_inout) {
-  Dev0Guard guard;
-  int32_t spp_out = spp_inout ? *spp_inout : 0;
-  for (int k = 0; k < g_ndev; ++k) {
-    int32_t spp_k = spp_inout ? *spp_inout : 0;
-    if (use_dev(k) || render_pass_one(p, spp_inout ? &spp_k : nullptr)) return 1;
-    if (k == 0) spp_out = spp_k;
-  }
-  if (spp_inout) *spp_inout = spp_out;
-  return 0;
-}
-static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
-  Ctx& c = g_ctx;
-  if (check_pass(p)) return 1;
-  if (p->render_type == ART_RT_DEBUG || p->render_type == ART_RT_WHITTED) return fail("debug render types go through art_debug_hit_pass");
-  if (p->render_type < ART_PT_STUPID || p->render_type > ART_PT_MIS) return fail("unknown render_type");
-  if (c.scene.n_inst > 0 && c.opt.trace_kernel != TRACE_COOP) return fail("an instanced scene renders through the record schedule only (option trace_kernel = 0)");
-  const int per = p->aa_on ? 4 : 1;
-  if (spp_inout) c.spp = *spp_inout;
-  if (p->aa_on && (c.spp % 4) != 0) return fail("with anti-aliasing on, spp must be a multiple of 4 (Generate4RayDirections order)");
-  const int S = p->vthreads * per;           // samples this pass
-  const int npix = c.npix_local;
-  DevFrame F; make_frame(p, F);
-  // batch = pixel chunk x sample chunk with pc * sc <= batch_paths.  The result does not depend on the batching (the RNG is keyed by
-  // pixel, sample and bounce), so when HBM is short (a shared GPU, a caller holding memory) the batch is halved until it fits.
-  int pc = 0, sc = 0;
-  if (npix > 0) {
-    int64_t cap = std::max<int64_t>(c.opt.batch_paths, per);
-    // Two buffers belong to a batch: the path state and the live-ray queue (one 64-byte trace record for each of the up to 2 rays of a path).
-    auto try_alloc = [&](size_t bytes, hipError_t& e) {          // true: the path state holds at least `bytes`
-      DevBuf& b = c.b_paths;
-      e = hipSuccess;
-      if (b.p && b.bytes >= bytes) return true;
-      release_paths(c);
-      e = hipErrorOutOfMemory; c.paths_are_spread = false;
-      // the default (-1): 64 MB chunks for a path state of a gigabyte or more -- where the mapping granularity decides the stage's rate
-      const int chunk_mb = c.opt.paths_spread_mb > 0 ? c.opt.paths_spread_mb : (c.opt.paths_spread_mb < 0 && bytes >= ((size_t)1 << 30)) ? 64 : 0;
-      if (chunk_mb > 0) {
-        const auto t0 = std::chrono::steady_clock::now();
-        e = alloc_spread(b, bytes, (size_t)chunk_mb << 20, c.device, c.spread_fail_at);
-        if (g_debug_addr) std::fprintf(stderr, "ART_DEBUG_ADDR alloc_spread %.2f GB in chunks of %d MB: %s, %.1f ms\n", (double)bytes / 1e9, chunk_mb, hipGetErrorString(e),
-                                       std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-        if (e == hipSuccess) { c.paths_are_spread = true; return true; }
-        b.p = nullptr; (void)hipGetLastError();
-      }
-      e = hipMalloc(&b.p, bytes);
-      if (e == hipSuccess) { b.bytes = bytes; return true; }
-      b.p = nullptr; (void)hipGetLastError();
-      return false;
-    };
-    const bool rec_layout = (c.opt.trace_kernel == TRACE_COOP);              // the cooperative schedule keeps its rays as trace records inside the path state
-    for (;;) {
-      // Samples first needs room for all S samples of at least kMinPixelChunk pixels (or of the whole frame); with less, the shape is the
-      // pixels-first one of before.  The minimum is a compatibility rule, not a measured one: tests/test_gpu_camera_dedup.py
-      // (test_small_batches) pins the pixels-first plan at the smallest batch_paths (1024 paths, 8 samples: 256 pixels x 4 samples with
-      // AA on, 8 * W * H camera rays traced), where the plain rule "sc = S whenever batch_paths >= S" gives 128 pixels x 8 samples.  256 is
-      // that pinned pixel chunk.  Smaller chunks work (a last partial chunk is samples first at any size); nothing below 256 * S paths
-      // per batch has been timed either way.
-      constexpr int64_t kMinPixelChunk = 256;
-      if (cap / S >= std::min<int64_t>(npix, kMinPixelChunk)) {
-        // Samples first: a pixel chunk carries all S samples of the pass, so each distinct camera ray of the pass is generated and traced in
-        // exactly one batch (camera_dedup: U * pn rays per batch, U * npix per pass, however many pixel chunks there are).  The pixel map is
-        // dealt in 32 x 32 tiles: a chunk that does not cover the frame is a whole number of them.
-        sc = S;
-        pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / sc));
-        if (pc < npix && pc >= 1024) pc = pc / 1024 * 1024;
-      } else {
-        // too few path slots for 256 pixels with all their samples: pixels first, as many Generate4RayDirections groups per pixel as fit; the camera
-        // rays of a pixel chunk are then traced once per sample chunk
-        pc = (int)std::min<int64_t>(npix, std::max<int64_t>(1, cap / per));
-        sc = (int)std::min<int64_t>(S, std::max<int64_t>(per, (cap / pc) / per * per));
-      }
-      hipError_t e;
-      if (try_alloc(path_floats((size_t)pc * sc, p->max_depth, rec_layout) * 4 + 256, e)) {
-        if (g_debug_live) std::fprintf(stderr, "path state: %d pixels x %d samples per batch, %.2f GB\n", pc, sc, (double)g_ctx.b_paths.bytes / 1e9);
-        if (g_debug_addr) {
-          DevPaths bk[2]; std::memset(bk, 0, sizeof bk);
-          carve(bk, pc * sc, p->max_depth, rec_layout);
-          std::fprintf(stderr, "ART_DEBUG_ADDR spread %d paths %p bytes %zu P %d rec %p hot0 %p hot1 %p stride %d cold %p live %p counters %p cursor %p\n", c.paths_are_spread ? 1 : 0, g_ctx.b_paths.p, g_ctx.b_paths.bytes, pc * sc,
-                       (void*)bk[0].rec, (void*)bk[0].hot, (void*)bk[1].hot, bk[0].stride, (void*)bk[0].cold, (void*)c.d_live, (void*)c.d_counters, (void*)c.d_cursor);
-        }
-        break;
-      }
-      if (g_debug_live) std::fprintf(stderr, "path state: %.2f GB refused (%s)\n", (double)(path_floats((size_t)pc * sc, p->max_depth, rec_layout) * 4 + 256) / 1e9, hipGetErrorString(e));
-      if (e != hipErrorOutOfMemory || cap <= 65536) return fail(std::string("path buffers: ") + hipGetErrorString(e));
-      cap /= 2;
-    }
-  }
-  EventPairs::Timer pass_timer;
-  HIP_TRY(c.pass_pairs.begin(pass_timer, c.stream));
-  struct Uncounted { EventPairs::Timer& t; ~Uncounted() { t.cancel(); } } uncounted{pass_timer};      // a pass that fails midway never enters pass_ms
-  const TraceLaunch launch = pass_launch();
-  Ctx::PassClock* clock = nullptr;
-  if (g_multi_api) { clock = new Ctx::PassClock; c.pass_clock.push_back(clock); HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t0)); }
-  if (npix > 0) {
-    for (int px0 = 0; px0 < npix; px0 += pc) {
-      const int pn = std::min(pc, npix - px0);
-      for (int s0 = 0; s0 < S; s0 += sc) {
-        const int sn = std::min(sc, S - s0);
-        DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
-        for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = (const uint32_t*)c.b_pixmap.p + px0; b.sample_base = (uint32_t)(c.spp + s0); }
-        carve(bank, bank[0].P, p->max_depth, c.opt.trace_kernel == TRACE_COOP);
-        // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_api_internal.h Options::opt_shade_per).
-        // Nothing here waits for the GPU: a trial batch only tags its shade launches' event pairs, and the next call that synchronises
-        // anyway reads them (collect_timing) -- Render_Pass releases all its workers before it waits for any (ray_tracer.adb:271-277).
-        int trial = 0, shade_per = c.opt.opt_shade_per ? c.opt.opt_shade_per : (c.auto_phase >= 4 ? c.auto_per : 4);
-        if (c.opt.opt_shade_per == 0 && c.auto_phase < 3 && c.opt.trace_kernel == TRACE_COOP) {
-          const int64_t Pb = (int64_t)pn * sn;
-          if (c.auto_phase == 0) c.auto_phase = 1;                                      // the warm batch: 4 items per thread, not measured
-          else if (c.auto_phase == 1) { trial = 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; c.auto_phase = 2; }
-          else if (Pb == c.auto_P[0]) { trial = 2; shade_per = 2; c.auto_ms[1] = 0.0; c.auto_P[1] = Pb; c.auto_phase = 3; }
-          else if (++c.auto_redo > 3) { c.auto_per = 4; c.auto_phase = 4; }             // batch sizes keep changing: no trial, 4 items per thread
-          else { trial = 1; c.auto_gen += 1; c.auto_ms[0] = 0.0; c.auto_P[0] = Pb; }    // a batch of another size: trial A again, on this size (new generation: the old trial's events no longer count)
-        }
-        // Option camera_dedup: the batch's distinct camera rays -- one per (pixel, sample & 3), DevPaths::cam_dedup -- are generated and traced
-        // once; bounce 0 still runs over all P slots and reads every slot's hit from its distinct ray.  The counting variant traces every
-        // sample's camera ray: its contract is "equal to the oracle's walk".
-        const bool dedup = c.opt.camera_dedup && !c.opt.count_tests && c.opt.trace_kernel == TRACE_COOP;
-        // U distinct rays per pixel: 4 with AA on (a sample chunk is a whole number of Generate4RayDirections groups: sc and S are multiples of 4), 1 with AA off
-        const int cam_u = p->aa_on ? 4 : 1;
-        const int cam_n = dedup ? cam_u * pn : bank[0].P;      // camera rays this batch generates and traces
-        c.camera_traced += (uint64_t)cam_n;
-        if (c.opt.trace_kernel == TRACE_COOP) {
-          // Compacted work sets: raygen fills bank 0 (one item per slot); stage b shades the items of bank b & 1 and writes the survivors
-          // densely into the other bank.  d_live[0] / d_live[32]: the banks' item counts.  Every stage leaves its rays as trace records in
-          // its output bank (round 3), at positions given by the item index; the trace kernel reads them from there in item order.
-          if (!c.d_live) HIP_TRY(hipMalloc(&c.d_live, 32 * 18 * sizeof(int)));          // d_live[32 k]: items of level k (the input set of bounce k), k = 1 .. max_depth <= 16
-          unsigned long long* const rays_b = c.opt.count_tests ? c.d_counters + CNT_TRACED : nullptr;
-          bank[0].rec_mode = REC_EXT;
-          DevPaths q = bank[0];                            // identity layout for raygen
-          q.slot_id = nullptr;
-          q.cam_dedup = dedup ? cam_u : 0;
-          DevPaths qgen = q; qgen.P = cam_n;               // raygen's slots: [0, cam_n) are the distinct rays (slot = (sample & 3 within the batch) * pn + pixel)
-          if (!c.d_items) { HIP_TRY(hipMalloc(&c.d_items, 32 * sizeof(unsigned long long))); HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream)); }
-          { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(2))); launch_raygen(c.stream, F, c.scene, qgen); }
-          launch_bump(c.stream, c.d_counters + CNT_RAYS, rays_b, (unsigned long long)q.P);      // ArtStats::rays: one camera query per sample (the reference's Find_Closest_Hit calls), however many were traced
-          { const RecordQueue rq = {cam_n, nullptr, 1}; TraceLaunch t = launch; t.records = &rq; if (trace(q, cam_n, t)) return 1; }
-          for (int b = 0; b < p->max_depth; ++b) {
-            const int in = b & 1, out = in ^ 1;
-            const DevPaths& qi = (b == 0) ? q : bank[in];
-            const bool last = b + 1 >= p->max_depth;
-            bank[out].rec_mode = (p->render_type == ART_PT_STUPID) ? REC_EXT : (last ? REC_SHADOW : REC_BOTH);
-            int* const n_in = c.d_live + 32 * b; int* const n_out = c.d_live + 32 * (b + 1);      // per level: the fold walks them again
-            HIP_TRY(hipMemsetAsync(n_out, 0, sizeof(int), c.stream));
-            { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(1, trial)));
-              launch_shade_compact(c.stream, F, c.scene, qi, bank[out], b, b == 0 ? nullptr : n_in, n_out,
-                                   const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + CNT_LOST, c.d_counters + CNT_RAYS, rays_b, shade_per); }
-            if (b == 0 && c.inject_lost) { launch_bump(c.stream, c.d_counters + CNT_LOST, nullptr, 1ull); c.inject_lost = 0; }      // test option: what a stage does when it loses a path
-            if (g_debug_live) {
-              int n = -1; unsigned long long r0 = 0;
-              (void)hipStreamSynchronize(c.stream); (void)hipMemcpy(&n, n_out, 4, hipMemcpyDeviceToHost); (void)hipMemcpy(&r0, c.d_counters + CNT_RAYS, 8, hipMemcpyDeviceToHost);
-              std::fprintf(stderr, "stage %d: items out %d of %d, rays so far %llu\n", b, n, q.P, r0);
-            }
-            if (!last || p->render_type != ART_PT_STUPID) {
-              const RecordQueue rq = {-1, n_out, bank[out].rec_mode == REC_BOTH ? 2 : 1};
-              TraceLaunch t = launch; t.item_count = n_out; t.records = &rq;
-              if (trace(bank[out], 2 * q.P, t)) return 1;
-            }
-          }
-          const int last = p->max_depth & 1;              // the bank the last stage wrote
-          EventPairs::Timer fold_timer;
-          HIP_TRY(c.stage_pairs.begin(fold_timer, c.stream, ev_tag(3)));
-          launch_resolve_last(c.stream, bank[last], c.d_live + 32 * p->max_depth, p->max_depth - 1);
-          if (bank[last].fold_dense) launch_fold_levels(c.stream, F, bank[last], p->max_depth, c.d_live);
-          else launch_fold(c.stream, F, bank[last]);
-          launch_accumulate(c.stream, F, q, sn, accum_ptr());
-          HIP_TRY(fold_timer.end());
-          launch_acc_items(c.stream, c.d_live, p->max_depth, q.P, c.d_items);
-          c.stage.batches += 1;
-        } else {                                          // one-ray-per-lane cross-check kernel: the plain schedule over all slots, in place
-          DevPaths q = bank[0];
-          q.slot_id = nullptr;
-          q.final_flags = q.flags;
-          launch_raygen(c.stream, F, c.scene, q);
-          for (int b = 0; b < p->max_depth; ++b) {
-            if (trace(q, b == 0 ? q.P : 2 * q.P, launch)) return 1;
-            launch_shade(c.stream, F, c.scene, q, b);
-          }
-          if (p->render_type != ART_PT_STUPID) { if (trace(q, 2 * q.P, launch)) return 1; }
-          launch_finish(c.stream, F, q, p->max_depth - 1);
-          launch_accumulate(c.stream, F, q, sn, accum_ptr());
-        }
-        HIP_TRY(hipGetLastError());
-      }
-    }
-  }
-  HIP_TRY(pass_timer.end());
-  if (clock) HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t1));
-  c.spp += S;
-  c.stats.samples += (uint64_t)npix * S;
-  if (spp_inout) *spp_inout = c.spp;
-  return 0;
-}
-
-static int synchronize_one();
-int synchronize() {
-  Dev0Guard guard;
-  int rc = 0;
-  for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || synchronize_one()) rc = 1; }      // (every device is waited for and checked, also after a failure on one)
-  if (g_devs[0].device_ready && !use_dev(0)) fold_reduce_events();
-  return rc;
-}
-static int synchronize_one() {
+int synchronize_one() {
   Ctx& c = g_ctx;
   if (!c.device_ready) return 0;
   HIP_TRY(hipStreamSynchronize(c.stream));
@@ -761,6 +367,11 @@ static int synchronize_one() {
     return fail("render self-check: " + std::to_string(n) + " path(s) lost by the wavefront stages (ArtStats::lost_paths); the image is not valid");
   }
   return 0;
+}
+int synchronize() {
+  const int rc = each_device(/*stop_at_failure=*/false, [](int) { return synchronize_one(); });      // (every device is waited for and checked, also after a failure on one)
+  if (g_devs[0].device_ready && !use_dev(0)) fold_reduce_events();
+  return rc;
 }
 
 // every pixel has one owner, so the other devices hold exact zeros there and the sum over devices is exact: ONE
@@ -814,7 +425,7 @@ int download(float* accum_host, uint32_t* screen_host, int layout, int spp) {
   return download_from(acc, accum_host, screen_host, layout, spp);
 }
 
-static int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host, int layout, int spp) {
+int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host, int layout, int spp) {
   Ctx& c = g_ctx;
   const int W = c.width, H = c.height; const size_t n = (size_t)W * H;
   if (screen_host) launch_resolve(c.stream, acc_dev, (int)n, 1.0f / (float)spp, (uint32_t*)c.b_screen.p);
@@ -836,60 +447,6 @@ static int download_from(const float* acc_dev, float* accum_host, uint32_t* scre
   HIP_TRY(hipStreamSynchronize(c.stream));
   HIP_TRY(hipGetLastError());
   return 0;
-}
-
-static int debug_pass_one(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
-// Debug_Ray_Tracing is one primary ray per pixel: in multi-device mode device 0 takes the whole frame for it (its tile ownership is
-// restored afterwards) -- there is nothing to shard.
-int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type) {
-  if (g_ndev == 1) return debug_pass_one(p, accum_host, screen_host, prim_index, mat_id, prim_type);
-  Dev0Guard guard;
-  if (use_dev(0)) return 1;
-  Ctx& c = g_ctx;
-  const int rank = c.rank, nranks = c.nranks;
-  c.rank = 0; c.nranks = 1;
-  int rc = (c.width > 0) ? build_shard() : 0;
-  if (!rc) rc = debug_pass_one(p, accum_host, screen_host, prim_index, mat_id, prim_type);
-  c.rank = rank; c.nranks = nranks;
-  if (c.width > 0 && build_shard()) return 1;
-  return rc;
-}
-static int debug_pass_one(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type) {
-  Ctx& c = g_ctx;
-  if (check_pass(p)) return 1;
-  ArtPassParams pp = *p; pp.aa_on = 0;
-  DevFrame F; make_frame(&pp, F);
-  const int npix = c.npix_local; const size_t n = (size_t)c.width * c.height;
-  if (ensure(c.b_ids, n * 12)) return 1;
-  HIP_TRY(hipMemsetAsync(c.b_ids.p, 0xff, n * 12, c.stream));
-  int32_t* d_pi = (int32_t*)c.b_ids.p; int32_t* d_mi = d_pi + n; int32_t* d_pt = d_mi + n;
-  const int pc = (int)std::min<int64_t>(npix, c.opt.batch_paths);
-  if (npix > 0 && ensure_paths((size_t)pc, 1, false)) return 1;
-  for (int px0 = 0; px0 < npix; px0 += pc) {
-    const int pn = std::min(pc, npix - px0);
-    DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
-    carve(bank, pn, 1, false);
-    DevPaths q = bank[0];
-    q.P = pn; q.npix = pn; q.pixmap = (const uint32_t*)c.b_pixmap.p + px0; q.sample_base = 0; q.slot_id = nullptr; q.final_flags = q.flags;
-    launch_raygen(c.stream, F, c.scene, q);
-    if (trace(q, pn, pass_launch())) return 1;
-    launch_debug(c.stream, F, c.scene, q, accum_ptr(), d_pi, d_mi, d_pt);
-  }
-  HIP_TRY(hipGetLastError());
-  // ray_tracer.adb:249-257: the debug image is resolved without dividing by spp
-  if (download_from(accum_ptr(), accum_host, screen_host, p->layout, 1)) return 1;
-  auto copy_ids = [&](int32_t* host, const int32_t* dev) -> int {
-    if (!host) return 0;
-    if (p->layout == ART_LAYOUT_ADA_XY) {
-      if (ensure(c.b_stage, n * 12)) return 1;
-      launch_to_xmajor_u32(c.stream, (const uint32_t*)dev, (uint32_t*)c.b_stage.p, c.width, c.height);
-      HIP_TRY(hipMemcpyAsync(host, c.b_stage.p, n * 4, hipMemcpyDeviceToHost, c.stream));
-    } else HIP_TRY(hipMemcpyAsync(host, dev, n * 4, hipMemcpyDeviceToHost, c.stream));
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    return 0;
-  };
-  if (copy_ids(prim_index, d_pi) || copy_ids(mat_id, d_mi) || copy_ids(prim_type, d_pt)) return 1;
-  return synchronize_one();
 }
 
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st) {
@@ -1439,21 +996,10 @@ int art_get_camera_rays_traced(uint64_t* out) {
   return 0;
 }
 
-static int set_option_one(const std::string& n, int64_t value);
-int art_set_option(const char* name, int64_t value) {      // applies to every device of the process
-  std::lock_guard<std::mutex> lk(g_mu);
-  if (!name) return fail("null option");
-  const std::string n(name);
-  Ctx* const saved = g_cur;
-  int rc = 0;
-  for (int k = 0; k < g_ndev && !rc; ++k) { g_cur = &g_devs[k]; rc = set_option_one(n, value); }
-  g_cur = saved;
-  return rc;
-}
 static int set_option_one(const std::string& n, int64_t value) {
   if (n == "trace_kernel") { if (value != TRACE_COOP && value != TRACE_SIMPLE) return fail("trace_kernel: 0 (cooperative) or 1 (simple)"); g_ctx.opt.trace_kernel = (int)value; }
   else if (n == "queue_segments") { if (value != 1 && value != 2 && value != 4 && value != 8) return fail("queue_segments: 1, 2, 4 or 8"); g_ctx.opt.queue_segments = (int)value; }
-  else if (n == "batch_paths") { if (value < 1024 || value > (1ll << 27)) return fail("batch_paths: 1024..2^27 (2 rays per path slot; the trace kernel addresses a ray's 16-byte hit record by a 32-bit byte offset)"); g_ctx.opt.batch_paths = value; g_ctx.auto_phase = 0; g_ctx.auto_redo = 0; g_ctx.auto_gen += 1; }
+  else if (n == "batch_paths") { if (value < 1024 || value > (1ll << 27)) return fail("batch_paths: 1024..2^27 (2 rays per path slot; the trace kernel addresses a ray's 16-byte hit record by a 32-bit byte offset)"); g_ctx.opt.batch_paths = value; g_ctx.trial.reset(); }
   else if (n == "paths_spread") { if (value < -1 || value > 65536) return fail("paths_spread: chunk size in MB, 0 = off (plain hipMalloc), -1 = automatic"); g_ctx.opt.paths_spread_mb = (int)value; release_paths(g_ctx); }
   else if (n == "spread_fail_at") { g_ctx.spread_fail_at = (int)value; release_paths(g_ctx); }      // test option: creating chunk number `value` of the path state fails (-1: never)
   else if (n == "inject_lost") { g_ctx.inject_lost = value != 0; }      // test option: the next pass counts one lost path in its first batch
@@ -1480,6 +1026,12 @@ static int set_option_one(const std::string& n, int64_t value) {
   else if (n == "bvh_node_cost_milli") { g_ctx.opt.bvh_params.node_cost = (float)value / 1000.0f; }
   else return fail("unknown option " + n);
   return 0;
+}
+int art_set_option(const char* name, int64_t value) {      // applies to every device of the process
+  std::lock_guard<std::mutex> lk(g_mu);
+  if (!name) return fail("null option");
+  const std::string n(name);
+  return each_device(/*stop_at_failure=*/true, [&](int) { return set_option_one(n, value); }, /*switch_gpu=*/false);
 }
 
 const char* art_last_error(void) { t_err = g_err; return t_err.c_str(); }

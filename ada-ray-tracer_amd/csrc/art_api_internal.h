@@ -9,11 +9,13 @@
 #include "art_event_pairs.h"
 #include "art_host_scene.h"
 #include "art_kernels.h"
+#include "art_pass_plan.h"
 
 namespace art {
 
 constexpr int kMaxDevices = 16;       // art_init_devices: GPUs one process may drive (an MI355X node has 8)
 constexpr int kCursorInts = 32 * 9;   // d_cursor: 3 scalars + one work cursor per queue segment, each on its own 128-byte line
+constexpr size_t kRecSlack = 4096;    // records past the last one the trace kernel's chunk prefetch may touch
 
 struct DevBuf {
   void* p = nullptr; size_t bytes = 0;
@@ -21,6 +23,8 @@ struct DevBuf {
   std::vector<hipMemGenericAllocationHandle_t> chunks; size_t chunk_bytes = 0, reserved = 0;
   void release();
 };
+// b = `bytes` of device memory as one address range over separately created chunks (release() is its inverse); fail_at: test option spread_fail_at
+hipError_t alloc_spread(DevBuf& b, size_t bytes, size_t chunk, int device, int fail_at = -1);
 
 // What every kind of device-side scene update (art_update.cpp) keeps per context besides its own plan.
 struct UpdateLane {
@@ -31,7 +35,7 @@ struct UpdateLane {
   uint64_t bad_last = 0; bool bad_reported = true;   // bad items (vertices, matrices) of the last update read; a synchronize reported them (or there were none)
 };
 
-// What art_set_option sets and art_init_devices hands to every context (derived state -- blocks_per_cu, auto_*, paths_are_spread -- is Ctx's).
+// What art_set_option sets and art_init_devices hands to every context (derived state -- blocks_per_cu, trial, paths_are_spread -- is Ctx's).
 struct Options {
   int trace_kernel = TRACE_COOP;
   int64_t batch_paths = 128ll << 20;  // path slots per batch (328 B each at depth 8 -> up to 44 GB of the 288 GB HBM; buffers are sized to the frame,
@@ -134,8 +138,7 @@ struct Ctx {
   unsigned long long* d_counters = nullptr;   // kCounters words, named by enum Counter
   uint64_t camera_traced = 0;     // camera rays the render passes generated and traced since art_resize (art_get_camera_rays_traced; host-side count)
   Options opt; int blocks_per_cu = 0;
-  int auto_per = 0, auto_phase = 0;      // the items-per-thread trial (Options::opt_shade_per).  auto_phase: 0 warm batch next, 1 trial A (4) next, 2 trial B (2) next, 3 both enqueued, 4 decided
-  double auto_ms[2] = {0.0, 0.0}; int64_t auto_P[2] = {0, 0}; int auto_redo = 0; unsigned auto_gen = 0;      // auto_gen: a trial's event pairs carry its generation (mod 4); a reset or a re-done trial starts a new one
+  ShadeTrial trial;              // the items-per-thread trial of the shade stage (Options::opt_shade_per, art_pass_plan.h)
   uint64_t lost_reported = 0;    // lost paths (d_counters[CNT_LOST], cumulative) already reported by a synchronize: only synchronize_one advances it
   // the two test options stay outside Options: art_init_devices has never carried them over to the contexts it creates
   int inject_lost = 0;           // test option: the next render pass bumps the self-check counter once in its first batch (tests/test_gpu_parity.py)
@@ -171,6 +174,20 @@ int fail(const std::string& msg);
 
 int use_dev(int k);                   // make device k's context the current one (g_ctx) and its GPU the current HIP device
 struct Dev0Guard { ~Dev0Guard() { g_cur = &g_devs[0]; if (g_devs[0].device >= 0) (void)hipSetDevice(g_devs[0].device); } };   // multi-device loops leave device 0 current on every exit path
+// f(k) with context k current, for every context of the process; 1 if any f(k) (or the switch to its GPU) failed.  stop_at_failure: the
+// contexts after a failure are not visited.  switch_gpu: context k's GPU is made current too, and device 0 is left current; false (f makes
+// no HIP call): only g_cur is repointed, and put back.
+template <class F>
+int each_device(bool stop_at_failure, F&& f, bool switch_gpu = true) {
+  Ctx* const saved = g_cur;
+  int rc = 0;
+  for (int k = 0; k < g_ndev && !(rc && stop_at_failure); ++k) {
+    if (!switch_gpu) g_cur = &g_devs[k];
+    if ((switch_gpu && use_dev(k)) || f(k)) rc = 1;
+  }
+  if (switch_gpu) { Dev0Guard leave_device_0_current; } else g_cur = saved;
+  return rc;
+}
 int ensure(DevBuf& b, size_t bytes);
 template <typename T>
 int upload(DevBuf& b, const std::vector<T>& v) {
@@ -203,6 +220,33 @@ int sync_updates();                   // art_synchronize, current context, strea
 int ensure_device();
 int upload_scene(const ArtSceneDesc* d);
 int resize(int w, int h);
+int build_shard();                    // the current context's pixel list (rank, nranks, tile) -> b_pixmap, stream-ordered
+inline float* accum_ptr() { return g_ctx.ext_accum ? g_ctx.ext_accum : (float*)g_ctx.b_accum.p; }
+int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host, int layout, int spp);
+int synchronize_one();                // the current context: wait for its stream, fold its event pairs and counters, report lost paths
+extern const bool g_debug_addr;       // ART_DEBUG_ADDR is set: device addresses of the path state and the shade trial's verdict on stderr
+extern bool g_multi_api;              // the process came up through art_init_devices: passes carry host-clock marks (Ctx::PassClock)
+void clock_cb(void* p);               // hipLaunchHostFunc: *(double*)p = the host clock, ms
+// ---- the render-pass driver (art_render.cpp) ----
+void release_paths(Ctx& c);           // the only way the path state is released
+void stack_plan(int& entries, bool& overflow);      // LDS stack entries per ray of a trace launch | rays that go deeper are finished by k_trace_overflow
+// One trace launch.  records != nullptr: the bank's rays are already trace records in item order (DevPaths::rec, written by the stage
+// that emitted them): no k_analytic pass, the queue is the record array itself.
+struct RecordQueue { int fixed; const int* items; int mul; };
+// What a trace launch runs on and with.  The render passes and the debug pass take the first three from the context; the
+// ray queries name their own, so nothing ever has to change the context for the length of a call.
+struct TraceLaunch {
+  hipStream_t stream; int kernel; bool count_tests;      // kernel: TRACE_COOP or TRACE_SIMPLE
+  bool timed = true;                                     // an event pair (tag 0) around the trace kernel
+  const int* item_count = nullptr;
+  const RecordQueue* records = nullptr;
+  unsigned long long* live_rays = nullptr;               // where the launch counts the rays it issued (nullptr: d_counters[CNT_RAYS], ArtStats::rays)
+};
+int trace(const DevPaths& q, int n_rays, const TraceLaunch& t);
+int check_pass(const ArtPassParams* p);
+void make_frame(const ArtPassParams* p, DevFrame& f);
+int render_pass_device(const ArtPassParams* p, int32_t* spp_inout);
+int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);

@@ -1,4 +1,4 @@
-// art_kernels.h -- launch interface between art_api.cpp (host driver) and art_kernels.hip.
+// art_kernels.h -- launch interface between the host driver (art_api.cpp, art_render.cpp) and art_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "art_shade.h"

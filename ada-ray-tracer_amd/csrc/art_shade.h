@@ -525,7 +525,7 @@ ART_HD int item_slot(const DevPaths& q, int w) { return q.slot_id ? (int)at(q.sl
 // the child word of a dense fold record: bits 0..27 the item at the next bounce, bits 28..29 the kind (0: that item exists; 1: the path ended
 // here, the record's w is its value; 2: a surface whose successor was not kept), bit 30: the shadow test this item resolved for its
 // PREDECESSOR came out "in shadow" (the predecessor's explicit light, e[this level][this item], then counts as 0)
-constexpr int32_t kFoldIndexMask = (1 << 28) - 1;      // (a batch has at most 2^27 items: art_api.cpp refuses more than 2^28 rays per trace launch)
+constexpr int32_t kFoldIndexMask = (1 << 28) - 1;      // (a batch has at most 2^27 items: art_render.cpp refuses more than 2^28 rays per trace launch)
 ART_HD int32_t fold_child_word(int32_t child, bool shadowed) {
   const int32_t kind = (child >= 0) ? 0 : (child == -1) ? 1 : 2;
   return ((child >= 0) ? child : 0) | (kind << 28) | (shadowed ? (1 << 30) : 0);
@@ -906,7 +906,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   ART_TPROBE(cx.tprobe, 75);        // fold record + output words stored
   if (qo.rec) {
     // the item's rays go out as trace records, at positions given by the item index (REC_BOTH: 2 wo and 2 wo + 1).  A ray the bank's
-    // mode has no record for cannot exist (the modes follow the integrator: art_api.cpp); should it ever, the self-check counts it.
+    // mode has no record for cannot exist (the modes follow the integrator: art_render.cpp); should it ever, the self-check counts it.
     const int mode = qo.rec_mode;
     const int per = (mode == REC_BOTH) ? 2 : 1;
     const bool blocks = cx.stage_count > 0;      // k_shade_compact: each kind of ray is its own contiguous block of the wave's records

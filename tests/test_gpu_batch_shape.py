@@ -17,7 +17,8 @@ CAPS = (DEFAULT_BATCH_PATHS, 5000, 20000)
 
 
 def plan(npix, S, cap, per=4):
-    """(pixel chunk, sample chunk) of render_pass_one: the issue's samples-first rule, taken only when all S samples of at least 256 pixels
+    """(pixel chunk, sample chunk) of a pass, the mirror of plan_batch in csrc/art_pass_plan.h (tests/test_pass_plan_host.py holds the two
+    together): the issue's samples-first rule, taken only when all S samples of at least 256 pixels
     (or of the frame) fit -- the minimum that keeps test_gpu_camera_dedup.py's pinned plan at batch_paths = 1024; else pixels first"""
     cap = max(cap, per)
     if cap // S >= min(npix, 256):

@@ -3,7 +3,7 @@ at its full frame size, through the C ABI.
 
 The other full-size tests compare 4 spp (Threads_Num = 1) and the small-frame parity tests stop at 24 spp.  What only these counts
 exercise: sample indices up to 1023 in the RNG key, the sample-chunk offsets of a pass that the backend cuts into several batches
-(a 256-spp 1080p pass is four 64-spp batches: sample_base = spp + 64 / 128 / 192, art_api.cpp render_pass_one), and the accumulation
+(a 256-spp 1080p pass is four 64-spp batches: sample_base = spp + 64 / 128 / 192, art_render.cpp render_pass_one), and the accumulation
 order over 16 / 64 / 256 virtual tasks (integrators.adb:42-52: color = (((bg + s0) + s1) + s2) + s3 per task, colBuff = color + colBuff
 in task order).  C2 is small enough for the oracle to render the whole frame; for C3 / C4 / C5 the oracle renders a sample of pixels
 spread over the frame with the per-pixel body of its own Render_Pass (orc_render_pixels), its mesh search walking the exported tree
