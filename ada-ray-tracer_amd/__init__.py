@@ -117,6 +117,11 @@ class ArtDenoiseParams(C.Structure):
                 ("normal_log2", C.c_int32), ("variant", C.c_int32), ("scale", C.c_float), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class ArtSvgfParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
+                ("normal_log2", C.c_int32), ("n_colours", C.c_int32), ("scale", C.c_float), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
+
+
 # Backend.render_aovs_torch: plane -> (field of ArtAovBuffers, floats or ints per pixel, integer plane)
 AOV_PLANES = collections.OrderedDict([("albedo", ("albedo3f", 3, False)), ("normal", ("normal3f", 3, False)), ("depth", ("depth", 1, False)),
                                       ("alpha", ("alpha", 1, False)), ("prim_type", ("prim_type", 1, True)), ("prim_index", ("prim_index", 1, True)),
@@ -196,6 +201,11 @@ def two_level_arrays(call):
     return out, 0
 
 
+# Backend.denoise_svgf_torch's defaults: the best setting of profiles/svgf/quality.json (the sweep of profiles/svgf/quality.py)
+SVGF_ITERATIONS = 1
+SVGF_SIGMA_COLOR = 2.0
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -203,8 +213,8 @@ class HitCpp(C.Structure):
 
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
-    "art_debug_hit_pass", "art_bind_accum", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_refit_device", "art_get_refit_info",
+    "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_denoise_svgf_device", "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_rebuild_instance_tree_device", "art_get_instance_rebuild_info", "art_get_instance_tree_cost",
@@ -244,12 +254,14 @@ def load_library():
     L.art_render_pass.argtypes = [C.POINTER(ArtPassParams), f32p, u32p, i32p]
     L.art_debug_hit_pass.argtypes = [C.POINTER(ArtPassParams), f32p, u32p, i32p, i32p, i32p]
     L.art_bind_accum.argtypes = [C.c_void_p]
+    L.art_bind_moments.argtypes = [C.c_void_p]
     L.art_download.argtypes = [f32p, u32p, C.c_int32, C.c_int32]
     L.art_trace_rays.argtypes = [f32p, f32p, f32p, C.c_int64, C.POINTER(ArtHit), C.c_int32, C.POINTER(ArtStats)]
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
     L.art_denoise_device.argtypes = [C.POINTER(ArtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+    L.art_denoise_svgf_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -399,6 +411,7 @@ class Backend:
             arr = (C.c_int32 * len(devices))(*devices)
             _check(self.lib.art_init_devices(len(devices), arr))
         self._accum_tensor = None                     # the tensor bind_accum holds while it is bound
+        self._moments_tensor = None                   # the same for bind_moments
 
     def reduce(self):
         _check(self.lib.art_reduce())
@@ -417,6 +430,9 @@ class Backend:
         t = self._accum_tensor
         if t is not None and t.numel() < 3 * width * height:
             raise ArtError("resize: the bound accum tensor holds %d elements, a %d x %d frame needs %d" % (t.numel(), width, height, 3 * width * height))
+        m = getattr(self, "_moments_tensor", None)
+        if m is not None and m.numel() < 2 * width * height:
+            raise ArtError("resize: the bound moments tensor holds %d elements, a %d x %d frame needs %d" % (m.numel(), width, height, 2 * width * height))
         self.width, self.height = width, height
         _check(self.lib.art_resize(width, height))
 
@@ -481,6 +497,29 @@ class Backend:
             held, accum = accum, accum.data_ptr()
         _check(self.lib.art_bind_accum(accum))         # (a refused pointer keeps the previous binding, and the tensor held for it)
         self._accum_tensor = held
+
+    def bind_moments(self, moments):
+        """Let the render passes keep the luminance moments {S1, S2} of every pixel in caller-owned device memory (art_bind_moments; the
+        contract is in include/art_hip.h): row-major float2, zeroed by the next resize, added to by every pass.  moments: None (no
+        moments, the default), an integer device address, or a contiguous float32 torch tensor on the library's GPU with at least
+        2 * W * H elements for the frame the next resize() sets.  Checked before any C call, held until the next bind_moments and
+        guarded by resize(), which refuses a frame the tensor is too small for, exactly as bind_accum's tensor."""
+        held = None
+        if moments is not None and not isinstance(moments, int):
+            torch = sys.modules.get("torch")
+            if torch is None or not isinstance(moments, torch.Tensor):
+                raise ArtError("bind_moments: None, an integer device address or a torch tensor is required, not %s" % type(moments).__name__)
+            if moments.device.type != "cuda":
+                raise ArtError("bind_moments: must be a GPU tensor on the library's device, not on %s" % moments.device)
+            if moments.dtype != torch.float32:
+                raise ArtError("bind_moments: dtype must be torch.float32, not %s" % moments.dtype)
+            if not moments.is_contiguous():
+                raise ArtError("bind_moments: the tensor must be contiguous (the library writes row-major float2 from its first element on)")
+            if moments.numel() == 0:
+                raise ArtError("bind_moments: the tensor is empty")
+            held, moments = moments, moments.data_ptr()
+        _check(self.lib.art_bind_moments(moments))     # (a refused pointer keeps the previous binding, and the tensor held for it)
+        self._moments_tensor = held
 
     def synchronize(self):
         _check(self.lib.art_synchronize())
@@ -607,6 +646,57 @@ class Backend:
         ptr = lambda x: None if x is None else x.data_ptr()
         stream = torch.cuda.current_stream(color.device).cuda_stream
         _check(self.lib.art_denoise_device(C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth), ptr(out), stream or HIP_STREAM_LEGACY))
+        return out
+
+    def denoise_svgf_torch(self, color, moments, n_colours, albedo=None, normal=None, depth=None, iterations=SVGF_ITERATIONS, scale=1.0,
+                           sigma_color=SVGF_SIGMA_COLOR, sigma_depth=1.0, normal_log2=7, demodulate=True, out=None, variance_out=None, **other_planes):
+        """The variance-guided variant of denoise_torch (art_denoise_svgf_device; include/art_hip.h states the arithmetic): the colour
+        stop is measured in standard deviations of the pixel's own estimate, which come from `moments`, float32 with 2 * H * W
+        elements ([H, W, 2] or flat: the tensor of bind_moments as it is) and `n_colours`, the colours behind them (spp / 4 with
+        anti-aliasing, else spp).  color, the guides, out and the stream are denoise_torch's; variance_out: float32 [H, W] or None,
+        receives the variance of the filtered luminance.  A tensor bound with bind_accum is accepted as it is when it is viewed as
+        [H, W, 3], and so is the dict of render_aovs_torch as keyword arguments.  Every tensor is checked before any C call.  The
+        defaults of iterations and sigma_color are the best setting of the sweep in profiles/svgf/quality.json."""
+        for name in other_planes:
+            if name not in AOV_PLANES:
+                raise TypeError("denoise_svgf_torch: unexpected keyword argument %r" % name)
+        torch = sys.modules.get("torch")
+        if torch is None or not isinstance(color, torch.Tensor):
+            raise ArtError("denoise_svgf_torch: color: a torch tensor is required, not %s" % type(color).__name__)
+        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
+            raise ArtError("denoise_svgf_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
+        h, w = int(color.shape[0]), int(color.shape[1])
+        planes = (("color", color, 3), ("moments", moments, 2), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3),
+                  ("variance_out", variance_out, 1))
+        for name, x, per in planes:
+            if x is None and name != "moments":
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise ArtError("denoise_svgf_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
+            if x.dtype != torch.float32:
+                raise ArtError("denoise_svgf_torch: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
+            if per == 2:
+                if x.numel() < 2 * h * w:
+                    raise ArtError("denoise_svgf_torch: moments: shape must hold at least %d elements ([H, W, 2]), not %s" % (2 * h * w, tuple(x.shape)))
+            elif tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
+                raise ArtError("denoise_svgf_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
+            if not x.is_contiguous():
+                raise ArtError("denoise_svgf_torch: %s: the tensor must be contiguous" % name)
+        for name, x, per in planes:                    # (the devices last: a wrong kind of argument is named before a wrong place)
+            if x is None:
+                continue
+            if x.device.type != "cuda" or x.device != color.device:
+                raise ArtError("denoise_svgf_torch: %s: must be a GPU tensor on %s, not on %s"
+                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        if int(n_colours) < 2:
+            raise ArtError("denoise_svgf_torch: n_colours must be at least 2 (a variance needs two colours), not %s" % (n_colours,))
+        if out is None:
+            out = torch.empty((h, w, 3), dtype=torch.float32, device=color.device)
+        p = ArtSvgfParams(w, h, int(iterations), 1 if demodulate else 0, int(normal_log2), int(n_colours), float(scale), float(sigma_color), float(sigma_depth))
+        ptr = lambda x: None if x is None else x.data_ptr()
+        stream = torch.cuda.current_stream(color.device).cuda_stream
+        _check(self.lib.art_denoise_svgf_device(C.byref(p), ptr(color), ptr(moments), ptr(albedo), ptr(normal), ptr(depth), ptr(out), ptr(variance_out),
+                                                stream or HIP_STREAM_LEGACY))
         return out
 
     def _vertex_tensors(self, pos, nrm):

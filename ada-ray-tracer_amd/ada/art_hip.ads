@@ -173,6 +173,29 @@ package Art_Hip is
                                hip_stream : System.Address) return int;
   pragma Import (C, art_denoise_device, "art_denoise_device");
 
+  --  The variance-guided variant (include/art_hip.h ArtSvgfParams, 36 bytes): moments2f is the plane of art_bind_moments (2 C floats per
+  --  pixel), n_colours the colours behind it; variance_out (1 C float per pixel) may be Null_Address.
+  type Art_Svgf_Params is record
+    width, height : int;
+    iterations    : int;     --  1 .. 8
+    demodulate    : int;
+    normal_log2   : int;     --  0 .. 10
+    n_colours     : int;     --  >= 2
+    scale         : C_float;
+    sigma_color   : C_float;
+    sigma_depth   : C_float;
+  end record;
+  pragma Convention (C, Art_Svgf_Params);
+
+  function art_denoise_svgf_device (p : access constant Art_Svgf_Params; color3f, moments2f, albedo3f, normal3f, depth, out3f,
+                                    variance_out : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_denoise_svgf_device, "art_denoise_svgf_device");
+
+  --  Luminance moments of the render passes in caller-owned DEVICE memory: 2 C floats {S1, S2} per pixel, row-major, zeroed by
+  --  art_resize, added to by every art_render_pass (include/art_hip.h).  Null_Address: none (the default).
+  function art_bind_moments (device_moments_rowmajor : System.Address) return int;
+  pragma Import (C, art_bind_moments, "art_bind_moments");
+
   --  Deforming mesh number `mesh` (an index into Art_Scene_Desc.meshes) of an uploaded instanced scene: pos3f / nrm3f are DEVICE memory
   --  of the library's GPU, 3 * nverts C floats in the vertex order of that mesh, object space; nrm3f = Null_Address keeps the normals;
   --  hip_stream = Null_Address is the library's stream.  Stream-ordered; the picture is the one of art_upload_scene with that mesh's

@@ -305,6 +305,7 @@ static int resize_one(int w, int h) {
   if (ensure(c.b_accum, n * 12) || ensure(c.b_screen, n * 4)) return 1;
   float* acc = c.ext_accum ? c.ext_accum : (float*)c.b_accum.p;
   HIP_TRY(hipMemsetAsync(acc, 0, n * 12, c.stream));
+  if (c.ext_moments) HIP_TRY(hipMemsetAsync(c.ext_moments, 0, n * 8, c.stream));
   c.spp = 0;
   c.stats = ArtStats();
   c.stage = ArtStageStats();
@@ -709,6 +710,50 @@ int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float*
   return rc;
 }
 
+// art_denoise_svgf_device: the variance-guided filter of art_denoise.h's second half.  Scratch (b_denoise, shared with art_denoise_device:
+// both run in the queries' stream order): two images, the guide records, the depth plane and the depth gradients, 60 bytes per pixel.
+int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
+                        float* out3f, float* variance_out, hipStream_t st) {
+  const std::string name = "art_denoise_svgf_device";
+  if (!p) return fail(name + ": null ArtSvgfParams");
+  if (!color3f || !out3f) return fail(name + ": null color3f or out3f");
+  if (!moments2f) return fail(name + ": null moments2f");
+  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return fail(name + ": width and height must be at least 1 and width * height at most 2^28");
+  if (p->iterations < 1 || p->iterations > 8) return fail(name + ": iterations must be 1 .. 8");
+  if (p->normal_log2 < 0 || p->normal_log2 > 10) return fail(name + ": normal_log2 must be 0 .. 10");
+  if (p->n_colours < 2) return fail(name + ": n_colours must be at least 2");
+  if (!std::isfinite(p->scale)) return fail(name + ": scale is not finite");
+  if (std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return fail(name + ": a sigma is NaN");
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)p->width * (size_t)p->height;
+  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || check_device_ptr(moments2f, 8 * N, "moments2f") ||
+      (albedo3f && check_device_ptr(albedo3f, 12 * N, "albedo3f")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
+      (depth && check_device_ptr(depth, 4 * N, "depth")) || (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")))
+    return 1;
+  StreamOrder order(c, st);
+  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2) + sizeof(float));
+  if (c.b_denoise.bytes < bytes) {        // growing it may wait: nothing enqueued may still use the old scratch
+    HIP_TRY(hipStreamSynchronize(c.stream));
+    if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
+    if (ensure(c.b_denoise, bytes)) return 1;
+  }
+  if (order.enter()) return 1;
+  SvgfArgs A; std::memset(&A, 0, sizeof A);
+  A.P.W = p->width; A.P.H = p->height; A.P.normal_log2 = p->normal_log2; A.P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
+  A.P.has_normal = normal3f ? 1 : 0; A.P.has_depth = depth ? 1 : 0;
+  A.P.scale = p->scale; A.P.sigma_color = p->sigma_color; A.P.sigma_depth = p->sigma_depth;
+  A.n = (int32_t)N; A.n_colours = p->n_colours;
+  A.color = color3f; A.moments = moments2f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f; A.variance_out = variance_out;
+  dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
+  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N); A.z = (float*)(A.grad + N);
+  launch_denoise_svgf(order.qs, A, p->iterations);
+  int rc = 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) { reset_reduce_info(); g_reduce_pairs.destroy(); }
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -839,6 +884,14 @@ int art_bind_accum(void* device_accum_rowmajor) {
   g_ctx.ext_accum = (float*)device_accum_rowmajor;
   return 0;
 }
+int art_bind_moments(void* device_moments_rowmajor) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  SINGLE_DEVICE_ONLY("art_bind_moments");
+  // (as art_bind_accum: only the kind of memory and its device can be checked here; a refused pointer leaves the binding as it was)
+  if (device_moments_rowmajor && (ensure_device() || check_device_ptr(device_moments_rowmajor, 0, "art_bind_moments: device_moments_rowmajor"))) return 1;
+  g_ctx.ext_moments = (float*)device_moments_rowmajor;
+  return 0;
+}
 void* art_accum_device(void) {          // device 0; in multi-device mode the reduced framebuffer (valid after a reduce: art_reduce / art_download)
   std::lock_guard<std::mutex> lk(g_mu);
   return (g_ndev > 1) ? g_devs[0].b_reduced.p : (void*)accum_ptr();
@@ -884,6 +937,12 @@ int art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, voi
 int art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return denoise_device(p, color3f, albedo3f, normal3f, depth, out3f, (hipStream_t)hip_stream);
+}
+
+int art_denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
+                            float* out3f, float* variance_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return denoise_svgf_device(p, color3f, moments2f, albedo3f, normal3f, depth, out3f, variance_out, (hipStream_t)hip_stream);
 }
 
 int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {

@@ -131,6 +131,7 @@ struct Ctx {
   int* d_live = nullptr;                       // item counts per level: d_live[32 k] = items of bounce k's input set (k >= 1); the dense fold walks them again
   DevBuf b_reduced;                            // device 0, multi-device mode: sum of every device's accum (the RCCL reduce target)
   float* ext_accum = nullptr;
+  float* ext_moments = nullptr;                // art_bind_moments: float2 {S1, S2} per pixel, row-major; nullptr: no moments (k_accumulate runs as ever)
   // the rank's pixel list on its way to b_pixmap (build_shard): a pinned copy, and the event behind its last stream-ordered upload
   uint32_t* pixmap_host = nullptr; size_t pixmap_host_bytes = 0; hipEvent_t pixmap_copied = nullptr;
   // work distribution / counters
@@ -251,6 +252,8 @@ int trace_rays(const float* origins, const float* dirs, const float* tfar, int64
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);
 int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st);
+int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
+                        float* out3f, float* variance_out, hipStream_t st);
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);

@@ -10,6 +10,16 @@
 //                    through LDS at a stride of 3 dwords (odd: no bank conflict), as k_aov_resolve stages its planes, so that every
 //                    store of a wave is 256 contiguous bytes.  No atomics: every output pixel has one owner.
 //
+//
+// art_denoise_svgf_device, the variance-guided variant (the second half of art_denoise.h), has kernels of its own:
+//   k_svgf_pack      k_denoise_pack plus v_0 from the luminance moments (binary64, once per pixel).  Record layout: the image record is
+//                    {r, g, b, v} and the guide record {nx, ny, nz, flags} as before; the depth, which held the image record's fourth
+//                    word, moves to a plane of its own.  A tap therefore stays at two 16-byte loads, plus one dword load when the depth
+//                    stop is on (a third 16-byte record would have carried 12 unused bytes per tap).
+//   k_svgf_atrous<LAST>  as k_atrous, with the 3 x 3 variance prefilter in front of the taps (nine more pairs of 16-byte loads per
+//                    centre, at spacing 1 whatever the iteration: neighbouring lanes' lines) and v carried through the filter.  LAST
+//                    stages the float3 output through LDS as k_atrous<true> does; variance_out is one dword per lane, contiguous as it is.
+//
 // A lane's pixel is its linear index (y * W + x): 256 consecutive pixels of a row-major frame per workgroup.
 #define ART_F64_CONST_FREE      // m1::exp_small's coefficients as plain literals: no asm pin in these kernels (the value is the literal's either way)
 #include <hip/hip_runtime.h>
@@ -62,6 +72,52 @@ void launch_denoise(hipStream_t st, const DenoiseArgs& A, int iterations) {
   hipLaunchKernelGGL(k_denoise_pack, grid, block, 0, st, A);
   for (int i = 0; i + 1 < iterations; ++i) hipLaunchKernelGGL(k_atrous<false>, grid, block, 0, st, A, i);
   hipLaunchKernelGGL(k_atrous<true>, grid, block, 0, st, A, iterations - 1);
+}
+
+// ---- art_denoise_svgf_device ------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(kDnBlock) void k_svgf_pack(const SvgfArgs A) {
+  const int p = blockIdx.x * kDnBlock + threadIdx.x;            // at most 2^28 pixels (the host's bound)
+  if (p >= A.n) return;
+  const int y = p / A.P.W, x = p - y * A.P.W;
+  dn::Rec4 c, g; dn::Rec2 d; float z;
+  dn::svgf_pack_pixel(A.P, A.n_colours, A.color, A.moments, A.albedo, A.normal, A.depth, x, y, c, g, z, d);
+  A.image[0][p] = c; A.guide[p] = g; A.z[p] = z; A.grad[p] = d;
+}
+
+// iteration i reads image[i & 1] and writes image[(i + 1) & 1] (LAST: the caller's planes).  All lanes of the workgroup reach the barrier.
+template <bool LAST>
+__global__ __launch_bounds__(kDnBlock) void k_svgf_atrous(const SvgfArgs A, const int i) {
+  __shared__ float s_out[LAST ? 3 * kDnBlock : 1];              // a lane's float3 at a stride of 3 dwords
+  const int b0 = blockIdx.x * kDnBlock;
+  const int p = b0 + (int)threadIdx.x;
+  if (p < A.n) {
+    const int y = p / A.P.W, x = p - y * A.P.W;
+    const dn::Rec4 c = dn::svgf_atrous_pixel(A.P, A.image[i & 1], A.guide, A.z, A.grad, x, y, i);
+    if constexpr (LAST) {
+      float r, g, b;
+      dn::finish_pixel(A.P, A.albedo, (size_t)p, c, r, g, b);
+      s_out[3 * threadIdx.x] = r; s_out[3 * threadIdx.x + 1] = g; s_out[3 * threadIdx.x + 2] = b;
+      if (A.variance_out) A.variance_out[p] = c.w;
+    } else {
+      A.image[(i + 1) & 1][p] = c;
+    }
+  }
+  if constexpr (LAST) {
+    __syncthreads();
+    const int nw = 3 * (A.n - b0);                               // floats of this workgroup's pixels that exist
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      const int k = j * kDnBlock + (int)threadIdx.x;
+      if (k < nw) A.out[3 * (size_t)b0 + k] = s_out[k];
+    }
+  }
+}
+
+void launch_denoise_svgf(hipStream_t st, const SvgfArgs& A, int iterations) {
+  const dim3 grid((unsigned)((A.n + kDnBlock - 1) / kDnBlock)), block(kDnBlock);
+  hipLaunchKernelGGL(k_svgf_pack, grid, block, 0, st, A);
+  for (int i = 0; i + 1 < iterations; ++i) hipLaunchKernelGGL(k_svgf_atrous<false>, grid, block, 0, st, A, i);
+  hipLaunchKernelGGL(k_svgf_atrous<true>, grid, block, 0, st, A, iterations - 1);
 }
 
 }  // namespace art

@@ -64,6 +64,7 @@ void launch_resolve_last(hipStream_t st, const DevPaths& Q, const int* n, int la
 void launch_fold(hipStream_t st, const DevFrame& F, const DevPaths& Q);
 void launch_fold_levels(hipStream_t st, const DevFrame& F, const DevPaths& Q, int max_depth, const int* counts);     // dense fold records: counts[32 k] = items of level k
 void launch_accumulate(hipStream_t st, const DevFrame& F, const DevPaths& Q, int samples_in_batch, float* accum);
+void launch_accumulate_moments(hipStream_t st, const DevFrame& F, const DevPaths& Q, int samples_in_batch, float* accum, float* moments);   // art_bind_moments: the accum and {S1, S2} in one walk
 void launch_resolve(hipStream_t st, const float* accum, int n_pixels, float norm_c, uint32_t* screen);
 void launch_debug(hipStream_t st, const DevFrame& F, const DevScene& S, const DevPaths& Q, float* accum, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 void launch_to_xmajor_f3(hipStream_t st, const float* src, float* dst, int w, int h);
@@ -119,6 +120,17 @@ struct DenoiseArgs {
   dn::Rec4* image[2]; dn::Rec4* guide; dn::Rec2* grad;
 };
 void launch_denoise(hipStream_t st, const DenoiseArgs& A, int iterations);      // the pack kernel and `iterations` filter launches
+
+// art_denoise_svgf_device (art_denoise.hip, art_api.cpp denoise_svgf_device): the same, with the moments plane, the optional variance
+// plane and the scratch layout of art_denoise.h's second half (the depth in a plane of its own)
+struct SvgfArgs {
+  dn::Params P;
+  int32_t n, n_colours;
+  const float* color; const float* moments; const float* albedo; const float* normal; const float* depth;
+  float* out; float* variance_out;
+  dn::Rec4* image[2]; dn::Rec4* guide; float* z; dn::Rec2* grad;
+};
+void launch_denoise_svgf(hipStream_t st, const SvgfArgs& A, int iterations);
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex

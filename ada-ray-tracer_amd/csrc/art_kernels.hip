@@ -1035,6 +1035,12 @@ __global__ __launch_bounds__(256) void k_accumulate(const DevFrame F, const DevP
   if (pl < Q.npix) accumulate_pixel(F, Q, pl, samples_in_batch, accum);
 }
 
+// the same walk with the luminance moments of art_bind_moments next to the accum (launched instead of k_accumulate while moments are bound)
+__global__ __launch_bounds__(256) void k_accumulate_moments(const DevFrame F, const DevPaths Q, int samples_in_batch, float* accum, float* moments) {
+  const int pl = blockIdx.x * blockDim.x + threadIdx.x;
+  if (pl < Q.npix) accumulate_pixel_moments(F, Q, pl, samples_in_batch, accum, moments);
+}
+
 __global__ __launch_bounds__(256) void k_resolve(const float* accum, int n_pixels, float norm_c, uint32_t* screen) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_pixels) screen[i] = resolve_pixel(mk3(accum[3 * (size_t)i], accum[3 * (size_t)i + 1], accum[3 * (size_t)i + 2]), norm_c);
@@ -1160,6 +1166,9 @@ void launch_finish(hipStream_t st, const DevFrame& F, const DevPaths& Q, int las
 }
 void launch_accumulate(hipStream_t st, const DevFrame& F, const DevPaths& Q, int samples_in_batch, float* accum) {
   hipLaunchKernelGGL(k_accumulate, dim3(blocks_for(Q.npix)), dim3(256), 0, st, F, Q, samples_in_batch, accum);
+}
+void launch_accumulate_moments(hipStream_t st, const DevFrame& F, const DevPaths& Q, int samples_in_batch, float* accum, float* moments) {
+  hipLaunchKernelGGL(k_accumulate_moments, dim3(blocks_for(Q.npix)), dim3(256), 0, st, F, Q, samples_in_batch, accum, moments);
 }
 void launch_resolve(hipStream_t st, const float* accum, int n_pixels, float norm_c, uint32_t* screen) {
   hipLaunchKernelGGL(k_resolve, dim3(blocks_for(n_pixels)), dim3(256), 0, st, accum, n_pixels, norm_c, screen);

@@ -275,7 +275,8 @@ static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const
   launch_resolve_last(c.stream, bank[last], c.d_live + 32 * p->max_depth, p->max_depth - 1);
   if (bank[last].fold_dense) launch_fold_levels(c.stream, F, bank[last], p->max_depth, c.d_live);
   else launch_fold(c.stream, F, bank[last]);
-  launch_accumulate(c.stream, F, q, sn, accum_ptr());
+  if (c.ext_moments) launch_accumulate_moments(c.stream, F, q, sn, accum_ptr(), c.ext_moments);
+  else launch_accumulate(c.stream, F, q, sn, accum_ptr());
   HIP_TRY(fold_timer.end());
   launch_acc_items(c.stream, c.d_live, p->max_depth, q.P, c.d_items);
   c.stage.batches += 1;
@@ -295,7 +296,8 @@ static int render_batch_plain(const ArtPassParams* p, const DevFrame& F, const T
   }
   if (p->render_type != ART_PT_STUPID) { if (trace(q, 2 * q.P, launch)) return 1; }
   launch_finish(c.stream, F, q, p->max_depth - 1);
-  launch_accumulate(c.stream, F, q, sn, accum_ptr());
+  if (c.ext_moments) launch_accumulate_moments(c.stream, F, q, sn, accum_ptr(), c.ext_moments);
+  else launch_accumulate(c.stream, F, q, sn, accum_ptr());
   return 0;
 }
 

@@ -1022,6 +1022,42 @@ ART_HD void accumulate_pixel(const DevFrame& f, const DevPaths& q, int pl, int s
   a[0] = acc.x; a[1] = acc.y; a[2] = acc.z;
 }
 
+// accumulate_pixel with the luminance moments of art_bind_moments (include/art_hip.h) in the same walk: every colour that is added to
+// the accum also adds its luminance l to S1 and l * l to S2, in the order of the additions, so the rad planes are read once.  The accum
+// update is accumulate_pixel's, operation for operation.
+ART_HD float colour_lum(f3 c) { return (0.2126f * c.x + 0.7152f * c.y) + 0.0722f * c.z; }      // dn::lum of art_denoise.h
+
+ART_HD void accumulate_pixel_moments(const DevFrame& f, const DevPaths& q, int pl, int samples_in_batch, float* accum /* row-major rgb */,
+                                     float* moments /* row-major {S1, S2} */) {
+  const uint32_t pixel = q.pixmap ? q.pixmap[pl] : (uint32_t)pl;
+  float* a = accum + 3 * (size_t)pixel;
+  float* m = moments + 2 * (size_t)pixel;
+  f3 acc = mk3(a[0], a[1], a[2]);
+  float s1 = m[0], s2 = m[1];
+  if (f.aa_on) {
+    for (int t = 0; t + 3 < samples_in_batch; t += 4) {
+      f3 color = ld3(f.background);
+      for (int i = 0; i < 4; ++i) {
+        const size_t si = (size_t)(t + i) * q.npix + pl;
+        color = color + mk3(q.rad_r[si], q.rad_g[si], q.rad_b[si]);
+      }
+      acc = color + acc;
+      const float l = colour_lum(color);
+      s1 = l + s1; s2 = l * l + s2;
+    }
+  } else {
+    for (int t = 0; t < samples_in_batch; ++t) {
+      const size_t si = (size_t)t * q.npix + pl;
+      const f3 color = mk3(q.rad_r[si], q.rad_g[si], q.rad_b[si]);
+      acc = color + acc;
+      const float l = colour_lum(color);
+      s1 = l + s1; s2 = l * l + s2;
+    }
+  }
+  a[0] = acc.x; a[1] = acc.y; a[2] = acc.z;
+  m[0] = s1; m[1] = s2;
+}
+
 // resolve (ray_tracer.adb:281-291, :19-57): gamma 2 -> clamp -> round-to-nearest pack R | G<<8 | B<<16
 ART_HD uint32_t ada_round_u32(float v) {
   if (!(v > 0.0f)) return 0u;

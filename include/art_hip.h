@@ -204,6 +204,22 @@ int  art_debug_hit_pass(const ArtPassParams* p, float* accum_host, uint32_t* scr
  * NULL unbinds: the library's own buffer is used again -- it holds what it held before the binding, so call art_resize -- and the
  * caller's buffer is never touched again. */
 int  art_bind_accum(void* device_accum_rowmajor);        /* NULL: back to the internal buffer */
+/* Luminance moments of the render passes, for a variance-guided denoiser (art_denoise_svgf_device) or an adaptive sampler: caller-owned
+ * float2 per pixel, ROW-MAJOR, {S1, S2} at floats 2*(y*width + x).  The rules of art_bind_accum hold: device memory of the library's
+ * device, else the call is refused ("... is not device memory") and the previous binding stays; the buffer is not touched at bind time and
+ * its size cannot be checked then: the caller keeps it at least width*height*8 bytes and alive until it is unbound.  art_resize zeroes
+ * its first width*height*8 bytes on the library's stream; single-device only (refused after art_init_devices(n > 1)); with art_set_shard
+ * only the pixels this rank owns are touched, every other pixel stays as it is, i.e. {+0.0f, +0.0f} since the resize.  There is no
+ * library-owned moments buffer: NULL (the default) means none, and a pass then launches exactly the kernels it launches without this call.
+ * What a pass adds.  One COLOUR of a pixel is one value the pass adds to the accum: with aa_on, background + the four samples of a
+ * Generate4RayDirections group, added in the group's order (((bg + s0) + s1) + s2) + s3; without aa_on, one sample.  For every colour
+ * (r, g, b) of the pass, in the order in which the colours are added to the accum:
+ *   l = (0.2126f * r + 0.7152f * g) + 0.0722f * b;   S1 = l + S1;   S2 = l * l + S2;
+ * in binary32, not contracted.  The sums run on over the batches of a pass and over the passes, so they do not depend on how a pass is
+ * cut into batches.  A colour that is not finite poisons the pixel's moments for good (NaN or infinity in S1 and S2), as it poisons the
+ * pixel's accum.  The number of colours since the resize is n = spp / (aa_on ? 4 : 1); the caller knows it.  art_debug_hit_pass leaves
+ * the moments alone.  The accum a pass writes is the same, bit for bit, with and without moments bound. */
+int  art_bind_moments(void* device_moments_rowmajor);   /* NULL: none (the default) */
 void* art_accum_device(void);
 int  art_download(float* accum_host, uint32_t* screen_host, int32_t layout, int32_t spp);
 int  art_synchronize(void);
@@ -318,6 +334,49 @@ typedef struct ArtDenoiseParams {
 } ArtDenoiseParams;
 int  art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth,
                         float* out3f, void* hip_stream);
+
+/* The variance-guided variant of the filter above (the spatial part of SVGF, Schied et al. 2017): the colour
+ * stop divides the luminance difference by the local standard deviation of the estimate, which comes from the luminance moments of the
+ * render passes (art_bind_moments), instead of by one global constant.  Pointers, layouts, overlap rule (out3f may equal color3f), stream
+ * order, scratch (60 bytes per pixel, the same buffer as art_denoise_device's) and the repair of non-finite pixels are those of
+ * art_denoise_device.  moments2f: float2 {S1, S2} per pixel, the layout of art_bind_moments; n_colours: the number n of colours the
+ * moments hold (spp / 4 with aa_on, else spp).  variance_out: one float per pixel, or NULL; it receives v after the last iteration, the
+ * variance of the filtered pixel's luminance in the units the filter works in (scaled, and demodulated when demodulation is on) -- what
+ * an adaptive sampler would read.
+ * Refused before anything is launched, with art_last_error set: everything art_denoise_device refuses (there is no variant), a null
+ * moments2f, n_colours < 2, and a moments2f or variance_out that is host memory, another device's memory or too small for its plane.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_denoise.h svgf_pack_pixel / svgf_atrous_pixel is its one definition).  The conventions and
+ * every symbol not defined here are those of THE ARITHMETIC of art_denoise_device.
+ * Preparation, once per call and pixel: c_0, a, gx, gy, BAD IN COLOUR and BAD IN GUIDES exactly as there.  In addition, in binary64
+ * (every operand converted first, n = (double)n_colours, each operation rounded to binary64, in the order written):
+ *   D = S2 - (S1 * S1) / n;   D0 = (D < 0) ? 0 : D  (a NaN stays a NaN);   v = (D0 * (n / (n - 1))) * (scale * scale);
+ *   with demodulation: la = lum(a) (binary32, a the floored albedo), v = v / (la * la).  This is an approximation: the variance of the
+ *   luminance of colour / albedo is not the luminance's variance over lum(albedo)^2 unless the albedo is grey.
+ *   v_0 = (float)v, the one rounding to binary32.  A v_0 that is not finite becomes +0.0f and marks the pixel NO COLOUR STOP.
+ * Iteration i, s = 1 << i, centre p = (x, y):
+ *   Variance prefilter: vs = 0, ks = 0; for dy = -1..1 outer, dx = -1..1 inner, q = p + (dx, dy) (spacing 1 in every iteration), each
+ *     q that is inside the image, not bad in guides and not bad in colour adds  vs += k * v_i(q);  ks += k;  with k = kk[|dx|] * kk[|dy|],
+ *     kk = {0.5f, 0.25f} (so 1/4, 1/8, 1/16).  vg = vs / ks when ks > 0, else 0.0f.
+ *   Taps: acc = 0, av = 0, wsum = 0; order, skipping rules, h, wn, xz, t, e, w and exp_small as in art_denoise_device, except
+ *     xc = fabsf(lum(c_i(p)) - lum(c_i(q))) / (sigma_color * sqrtf(vg) + 1e-6f), sqrtf correctly rounded; there is no 2^-i factor.
+ *     xc = 0 when sigma_color <= 0, the centre is bad in colour or the centre is marked no colour stop.
+ *     Each tap that is not skipped adds, in this order,  acc += w * c_i(q);  av += (w * w) * v_i(q);  wsum += w.
+ *   c_{i+1}(p) = acc / wsum and v_{i+1}(p) = av / (wsum * wsum) when wsum > 0, else both stay as they were.
+ * After the last iteration: out = c * a with demodulation, else c; variance_out = v (not multiplied back).
+ * Quality: profiles/svgf/quality.json holds the sweep the defaults of Backend.denoise_svgf_torch were chosen by. */
+typedef struct ArtSvgfParams {
+  int32_t width, height;     /* the image's own size, row-major; independent of art_resize */
+  int32_t iterations;        /* 1..8 */
+  int32_t demodulate;        /* as ArtDenoiseParams */
+  int32_t normal_log2;       /* 0..10 */
+  int32_t n_colours;         /* >= 2: colours behind the moments (art_bind_moments) */
+  float   scale;             /* colour is multiplied by this first (1/spp for an accum buffer); v_0 is then the variance of that mean */
+  float   sigma_color;       /* <= 0: no colour term; in standard deviations of the pixel's luminance estimate */
+  float   sigma_depth;       /* <= 0: no depth term */
+} ArtSvgfParams;
+int  art_denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f,
+                             const float* normal3f, const float* depth, float* out3f, float* variance_out, void* hip_stream);
 
 /* Moving geometry.  Moves the vertices of the scene's ART_MESH_CLOSEST mesh and refits its tree in place: same
  * topology, same leaf order, new boxes (the builders' padding rule, quantised again at width 4), for every builder and both widths.
