@@ -122,6 +122,15 @@ class ArtSvgfParams(C.Structure):
                 ("normal_log2", C.c_int32), ("n_colours", C.c_int32), ("scale", C.c_float), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
 
 
+class ArtTemporalCamera(C.Structure):
+    _fields_ = [("cam_pos", C.c_float * 3), ("cam_matrix", C.c_float * 16), ("width", C.c_int32), ("height", C.c_int32)]
+
+
+class ArtTemporalParams(C.Structure):
+    _fields_ = [("cur", ArtTemporalCamera), ("prev", ArtTemporalCamera), ("n_colours", C.c_int32), ("max_history", C.c_int32),
+                ("scale", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float)]
+
+
 # Backend.render_aovs_torch: plane -> (field of ArtAovBuffers, floats or ints per pixel, integer plane)
 AOV_PLANES = collections.OrderedDict([("albedo", ("albedo3f", 3, False)), ("normal", ("normal3f", 3, False)), ("depth", ("depth", 1, False)),
                                       ("alpha", ("alpha", 1, False)), ("prim_type", ("prim_type", 1, True)), ("prim_index", ("prim_index", 1, True)),
@@ -206,6 +215,12 @@ SVGF_ITERATIONS = 1
 SVGF_SIGMA_COLOR = 2.0
 
 
+# Backend.temporal_torch's defaults: the best setting of profiles/temporal/quality.json (the sweep of profiles/temporal/quality.py)
+TEMPORAL_MAX_HISTORY = 64
+TEMPORAL_DEPTH_TOL = 0.2
+TEMPORAL_NORMAL_MIN = 0.5
+
+
 class HitCpp(C.Structure):
     _fields_ = [("primIndex", C.c_int32), ("geomIndex", C.c_int32), ("instIndex", C.c_int32), ("t", C.c_float),
                 ("normal", C.c_float * 3), ("texCoord", C.c_float * 2)]
@@ -214,7 +229,8 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_denoise_svgf_device", "art_refit_device", "art_get_refit_info",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_history_bytes", "art_set_camera",
+    "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
     "art_rebuild_instance_tree_device", "art_get_instance_rebuild_info", "art_get_instance_tree_cost",
@@ -262,6 +278,11 @@ def load_library():
     L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
     L.art_denoise_device.argtypes = [C.POINTER(ArtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_denoise_svgf_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
+    L.art_set_camera.argtypes = [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 16)]
+    L.art_denoise_svgf_var_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
+    L.art_temporal_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 11
+    L.art_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
+    L.art_temporal_history_bytes.restype = C.c_int64
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -648,15 +669,17 @@ class Backend:
         _check(self.lib.art_denoise_device(C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth), ptr(out), stream or HIP_STREAM_LEGACY))
         return out
 
-    def denoise_svgf_torch(self, color, moments, n_colours, albedo=None, normal=None, depth=None, iterations=SVGF_ITERATIONS, scale=1.0,
-                           sigma_color=SVGF_SIGMA_COLOR, sigma_depth=1.0, normal_log2=7, demodulate=True, out=None, variance_out=None, **other_planes):
+    def denoise_svgf_torch(self, color, moments=None, n_colours=0, albedo=None, normal=None, depth=None, iterations=SVGF_ITERATIONS, scale=1.0,
+                           sigma_color=SVGF_SIGMA_COLOR, sigma_depth=1.0, normal_log2=7, demodulate=True, out=None, variance_out=None, variance=None, **other_planes):
         """The variance-guided variant of denoise_torch (art_denoise_svgf_device; include/art_hip.h states the arithmetic): the colour
         stop is measured in standard deviations of the pixel's own estimate, which come from `moments`, float32 with 2 * H * W
         elements ([H, W, 2] or flat: the tensor of bind_moments as it is) and `n_colours`, the colours behind them (spp / 4 with
         anti-aliasing, else spp).  color, the guides, out and the stream are denoise_torch's; variance_out: float32 [H, W] or None,
         receives the variance of the filtered luminance.  A tensor bound with bind_accum is accepted as it is when it is viewed as
         [H, W, 3], and so is the dict of render_aovs_torch as keyword arguments.  Every tensor is checked before any C call.  The
-        defaults of iterations and sigma_color are the best setting of the sweep in profiles/svgf/quality.json."""
+        defaults of iterations and sigma_color are the best setting of the sweep in profiles/svgf/quality.json.
+        variance: float32 [H, W], given INSTEAD of moments and n_colours (art_denoise_svgf_var_device): the variance of each pixel's
+        luminance estimate in the units of color before scale -- temporal_torch's second result, with scale = 1."""
         for name in other_planes:
             if name not in AOV_PLANES:
                 raise TypeError("denoise_svgf_torch: unexpected keyword argument %r" % name)
@@ -666,7 +689,10 @@ class Backend:
         if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
             raise ArtError("denoise_svgf_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
         h, w = int(color.shape[0]), int(color.shape[1])
-        planes = (("color", color, 3), ("moments", moments, 2), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3),
+        if variance is not None and (moments is not None or n_colours):
+            raise ArtError("denoise_svgf_torch: give moments (with n_colours) or variance, not both")
+        first = ("variance", variance, 1) if variance is not None else ("moments", moments, 2)
+        planes = (("color", color, 3), first, ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3),
                   ("variance_out", variance_out, 1))
         for name, x, per in planes:
             if x is None and name != "moments":
@@ -688,16 +714,100 @@ class Backend:
             if x.device.type != "cuda" or x.device != color.device:
                 raise ArtError("denoise_svgf_torch: %s: must be a GPU tensor on %s, not on %s"
                                % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
-        if int(n_colours) < 2:
+        if variance is None and int(n_colours) < 2:
             raise ArtError("denoise_svgf_torch: n_colours must be at least 2 (a variance needs two colours), not %s" % (n_colours,))
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.float32, device=color.device)
         p = ArtSvgfParams(w, h, int(iterations), 1 if demodulate else 0, int(normal_log2), int(n_colours), float(scale), float(sigma_color), float(sigma_depth))
         ptr = lambda x: None if x is None else x.data_ptr()
         stream = torch.cuda.current_stream(color.device).cuda_stream
+        if variance is not None:
+            _check(self.lib.art_denoise_svgf_var_device(C.byref(p), ptr(color), ptr(variance), ptr(albedo), ptr(normal), ptr(depth), ptr(out),
+                                                        ptr(variance_out), stream or HIP_STREAM_LEGACY))
+            return out
         _check(self.lib.art_denoise_svgf_device(C.byref(p), ptr(color), ptr(moments), ptr(albedo), ptr(normal), ptr(depth), ptr(out), ptr(variance_out),
                                                 stream or HIP_STREAM_LEGACY))
         return out
+
+    @staticmethod
+    def temporal_camera(cam, width, height):
+        """(cam_pos [3], cam_matrix [16] or [4, 4]) and the frame's size -> ArtTemporalCamera"""
+        pos, mat = cam
+        pos = [float(v) for v in np.asarray(pos, np.float32).reshape(-1)]
+        mat = [float(v) for v in np.asarray(mat, np.float32).reshape(-1)]
+        if len(pos) != 3 or len(mat) != 16:
+            raise ArtError("temporal_torch: a camera is (cam_pos of 3 floats, cam_matrix of 16 floats, row-major)")
+        return ArtTemporalCamera((C.c_float * 3)(*pos), (C.c_float * 16)(*mat), int(width), int(height))
+
+    def temporal_torch(self, cur, history, cam_cur, cam_prev, n_colours, max_history=TEMPORAL_MAX_HISTORY, depth_tol=TEMPORAL_DEPTH_TOL,
+                       normal_min=TEMPORAL_NORMAL_MIN, scale=1.0, id_plane="prim_index"):
+        """Temporal reprojection and accumulation (art_temporal_device; include/art_hip.h states the arithmetic).  cur: a dict -- the one
+        of render_aovs_torch plus "color" (float32 [H, W, 3]; the tensor of bind_accum viewed so is accepted as it is, scale = 1 / spp)
+        and "moments" (float32 with 2 * H * W elements: the tensor of bind_moments as it is); of the guides "normal" [H, W, 3], "depth"
+        [H, W] and cur[id_plane] (int32 [H, W]) are read where present, every other entry is ignored.  history: the fourth result of
+        the previous call, or None for the first frame (cam_prev is then not read and may be None); its frame size is its own.
+        cam_cur, cam_prev: (cam_pos, cam_matrix).  n_colours: the colours behind color and moments.  Returns (out [H, W, 3], variance
+        [H, W], length [H, W], new_history [3, H, W, 4]), float32 tensors on color's device, enqueued on torch.cuda.current_stream()
+        without waiting for it.  Every tensor is checked before any C call.  The defaults of max_history, depth_tol and normal_min are
+        the best setting of the sweep in profiles/temporal/quality.json."""
+        torch = sys.modules.get("torch")
+        if not isinstance(cur, dict):
+            raise ArtError("temporal_torch: cur: a dict of planes is required, not %s" % type(cur).__name__)
+        color = cur.get("color")
+        if torch is None or not isinstance(color, torch.Tensor):
+            raise ArtError("temporal_torch: color: a torch tensor is required, not %s" % type(color).__name__)
+        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
+            raise ArtError("temporal_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
+        h, w = int(color.shape[0]), int(color.shape[1])
+        planes = [("color", color, 3, torch.float32), ("moments", cur.get("moments"), 2, torch.float32), ("normal", cur.get("normal"), 3, torch.float32),
+                  ("depth", cur.get("depth"), 1, torch.float32), (id_plane, cur.get(id_plane) if id_plane else None, 1, torch.int32),
+                  ("history", history, 0, torch.float32)]
+        for name, x, per, dtype in planes:
+            if x is None and name != "moments":
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise ArtError("temporal_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
+            if x.dtype != dtype:
+                raise ArtError("temporal_torch: %s: dtype must be %s, not %s" % (name, dtype, x.dtype))
+            if per == 2:
+                if x.numel() < 2 * h * w:
+                    raise ArtError("temporal_torch: moments: shape must hold at least %d elements ([H, W, 2]), not %s" % (2 * h * w, tuple(x.shape)))
+            elif per == 0:
+                if x.dim() != 4 or x.shape[0] != 3 or x.shape[3] != 4 or x.numel() == 0:
+                    raise ArtError("temporal_torch: history: shape must be [3, H', W', 4], not %s" % (tuple(x.shape),))
+            elif tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
+                raise ArtError("temporal_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
+            if not x.is_contiguous():
+                raise ArtError("temporal_torch: %s: the tensor must be contiguous" % name)
+        if history is not None and cam_prev is None:
+            raise ArtError("temporal_torch: cam_prev: a history needs the camera it was rendered with")
+        for name, cam in (("cam_cur", cam_cur), ("cam_prev", cam_prev if history is not None else None)):
+            if cam is not None and not (isinstance(cam, (tuple, list)) and len(cam) == 2):
+                raise ArtError("temporal_torch: %s: a camera is (cam_pos, cam_matrix)" % name)
+        if cam_cur is None:
+            raise ArtError("temporal_torch: cam_cur: a camera is (cam_pos, cam_matrix)")
+        for name, x, per, dtype in planes:
+            if x is not None and (x.device.type != "cuda" or x.device != color.device):
+                raise ArtError("temporal_torch: %s: must be a GPU tensor on %s, not on %s"
+                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        if int(n_colours) < 1:
+            raise ArtError("temporal_torch: n_colours must be at least 1, not %s" % (n_colours,))
+        p = ArtTemporalParams()
+        p.cur = self.temporal_camera(cam_cur, w, h)
+        if history is not None:
+            p.prev = self.temporal_camera(cam_prev, int(history.shape[2]), int(history.shape[1]))
+        p.n_colours, p.max_history = int(n_colours), int(max_history)
+        p.scale, p.depth_tol, p.normal_min = float(scale), float(depth_tol), float(normal_min)
+        dev = color.device
+        out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        var = torch.empty((h, w), dtype=torch.float32, device=dev)
+        length = torch.empty((h, w), dtype=torch.float32, device=dev)
+        new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
+        ptr = lambda x: None if x is None else x.data_ptr()
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.lib.art_temporal_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
+                                            ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
+        return out, var, length, new
 
     def _vertex_tensors(self, pos, nrm):
         """Validated, contiguous vertex tensors of refit_torch / rebuild_torch, and torch's current stream of their device."""
@@ -722,6 +832,16 @@ class Backend:
             if x is not None and (x.device.type != "cuda" or x.device != dev):
                 raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
         return torch, p, q, n, torch.cuda.current_stream(dev)
+
+    def set_camera(self, cam_pos, cam_matrix=None):
+        """Replace the camera of the uploaded scene without a rebuild (art_set_camera): cam_pos 3 floats, cam_matrix 16 floats row-major
+        or [4, 4] (None: the identity).  Stream-ordered on the library's stream: passes enqueued before see the old camera, later ones
+        the new; the result is a fresh upload's with that camera, bit for bit."""
+        pos = [float(v) for v in np.asarray(cam_pos, np.float32).reshape(-1)]
+        mat = [float(v) for v in (np.eye(4, dtype=np.float32) if cam_matrix is None else np.asarray(cam_matrix, np.float32)).reshape(-1)]
+        if len(pos) != 3 or len(mat) != 16:
+            raise ArtError("set_camera: cam_pos takes 3 floats and cam_matrix 16")
+        _check(self.lib.art_set_camera(C.byref((C.c_float * 3)(*pos)), C.byref((C.c_float * 16)(*mat))))
 
     def refit_torch(self, pos, nrm=None, check=True):
         """Move the vertices of the scene's CLOSEST mesh and refit its tree in place (art_refit_device): pos, nrm float32 [nverts, 3] tensors on

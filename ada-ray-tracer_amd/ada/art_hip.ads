@@ -191,8 +191,43 @@ package Art_Hip is
                                     variance_out : System.Address; hip_stream : System.Address) return int;
   pragma Import (C, art_denoise_svgf_device, "art_denoise_svgf_device");
 
+  --  The same filter fed by a variance plane (1 C float per pixel, art_temporal_device's variance_out) instead of the moments;
+  --  p.n_colours is ignored.
+  function art_denoise_svgf_var_device (p : access constant Art_Svgf_Params; color3f, variance1f, albedo3f, normal3f, depth, out3f,
+                                        variance_out : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_denoise_svgf_var_device, "art_denoise_svgf_var_device");
+
+  --  Temporal reprojection and accumulation (include/art_hip.h ArtTemporalParams, 188 bytes, states the arithmetic): the current frame's
+  --  planes, the previous history (Null_Address: the first frame) and the new one, art_temporal_history_bytes (w, h) bytes each, all
+  --  DEVICE memory; normal3f, depth, id, out3f, variance_out and length_out may be Null_Address.
+  type Art_Temporal_Camera is record
+    cam_pos       : Float3_C;
+    cam_matrix    : Float16_C;    --  row-major; elements 3, 7 and 11 must be zero
+    width, height : int;
+  end record;
+  pragma Convention (C, Art_Temporal_Camera);
+  type Art_Temporal_Params is record
+    cur, prev   : Art_Temporal_Camera;
+    n_colours   : int;     --  >= 1
+    max_history : int;     --  n_colours .. 2 ** 24
+    scale       : C_float;
+    depth_tol   : C_float;
+    normal_min  : C_float;
+  end record;
+  pragma Convention (C, Art_Temporal_Params);
+
+  function art_temporal_device (p : access constant Art_Temporal_Params; color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f,
+                                variance_out, length_out : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_temporal_device, "art_temporal_device");
+  function art_temporal_history_bytes (width, height : int) return long;
+  pragma Import (C, art_temporal_history_bytes, "art_temporal_history_bytes");
+
   --  Luminance moments of the render passes in caller-owned DEVICE memory: 2 C floats {S1, S2} per pixel, row-major, zeroed by
   --  art_resize, added to by every art_render_pass (include/art_hip.h).  Null_Address: none (the default).
+  --  The camera of the uploaded scene, without a rebuild (include/art_hip.h): stream-ordered on the library's stream, every context.
+  function art_set_camera (cam_pos : access constant Float3_C; cam_matrix : access constant Float16_C) return int;
+  pragma Import (C, art_set_camera, "art_set_camera");
+
   function art_bind_moments (device_moments_rowmajor : System.Address) return int;
   pragma Import (C, art_bind_moments, "art_bind_moments");
 

@@ -713,21 +713,21 @@ int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float*
 // art_denoise_svgf_device: the variance-guided filter of art_denoise.h's second half.  Scratch (b_denoise, shared with art_denoise_device:
 // both run in the queries' stream order): two images, the guide records, the depth plane and the depth gradients, 60 bytes per pixel.
 int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
-                        float* out3f, float* variance_out, hipStream_t st) {
-  const std::string name = "art_denoise_svgf_device";
+                        float* out3f, float* variance_out, hipStream_t st, bool variance_plane) {
+  const std::string name = variance_plane ? "art_denoise_svgf_var_device" : "art_denoise_svgf_device";
   if (!p) return fail(name + ": null ArtSvgfParams");
   if (!color3f || !out3f) return fail(name + ": null color3f or out3f");
-  if (!moments2f) return fail(name + ": null moments2f");
+  if (!moments2f) return fail(name + (variance_plane ? ": null variance1f" : ": null moments2f"));
   if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return fail(name + ": width and height must be at least 1 and width * height at most 2^28");
   if (p->iterations < 1 || p->iterations > 8) return fail(name + ": iterations must be 1 .. 8");
   if (p->normal_log2 < 0 || p->normal_log2 > 10) return fail(name + ": normal_log2 must be 0 .. 10");
-  if (p->n_colours < 2) return fail(name + ": n_colours must be at least 2");
+  if (!variance_plane && p->n_colours < 2) return fail(name + ": n_colours must be at least 2");
   if (!std::isfinite(p->scale)) return fail(name + ": scale is not finite");
   if (std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return fail(name + ": a sigma is NaN");
   if (ensure_device()) return 1;
   Ctx& c = g_ctx;
   const size_t N = (size_t)p->width * (size_t)p->height;
-  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || check_device_ptr(moments2f, 8 * N, "moments2f") ||
+  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || check_device_ptr(moments2f, (variance_plane ? 4 : 8) * N, variance_plane ? "variance1f" : "moments2f") ||
       (albedo3f && check_device_ptr(albedo3f, 12 * N, "albedo3f")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
       (depth && check_device_ptr(depth, 4 * N, "depth")) || (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")))
     return 1;
@@ -747,7 +747,34 @@ int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const floa
   A.color = color3f; A.moments = moments2f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f; A.variance_out = variance_out;
   dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
   A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N); A.z = (float*)(A.grad + N);
-  launch_denoise_svgf(order.qs, A, p->iterations);
+  if (variance_plane) launch_denoise_svgf_var(order.qs, A, p->iterations);      // (A.moments: the variance plane; A.n_colours is not read)
+  else launch_denoise_svgf(order.qs, A, p->iterations);
+  int rc = 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
+// art_temporal_device: one kernel over the caller's planes and histories (art_temporal.h), in the queries' stream order.  It has no scratch
+// (so nothing can make the host wait), needs no scene and no viewport and takes no event pair: ArtStats and ArtStageStats do not see it.
+int temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
+                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st) {
+  const std::string name = "art_temporal_device";
+  TemporalArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = tp::params_from_abi(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.cur.W * (size_t)A.P.cur.H, NP = (size_t)A.P.prev.W * (size_t)A.P.prev.H;
+  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(moments2f, 8 * N, "moments2f") || check_device_ptr(hist_out, 48 * N, "hist_out") ||
+      (hist_in && check_device_ptr(hist_in, 48 * NP, "hist_in")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
+      (depth && check_device_ptr(depth, 4 * N, "depth")) || (id && check_device_ptr(id, 4 * N, "id")) || (out3f && check_device_ptr(out3f, 12 * N, "out3f")) ||
+      (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")) || (length_out && check_device_ptr(length_out, 4 * N, "length_out")))
+    return 1;
+  StreamOrder order(c, st);
+  if (order.enter()) return 1;
+  A.n = (int32_t)N; A.color = color3f; A.moments = moments2f; A.normal = normal3f; A.depth = depth; A.id = id;
+  A.hist_in = (const tp::Rec4*)hist_in; A.hist_out = (tp::Rec4*)hist_out; A.out = out3f; A.variance_out = variance_out; A.length_out = length_out;
+  launch_temporal(order.qs, A);
   int rc = 0;
   if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
   if (order.leave()) return 1;          // (also after a failed launch)
@@ -944,6 +971,25 @@ int art_denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const 
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return denoise_svgf_device(p, color3f, moments2f, albedo3f, normal3f, depth, out3f, variance_out, (hipStream_t)hip_stream);
 }
+
+int art_denoise_svgf_var_device(const ArtSvgfParams* p, const float* color3f, const float* variance1f, const float* albedo3f, const float* normal3f, const float* depth,
+                                float* out3f, float* variance_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return denoise_svgf_device(p, color3f, variance1f, albedo3f, normal3f, depth, out3f, variance_out, (hipStream_t)hip_stream, true);
+}
+
+int art_temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
+                        const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return temporal_device(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f, variance_out, length_out, (hipStream_t)hip_stream);
+}
+
+int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
+  if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
+  return 48 * (int64_t)width * height;
+}
+
+int art_set_camera(const float cam_pos[3], const float cam_matrix[16]) { std::lock_guard<std::mutex> lk(g_mu); return set_camera(cam_pos, cam_matrix); }
 
 int art_refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);

@@ -253,7 +253,9 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
 int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);
 int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st);
 int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
-                        float* out3f, float* variance_out, hipStream_t st);
+                        float* out3f, float* variance_out, hipStream_t st, bool variance_plane = false);      // variance_plane: art_denoise_svgf_var_device, moments2f is variance1f
+int temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
+                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st);
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);
@@ -262,6 +264,7 @@ int get_rebuild_info(ArtRebuildInfo* out);
 int get_tree_cost(ArtTreeCost* out);
 int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st);
 int get_move_info(ArtMoveInfo* out);
+int set_camera(const float* cam_pos, const float* cam_matrix);
 int refit_mesh_device(int32_t mesh, const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_mesh_refit_info(ArtMeshRefitInfo* out);
 int rebuild_instance_tree_device(hipStream_t st);

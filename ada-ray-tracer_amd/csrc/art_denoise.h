@@ -153,6 +153,24 @@ ART_HD void svgf_pack_pixel(const Params& P, int32_t n_colours, const float* col
   }
 }
 
+// art_denoise_svgf_var_device: the same preparation with v_0 from a variance plane (one float per pixel) instead of the moments
+ART_HD void svgf_var_pack_pixel(const Params& P, const float* color, const float* variance, const float* albedo, const float* normal,
+                                const float* depth, int x, int y, Rec4& c, Rec4& g, float& z, Rec2& d) {
+  pack_pixel(P, color, albedo, normal, depth, x, y, c, g, d);
+  z = c.w;
+  const size_t p = (size_t)y * (size_t)P.W + (size_t)x;
+  double v = (double)variance[p] * ((double)P.scale * (double)P.scale);
+  if (P.demod) {
+    const double la = (double)lum3(albedo_floor(albedo[3 * p]), albedo_floor(albedo[3 * p + 1]), albedo_floor(albedo[3 * p + 2]));
+    v = v / (la * la);
+  }
+  c.w = (float)v;
+  if (!finite_f(c.w)) {
+    c.w = 0.0f;
+    g.w = __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, g.w) | kNoColourStop);
+  }
+}
+
 // iteration i at centre (x, y): {c_{i+1}, v_{i+1}}
 ART_HD Rec4 svgf_atrous_pixel(const Params& P, const Rec4* image, const Rec4* guide, const float* zplane, const Rec2* grad, int x, int y, int i) {
   const int s = 1 << i;

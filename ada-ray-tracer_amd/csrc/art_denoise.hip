@@ -20,6 +20,8 @@
 //                    centre, at spacing 1 whatever the iteration: neighbouring lanes' lines) and v carried through the filter.  LAST
 //                    stages the float3 output through LDS as k_atrous<true> does; variance_out is one dword per lane, contiguous as it is.
 //
+// art_denoise_svgf_var_device runs the same filter kernels behind k_svgf_var_pack, whose v_0 comes from a variance plane (one dword per lane).
+//
 // A lane's pixel is its linear index (y * W + x): 256 consecutive pixels of a row-major frame per workgroup.
 #define ART_F64_CONST_FREE      // m1::exp_small's coefficients as plain literals: no asm pin in these kernels (the value is the literal's either way)
 #include <hip/hip_runtime.h>
@@ -116,6 +118,24 @@ __global__ __launch_bounds__(kDnBlock) void k_svgf_atrous(const SvgfArgs A, cons
 void launch_denoise_svgf(hipStream_t st, const SvgfArgs& A, int iterations) {
   const dim3 grid((unsigned)((A.n + kDnBlock - 1) / kDnBlock)), block(kDnBlock);
   hipLaunchKernelGGL(k_svgf_pack, grid, block, 0, st, A);
+  for (int i = 0; i + 1 < iterations; ++i) hipLaunchKernelGGL(k_svgf_atrous<false>, grid, block, 0, st, A, i);
+  hipLaunchKernelGGL(k_svgf_atrous<true>, grid, block, 0, st, A, iterations - 1);
+}
+
+// ---- art_denoise_svgf_var_device: k_svgf_pack with v_0 from the caller's variance plane (A.moments names it); the filter launches are
+// art_denoise_svgf_device's own kernels
+__global__ __launch_bounds__(kDnBlock) void k_svgf_var_pack(const SvgfArgs A) {
+  const int p = blockIdx.x * kDnBlock + threadIdx.x;            // at most 2^28 pixels (the host's bound)
+  if (p >= A.n) return;
+  const int y = p / A.P.W, x = p - y * A.P.W;
+  dn::Rec4 c, g; dn::Rec2 d; float z;
+  dn::svgf_var_pack_pixel(A.P, A.color, A.moments, A.albedo, A.normal, A.depth, x, y, c, g, z, d);
+  A.image[0][p] = c; A.guide[p] = g; A.z[p] = z; A.grad[p] = d;
+}
+
+void launch_denoise_svgf_var(hipStream_t st, const SvgfArgs& A, int iterations) {
+  const dim3 grid((unsigned)((A.n + kDnBlock - 1) / kDnBlock)), block(kDnBlock);
+  hipLaunchKernelGGL(k_svgf_var_pack, grid, block, 0, st, A);
   for (int i = 0; i + 1 < iterations; ++i) hipLaunchKernelGGL(k_svgf_atrous<false>, grid, block, 0, st, A, i);
   hipLaunchKernelGGL(k_svgf_atrous<true>, grid, block, 0, st, A, iterations - 1);
 }

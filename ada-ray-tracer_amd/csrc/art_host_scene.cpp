@@ -90,9 +90,11 @@ bool flatten_scene(const ArtSceneDesc& d, const BvhBuildParams& bp, HostScene& o
     // follows it and the instances' inverse matrices, art_instanced_build.cpp)
     float extent = 0.0f;
     auto reach = [&](float v) { if (std::isfinite(v)) extent = std::max(extent, std::fabs(v)); };
-    for (int k = 0; k < 3; ++k) { reach(d.cam_pos[k]); if (d.has_cornell) { reach(d.cb_min[k]); reach(d.cb_max[k]); } }
+    for (int k = 0; k < 3; ++k) if (d.has_cornell) { reach(d.cb_min[k]); reach(d.cb_max[k]); }
     for (int i = 0; i < d.n_spheres; ++i) for (int k = 0; k < 3; ++k) reach(std::fabs(d.spheres[i].pos[k]) + std::fabs(d.spheres[i].r));
     for (int i = 0; i < d.n_lights; ++i) for (int k = 0; k < 3; ++k) { reach(d.lights[i].boxMin[k]); reach(d.lights[i].boxMax[k]); reach(std::fabs(d.lights[i].center[k]) + std::fabs(d.lights[i].radius)); }
+    out.extent_rest = extent;                                       // (max is exact and order-free: the camera's reach may come last)
+    for (int k = 0; k < 3; ++k) reach(d.cam_pos[k]);
     if (!build_two_level_host(meshes, insts, out.two, err, false, 1.0e-4f, 1.0e-5f, bp.inst_open, extent)) return false;
     int shift = 0; while ((1 << shift) < max_tris) ++shift;
     if (shift > 27 || ((uint64_t)d.n_instances << shift) > (1ull << 28)) { err = "scene: instances x triangles per mesh exceed the 28-bit hit index"; return false; }

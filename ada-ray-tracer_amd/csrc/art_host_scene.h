@@ -11,6 +11,7 @@
 namespace art {
 
 struct HostScene {
+  float extent_rest = 0.0f;           // instanced scenes: the scene extent without the camera (walls, spheres, lights); art_set_camera adds the camera's reach again
   std::vector<DevSphere> spheres; std::vector<int32_t> sphere_mat;
   std::vector<DevLight> lights;
   std::vector<DevMaterial> materials;

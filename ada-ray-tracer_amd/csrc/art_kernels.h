@@ -5,6 +5,7 @@
 #include "art_qnode.h"
 #include "art_instanced.h"
 #include "art_denoise.h"
+#include "art_temporal.h"
 
 namespace art {
 
@@ -131,6 +132,20 @@ struct SvgfArgs {
   dn::Rec4* image[2]; dn::Rec4* guide; float* z; dn::Rec2* grad;
 };
 void launch_denoise_svgf(hipStream_t st, const SvgfArgs& A, int iterations);
+// art_denoise_svgf_var_device: the same launches behind a pack kernel of its own, which reads A.moments as the variance plane (one float per
+// pixel) and ignores A.n_colours
+void launch_denoise_svgf_var(hipStream_t st, const SvgfArgs& A, int iterations);
+
+// art_temporal_device (art_temporal.hip, art_api.cpp temporal_device): the caller's current planes (normal / depth / id nullptr: not given),
+// the two histories (hist_in nullptr: the first frame) and the optional outputs; n = W * H of the current frame
+struct TemporalArgs {
+  tp::Params P;
+  int32_t n;
+  const float* color; const float* moments; const float* normal; const float* depth; const int32_t* id;
+  const tp::Rec4* hist_in; tp::Rec4* hist_out;
+  float* out; float* variance_out; float* length_out;
+};
+void launch_temporal(hipStream_t st, const TemporalArgs& A);
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex
@@ -145,6 +160,9 @@ struct RefitArgs {
   int32_t width; float inflate_rel, inflate_abs;
 };
 void launch_refit_tris(hipStream_t st, const RefitArgs& R);
+// art_set_camera (art_refit.hip): the 19 camera words of the scene header in HBM, passed by value so that the host's copy may change at once
+struct CameraWords { float w[19]; };           // cam_pos[3], cam_matrix[16]
+void launch_set_camera(hipStream_t st, DevScene* d_scene, const CameraWords& C);
 void launch_refit_level(hipStream_t st, const RefitArgs& R, const int32_t* level_nodes, int n);
 
 // a new tree from moved vertices and the cost figure of the tree in HBM (art_rebuild.hip, art_update.cpp art_rebuild_device / art_get_tree_cost)

@@ -73,6 +73,14 @@ __global__ __launch_bounds__(kRefitLevelBlock) void k_refit_level(const RefitArg
   });
 }
 
+// art_set_camera: lane k < 3 writes cam_pos[k], lane 3 + k cam_matrix[k] of the header the trace kernels take by pointer
+__global__ __launch_bounds__(64) void k_set_camera(DevScene* d, const CameraWords C) {
+  const int t = threadIdx.x;
+  if (t < 3) d->cam_pos[t] = C.w[t];
+  else if (t < 19) d->cam_matrix[t - 3] = C.w[t];
+}
+void launch_set_camera(hipStream_t st, DevScene* d_scene, const CameraWords& C) { hipLaunchKernelGGL(k_set_camera, dim3(1), dim3(64), 0, st, d_scene, C); }
+
 void launch_refit_tris(hipStream_t st, const RefitArgs& R) {
   const int64_t lanes = std::max<int64_t>({R.nverts, (int64_t)R.n_recs, R.nrm3f ? (int64_t)R.n_prims : 0});   // (n_recs = 0: art_rebuild_device, the shading records only)
   if (lanes <= 0) return;

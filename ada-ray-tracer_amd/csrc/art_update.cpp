@@ -381,6 +381,58 @@ int move_instances_device(const float* m12f, int64_t n_instances, hipStream_t st
                     [&](const void* const* src, hipStream_t s) { return move_one((const float*)src[0], s); });
 }
 
+// ---- the camera of the uploaded scene (art_set_camera) ------------------------------------------------------------------------------
+// What depends on the camera: cam_pos / cam_matrix of the scene header -- the host's copy (Ctx::scene), which raygen, shade, the AOV and
+// the query kernels take by value at launch, and the copy in HBM (d_scene) the trace kernels take by pointer (they do not read the
+// camera; it is kept equal) -- and, on an instanced scene, the scene extent (art_host_scene.cpp: the largest |coordinate| a ray can start
+// at), which the absolute pad of every mesh's boxes follows (art_move.hip k_move_pads_inst).  Pads only grow, as for a move: a camera
+// inside the extent the pads were made for changes nothing else; one outside it raises the extent and runs the move pipeline at the
+// matrices in force (pads, re-pad of the meshes that outgrow theirs, entry-point boxes, instance tree).  The flat tree, the BF mesh, the
+// spheres, lights and materials, the pixel map and the path state do not depend on the camera.
+static void set_camera_one(Ctx& c, const CameraWords& w, hipStream_t s) {
+  std::memcpy(c.scene.cam_pos, w.w, 12); std::memcpy(c.scene.cam_matrix, w.w + 3, 64);
+  launch_set_camera(s, c.d_scene, w);
+}
+
+int set_camera(const float* cam_pos, const float* cam_matrix) {
+  const std::string name = "art_set_camera";
+  Ctx& c0 = g_devs[0];
+  if (!c0.scene_ready) return fail(name + ": no scene uploaded");
+  HostScene& hs = c0.host_scene;
+  if (hs.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which has no camera");
+  if (!cam_pos || !cam_matrix) return fail(name + ": null cam_pos or cam_matrix");
+  CameraWords w;
+  std::memcpy(w.w, cam_pos, 12); std::memcpy(w.w + 3, cam_matrix, 64);
+  for (float v : w.w) if (!std::isfinite(v)) return fail(name + ": a component of the camera is not finite");
+  float extent = hs.extent_rest;
+  for (int k = 0; k < 3; ++k) extent = std::max(extent, std::fabs(cam_pos[k]));
+  const bool grow = c0.scene.n_inst > 0 && extent > hs.two.scene_extent;
+  auto note = [&] { std::memcpy(hs.hdr.cam_pos, w.w, 12); std::memcpy(hs.hdr.cam_matrix, w.w + 3, 64); };
+  if (!grow) {                             // every context's header, on its own stream: no plan, no wait
+    Dev0Guard guard;
+    for (int k = 0; k < g_ndev; ++k) {
+      if (use_dev(k)) return 1;
+      set_camera_one(g_ctx, w, g_ctx.stream);
+      if (hipGetLastError() != hipSuccess) return fail(name + ": kernel launch failed");
+    }
+    note();
+    return 0;
+  }
+  // the camera leaves the extent the pads were made for (the first update after an upload builds the plan a move shares, and waits for it)
+  return run_update(name, nullptr, [](Ctx& c) -> UpdateLane& { return c.move.lane; }, {},
+                    [&] { return !g_ctx.move.ready && build_move_plan(hs, name, g_move_info.plan_ms); },
+                    [&] { note(); hs.two.scene_extent = extent; },
+                    [&](const void* const*, hipStream_t s) {
+                      Ctx& c = g_ctx;
+                      set_camera_one(c, w, s);
+                      c.move.args.extent = (double)extent;
+                      MoveArgs A = c.move.args;
+                      A.m12f = A.m_cur; A.m_cur_out = nullptr; A.bad_total = nullptr; A.repads = A.state + 3;      // (a re-pad counts with the moves')
+                      launch_move_pipeline(c.move, A, s);
+                      return hipGetLastError() == hipSuccess ? 0 : fail(name + ": kernel launch failed");
+                    });
+}
+
 int get_move_info(ArtMoveInfo* out) { return get_info(out, "null ArtMoveInfo", g_move_info, fold_move); }
 
 // ---- deforming a mesh of an instanced scene (art_refit_mesh_device, art_refit.hip + art_move.hip) ---------------------------------

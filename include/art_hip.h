@@ -378,6 +378,115 @@ typedef struct ArtSvgfParams {
 int  art_denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f,
                              const float* normal3f, const float* depth, float* out3f, float* variance_out, void* hip_stream);
 
+/* The same filter fed by a variance plane instead of the moments: what art_temporal_device's variance_out is
+ * for, where every pixel has a history length of its own and one n_colours for the frame cannot express it.  variance1f: one float per
+ * pixel, row-major, the variance of the pixel's luminance estimate in the units of color3f BEFORE scale.  p->n_colours is ignored.
+ * Everything else -- pointers, overlap rule, stream order, scratch, refusals (a null variance1f in place of a null moments2f; no test of
+ * n_colours) -- is art_denoise_svgf_device's, and so is THE ARITHMETIC, except for v in the preparation, in binary64:
+ *   v = (double)variance1f * ((double)scale * (double)scale);   with demodulation v = v / (la * la) as there;   v_0 = (float)v,
+ *   and a v_0 that is not finite (a variance of +infinity: a pixel with fewer than two colours behind it) becomes +0.0f and marks the
+ *   pixel NO COLOUR STOP, exactly as there.  Everything after the preparation is the same text (csrc/art_denoise.h svgf_atrous_pixel).
+ * Against art_denoise_svgf_device: with variance1f = (float)(D0 * (n / (n - 1))) of that call's own formula the two calls round v twice
+ * and once, so their outputs are NOT the same bits in general.  They are when the second rounding is exact: scale a power of two, no
+ * demodulation, and neither v nor variance1f subnormal or overflowing (a power-of-two factor commutes with the rounding to binary32). */
+int  art_denoise_svgf_var_device(const ArtSvgfParams* p, const float* color3f, const float* variance1f, const float* albedo3f,
+                                 const float* normal3f, const float* depth, float* out3f, float* variance_out, void* hip_stream);
+
+/* Temporal reprojection and accumulation, the temporal half of SVGF (Schied et al. 2017): the previous frames'
+ * colour and luminance moments are reprojected into the current view by the two cameras and the current depth, checked against depth,
+ * normal and id, and blended with the current frame, so that the variance the spatial filter steers by comes from the whole history.
+ * Scene-independent like the denoisers: it needs an initialised device only, both cameras arrive in the params, and it touches no accum
+ * buffer, spp, ArtStats, ArtStageStats, path state or scratch (it has none: the host never waits).  Stream order and pointer rules are
+ * art_denoise_device's: every pointer is device memory of the library's device, row-major; NULL hip_stream = the library's stream.
+ * Current frame (cur.width x cur.height): color3f with scale as the denoisers take it; moments2f {S1, S2} and n_colours >= 1 in
+ * art_bind_moments' convention; normal3f, depth and id (an int32 plane, e.g. ArtAovBuffers::prim_index or mat) may each be NULL: its test
+ * is then passed by every tap, and without depth there is no reprojection (every pixel maps to itself).
+ * History: the caller's, one buffer in (hist_in, of the PREVIOUS frame's size prev.width x prev.height; NULL = the first frame, prev is
+ * then not read) and one out (hist_out, of the current frame's size), art_temporal_history_bytes(w, h) = 48 * w * h bytes each (0 for a
+ * size the call refuses).  They must not overlap: the kernel gathers neighbours.  Layout, for numpy to build and read: three planes of
+ * 16-byte records of four binary32 words, plane k at byte 16 * w * h * k, pixel (x, y) at record y * w + x:
+ *   plane 0 {r, g, b, n}     the mean colour (scaled) and the history length n in colours, as a float
+ *   plane 1 {m1, m2, z, id}  the mean luminance and the mean squared luminance per colour, the frame's depth and id (the int32's bits)
+ *   plane 2 {nx, ny, nz, 0}  the frame's normal
+ *   (z = +0.0f, id = 0, normal = (0, 0, 0) where the plane is not given).
+ * Outputs, each may be NULL: out3f = the blended mean colour (plane 0's r, g, b), length_out = n, variance_out = the variance of that
+ * mean's luminance, what art_denoise_svgf_var_device takes (with scale = 1).
+ * Refused before anything is launched, with art_last_error set: null p, color3f, moments2f or hist_out; a width or height < 1 or width *
+ * height > 2^28 (cur; prev when hist_in is given); n_colours < 1; max_history < n_colours or > 2^24; a scale that is not finite; depth_tol
+ * or normal_min NaN; a camera (cur; prev when hist_in is given) with a component that is not finite, with m[3], m[7] or m[11] not zero
+ * (camera_dir adds the translation column to a direction, a quirk of the reference no committed scene uses; this call does not follow
+ * it) or with a singular 3 x 3; hist_in and hist_out overlapping; any given pointer that is host memory, another device's memory or too
+ * small for its plane.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_temporal.h is its one definition, compiled for the GPU and for the host).  Binary32, not
+ * contracted, in the order written, division and sqrtf correctly rounded, except where binary64 is named.  dot(a, b) = (ax * bx + ay * by)
+ * + az * bz.  finite(v): neither NaN nor an infinity.  W, H = cur.width, cur.height; Wp, Hp = prev.width, prev.height.
+ * Per camera, on the host: cam_z = -(float)width / T with T = safe_tan(pi / 4) = 1.0f exactly (what make_frame computes, art_render.cpp);
+ *   M = rows (m[0], m[1], m[2]), (m[4], m[5], m[6]), (m[8], m[9], m[10]) of cam_matrix; its inverse I in binary64 from the binary32
+ *   elements: det = (M00 * C00 - M01 * C01) + M02 * C02 with C00 = M11 * M22 - M12 * M21, C01 = M10 * M22 - M12 * M20, C02 = M10 * M21 -
+ *   M11 * M20;  I = [ C00, M02 * M21 - M01 * M22, M01 * M12 - M02 * M11;  M12 * M20 - M10 * M22, M00 * M22 - M02 * M20, M02 * M10 - M00 * M12;
+ *   C02, M01 * M20 - M00 * M21, M00 * M11 - M01 * M10 ] / det, every product, difference and quotient rounded to binary64, each element
+ *   then rounded once to binary32.  Singular: det is zero or not finite, or an element of I is not finite in binary32.
+ * Pixel p = (x, y), n_cur = (float)n_colours:
+ *  1. c = scale * color;  m1 = S1 / n_cur;  m2 = S2 / n_cur;  z, id, N = the guides (the values above where a plane is not given).
+ *  2. The pixel takes NO HISTORY when hist_in is NULL; when depth is given and !(z > 0) (a miss: depth == 0 in the AOV convention) or z is
+ *     not finite; when normal3f is given and a component of N is not finite.
+ *  3. Where to look.  Without depth, or when prev equals cur word for word (cam_pos, cam_matrix, width, height): fx = (float)x + 0.5f,
+ *     fy = (float)y + 0.5f, e = z -- no reprojection, the fractional parts below are exactly 0.  Otherwise:
+ *       r = (((float)x + 0.5f) - (float)W / 2.0f, ((float)y + 0.5f) - (float)H / 2.0f, cam_z_cur);   u = (1.0f / sqrtf(dot(r, r))) * r;
+ *       t = M_cur u (row k: (Mk0 * ux + Mk1 * uy) + Mk2 * uz);   d = (1.0f / sqrtf(dot(t, t))) * t   -- camera_dir of the pixel centre;
+ *       v = (cam_pos_cur + z * d) - cam_pos_prev (per component);   e = sqrtf(dot(v, v));   q = I_prev v (rows as for M);
+ *       !(q.z * cam_z_prev > 0): behind the previous camera, NO HISTORY;   k = cam_z_prev / q.z;
+ *       fx = q.x * k + (float)Wp / 2.0f;   fy = q.y * k + (float)Hp / 2.0f   (previous-frame coordinates, pixel centres at + 0.5).
+ *     With aa_on the AOV depth is the mean of four rays' depths, not the centre ray's: the world point is then an approximation.
+ *  4. Gather.  gx = fx - 0.5f, gy = fy - 0.5f;  NO HISTORY unless gx > -1 and gx < (float)Wp and gy > -1 and gy < (float)Hp (a NaN fails).
+ *     ix = floorf(gx), ax = gx - floorf(gx), likewise iy, ay.  The taps t = 0..3 in this order: (ix, iy), (ix + 1, iy), (ix, iy + 1),
+ *     (ix + 1, iy + 1), with w = wx * wy, wx = ax for the right column and 1.0f - ax for the left, wy likewise.  A tap COUNTS when w > 0;
+ *     it is inside the previous frame; its r, g, b, n, m1, m2, z, nx, ny, nz are finite and its n > 0; with depth given,
+ *     fabsf(z_tap - e) <= depth_tol * e; with normal3f given, dot(N, N_tap) >= normal_min; with id given, id_tap == id.
+ *     Each tap that counts adds, per field of {r, g, b, n, m1, m2}:  sum += w * field;  and  wsum += w.  NO HISTORY unless wsum > 0;
+ *     else hist = sum / wsum per field, n_h = hist.n.  (SVGF searches a 3 x 3 neighbourhood when no tap counts; this call does not.)
+ *  5. Blend.  NO HISTORY: the pixel becomes its own history, colour c, m1, m2, n = n_cur.  Else cap = (float)max_history - n_cur;
+ *     f = (n_h > cap) ? cap / n_h : 1.0f;   n = n_cur + f * n_h;   a = n_cur / n;   b = 1.0f - a;
+ *     colour = a * c + b * hist.colour;   m1 = a * m1 + b * hist.m1;   m2 = a * m2 + b * hist.m2.
+ *     A colour that is not finite goes into the history as it is; no later frame counts that record as a tap, so the pixel starts again.
+ *  6. hist_out: plane 0 {colour, n}, plane 1 {m1, m2, z, id}, plane 2 {N, 0} -- the current frame's guides.  out3f = colour, length_out = n.
+ *     variance_out = +infinity where n < 2 (art_denoise_svgf_var_device reads it as "no colour stop"), else in binary64 (operands converted
+ *     first): D = m2 - m1 * m1;  D0 = (D < 0) ? 0 : D (a NaN stays);  (float)((D0 * (n / (n - 1))) / n).
+ * Reprojection is by camera only: a pixel on a surface that moved fails its depth or id test and starts again.  Quality:
+ * profiles/temporal/quality.json holds the sweep the defaults of Backend.temporal_torch were chosen by. */
+typedef struct ArtTemporalCamera {
+  float   cam_pos[3];
+  float   cam_matrix[16];    /* row-major, as ArtSceneDesc::cam_matrix; m[3], m[7], m[11] must be zero */
+  int32_t width, height;     /* the frame rendered with this camera */
+} ArtTemporalCamera;
+typedef struct ArtTemporalParams {
+  ArtTemporalCamera cur, prev;   /* prev: read only when hist_in is given */
+  int32_t n_colours;         /* >= 1: colours behind color3f and moments2f (spp / 4 with aa_on, else spp) */
+  int32_t max_history;       /* n_colours .. 2^24: the history length is capped here, so older frames fade out */
+  float   scale;             /* colour is multiplied by this first (1 / spp for an accum buffer) */
+  float   depth_tol;         /* a tap's depth may differ from the expected distance by this share of it */
+  float   normal_min;        /* least dot product of the two normals */
+} ArtTemporalParams;
+int  art_temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth,
+                         const int32_t* id, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
+                         void* hip_stream);
+int64_t art_temporal_history_bytes(int32_t width, int32_t height);
+
+/* The camera of the uploaded scene: cam_pos and cam_matrix replace ArtSceneDesc's in every context under
+ * art_init_devices, without a rebuild.  Stream-ordered on the library's stream (art_set_stream), like the other scene updates: work
+ * enqueued before the call sees the old camera, work enqueued after it the new one.  Every later pass, AOV call and query gives, bit for
+ * bit, what a fresh art_upload_scene of the same scene with that camera gives.  What follows the camera: the scene header (the host's
+ * copy the kernels take at launch, and the copy in HBM), and on an instanced scene the scene's extent -- the largest |coordinate| a ray
+ * can start at, the camera's included -- which the absolute pad of every mesh's boxes follows.  Pads only grow, as for
+ * art_move_instances_device: a camera inside the extent the pads were made for changes the header alone and the host never waits; a
+ * camera OUTSIDE it raises the extent and re-pads at the matrices in force by the kernels of a move (its re-pads count in
+ * ArtMoveInfo::repads), and the host waits only where that builds the plan a move shares (the first update after an upload).  The flat
+ * mesh's tree, the spheres, lights, materials, the pixel tiles and the path state do not depend on the camera.
+ * Refused before anything changes, with art_last_error set: no scene, a scene committed through gcore_commit_scene, a null pointer, a
+ * component that is not finite. */
+int  art_set_camera(const float cam_pos[3], const float cam_matrix[16]);
+
 /* Moving geometry.  Moves the vertices of the scene's ART_MESH_CLOSEST mesh and refits its tree in place: same
  * topology, same leaf order, new boxes (the builders' padding rule, quantised again at width 4), for every builder and both widths.
  * pos3f: device memory, 3*nverts floats, in the vertex order of the ArtMesh.pos uploaded; nrm3f: the same for normals, or NULL = keep

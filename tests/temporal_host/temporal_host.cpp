@@ -1,0 +1,124 @@
+// TEST-ONLY: art_temporal_device and art_denoise_svgf_var_device on host arrays, through the product's own per-pixel text
+// (csrc/art_temporal.h, csrc/art_denoise.h) compiled by g++.  The argument rules are the ABI's (include/art_hip.h); pointers are host
+// memory.  With -DTEMPORAL_HOST_MAIN the file is a program that runs both over inputs of its own and checks what can be checked without
+// a reference (the sanitizer build's target).
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <vector>
+#include "art_hip.h"
+#include "../../ada-ray-tracer_amd/csrc/art_temporal.h"
+
+using namespace art;
+
+extern "C" int th_temporal(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth,
+                           const int32_t* id, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out) {
+  tp::Params P;
+  if (tp::params_from_abi(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, P)) return 1;      // (the library's own derivation and refusals)
+  const size_t N = (size_t)P.cur.W * (size_t)P.cur.H;
+  tp::Rec4* ho = (tp::Rec4*)hist_out;
+  for (int y = 0; y < P.cur.H; ++y)
+    for (int x = 0; x < P.cur.W; ++x) {
+      const size_t q = (size_t)y * P.cur.W + x;
+      const tp::Out o = tp::temporal_pixel(P, color3f, moments2f, normal3f, depth, id, (const tp::Rec4*)hist_in, x, y);
+      ho[q] = o.h0; ho[N + q] = o.h1; ho[2 * N + q] = o.h2;
+      if (out3f) { out3f[3 * q] = o.h0.x; out3f[3 * q + 1] = o.h0.y; out3f[3 * q + 2] = o.h0.z; }
+      if (variance_out) variance_out[q] = o.variance;
+      if (length_out) length_out[q] = o.h0.w;
+    }
+  return 0;
+}
+
+extern "C" int th_denoise_svgf_var(const ArtSvgfParams* p, const float* color3f, const float* variance1f, const float* albedo3f, const float* normal3f,
+                                   const float* depth, float* out3f, float* variance_out) {
+  if (!p || !color3f || !out3f || !variance1f || p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return 1;
+  if (p->iterations < 1 || p->iterations > 8 || p->normal_log2 < 0 || p->normal_log2 > 10) return 1;
+  if (!std::isfinite(p->scale) || std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return 1;
+  dn::Params P;
+  P.W = p->width; P.H = p->height; P.normal_log2 = p->normal_log2; P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
+  P.has_normal = normal3f ? 1 : 0; P.has_depth = depth ? 1 : 0;
+  P.scale = p->scale; P.sigma_color = p->sigma_color; P.sigma_depth = p->sigma_depth;
+  const size_t N = (size_t)P.W * (size_t)P.H;
+  std::vector<dn::Rec4> image[2] = {std::vector<dn::Rec4>(N), std::vector<dn::Rec4>(N)}, guide(N);
+  std::vector<dn::Rec2> grad(N);
+  std::vector<float> z(N);
+  for (int y = 0; y < P.H; ++y)
+    for (int x = 0; x < P.W; ++x) {
+      const size_t q = (size_t)y * P.W + x;
+      dn::svgf_var_pack_pixel(P, color3f, variance1f, albedo3f, normal3f, depth, x, y, image[0][q], guide[q], z[q], grad[q]);
+    }
+  for (int i = 0; i < p->iterations; ++i)
+    for (int y = 0; y < P.H; ++y)
+      for (int x = 0; x < P.W; ++x)
+        image[(i + 1) & 1][(size_t)y * P.W + x] = dn::svgf_atrous_pixel(P, image[i & 1].data(), guide.data(), z.data(), grad.data(), x, y, i);
+  const std::vector<dn::Rec4>& last = image[p->iterations & 1];
+  for (size_t q = 0; q < N; ++q) {
+    dn::finish_pixel(P, albedo3f, q, last[q], out3f[3 * q], out3f[3 * q + 1], out3f[3 * q + 2]);
+    if (variance_out) variance_out[q] = last[q].w;
+  }
+  return 0;
+}
+
+#ifdef TEMPORAL_HOST_MAIN
+static uint32_t lcg(uint32_t& s) { s = s * 1664525u + 1013904223u; return s >> 8; }
+static float uni(uint32_t& s) { return (float)lcg(s) * (1.0f / 16777216.0f); }
+
+static ArtTemporalCamera camera(float px, float py, float pz, float yaw, int W, int H) {
+  ArtTemporalCamera c; std::memset(&c, 0, sizeof c);
+  c.cam_pos[0] = px; c.cam_pos[1] = py; c.cam_pos[2] = pz;
+  const float cs = std::cos(yaw), sn = std::sin(yaw);
+  c.cam_matrix[0] = cs; c.cam_matrix[2] = sn; c.cam_matrix[5] = 1.0f; c.cam_matrix[8] = -sn; c.cam_matrix[10] = cs; c.cam_matrix[15] = 1.0f;
+  c.width = W; c.height = H;
+  return c;
+}
+
+int main() {
+  uint32_t seed = 4321u;
+  int bad = 0;
+  if (art::safe_tan(art::kHalfPi / 2.0f) != 1.0f) { std::puts("safe_tan(pi / 4) is not 1.0f: the header's cam_z is wrong"); ++bad; }
+  const int sizes[][2] = {{1, 1}, {1, 7}, {7, 1}, {13, 9}, {64, 33}};
+  for (const auto& wh : sizes) {
+    const int W = wh[0], H = wh[1]; const size_t N = (size_t)W * H;
+    std::vector<float> color(3 * N), mom(2 * N), nrm(3 * N), dep(N), out(3 * N), var(N), len(N);
+    std::vector<int32_t> id(N);
+    std::vector<float> hist[2] = {std::vector<float>(12 * N), std::vector<float>(12 * N)};
+    const ArtTemporalCamera cams[5] = {camera(0, 0, 0, 0, W, H), camera(0, 0, 0, 0, W, H), camera(0.05f, 0, 0, 0.01f, W, H), camera(0, 0, -2, 0, W, H), camera(0, 0, -30, 3.0f, W, H)};
+    for (int f = 0; f < 5; ++f) {
+      for (size_t k = 0; k < N; ++k) {
+        for (int c = 0; c < 3; ++c) { color[3 * k + c] = 4.0f * uni(seed); nrm[3 * k + c] = (c == 2) ? 1.0f : 0.0f; }
+        const float l = dn::lum3(color[3 * k], color[3 * k + 1], color[3 * k + 2]);
+        mom[2 * k] = l; mom[2 * k + 1] = l * l / 4.0f * (1.0f + uni(seed));
+        dep[k] = 10.0f + 0.01f * uni(seed); id[k] = (int32_t)(k % 3);
+      }
+      if (N > 3 && f == 2) { color[3] = NAN; dep[N - 1] = NAN; nrm[6] = INFINITY; dep[2] = 0.0f; }
+      ArtTemporalParams p; std::memset(&p, 0, sizeof p);
+      p.cur = cams[f]; p.prev = cams[f ? f - 1 : 0]; p.n_colours = 4; p.max_history = 10; p.scale = 0.25f; p.depth_tol = 0.1f; p.normal_min = 0.9f;
+      const int rc = th_temporal(&p, color.data(), mom.data(), nrm.data(), dep.data(), id.data(), f ? hist[(f + 1) & 1].data() : nullptr, hist[f & 1].data(),
+                                 out.data(), var.data(), len.data());
+      if (rc) { std::printf("th_temporal refused frame %d (%d)\n", f, rc); return 1; }
+      for (size_t k = 0; k < N; ++k) {
+        if (!(len[k] >= 4.0f && len[k] <= 10.0f)) { std::printf("%d x %d frame %d: length of pixel %zu is %g\n", W, H, f, k, len[k]); ++bad; }
+        if (!(var[k] >= 0.0f) && !(N > 3 && f >= 2)) { std::printf("%d x %d frame %d: variance of pixel %zu is %g\n", W, H, f, k, var[k]); ++bad; }
+        if (f == 1 && len[k] != 8.0f) { std::printf("%d x %d: cameras at rest, pixel %zu has length %g, not 8\n", W, H, k, len[k]); ++bad; }
+        if (f == 0 && len[k] != 4.0f) { std::printf("%d x %d: first frame, pixel %zu has length %g\n", W, H, k, len[k]); ++bad; }
+      }
+      // the variance plane into the filter
+      ArtSvgfParams s = {W, H, 2, 0, 7, 0, 1.0f, 2.0f, 1.0f};
+      std::vector<float> fo(3 * N), fv(N);
+      if (th_denoise_svgf_var(&s, out.data(), var.data(), nullptr, nrm.data(), dep.data(), fo.data(), fv.data())) { std::puts("th_denoise_svgf_var refused"); return 1; }
+      for (size_t k = 0; k < N; ++k) if (!(fv[k] >= 0.0f)) { std::printf("%d x %d frame %d: filtered variance of pixel %zu is %g\n", W, H, f, k, fv[k]); ++bad; }
+    }
+    ArtTemporalParams r; std::memset(&r, 0, sizeof r);
+    r.cur = cams[0]; r.prev = cams[0]; r.n_colours = 4; r.max_history = 3; r.scale = 1.0f;
+    if (!th_temporal(&r, color.data(), mom.data(), nullptr, nullptr, nullptr, nullptr, hist[0].data(), nullptr, nullptr, nullptr)) { std::puts("max_history < n_colours was accepted"); ++bad; }
+    r.max_history = 8; r.cur.cam_matrix[3] = 1.0f;
+    if (th_temporal(&r, color.data(), mom.data(), nullptr, nullptr, nullptr, nullptr, hist[0].data(), nullptr, nullptr, nullptr) == 0) { std::puts("a translation column was accepted"); ++bad; }
+    r.cur = cams[0]; r.cur.cam_matrix[0] = 0.0f; r.cur.cam_matrix[2] = 0.0f;
+    if (th_temporal(&r, color.data(), mom.data(), nullptr, nullptr, nullptr, nullptr, hist[0].data(), nullptr, nullptr, nullptr) == 0) { std::puts("a singular matrix was accepted"); ++bad; }
+    r.cur = cams[0];
+    if (th_temporal(&r, color.data(), mom.data(), nullptr, nullptr, nullptr, hist[0].data(), hist[0].data(), nullptr, nullptr, nullptr) == 0) { std::puts("overlapping histories were accepted"); ++bad; }
+  }
+  std::printf("temporal_host: %s\n", bad ? "FAILED" : "ok");
+  return bad ? 1 : 0;
+}
+#endif
