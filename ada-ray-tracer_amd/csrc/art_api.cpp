@@ -1112,6 +1112,7 @@ static int set_option_one(const std::string& n, int64_t value) {
   else if (n == "query_slice") { if (value < 1 || value > (1ll << 28)) return fail("query_slice: 1 .. 2^28 rays per slice of a device query"); g_ctx.opt.query_slice = value; }
   else if (n == "count_tests") { g_ctx.opt.count_tests = value != 0; }
   else if (n == "camera_dedup") { if (value != 0 && value != 1) return fail("camera_dedup: 0 (every sample's camera ray is traced) or 1 (each distinct camera ray once per batch)"); g_ctx.opt.camera_dedup = value != 0; }
+  else if (n == "camera_order") { if (value != 0 && value != 1) return fail("camera_order: 0 (bounce 0 visits the path slots in slot order) or 1 (tile-major: all samples of a 1024-pixel block before the next block)"); g_ctx.opt.camera_order = (int)value; }
   else if (n == "shadow_anyhit") { g_ctx.opt.shadow_anyhit = value != 0; }
   else if (n == "skip_null_shadow") { g_ctx.opt.skip_null_shadow = value != 0; }
   else if (n == "inst_coop") { g_ctx.opt.inst_coop = value != 0; }

@@ -43,6 +43,8 @@ struct Options {
   int opt_blocks_per_cu = 0;
   bool count_tests = false;
   bool camera_dedup = true;      // each distinct camera ray of a batch is generated and traced once (DevPaths::cam_dedup); false: once per sample
+  int camera_order = 1;          // the order in which bounce 0 visits a batch's slots (and every later stage its items): 0 slot order (sample-major), 1 tile-major -- all samples
+                                 // of 1024 pixels before the next 1024 (art_camera_order.h).  The frame does not depend on it.  Measured: profiles/camera_order/README.md
   int node_min = 0;              // the trace kernel leaves its node loop when fewer than 8 x node_min lanes still expand nodes.  0: 4 (the optimum on C4, profiles/r2_sensitivity.json);
                                  // 2 for an instanced scene -- its groups also wait for instance entries, and leaving the loop for them less often is worth 6 % on I64 (profiles/r5_inst_sweep.py)
   int refill_min = 2;            // idle ray groups of a wave take new rays when two of them are idle (1: at once; measured 0.5-1 % slower)

@@ -22,6 +22,7 @@
 #include <algorithm>
 #include <type_traits>
 #include "art_kernels.h"
+#include "art_camera_order.h"
 
 namespace art {
 
@@ -846,6 +847,9 @@ constexpr int kShadePerThread = 4;
 constexpr int kShadeWavesPerSimd = 6;
 // CAMERA: bounce 0 over raygen's bank (DevPaths::synth0: flags, previous pdf and the camera ray are recomputed, not read) -- its own
 // instantiation, so that the other bounces' code is exactly what it was (as one kernel the extra branch cost 17 more spilled VGPRs: +7 %)
+// CAMERA items are slots, so a round may take ANY 256 consecutive slots of a sample row: with option camera_order = 1 round k of
+// workgroup g takes unit g * PER + k of the tile-major order of art_camera_order.h (all samples of 1024 pixels before the next 1024)
+// instead of slots [c0 + 256 k, c0 + 256 k + 256).  The unit's first slot and size are wave-uniform: scalars, computed once per round.
 // The stage's arguments as ONE struct: about 240 dwords of scene header and array pointers.  Taken by value the compiler loads all of them
 // into SGPRs at the kernel's entry and keeps them live to its end (spilled to VGPR lanes).  The code reads the fields through a pointer
 // to the kernarg segment instead, laundered at the head of every round so that a field is a scalar load (scalar cache) where it is used
@@ -853,6 +857,7 @@ constexpr int kShadeWavesPerSimd = 6;
 struct ShadeKernArgs {
   DevFrame F; DevScene S; DevPaths Qi; DevPaths Qo; int bounce;
   const int* n_in_ptr; int* n_out_ptr; uint32_t* slot_out; unsigned long long* lost; unsigned long long* rays_a; unsigned long long* rays_b;
+  int cam_order, cam_sn;      // CAMERA only (the last fields: the other instantiation's offsets are what they were): option camera_order, samples of the batch (P / npix)
 };
 static_assert(sizeof(ShadeKernArgs) <= 4096 && __is_trivially_copyable(ShadeKernArgs), "ShadeKernArgs is the kernel's ONLY parameter: it sits at offset 0 of the kernarg segment");
 typedef const __attribute__((address_space(4))) ShadeKernArgs* ShadeKArgs;
@@ -870,6 +875,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kShadeWaves
   __shared__ int s_tot[PER * kItemClasses];                // items of each class in each round (256 items) of the chunk
   __shared__ int s_base, s_rays;
   __shared__ int s_nall[PER], s_nkeep[PER], s_out0[PER];   // per round: items, survivors, first output item (relative to s_base)
+  __shared__ int s_slot0[CAMERA ? PER : 1];                // CAMERA: per round, the first of its 256 consecutive slots
   // [round][sorted position] -> { hit key, thread that classified the item | surface flag << 8 | material index << 9 }: what the
   // classification fetched goes along (ItemHint), so that shade_item asks for the triangle's normals and the material record at once
   __shared__ uint2 s_hint[kShadeChunk];
@@ -881,7 +887,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kShadeWaves
   __shared__ DevLight s_lgt[kShadeLdsLights];
   const int n_in = n_in_ptr ? *n_in_ptr : Qi.P;
   const int c0 = blockIdx.x * kShadeChunk;
-  if (c0 >= n_in) return;                                // the grid covers Qi.P items; the work set has shrunk to n_in
+  const int cam_order = CAMERA ? K->cam_order : 0;
+  if (CAMERA && cam_order) { if ((int)blockIdx.x * PER >= camera_order_units(Qi.npix, K->cam_sn)) return; }      // the grid covers the visiting space, in units
+  else if (c0 >= n_in) return;                           // the grid covers Qi.P items; the work set has shrunk to n_in
   // (the material table stays in global memory: a 40-byte per-lane-indexed record out of LDS measured 7 % slower than the cached global read)
   const bool tables_in_lds = (S.n_spheres <= kAnalyticLdsSpheres) && (S.n_lights <= kShadeLdsLights);
   if (tables_in_lds) {
@@ -910,7 +918,20 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kShadeWaves
     // the PER classifications as ONE batch of loads per step (item_classes: 3 memory round trips; item by item through item_class they were 20)
     int wk[PER]; bool on[PER];
 #pragma unroll
-    for (int k = 0; k < PER; ++k) { wk[k] = c0 + k * 256 + (int)threadIdx.x; on[k] = wk[k] < n_in; hint[k].key = KEY_MISS; hint[k].mat = 0; cls[k] = kItemClasses; }
+    for (int k = 0; k < PER; ++k) {
+      if (CAMERA) {
+        OrderUnit u; u.slot0 = c0 + k * 256; u.count = n_in - u.slot0;      // slot order
+        if (cam_order) {
+          const int ui = (int)blockIdx.x * PER + k;                          // tile-major: a unit past the last one is padding
+          u.count = 0;
+          if (ui < camera_order_units(Qi.npix, K->cam_sn)) u = camera_order_unit(Qi.npix, K->cam_sn, ui);
+        }
+        u.slot0 = __builtin_amdgcn_readfirstlane(u.slot0); u.count = __builtin_amdgcn_readfirstlane(u.count);
+        wk[k] = u.slot0 + (int)threadIdx.x; on[k] = (int)threadIdx.x < u.count;
+        if (threadIdx.x == 0) s_slot0[k] = u.slot0;                          // (read after barrier 1)
+      } else { wk[k] = c0 + k * 256 + (int)threadIdx.x; on[k] = wk[k] < n_in; }
+      hint[k].key = KEY_MISS; hint[k].mat = 0; cls[k] = kItemClasses;
+    }
     item_classes<PER>(S, Qi, wk, on, tables, CAMERA, cls, hint);
   }
   ART_TPROBE(tables.tprobe, 64);      // classification loads
@@ -973,7 +994,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kShadeWaves
     const int wo = r < n_keep_k ? base + out0_k + r : -1;
     if (r < n_all_k) {
       const uint2 hk = s_hint[k * 256 + r];
-      const int w = c0 + k * 256 + (int)(hk.y & 255u);
+      const int w = (CAMERA ? __builtin_amdgcn_readfirstlane(s_slot0[k]) : c0 + k * 256) + (int)(hk.y & 255u);
       ItemHint ih; ih.key = hk.x; ih.mat = (hk.y & 256u) ? (int32_t)(hk.y >> 9) : -1;      // mat < 0: no hint (shade_item)
       // (the output item's slot word is written by shade_item with the item's other words: qo.slot_id IS slot_out)
       StageCtx cy = tables;
@@ -1124,14 +1145,19 @@ __global__ void k_probe_on(int v) { g_lane_probe_on = v; }
 #endif
 void launch_shade_compact(hipStream_t st, const DevFrame& F, const DevScene& S, const DevPaths& Qi, const DevPaths& Qo, int bounce,
                           const int* n_in, int* n_out, uint32_t* slot_out, unsigned long long* lost, unsigned long long* rays_a, unsigned long long* rays_b,
-                          int per) {
+                          int per, int camera_order) {
   const bool camera = Qi.synth0 && Qi.slot_id == nullptr;
   const int per_now = (per == 2) ? 2 : kShadePerThread;      // items per thread of this launch
-  const dim3 grid((Qi.P + 256 * per_now - 1) / (256 * per_now));
+  // rounds of 256 items: the items of the bank, or (bounce 0, option camera_order) the units of the tile-major visiting order
+  const int cam_sn = Qi.npix > 0 ? Qi.P / Qi.npix : 0;
+  const bool tile_major = camera && camera_order != 0 && cam_sn > 0;
+  const int rounds = tile_major ? camera_order_units(Qi.npix, cam_sn) : (Qi.P + 255) / 256;
+  const dim3 grid((rounds + per_now - 1) / per_now);
 #if defined(ART_LANE_PROBE)
   hipLaunchKernelGGL(k_probe_on, dim3(1), dim3(1), 0, st, 1);
 #endif
   ShadeKernArgs A; A.F = F; A.S = S; A.Qi = Qi; A.Qo = Qo; A.bounce = bounce; A.n_in_ptr = n_in; A.n_out_ptr = n_out; A.slot_out = slot_out; A.lost = lost; A.rays_a = rays_a; A.rays_b = rays_b;
+  A.cam_order = tile_major ? 1 : 0; A.cam_sn = cam_sn;
   if (per_now == 2) {
     if (camera) hipLaunchKernelGGL((k_shade_compact<2, true>), grid, dim3(256), 0, st, A);
     else hipLaunchKernelGGL((k_shade_compact<2, false>), grid, dim3(256), 0, st, A);

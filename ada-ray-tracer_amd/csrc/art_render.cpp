@@ -256,7 +256,7 @@ static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const
     HIP_TRY(hipMemsetAsync(n_out, 0, sizeof(int), c.stream));
     { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(1, trial)));
       launch_shade_compact(c.stream, F, c.scene, qi, bank[out], b, b == 0 ? nullptr : n_in, n_out,
-                           const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + CNT_LOST, c.d_counters + CNT_RAYS, rays_b, shade_per); }
+                           const_cast<uint32_t*>(bank[out].slot_id), c.d_counters + CNT_LOST, c.d_counters + CNT_RAYS, rays_b, shade_per, c.opt.camera_order); }
     if (b == 0 && c.inject_lost) { launch_bump(c.stream, c.d_counters + CNT_LOST, nullptr, 1ull); c.inject_lost = 0; }      // test option: what a stage does when it loses a path
     if (g_debug_live) {
       int n = -1; unsigned long long r0 = 0;
