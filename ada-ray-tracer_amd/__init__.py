@@ -112,6 +112,10 @@ class ArtAovBuffers(C.Structure):
                 ("prim_type", C.c_void_p), ("prim_index", C.c_void_p), ("mat", C.c_void_p)]
 
 
+class ArtMotionSource(C.Structure):
+    _fields_ = [("cur_pos3f", C.c_void_p), ("prev_pos3f", C.c_void_p), ("nverts", C.c_int64), ("prev_m12f", C.c_void_p), ("n_instances", C.c_int64)]
+
+
 class ArtDenoiseParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("iterations", C.c_int32), ("demodulate", C.c_int32),
                 ("normal_log2", C.c_int32), ("variant", C.c_int32), ("scale", C.c_float), ("sigma_color", C.c_float), ("sigma_depth", C.c_float)]
@@ -229,7 +233,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_history_bytes", "art_set_camera",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_set_camera",
     "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
@@ -276,11 +280,13 @@ def load_library():
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
+    L.art_render_aovs_motion_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.POINTER(ArtMotionSource), C.c_void_p, C.c_void_p]
     L.art_denoise_device.argtypes = [C.POINTER(ArtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_denoise_svgf_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
     L.art_set_camera.argtypes = [C.POINTER(C.c_float * 3), C.POINTER(C.c_float * 16)]
     L.art_denoise_svgf_var_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
     L.art_temporal_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 11
+    L.art_temporal_motion_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 12
     L.art_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
     L.art_temporal_history_bytes.restype = C.c_int64
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -627,6 +633,53 @@ class Backend:
         _check(self.lib.art_render_aovs_device(C.byref(params), C.byref(buf), stream or HIP_STREAM_LEGACY))
         return out
 
+    def render_aovs_torch_motion(self, params, want=tuple(AOV_PLANES), cur_pos=None, prev_pos=None, prev_matrices=None):
+        """render_aovs_torch plus the motion plane (art_render_aovs_motion_device; include/art_hip.h states the arithmetic): the same
+        dict with "motion", float32 [H, W, 3] -- where each pixel's surface point was one update ago minus where it is -- from one
+        trace of the camera rays.  Flat scene: cur_pos = the vertices in force (what refit_torch was last given), prev_pos = those one
+        update earlier, float32 [nverts, 3] GPU tensors, both or neither.  Instanced scene: prev_matrices = the matrices one update
+        earlier, float32 [n_instances, 12] (or [n, 3, 4]).  All None: the plane is zero.  `want` may be empty.  Every tensor is checked
+        before any C call; what the library refuses (a wrong count, arrays of the other kind of scene) raises ArtError."""
+        want = tuple(want)
+        for name in want:
+            if name not in AOV_PLANES:
+                raise ValueError("render_aovs_torch_motion: unknown plane %r (known: %s)" % (name, ", ".join(AOV_PLANES)))
+        import torch
+        src = ArtMotionSource()
+        for name, x, last in (("cur_pos", cur_pos, 3), ("prev_pos", prev_pos, 3), ("prev_matrices", prev_matrices, 12)):
+            if x is None:
+                continue
+            if not isinstance(x, torch.Tensor):
+                raise ArtError("render_aovs_torch_motion: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
+            if x.dtype != torch.float32:
+                raise ArtError("render_aovs_torch_motion: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
+            if x.dim() < 2 or x.numel() == 0 or x.numel() != x.shape[0] * last:
+                raise ArtError("render_aovs_torch_motion: %s: shape must be [n, %d], not %s" % (name, last, tuple(x.shape)))
+            if not x.is_contiguous():
+                raise ArtError("render_aovs_torch_motion: %s: the tensor must be contiguous" % name)
+            if x.device.type != "cuda":
+                raise ArtError("render_aovs_torch_motion: %s: must be a GPU tensor, not on %s" % (name, x.device))
+        if (cur_pos is None) != (prev_pos is None):
+            raise ArtError("render_aovs_torch_motion: cur_pos and prev_pos must both be given or both be None")
+        if cur_pos is not None:
+            if cur_pos.shape[0] != prev_pos.shape[0]:
+                raise ArtError("render_aovs_torch_motion: cur_pos and prev_pos differ in length")
+            src.cur_pos3f, src.prev_pos3f, src.nverts = cur_pos.data_ptr(), prev_pos.data_ptr(), int(cur_pos.shape[0])
+        if prev_matrices is not None:
+            src.prev_m12f, src.n_instances = prev_matrices.data_ptr(), int(prev_matrices.shape[0])
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+        dev = torch.device("cuda", torch.cuda.current_device())
+        h, w = getattr(self, "height", 0), getattr(self, "width", 0)
+        out, buf = {}, ArtAovBuffers()
+        for name in want:
+            field, per, integer = AOV_PLANES[name]
+            out[name] = torch.empty((h, w, 3) if per == 3 else (h, w), dtype=torch.int32 if integer else torch.float32, device=dev)
+            setattr(buf, field, out[name].data_ptr() or None)
+        out["motion"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.lib.art_render_aovs_motion_device(C.byref(params), C.byref(buf), C.byref(src), out["motion"].data_ptr() or None, stream or HIP_STREAM_LEGACY))
+        return out
+
     def denoise_torch(self, color, albedo=None, normal=None, depth=None, iterations=5, scale=1.0, sigma_color=4.0, sigma_depth=1.0,
                       normal_log2=7, demodulate=True, out=None, variant=0, **other_planes):
         """Edge-avoiding a-trous filter of `color` guided by the feature buffers (art_denoise_device; include/art_hip.h states the
@@ -740,7 +793,7 @@ class Backend:
         return ArtTemporalCamera((C.c_float * 3)(*pos), (C.c_float * 16)(*mat), int(width), int(height))
 
     def temporal_torch(self, cur, history, cam_cur, cam_prev, n_colours, max_history=TEMPORAL_MAX_HISTORY, depth_tol=TEMPORAL_DEPTH_TOL,
-                       normal_min=TEMPORAL_NORMAL_MIN, scale=1.0, id_plane="prim_index"):
+                       normal_min=TEMPORAL_NORMAL_MIN, scale=1.0, id_plane="prim_index", motion=None):
         """Temporal reprojection and accumulation (art_temporal_device; include/art_hip.h states the arithmetic).  cur: a dict -- the one
         of render_aovs_torch plus "color" (float32 [H, W, 3]; the tensor of bind_accum viewed so is accepted as it is, scale = 1 / spp)
         and "moments" (float32 with 2 * H * W elements: the tensor of bind_moments as it is); of the guides "normal" [H, W, 3], "depth"
@@ -749,7 +802,9 @@ class Backend:
         cam_cur, cam_prev: (cam_pos, cam_matrix).  n_colours: the colours behind color and moments.  Returns (out [H, W, 3], variance
         [H, W], length [H, W], new_history [3, H, W, 4]), float32 tensors on color's device, enqueued on torch.cuda.current_stream()
         without waiting for it.  Every tensor is checked before any C call.  The defaults of max_history, depth_tol and normal_min are
-        the best setting of the sweep in profiles/temporal/quality.json."""
+        the best setting of the sweep in profiles/temporal/quality.json.
+        motion: float32 [H, W, 3] or None -- the "motion" plane of render_aovs_torch_motion for this frame; given, the call is
+        art_temporal_motion_device, which follows surfaces that moved (cur["motion"] is NOT read: the plane is named explicitly)."""
         torch = sys.modules.get("torch")
         if not isinstance(cur, dict):
             raise ArtError("temporal_torch: cur: a dict of planes is required, not %s" % type(cur).__name__)
@@ -761,7 +816,7 @@ class Backend:
         h, w = int(color.shape[0]), int(color.shape[1])
         planes = [("color", color, 3, torch.float32), ("moments", cur.get("moments"), 2, torch.float32), ("normal", cur.get("normal"), 3, torch.float32),
                   ("depth", cur.get("depth"), 1, torch.float32), (id_plane, cur.get(id_plane) if id_plane else None, 1, torch.int32),
-                  ("history", history, 0, torch.float32)]
+                  ("history", history, 0, torch.float32), ("motion", motion, 3, torch.float32)]
         for name, x, per, dtype in planes:
             if x is None and name != "moments":
                 continue
@@ -805,6 +860,10 @@ class Backend:
         new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
         ptr = lambda x: None if x is None else x.data_ptr()
         stream = torch.cuda.current_stream(dev).cuda_stream
+        if motion is not None:
+            _check(self.lib.art_temporal_motion_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
+                                                       ptr(motion), ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
+            return out, var, length, new
         _check(self.lib.art_temporal_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
                                             ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
         return out, var, length, new

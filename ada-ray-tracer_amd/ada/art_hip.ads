@@ -154,6 +154,21 @@ package Art_Hip is
                                    hip_stream : System.Address) return int;
   pragma Import (C, art_render_aovs_device, "art_render_aovs_device");
 
+  --  The same call with a motion plane (3 C floats per pixel, DEVICE memory): where each pixel's surface point was one scene update ago
+  --  minus where it is (include/art_hip.h ArtMotionSource, 40 bytes, states the arithmetic).  Flat scene: cur_pos3f and prev_pos3f, both or
+  --  neither; instanced scene: prev_m12f; Null_Address: nothing moved.  buffers may be null when motion3f is given.
+  type Art_Motion_Source is record
+    cur_pos3f, prev_pos3f : System.Address;         --  3 C floats per vertex, DEVICE memory
+    nverts                : Interfaces.Integer_64;
+    prev_m12f             : System.Address;         --  12 C floats per instance, DEVICE memory
+    n_instances           : Interfaces.Integer_64;
+  end record;
+  pragma Convention (C, Art_Motion_Source);
+  function art_render_aovs_motion_device (p : access constant Art_Pass_Params; buffers : access constant Art_Aov_Buffers;
+                                          src : access constant Art_Motion_Source; motion3f : System.Address;
+                                          hip_stream : System.Address) return int;
+  pragma Import (C, art_render_aovs_motion_device, "art_render_aovs_motion_device");
+
   --  Edge-avoiding a-trous denoiser over device planes (include/art_hip.h ArtDenoiseParams, 36 bytes, states the arithmetic): color3f,
   --  albedo3f, normal3f (3 C floats per pixel) and depth (1) are DEVICE memory of the library's GPU, row-major; the three guides may be
   --  Null_Address; out3f may be color3f.  Needs no scene and no viewport; hip_stream = Null_Address is the library's stream.
@@ -219,6 +234,11 @@ package Art_Hip is
   function art_temporal_device (p : access constant Art_Temporal_Params; color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f,
                                 variance_out, length_out : System.Address; hip_stream : System.Address) return int;
   pragma Import (C, art_temporal_device, "art_temporal_device");
+  --  art_temporal_device following moved geometry: motion3f is art_render_aovs_motion_device's plane of the current frame
+  --  (Null_Address: the call is art_temporal_device).
+  function art_temporal_motion_device (p : access constant Art_Temporal_Params; color3f, moments2f, normal3f, depth, id, motion3f, hist_in,
+                                       hist_out, out3f, variance_out, length_out : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_temporal_motion_device, "art_temporal_motion_device");
   function art_temporal_history_bytes (width, height : int) return long;
   pragma Import (C, art_temporal_history_bytes, "art_temporal_history_bytes");
 

@@ -9,10 +9,13 @@
 //                   sums (((v0 + v1) + v2) + v3) * 0.25f (k = 1: v0).  The float3 planes are staged through LDS at a stride of 3
 //                   dwords (odd: no bank conflict), as k_query_finalize stages its records, so that every store of a wave is 256
 //                   contiguous bytes; the scalar planes are stored directly.  A plane that is not wanted costs no store, and the work
-//                   that only it needs -- surface_at(), the material fetch -- is not done.
+//                   that only it needs -- surface_at(), the material fetch -- is not done.  The motion plane of
+//                   art_render_aovs_motion_device is a template flag: a third float3 staged the same way, its per-hit arithmetic in
+//                   art_motion.h.
 //
 // Between the two the rays go through the render loop's own trace launch (art_api.cpp trace()).
 #include <hip/hip_runtime.h>
+#include <type_traits>
 #include "art_kernels.h"
 
 namespace art {
@@ -29,9 +32,15 @@ __global__ __launch_bounds__(kAovBlock) void k_aov_raygen(const DevFrame F, cons
   A.tf[i] = kInfinity;
 }
 
-// K: rays per pixel (4 or 1).  All lanes of the workgroup reach the barrier.
-template <int K>
-__global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, const DevScene S, const AovArgs A) {
+// the motion plane's staging area, a lane's float3 at a stride of 3 dwords like the two below: only the MOTION instantiations call this,
+// so only they carry the 3 KB
+__device__ __forceinline__ float* motion_lds() { __shared__ float s_mot[3 * kAovBlock]; return s_mot; }
+
+// K: rays per pixel (4 or 1).  MOTION: the call wants the motion plane (AovMotionArgs; art_motion.h) -- its loads (the index triple and
+// six vertices of a flat mesh hit, two instance records and the ray of an instanced one) exist in these instantiations only, and the
+// others are the kernels they were before the plane existed.  All lanes of the workgroup reach the barrier.
+template <int K, bool MOTION>
+__global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, const DevScene S, const std::conditional_t<MOTION, AovMotionArgs, AovArgs> A) {
   __shared__ float s_alb[3 * kAovBlock], s_nrm[3 * kAovBlock];  // a lane's float3 at a stride of 3 dwords
   const int b0 = blockIdx.x * kAovBlock;
   const int l = b0 + (int)threadIdx.x;
@@ -39,6 +48,7 @@ __global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, con
   if (l < A.n) {
     const f3 o = ld3(S.cam_pos), zero = mk3(0.0f, 0.0f, 0.0f), bg = ld3(F.background);
     f3 alb[K], nrm[K]; float dep[K], cov[K];
+    [[maybe_unused]] float mx[K], my[K], mz[K];
     int32_t pt = -1, pi = -1, pm = -1;
 #pragma unroll
     for (int s = 0; s < K; ++s) {
@@ -59,6 +69,14 @@ __global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, con
         pt = (cls == KEY_CORNELL) ? 0 : (cls == KEY_SPHERE) ? 1 : (cls == KEY_QUAD) ? 3 : 2;
         pi = (int32_t)(h.key & KEY_INDEX_MASK);
       }
+      if constexpr (MOTION) {
+        mo::V3 dl = {0.0f, 0.0f, 0.0f};
+        if (hit && (h.key & ~KEY_INDEX_MASK) == KEY_TRI) {
+          const bool ray = A.src.inst != nullptr && A.src.prev_m != nullptr;             // only an instanced hit needs the hit point
+          dl = mo::hit_delta(A.src, S.cam_pos, h.key, h.t, h.u, h.v, ray ? A.dx[i] : 0.0f, ray ? A.dy[i] : 0.0f, ray ? A.dz[i] : 0.0f);
+        }
+        mx[s] = dl.x; my[s] = dl.y; mz[s] = dl.z;
+      }
     }
     auto mean = [](const float (&v)[K]) { if constexpr (K == 4) return (((v[0] + v[1]) + v[2]) + v[3]) * 0.25f; else return v[0]; };
     if (A.albedo) {
@@ -73,13 +91,17 @@ __global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, con
       for (int s = 0; s < K; ++s) { x[s] = nrm[s].x; y[s] = nrm[s].y; z[s] = nrm[s].z; }
       s_nrm[3 * threadIdx.x] = mean(x); s_nrm[3 * threadIdx.x + 1] = mean(y); s_nrm[3 * threadIdx.x + 2] = mean(z);
     }
+    if constexpr (MOTION) {
+      float* s_mot = motion_lds();
+      s_mot[3 * threadIdx.x] = mean(mx); s_mot[3 * threadIdx.x + 1] = mean(my); s_mot[3 * threadIdx.x + 2] = mean(mz);
+    }
     if (A.depth) A.depth[l] = mean(dep);
     if (A.alpha) A.alpha[l] = mean(cov);
     if (A.prim_type) A.prim_type[l] = pt;
     if (A.prim_index) A.prim_index[l] = pi;
     if (A.mat) A.mat[l] = pm;
   }
-  if (!want_surface) return;                                     // (uniform over the launch)
+  if constexpr (!MOTION) { if (!want_surface) return; }         // (uniform over the launch)
   __syncthreads();
   const int nw = 3 * (A.n - b0);                                 // floats of this workgroup's pixels that exist
 #pragma unroll
@@ -88,6 +110,7 @@ __global__ __launch_bounds__(kAovBlock) void k_aov_resolve(const DevFrame F, con
     if (k < nw) {
       if (A.albedo) A.albedo[3 * (size_t)b0 + k] = s_alb[k];
       if (A.normal) A.normal[3 * (size_t)b0 + k] = s_nrm[k];
+      if constexpr (MOTION) A.motion[3 * (size_t)b0 + k] = motion_lds()[k];
     }
   }
 }
@@ -98,8 +121,12 @@ void launch_aov_raygen(hipStream_t st, const DevFrame& F, const DevScene& S, con
   hipLaunchKernelGGL(k_aov_raygen, dim3(aov_blocks((int64_t)A.k * A.n)), dim3(kAovBlock), 0, st, F, S, A);
 }
 void launch_aov_resolve(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A) {
-  if (A.k == 4) hipLaunchKernelGGL(k_aov_resolve<4>, dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
-  else hipLaunchKernelGGL(k_aov_resolve<1>, dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
+  if (A.k == 4) hipLaunchKernelGGL((k_aov_resolve<4, false>), dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
+  else hipLaunchKernelGGL((k_aov_resolve<1, false>), dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
+}
+void launch_aov_resolve_motion(hipStream_t st, const DevFrame& F, const DevScene& S, const AovMotionArgs& A) {
+  if (A.k == 4) hipLaunchKernelGGL((k_aov_resolve<4, true>), dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
+  else hipLaunchKernelGGL((k_aov_resolve<1, true>), dim3(aov_blocks(A.n)), dim3(kAovBlock), 0, st, F, S, A);
 }
 
 }  // namespace art

@@ -611,20 +611,39 @@ int query_rays(const float* o3, const float* d3, const float* tnear, const float
 // art_render_aovs_device: the whole frame's camera rays (k per pixel) in slices of whole pixels, k * pixels <= query_slice, through the
 // queries' scratch and stream order; per slice k_aov_raygen, the render loop's trace launch, k_aov_resolve.  Like a query it counts its
 // rays into the scratch's sink and takes no event pair: ArtStats and ArtStageStats do not see it.
-int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st) {
+// motion3f (art_render_aovs_motion_device): the resolve's MOTION instantiation also writes the motion plane from src (art_motion.h); the
+// flat mesh's index triples are the refit plan's, which is built here where no refit has (the one time the host waits).
+int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st, const ArtMotionSource* src, float* motion3f) {
   Ctx& c = g_ctx;
-  const std::string name = "art_render_aovs_device";
+  const std::string name = motion3f ? "art_render_aovs_motion_device" : "art_render_aovs_device";
+  static const ArtAovBuffers no_planes = ArtAovBuffers();
   if (!p) return fail(name + ": null ArtPassParams");
+  if (!out && motion3f) out = &no_planes;
   if (!out) return fail(name + ": null ArtAovBuffers");
-  if (!out->albedo3f && !out->normal3f && !out->depth && !out->alpha && !out->prim_type && !out->prim_index && !out->mat) return fail(name + ": no plane is wanted (all seven pointers are null)");
+  if (!motion3f && !out->albedo3f && !out->normal3f && !out->depth && !out->alpha && !out->prim_type && !out->prim_index && !out->mat) return fail(name + ": no plane is wanted (all seven pointers are null)");
+  if (motion3f && !src) return fail(name + ": motion3f needs an ArtMotionSource (null src)");
   if (!c.scene_ready) return fail(name + ": no scene uploaded");
   if (c.host_scene.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which has no camera");
   if (c.width <= 0) return fail(name + ": no viewport (art_resize)");
   const int kernel = c.opt.trace_kernel;
   if (c.scene.n_inst > 0 && kernel != TRACE_COOP) return fail(name + ": an instanced scene is traced through the record schedule only (option trace_kernel = 0)");
+  const bool instanced = c.scene.n_inst > 0;
+  const bool flat_src = motion3f && (src->cur_pos3f || src->prev_pos3f), inst_src = motion3f && src->prev_m12f;
+  if (motion3f) {
+    if ((src->cur_pos3f != nullptr) != (src->prev_pos3f != nullptr)) return fail(name + ": cur_pos3f and prev_pos3f must both be given or both be null");
+    if (flat_src && instanced) return fail(name + ": vertex arrays are given but the scene is instanced (its motion comes from prev_m12f)");
+    if (inst_src && !instanced) return fail(name + ": prev_m12f is given but the scene is not instanced (its motion comes from cur_pos3f and prev_pos3f)");
+    if (flat_src && c.host_scene.m_nverts == 0) return fail(name + ": vertex arrays are given but the scene has no ART_MESH_CLOSEST mesh");
+    if (flat_src && src->nverts != c.host_scene.m_nverts) return fail(name + ": nverts " + std::to_string(src->nverts) + " differs from the uploaded mesh's " + std::to_string(c.host_scene.m_nverts));
+    if (inst_src && src->n_instances != c.scene.n_inst) return fail(name + ": n_instances " + std::to_string(src->n_instances) + " differs from the uploaded count " + std::to_string(c.scene.n_inst));
+  }
   if (ensure_device()) return 1;
   const int64_t npix = (int64_t)c.width * c.height;
   const size_t N = (size_t)npix;
+  if (motion3f && (check_device_ptr(motion3f, 12 * N, "motion3f") ||
+                   (flat_src && (check_device_ptr(src->cur_pos3f, 12 * (size_t)src->nverts, "cur_pos3f") || check_device_ptr(src->prev_pos3f, 12 * (size_t)src->nverts, "prev_pos3f"))) ||
+                   (inst_src && check_device_ptr(src->prev_m12f, 48 * (size_t)src->n_instances, "prev_m12f"))))
+    return 1;
   if ((out->albedo3f && check_device_ptr(out->albedo3f, 12 * N, "albedo3f")) || (out->normal3f && check_device_ptr(out->normal3f, 12 * N, "normal3f")) ||
       (out->depth && check_device_ptr(out->depth, 4 * N, "depth")) || (out->alpha && check_device_ptr(out->alpha, 4 * N, "alpha")) ||
       (out->prim_type && check_device_ptr(out->prim_type, 4 * N, "prim_type")) || (out->prim_index && check_device_ptr(out->prim_index, 4 * N, "prim_index")) ||
@@ -640,6 +659,13 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
   const hipStream_t qs = order.qs;
   const bool coop = (kernel == TRACE_COOP);
   if (ensure_query_scratch(order, S, coop)) return 1;
+  mo::Source ms; std::memset(&ms, 0, sizeof ms);
+  if (flat_src) {
+    if (ensure_refit_plan()) return 1;
+    ms.idx = (const int32_t*)c.refit.b_idx.p; ms.cur = src->cur_pos3f; ms.prev = src->prev_pos3f;
+    if (!ms.idx) return fail(name + ": internal: the refit plan holds no index triples");
+  }
+  if (instanced && motion3f) { ms.inst = c.scene.inst; ms.prev_m = src->prev_m12f; ms.inst_shift = c.scene.inst_shift; }
   if (order.enter()) return 1;
   char* base = (char*)c.b_query.p;
   unsigned long long* sink = (unsigned long long*)base;
@@ -649,7 +675,8 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
   int rc = 0;
   for (int64_t p0 = 0; p0 < npix && !rc; p0 += ns) {
     const int n = (int)std::min<int64_t>(ns, npix - p0);
-    AovArgs A; std::memset(&A, 0, sizeof A);
+    AovMotionArgs A; std::memset((void*)&A, 0, sizeof A);      // (its AovArgs part is all the launches without the plane see)
+    A.motion = motion3f ? motion3f + 3 * p0 : nullptr; A.src = ms;
     A.n = n; A.k = k; A.pixel0 = (uint32_t)p0;
     A.ox = f; A.oy = f + S; A.oz = f + 2 * S; A.dx = f + 3 * S; A.dy = f + 4 * S; A.dz = f + 5 * S; A.tf = f + 6 * S; A.hit = dh;
     A.albedo = out->albedo3f ? out->albedo3f + 3 * p0 : nullptr; A.normal = out->normal3f ? out->normal3f + 3 * p0 : nullptr;
@@ -662,7 +689,8 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
     q.P = 0;                                                         // (no shadow minima: every ray is a closest-hit query)
     rc = trace(q, k * n, launch);
     if (rc) break;
-    launch_aov_resolve(qs, F, c.scene, A);
+    if (motion3f) launch_aov_resolve_motion(qs, F, c.scene, A);
+    else launch_aov_resolve(qs, F, c.scene, A);
     if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
   }
   if (order.leave()) return 1;          // (also after a failed launch)
@@ -758,20 +786,22 @@ int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const floa
 // art_temporal_device: one kernel over the caller's planes and histories (art_temporal.h), in the queries' stream order.  It has no scratch
 // (so nothing can make the host wait), needs no scene and no viewport and takes no event pair: ArtStats and ArtStageStats do not see it.
 int temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
-                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st) {
-  const std::string name = "art_temporal_device";
+                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st, const float* motion3f, const char* call) {
+  const std::string name = call;
   TemporalArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = tp::params_from_abi(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (const char* why = tp::params_from_abi(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, A.P, motion3f)) return fail(name + ": " + why);      // (before the device is looked for)
   if (ensure_device()) return 1;
   Ctx& c = g_ctx;
   const size_t N = (size_t)A.P.cur.W * (size_t)A.P.cur.H, NP = (size_t)A.P.prev.W * (size_t)A.P.prev.H;
   if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(moments2f, 8 * N, "moments2f") || check_device_ptr(hist_out, 48 * N, "hist_out") ||
       (hist_in && check_device_ptr(hist_in, 48 * NP, "hist_in")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
       (depth && check_device_ptr(depth, 4 * N, "depth")) || (id && check_device_ptr(id, 4 * N, "id")) || (out3f && check_device_ptr(out3f, 12 * N, "out3f")) ||
-      (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")) || (length_out && check_device_ptr(length_out, 4 * N, "length_out")))
+      (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")) || (length_out && check_device_ptr(length_out, 4 * N, "length_out")) ||
+      (motion3f && check_device_ptr(motion3f, 12 * N, "motion3f")))
     return 1;
   StreamOrder order(c, st);
   if (order.enter()) return 1;
+  A.motion = motion3f; A.has_motion = motion3f ? 1 : 0;
   A.n = (int32_t)N; A.color = color3f; A.moments = moments2f; A.normal = normal3f; A.depth = depth; A.id = id;
   A.hist_in = (const tp::Rec4*)hist_in; A.hist_out = (tp::Rec4*)hist_out; A.out = out3f; A.variance_out = variance_out; A.length_out = length_out;
   launch_temporal(order.qs, A);
@@ -961,6 +991,11 @@ int art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, voi
   return render_aovs(p, out, (hipStream_t)hip_stream);
 }
 
+int art_render_aovs_motion_device(const ArtPassParams* p, const ArtAovBuffers* out, const ArtMotionSource* src, float* motion3f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return render_aovs(p, out, (hipStream_t)hip_stream, motion3f ? src : nullptr, motion3f);
+}
+
 int art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return denoise_device(p, color3f, albedo3f, normal3f, depth, out3f, (hipStream_t)hip_stream);
@@ -982,6 +1017,13 @@ int art_temporal_device(const ArtTemporalParams* p, const float* color3f, const 
                         const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return temporal_device(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f, variance_out, length_out, (hipStream_t)hip_stream);
+}
+
+int art_temporal_motion_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
+                               const float* motion3f, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return temporal_device(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f, variance_out, length_out, (hipStream_t)hip_stream, motion3f,
+                         motion3f ? "art_temporal_motion_device" : "art_temporal_device");
 }
 
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {

@@ -252,12 +252,14 @@ int render_pass_device(const ArtPassParams* p, int32_t* spp_inout);
 int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
-int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st);
+int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st, const ArtMotionSource* src = nullptr, float* motion3f = nullptr);   // motion3f: art_render_aovs_motion_device
+int ensure_refit_plan();              // the current context's refit plan exists (art_update.cpp); its b_idx holds the flat mesh's index triples
 int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st);
 int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
                         float* out3f, float* variance_out, hipStream_t st, bool variance_plane = false);      // variance_plane: art_denoise_svgf_var_device, moments2f is variance1f
 int temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
-                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st);
+                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st,
+                    const float* motion3f = nullptr, const char* call = "art_temporal_device");      // motion3f: art_temporal_motion_device
 void shutdown();
 int refit_device(const float* pos3f, const float* nrm3f, int64_t nverts, hipStream_t st);
 int get_refit_info(ArtRefitInfo* out);

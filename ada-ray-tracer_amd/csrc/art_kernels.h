@@ -6,6 +6,7 @@
 #include "art_instanced.h"
 #include "art_denoise.h"
 #include "art_temporal.h"
+#include "art_motion.h"
 
 namespace art {
 
@@ -110,6 +111,13 @@ struct AovArgs {
 };
 void launch_aov_raygen(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
 void launch_aov_resolve(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
+// art_render_aovs_motion_device: the same slice with the motion plane (3 floats per pixel, advanced to the slice; never nullptr here) and
+// what its deltas are made from (art_motion.h).  A type of its own, so that the kernels without the plane keep their arguments.
+struct AovMotionArgs : AovArgs {
+  float* motion;
+  mo::Source src;
+};
+void launch_aov_resolve_motion(hipStream_t st, const DevFrame& F, const DevScene& S, const AovMotionArgs& A);
 
 // art_denoise_device (art_denoise.hip, art_api.cpp denoise_device): the caller's planes (albedo / normal / depth nullptr: not given; out
 // may be color) and the library's scratch records of art_denoise.h, n = W * H of each
@@ -141,11 +149,13 @@ void launch_denoise_svgf_var(hipStream_t st, const SvgfArgs& A, int iterations);
 struct TemporalArgs {
   tp::Params P;
   int32_t n;
+  int32_t has_motion;              // art_temporal_motion_device with a motion plane: the MOTION instantiation runs (the word lies in what was padding)
   const float* color; const float* moments; const float* normal; const float* depth; const int32_t* id;
   const tp::Rec4* hist_in; tp::Rec4* hist_out;
   float* out; float* variance_out; float* length_out;
+  const float* motion;             // art_temporal_motion_device: 3 floats per pixel of the current frame; else nullptr
 };
-void launch_temporal(hipStream_t st, const TemporalArgs& A);
+void launch_temporal(hipStream_t st, const TemporalArgs& A);      // A.has_motion selects the motion variant of the kernel
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex

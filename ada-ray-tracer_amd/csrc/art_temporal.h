@@ -62,8 +62,9 @@ inline bool camera_from_abi(const float* cam_pos, const float* cam_matrix, int32
 // ArtTemporalParams and which pointers are given -> the kernel's Params: every refusal that needs no device, the two cameras, and the rule
 // of step 3 (no reprojection without depth, without history, or between cameras that are the same words).  Returns nullptr, or why the
 // call is refused.  The library (art_api.cpp) and tests/temporal_host both derive their Params here.
+// motion3f: art_temporal_motion_device's plane (nullptr: art_temporal_device's rules, word for word).
 inline const char* params_from_abi(const ArtTemporalParams* p, const void* color3f, const void* moments2f, const void* normal3f, const void* depth, const void* id,
-                                   const void* hist_in, const void* hist_out, Params& P) {
+                                   const void* hist_in, const void* hist_out, Params& P, const void* motion3f = nullptr) {
   if (!p) return "null ArtTemporalParams";
   if (!color3f || !moments2f || !hist_out) return "null color3f, moments2f or hist_out";
   const ArtTemporalCamera& cc = p->cur; const ArtTemporalCamera& pc = p->prev;
@@ -90,6 +91,7 @@ inline const char* params_from_abi(const ArtTemporalParams* p, const void* color
   P.has_hist = hist_in ? 1 : 0; P.has_normal = normal3f ? 1 : 0; P.has_depth = depth ? 1 : 0; P.has_id = id ? 1 : 0;
   const bool same = memcmp(cc.cam_pos, pc.cam_pos, 12) == 0 && memcmp(cc.cam_matrix, pc.cam_matrix, 64) == 0 && cc.width == pc.width && cc.height == pc.height;
   P.reproject = (depth && hist_in && !same) ? 1 : 0;
+  if (motion3f) P.reproject = (depth && hist_in) ? 1 : 0;      // a surface may have moved under cameras at rest
   P.n_cur = (float)p->n_colours; P.max_history = (float)p->max_history;
   P.scale = p->scale; P.depth_tol = p->depth_tol; P.normal_min = p->normal_min;
   return nullptr;
@@ -99,9 +101,12 @@ ART_HD float dot3(float ax, float ay, float az, float bx, float by, float bz) { 
 
 struct Out { Rec4 h0, h1, h2; float variance; };
 
-// pixel (x, y) of the current frame: its three history records and the variance of its mean luminance (h0 holds out3f and length_out)
+// pixel (x, y) of the current frame: its three history records and the variance of its mean luminance (h0 holds out3f and length_out).
+// MOTION (art_temporal_motion_device with a motion plane; P comes from params_from_abi with that plane named): the world point of step 3
+// is taken back by the pixel's delta.  Without it motion is not read: the text is art_temporal_device's.
+template <bool MOTION = false>
 ART_HD Out temporal_pixel(const Params& P, const float* color, const float* moments, const float* normal, const float* depth, const int32_t* id,
-                          const Rec4* hist, int x, int y) {
+                          const Rec4* hist, int x, int y, const float* motion = nullptr) {
   const size_t p = (size_t)y * (size_t)P.cur.W + (size_t)x;
   const float cr = P.scale * color[3 * p], cg = P.scale * color[3 * p + 1], cb = P.scale * color[3 * p + 2];
   const float m1 = moments[2 * p] / P.n_cur, m2 = moments[2 * p + 1] / P.n_cur;
@@ -125,7 +130,14 @@ ART_HD Out temporal_pixel(const Params& P, const float* color, const float* mome
       const float tx = (M[0] * ux + M[1] * uy) + M[2] * uz, ty = (M[3] * ux + M[4] * uy) + M[5] * uz, tz = (M[6] * ux + M[7] * uy) + M[8] * uz;
       const float lj = 1.0f / sqrtf(dot3(tx, ty, tz, tx, ty, tz));
       const float dx = lj * tx, dy = lj * ty, dz = lj * tz;
-      const float vx = (P.cur.pos[0] + z * dx) - P.prev.pos[0], vy = (P.cur.pos[1] + z * dy) - P.prev.pos[1], vz = (P.cur.pos[2] + z * dz) - P.prev.pos[2];
+      float vx, vy, vz;
+      if constexpr (MOTION) {
+        const float mx = motion[3 * p], my = motion[3 * p + 1], mz = motion[3 * p + 2];
+        if (!(finite_f(mx) && finite_f(my) && finite_f(mz))) ok = false;
+        vx = ((P.cur.pos[0] + z * dx) + mx) - P.prev.pos[0]; vy = ((P.cur.pos[1] + z * dy) + my) - P.prev.pos[1]; vz = ((P.cur.pos[2] + z * dz) + mz) - P.prev.pos[2];
+      } else {
+        vx = (P.cur.pos[0] + z * dx) - P.prev.pos[0]; vy = (P.cur.pos[1] + z * dy) - P.prev.pos[1]; vz = (P.cur.pos[2] + z * dz) - P.prev.pos[2];
+      }
       e = sqrtf(dot3(vx, vy, vz, vx, vy, vz));
       const float* I = P.prev.minv;
       const float qx = (I[0] * vx + I[1] * vy) + I[2] * vz, qy = (I[3] * vx + I[4] * vy) + I[5] * vz, qz = (I[6] * vx + I[7] * vy) + I[8] * vz;

@@ -28,11 +28,14 @@ namespace art {
 
 constexpr int kTpBlock = 256;
 
+// MOTION: art_temporal_motion_device with a motion plane, read at the lane's own index like the colour (12 more bytes per pixel: 168).
+// The instantiation without it is art_temporal_device's kernel.
+template <bool MOTION>
 __global__ __launch_bounds__(kTpBlock) void k_temporal(const TemporalArgs A) {
   const int p = blockIdx.x * kTpBlock + threadIdx.x;             // at most 2^28 pixels (the host's bound)
   if (p >= A.n) return;
   const int y = p / A.P.cur.W, x = p - y * A.P.cur.W;
-  const tp::Out o = tp::temporal_pixel(A.P, A.color, A.moments, A.normal, A.depth, A.id, A.hist_in, x, y);
+  const tp::Out o = tp::temporal_pixel<MOTION>(A.P, A.color, A.moments, A.normal, A.depth, A.id, A.hist_in, x, y, A.motion);
   A.hist_out[p] = o.h0; A.hist_out[(size_t)A.n + p] = o.h1; A.hist_out[2 * (size_t)A.n + p] = o.h2;
   if (A.out) { A.out[3 * (size_t)p] = o.h0.x; A.out[3 * (size_t)p + 1] = o.h0.y; A.out[3 * (size_t)p + 2] = o.h0.z; }
   if (A.variance_out) A.variance_out[p] = o.variance;
@@ -41,7 +44,8 @@ __global__ __launch_bounds__(kTpBlock) void k_temporal(const TemporalArgs A) {
 
 void launch_temporal(hipStream_t st, const TemporalArgs& A) {
   const dim3 grid((unsigned)((A.n + kTpBlock - 1) / kTpBlock)), block(kTpBlock);
-  hipLaunchKernelGGL(k_temporal, grid, block, 0, st, A);
+  if (A.has_motion) hipLaunchKernelGGL(k_temporal<true>, grid, block, 0, st, A);
+  else hipLaunchKernelGGL(k_temporal<false>, grid, block, 0, st, A);
 }
 
 }  // namespace art

@@ -213,6 +213,10 @@ static int build_refit_plan(const HostScene& hs) {
   return 0;
 }
 
+// art_render_aovs_motion_device reads the plan's index triples: the current context's plan, built here when no refit has built it since the
+// upload or the last rebuild (the host then waits for the context stream, as the first refit does)
+int ensure_refit_plan() { return !g_ctx.refit.ready && build_refit_plan(g_devs[0].host_scene); }
+
 // the current context's refit on stream s, from positions (and normals) in this context's device memory
 static int refit_one(const HostScene& hs, const float* pos, const float* nrm, hipStream_t s) {
   Ctx& c = g_ctx;

@@ -279,6 +279,47 @@ typedef struct ArtAovBuffers {
 } ArtAovBuffers;
 int  art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream);
 
+/* The feature buffers plus a MOTION plane: where each pixel's surface point was one scene update ago, for
+ * art_temporal_motion_device to follow geometry that art_refit_device or art_move_instances_device moved.  ONE trace of the camera rays
+ * serves all planes: it is art_render_aovs_device's trace, with its slices, its stream rules and its refusals.  out may be NULL, or have
+ * all seven pointers NULL, when motion3f is given.  With motion3f NULL the call IS art_render_aovs_device and src is not read.
+ * motion3f: device memory, 3 floats per pixel, row-major: the world-space displacement BACK in time of the pixel's surface point -- where
+ * the point was, minus where it is.  The caller says what "was" means through ArtMotionSource:
+ *   flat scene       cur_pos3f = the vertices in force (what the last art_refit_device, art_rebuild_device or upload put there) and
+ *                    prev_pos3f = the vertices one update earlier, both 3 * nverts floats in the uploaded vertex order, both device
+ *                    memory; both given or both NULL (NULL: nothing moved).  prev_m12f must be NULL.
+ *   instanced scene  prev_m12f = the matrices one update earlier, 12 * n_instances floats as art_move_instances_device takes them; NULL:
+ *                    nothing moved.  The vertex pointers must be NULL.  The matrices in force are the library's own (the instance table).
+ * The library does NOT check that cur_pos3f is what the tree holds: a wrong array gives a wrong plane and touches nothing else.
+ * THE ARITHMETIC (the contract; csrc/art_motion.h is its one definition, compiled for the GPU and for the host).  Binary32, not
+ * contracted, in the order written.  T(m, p), row k of a 3 x 4 matrix applied to a point: ((m[4k] * px + m[4k+1] * py) + m[4k+2] * pz) +
+ * m[4k+3].  Ray s of the pixel (K = 4 with aa_on, else 1), with h_s its hit record (t, u, v as ArtHit reports them):
+ *   a miss, a sphere, a Cornell plane, a rect light, a REFERENCE_BF triangle:   delta_s = (0, 0, 0)
+ *   flat scene, CLOSEST triangle i:   (a, b, c) = idx[3i .. 3i + 2];   w = (1.0f - u) - v;   d_k = prev[k] - cur[k] per component of vertex k;
+ *       delta_s = (w * d_a + v * d_b) + u * d_c     (u weights C and v weights B, as ArtHit says).  Displacements are interpolated, not
+ *       positions: an unmoved (finite) vertex triple gives exactly +0.  Both vertex pointers NULL: delta_s = 0.
+ *   instanced scene, triangle of instance j = prim_index >> shift:   Pw = cam_pos + t * d_s per component (d_s the ray's direction);
+ *       Po = T(minv_cur[j], Pw);   delta_s = T(prev_m12f[j], Po) - T(m_cur[j], Po) per row, with m_cur and minv_cur record j of the
+ *       instance table in force.  A previous matrix equal to the current one word for word gives exactly 0.  prev_m12f NULL: delta_s = 0.
+ * The plane holds (((v_0 + v_1) + v_2) + v_3) * 0.25f per component, the association of the other float planes (K = 1: v_0).  A delta
+ * that is not finite is stored as it is (art_temporal_motion_device gives such a pixel no history).
+ * The flat mesh's index triples are the refit plan's: where no art_refit_device has built the plan since the upload or the last
+ * art_rebuild_device, this call builds it as the first refit does, AND THE HOST WAITS for the library's stream that one time.
+ * OUT OF SCOPE: a mesh of an instanced scene deformed by art_refit_mesh_device gets the rigid motion of its instance only; what the
+ * deformation moved is left to the depth, normal and id tests of the temporal call, as before.
+ * Refused before anything is launched, with art_last_error set: everything art_render_aovs_device refuses (but null planes where
+ * motion3f is given); motion3f with a null src; only one of cur_pos3f and prev_pos3f; nverts or n_instances other than the uploaded
+ * count; vertex arrays on an instanced scene or on a scene without a CLOSEST mesh, matrices on a flat one; any given pointer that is host
+ * memory, another device's memory or too small. */
+typedef struct ArtMotionSource {
+  const float* cur_pos3f;          /* flat scene: the vertices in force, 3 * nverts floats, device memory */
+  const float* prev_pos3f;         /* flat scene: the vertices one update earlier, same order, device memory */
+  int64_t      nverts;
+  const float* prev_m12f;          /* instanced scene: the matrices one update earlier, 12 * n_instances floats, device memory */
+  int64_t      n_instances;
+} ArtMotionSource;
+int  art_render_aovs_motion_device(const ArtPassParams* p, const ArtAovBuffers* out, const ArtMotionSource* src, float* motion3f, void* hip_stream);
+
 /* Edge-avoiding a-trous wavelet denoiser (Dammertz et al. 2010, with the depth-gradient and normal-power edge stops of SVGF), guided by
  * the feature buffers above.  Every pointer is device memory of the library's device (device 0 under
  * art_init_devices), row-major, float3 / float per pixel: the layout of art_bind_accum and ArtAovBuffers.  albedo3f, normal3f and depth
@@ -453,7 +494,8 @@ int  art_denoise_svgf_var_device(const ArtSvgfParams* p, const float* color3f, c
  *  6. hist_out: plane 0 {colour, n}, plane 1 {m1, m2, z, id}, plane 2 {N, 0} -- the current frame's guides.  out3f = colour, length_out = n.
  *     variance_out = +infinity where n < 2 (art_denoise_svgf_var_device reads it as "no colour stop"), else in binary64 (operands converted
  *     first): D = m2 - m1 * m1;  D0 = (D < 0) ? 0 : D (a NaN stays);  (float)((D0 * (n / (n - 1))) / n).
- * Reprojection is by camera only: a pixel on a surface that moved fails its depth or id test and starts again.  Quality:
+ * Reprojection is by camera only: a pixel on a surface that moved fails its depth or id test and starts again
+ * (art_temporal_motion_device below follows such a surface).  Quality:
  * profiles/temporal/quality.json holds the sweep the defaults of Backend.temporal_torch were chosen by. */
 typedef struct ArtTemporalCamera {
   float   cam_pos[3];
@@ -472,6 +514,23 @@ int  art_temporal_device(const ArtTemporalParams* p, const float* color3f, const
                          const int32_t* id, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
                          void* hip_stream);
 int64_t art_temporal_history_bytes(int32_t width, int32_t height);
+
+/* art_temporal_device following moved geometry: the same arguments with motion3f after id -- the plane of
+ * art_render_aovs_motion_device for the current frame, 3 floats per pixel, device memory (refused like the other planes when it is host
+ * memory, another device's or too small).  With motion3f NULL the call IS art_temporal_device, bit for bit.  With it given, step 3 of THE
+ * ARITHMETIC above changes in three places and nowhere else:
+ *   - reprojection happens whenever depth and hist_in are given: equal cameras no longer switch it off (without depth there is still no
+ *     reprojection, and motion3f is then not read);
+ *   - v = ((cam_pos_cur + z * d) + delta) - cam_pos_prev per component, delta = the pixel's three motion floats: the surface point is
+ *     taken back to where it was before it is looked up in the previous frame, and e, the distance the tap's depth is held to, follows;
+ *   - a pixel whose delta has a component that is not finite takes NO HISTORY.
+ * e, q, the behind-the-camera test, the gather, its tests and the blend (the rest of step 3 and steps 4 to 6) stay word for word.  With
+ * a delta of zero the call gives art_temporal_device's bits, except between equal cameras: there the old rule skips the projection and
+ * this one runs it, so fx, fy come out of the arithmetic and their fractional parts need not be exactly 0.
+ * Compulsory traffic: 12 bytes per pixel more than art_temporal_device. */
+int  art_temporal_motion_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth,
+                                const int32_t* id, const float* motion3f, const void* hist_in, void* hist_out, float* out3f, float* variance_out,
+                                float* length_out, void* hip_stream);
 
 /* The camera of the uploaded scene: cam_pos and cam_matrix replace ArtSceneDesc's in every context under
  * art_init_devices, without a rebuild.  Stream-ordered on the library's stream (art_set_stream), like the other scene updates: work
