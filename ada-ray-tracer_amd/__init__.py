@@ -135,6 +135,11 @@ class ArtTemporalParams(C.Structure):
                 ("scale", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float)]
 
 
+class ArtAdaptiveParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("aa_on", C.c_int32), ("min_colours", C.c_int32), ("max_samples", C.c_int32),
+                ("threshold", C.c_float), ("lum_floor", C.c_float)]
+
+
 # Backend.render_aovs_torch: plane -> (field of ArtAovBuffers, floats or ints per pixel, integer plane)
 AOV_PLANES = collections.OrderedDict([("albedo", ("albedo3f", 3, False)), ("normal", ("normal3f", 3, False)), ("depth", ("depth", 1, False)),
                                       ("alpha", ("alpha", 1, False)), ("prim_type", ("prim_type", 1, True)), ("prim_index", ("prim_index", 1, True)),
@@ -223,6 +228,10 @@ SVGF_SIGMA_COLOR = 2.0
 TEMPORAL_MAX_HISTORY = 64
 TEMPORAL_DEPTH_TOL = 0.2
 TEMPORAL_NORMAL_MIN = 0.5
+# Backend.render_adaptive's and adaptive_estimate_torch's defaults: the best setting of profiles/adaptive/quality.json (the sweep of profiles/adaptive/quality.py)
+ADAPTIVE_THRESHOLD = 0.1
+ADAPTIVE_LUM_FLOOR = 1.0
+ADAPTIVE_MIN_COLOURS = 16
 
 
 class HitCpp(C.Structure):
@@ -234,6 +243,7 @@ EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_set_camera",
+    "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device",
     "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
@@ -289,6 +299,9 @@ def load_library():
     L.art_temporal_motion_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 12
     L.art_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
     L.art_temporal_history_bytes.restype = C.c_int64
+    L.art_compact_mask_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
+    L.art_render_pass_masked.argtypes = [C.POINTER(ArtPassParams), C.c_void_p, C.c_void_p, i32p, C.POINTER(C.c_int64)]
+    L.art_adaptive_estimate_device.argtypes = [C.POINTER(ArtAdaptiveParams)] + [C.c_void_p] * 8
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -867,6 +880,128 @@ class Backend:
         _check(self.lib.art_temporal_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
                                             ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
         return out, var, length, new
+
+    def _frame_tensor(self, torch, call, name, x, dtype, elements, optional=False):
+        """A plane of the adaptive calls, checked as bind_moments checks its tensor: a contiguous GPU tensor of `dtype` with at least
+        `elements` elements.  Returns its device address (None for an absent optional plane)."""
+        if x is None and optional:
+            return None
+        if torch is None or not isinstance(x, torch.Tensor):
+            raise ArtError("%s: %s: a torch tensor is required, not %s" % (call, name, type(x).__name__))
+        if x.device.type != "cuda":
+            raise ArtError("%s: %s: must be a GPU tensor on the library's device, not on %s" % (call, name, x.device))
+        if x.dtype != dtype:
+            raise ArtError("%s: %s: dtype must be %s, not %s" % (call, name, dtype, x.dtype))
+        if not x.is_contiguous():
+            raise ArtError("%s: %s: the tensor must be contiguous" % (call, name))
+        if x.numel() < elements:
+            raise ArtError("%s: %s: the tensor holds %d elements, the frame needs %d" % (call, name, x.numel(), elements))
+        return x.data_ptr()
+
+    def _mask_tensor(self, torch, call, mask):
+        if torch is not None and isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
+            mask = mask.view(torch.uint8)                   # (a bool tensor is one byte per element, 0 or 1)
+        return mask, self._frame_tensor(torch, call, "mask", mask, None if torch is None else torch.uint8, self.width * self.height)
+
+    def compact_mask_torch(self, mask):
+        """The selected pixels of this rank's list, in list order (art_compact_mask_device; include/art_hip.h): mask is a uint8 or bool GPU
+        tensor with H * W elements ([H, W] or flat), non-zero = selected.  Returns (pixels, count): a uint32-valued int32 tensor of H * W
+        words whose first `count` hold the global pixel indices y * W + x, and count as a one-element int32 tensor -- both stay on the GPU,
+        enqueued on torch.cuda.current_stream() without waiting for it."""
+        torch = sys.modules.get("torch")
+        mask, mp = self._mask_tensor(torch, "compact_mask_torch", mask)
+        n = self.width * self.height
+        pixels = torch.empty(n, dtype=torch.int32, device=mask.device)
+        count = torch.empty(1, dtype=torch.int32, device=mask.device)
+        stream = torch.cuda.current_stream(mask.device).cuda_stream
+        _check(self.lib.art_compact_mask_device(mp, pixels.data_ptr(), n, count.data_ptr(), stream or HIP_STREAM_LEGACY))
+        return pixels, count
+
+    def render_pass_masked(self, params, spp, mask, counts=None):
+        """One render pass over the pixels mask selects (art_render_pass_masked; include/art_hip.h): bit for bit the full pass at that spp
+        restricted to them; spp advances by the pass's samples whatever the mask holds.  mask: uint8 or bool GPU tensor with H * W
+        elements; counts: None or an int32 GPU tensor with H * W elements (uint32 words), to whose selected pixels the pass's samples are
+        added.  Tensors are checked before any C call.  The host waits once for the list's length and at the end, as render_pass does.
+        Returns (new spp, pixels rendered)."""
+        torch = sys.modules.get("torch")
+        mask, mp = self._mask_tensor(torch, "render_pass_masked", mask)
+        cp = self._frame_tensor(torch, "render_pass_masked", "counts", counts, torch.int32, self.width * self.height, optional=True)
+        s = C.c_int32(spp); k = C.c_int64(0)
+        _check(self.lib.art_render_pass_masked(C.byref(params), mp, cp, C.byref(s), C.byref(k)))
+        return s.value, k.value
+
+    def adaptive_estimate_torch(self, accum, moments, counts, aa_on, threshold=None, lum_floor=None, min_colours=None, max_samples=1 << 30,
+                                want=("mean", "variance", "error", "mask")):
+        """Per pixel the mean colour, the variance of the mean's luminance, the relative error and the next mask
+        (art_adaptive_estimate_device; include/art_hip.h states the arithmetic).  accum: float32 with 3 * H * W elements (the tensor of
+        bind_accum as it is), moments: float32 with 2 * H * W (bind_moments), counts: int32 with H * W (uint32 words: the samples behind
+        each pixel), all on the GPU, for the frame of resize().  Returns a dict of the planes named in `want`: mean [H, W, 3] float32,
+        variance and error [H, W] float32, mask [H, W] uint8, enqueued on torch.cuda.current_stream() without waiting for it.  The
+        defaults of threshold, lum_floor and min_colours are the best setting of the sweep in profiles/adaptive/quality.json."""
+        torch = sys.modules.get("torch")
+        call = "adaptive_estimate_torch"
+        w, h = self.width, self.height
+        ap = self._frame_tensor(torch, call, "accum", accum, None if torch is None else torch.float32, 3 * w * h)
+        mp = self._frame_tensor(torch, call, "moments", moments, torch.float32, 2 * w * h)
+        cp = self._frame_tensor(torch, call, "counts", counts, torch.int32, w * h)
+        for name in want:
+            if name not in ("mean", "variance", "error", "mask"):
+                raise ArtError("%s: want: unknown plane %r" % (call, name))
+        if not want:
+            raise ArtError("%s: want: at least one plane" % call)
+        dev = accum.device
+        out = {}
+        if "mean" in want:
+            out["mean"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        for name in ("variance", "error"):
+            if name in want:
+                out[name] = torch.empty((h, w), dtype=torch.float32, device=dev)
+        if "mask" in want:
+            out["mask"] = torch.empty((h, w), dtype=torch.uint8, device=dev)
+        p = ArtAdaptiveParams(w, h, 1 if aa_on else 0, int(ADAPTIVE_MIN_COLOURS if min_colours is None else min_colours), int(max_samples),
+                              float(ADAPTIVE_THRESHOLD if threshold is None else threshold), float(ADAPTIVE_LUM_FLOOR if lum_floor is None else lum_floor))
+        ptr = lambda name: out[name].data_ptr() if name in out else None
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        _check(self.lib.art_adaptive_estimate_device(C.byref(p), ap, mp, cp, ptr("mean"), ptr("variance"), ptr("error"), ptr("mask"), stream or HIP_STREAM_LEGACY))
+        return out
+
+    def render_adaptive(self, params, budget_samples, step_vthreads, threshold=None, lum_floor=None, min_colours=None, max_samples=1 << 30,
+                        first_vthreads=None, max_passes=1 << 20):
+        """The plain adaptive loop on the frame of resize(): one full pass of first_vthreads (default step_vthreads) virtual threads, then
+        estimate and masked pass of step_vthreads until the mask is empty, the next pass would take the total past budget_samples
+        (camera samples over the whole frame), or max_passes is reached.  Binds an accum, a moments and a counts tensor of its own for the
+        run (resize() zeroes the first two) and unbinds them at the end; single device, the whole frame (no set_shard).  Returns a dict: accum
+        [H, W, 3] and moments [H, W, 2] float32, counts [H, W] int32, spp, passes and samples (the total), and mean [H, W, 3] =
+        accum / counts from the estimate kernel."""
+        import torch
+        w, h = self.width, self.height
+        per = 4 if params.aa_on else 1
+        dev = torch.device("cuda", torch.cuda.current_device())
+        accum = torch.zeros((h, w, 3), dtype=torch.float32, device=dev)
+        moments = torch.zeros((h, w, 2), dtype=torch.float32, device=dev)
+        counts = torch.zeros((h, w), dtype=torch.int32, device=dev)
+        step = ArtPassParams.from_buffer_copy(params); step.vthreads = int(step_vthreads)
+        first = ArtPassParams.from_buffer_copy(params); first.vthreads = int(first_vthreads or step_vthreads)
+        self.bind_accum(accum); self.bind_moments(moments)
+        try:
+            self.resize(w, h)
+            spp = self.render_pass_device(first, 0)
+            counts += spp
+            passes, used = 1, spp * w * h
+            kw = dict(threshold=threshold, lum_floor=lum_floor, min_colours=min_colours, max_samples=max_samples)
+            while passes < max_passes:
+                mask = self.adaptive_estimate_torch(accum, moments, counts, params.aa_on, want=("mask",), **kw)["mask"]
+                k = int(mask.count_nonzero())
+                if k == 0 or used + k * step.vthreads * per > budget_samples:
+                    break
+                spp, rendered = self.render_pass_masked(step, spp, mask, counts)
+                used += rendered * step.vthreads * per
+                passes += 1
+            mean = self.adaptive_estimate_torch(accum, moments, counts, params.aa_on, want=("mean",), **kw)["mean"]
+            torch.cuda.synchronize()
+        finally:
+            self.bind_moments(None); self.bind_accum(None)
+        return dict(accum=accum, moments=moments, counts=counts, spp=spp, passes=passes, samples=used, mean=mean)
 
     def _vertex_tensors(self, pos, nrm):
         """Validated, contiguous vertex tensors of refit_torch / rebuild_torch, and torch's current stream of their device."""

@@ -242,6 +242,33 @@ package Art_Hip is
   function art_temporal_history_bytes (width, height : int) return long;
   pragma Import (C, art_temporal_history_bytes, "art_temporal_history_bytes");
 
+  --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
+  --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
+  --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).
+  function art_compact_mask_device (mask1b, pixels_out : System.Address; cap : long; count_out : System.Address;
+                                    hip_stream : System.Address) return int;
+  pragma Import (C, art_compact_mask_device, "art_compact_mask_device");
+  --  One Render_Pass over the selected pixels only; spp advances by the pass's samples whatever the mask holds.  counts1u (DEVICE, one
+  --  32-bit word per pixel, may be Null_Address) receives the samples added; pixels_out (host, may be null) the pixels rendered.
+  --  The host waits once for the list's length, and at the end as art_render_pass does.
+  function art_render_pass_masked (p : access constant Art_Pass_Params; mask1b, counts1u : System.Address; spp_inout : access int;
+                                   pixels_out : access long) return int;
+  pragma Import (C, art_render_pass_masked, "art_render_pass_masked");
+  --  Per pixel: mean colour, variance of the mean's luminance, relative error and the next mask (ArtAdaptiveParams, 28 bytes).  The four
+  --  outputs may each be Null_Address, but not all.
+  type Art_Adaptive_Params is record
+    width, height : int;
+    aa_on         : int;
+    min_colours   : int;     --  >= 2
+    max_samples   : int;     --  >= 0
+    threshold     : C_float;
+    lum_floor     : C_float; --  >= 0
+  end record;
+  pragma Convention (C, Art_Adaptive_Params);
+  function art_adaptive_estimate_device (p : access constant Art_Adaptive_Params; accum3f, moments2f, counts1u, mean3f, variance1f, error1f,
+                                         mask1b : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_adaptive_estimate_device, "art_adaptive_estimate_device");
+
   --  Luminance moments of the render passes in caller-owned DEVICE memory: 2 C floats {S1, S2} per pixel, row-major, zeroed by
   --  art_resize, added to by every art_render_pass (include/art_hip.h).  Null_Address: none (the default).
   --  The camera of the uploaded scene, without a rebuild (include/art_hip.h): stream-ordered on the library's stream, every context.

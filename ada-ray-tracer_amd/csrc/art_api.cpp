@@ -811,6 +811,30 @@ int temporal_device(const ArtTemporalParams* p, const float* color3f, const floa
   return rc;
 }
 
+// art_adaptive_estimate_device: one kernel over the caller's planes (art_adaptive.h), in the queries' stream order.  Like art_temporal_device
+// it has no scratch, needs no scene and no viewport and takes no event pair.
+int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u, float* mean3f, float* variance1f,
+                             float* error1f, uint8_t* mask1b, hipStream_t st) {
+  const std::string name = "art_adaptive_estimate_device";
+  AdaptiveArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = ad::params_from_abi(p, accum3f, moments2f, counts1u, mean3f, variance1f, error1f, mask1b, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.n;
+  if (check_device_ptr(accum3f, 12 * N, "accum3f") || check_device_ptr(moments2f, 8 * N, "moments2f") || check_device_ptr(counts1u, 4 * N, "counts1u") ||
+      (mean3f && check_device_ptr(mean3f, 12 * N, "mean3f")) || (variance1f && check_device_ptr(variance1f, 4 * N, "variance1f")) ||
+      (error1f && check_device_ptr(error1f, 4 * N, "error1f")) || (mask1b && check_device_ptr(mask1b, N, "mask1b")))
+    return 1;
+  StreamOrder order(c, st);
+  if (order.enter()) return 1;
+  A.accum = accum3f; A.moments = moments2f; A.counts = counts1u; A.mean = mean3f; A.variance = variance1f; A.error = error1f; A.mask = mask1b;
+  launch_adaptive_estimate(order.qs, A);
+  int rc = 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) { reset_reduce_info(); g_reduce_pairs.destroy(); }
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -824,7 +848,7 @@ void shutdown() {
       DevBuf* bufs[] = {&c.b_spheres, &c.b_sphere_mat, &c.b_lights, &c.b_materials, &c.b_bf_pos, &c.b_bf_nrm, &c.b_bf_uv, &c.b_bf_idx,
                         &c.b_nodes, &c.b_qnodes, &c.b_tris, &c.b_qtris, &c.b_m_shade, &c.b_accum, &c.b_screen, &c.b_stage,
                         &c.b_pixmap, &c.b_paths, &c.b_rays, &c.b_ids, &c.b_queue, &c.b_ovf,
-                        &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query, &c.b_denoise};
+                        &c.b_inst, &c.b_tlas_nodes, &c.b_tlas_tris, &c.b_blas_nodes, &c.b_blas_tris, &c.b_query, &c.b_denoise, &c.b_select, &c.b_masklist};
       for (DevBuf* b : bufs) b->release();
       for (void* p : {(void*)c.d_cursor, (void*)c.d_scene, (void*)c.d_counters, (void*)c.d_live, (void*)c.d_items}) if (p) (void)hipFree(p);
       c.stage_pairs.destroy(); c.pass_pairs.destroy(); c.rebuild_pairs.destroy();
@@ -1024,6 +1048,24 @@ int art_temporal_motion_device(const ArtTemporalParams* p, const float* color3f,
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return temporal_device(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, out3f, variance_out, length_out, (hipStream_t)hip_stream, motion3f,
                          motion3f ? "art_temporal_motion_device" : "art_temporal_device");
+}
+
+int art_compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap, uint32_t* count_out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return compact_mask_device(mask1b, pixels_out, cap, count_out, (hipStream_t)hip_stream);
+}
+
+int art_render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* counts1u, int32_t* spp_inout, int64_t* pixels_out) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  SINGLE_DEVICE_ONLY("art_render_pass_masked");
+  if (render_pass_masked(p, mask1b, counts1u, spp_inout, pixels_out)) return 1;
+  return synchronize();
+}
+
+int art_adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u,
+                                 float* mean3f, float* variance1f, float* error1f, uint8_t* mask1b, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return adaptive_estimate_device(p, accum3f, moments2f, counts1u, mean3f, variance1f, error1f, mask1b, (hipStream_t)hip_stream);
 }
 
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {

@@ -100,6 +100,7 @@ struct Ctx {
   DevBuf b_accum, b_screen, b_stage, b_pixmap, b_paths, b_rays, b_ids, b_queue, b_ovf;
   DevBuf b_query;                              // device-resident ray queries: SoA rays + shadow minima + hit records of one slice, and a counter sink
   DevBuf b_denoise;                            // art_denoise_device: its working images, guide records and depth gradients (art_denoise.h)
+  DevBuf b_select, b_masklist;                 // mask compaction (art_select.hip): a count word (256 B) + one word per 256 list entries | the masked pass's pixel list; both only grow, like b_pixmap
   hipEvent_t q_ev[2] = {nullptr, nullptr};     // ... their ordering with the context stream when they run on another stream (library -> query, query -> library)
   // art_refit_device (art_refit.hip): the plan is built on the first refit after an upload (the upload drops it); per context, because
   // the GPU builders may number the nodes differently on every device
@@ -249,6 +250,10 @@ int trace(const DevPaths& q, int n_rays, const TraceLaunch& t);
 int check_pass(const ArtPassParams* p);
 void make_frame(const ArtPassParams* p, DevFrame& f);
 int render_pass_device(const ArtPassParams* p, int32_t* spp_inout);
+int compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap, uint32_t* count_out, hipStream_t st);
+int render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* counts1u, int32_t* spp_inout, int64_t* pixels_out);   // single device (the caller checked), no synchronize
+int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u, float* mean3f, float* variance1f,
+                             float* error1f, uint8_t* mask1b, hipStream_t st);
 int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);

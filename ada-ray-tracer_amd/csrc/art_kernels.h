@@ -7,6 +7,7 @@
 #include "art_denoise.h"
 #include "art_temporal.h"
 #include "art_motion.h"
+#include "art_adaptive.h"
 
 namespace art {
 
@@ -156,6 +157,24 @@ struct TemporalArgs {
   const float* motion;             // art_temporal_motion_device: 3 floats per pixel of the current frame; else nullptr
 };
 void launch_temporal(hipStream_t st, const TemporalArgs& A);      // A.has_motion selects the motion variant of the kernel
+
+// art_compact_mask_device and the masked render pass (art_select.hip): the n entries of a pixel list, the frame's byte mask, one word per
+// workgroup of 256 entries (select_blocks(n) words of scratch: counts, then their exclusive prefix sums) and the compacted list
+struct SelectArgs {
+  const uint8_t* mask; const uint32_t* pixmap; int32_t n;
+  uint32_t* block_sums; uint32_t* out;
+};
+int select_blocks(int n);
+void launch_compact_mask(hipStream_t st, const SelectArgs& A, uint32_t* count_out);      // three launches: count, scan (one workgroup), scatter
+void launch_add_counts(hipStream_t st, const uint32_t* list, int n, uint32_t* counts, uint32_t samples);   // counts[list[i]] += samples, i < n
+
+// art_adaptive_estimate_device (art_adaptive.hip, art_api.cpp adaptive_estimate_device): the caller's planes, outputs nullptr where not wanted
+struct AdaptiveArgs {
+  ad::Params P;
+  const float* accum; const float* moments; const uint32_t* counts;
+  float* mean; float* variance; float* error; uint8_t* mask;
+};
+void launch_adaptive_estimate(hipStream_t st, const AdaptiveArgs& A);
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex

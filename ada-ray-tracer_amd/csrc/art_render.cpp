@@ -301,17 +301,22 @@ static int render_batch_plain(const ArtPassParams* p, const DevFrame& F, const T
   return 0;
 }
 
-// The batch of samples [s0, s0 + sn) of the pixels [px0, px0 + pn) of this context's pixel list.
-static int render_batch(const ArtPassParams* p, const DevFrame& F, const TraceLaunch& launch, int px0, int pn, int s0, int sn) {
+// A pixel list a pass walks: the context's own (b_pixmap, npix_local), or the compacted list of a masked pass.
+struct PixelList { const uint32_t* pixels; int n; bool masked; };
+
+// The batch of samples [s0, s0 + sn) of the pixels [px0, px0 + pn) of the pixel list L.
+static int render_batch(const ArtPassParams* p, const DevFrame& F, const TraceLaunch& launch, const PixelList& L, int px0, int pn, int s0, int sn) {
   Ctx& c = g_ctx;
   const bool records = (c.opt.trace_kernel == TRACE_COOP);
   DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
-  for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = (const uint32_t*)c.b_pixmap.p + px0; b.sample_base = (uint32_t)(c.spp + s0); }
+  for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = L.pixels + px0; b.sample_base = (uint32_t)(c.spp + s0); }
   carve(bank, bank[0].P, p->max_depth, records);
   // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_pass_plan.h ShadeTrial).
   // Nothing here waits for the GPU: a trial batch only tags its shade launches' event pairs, and the next call that synchronises
   // anyway reads them (collect_timing) -- Render_Pass releases all its workers before it waits for any (ray_tracer.adb:271-277).
-  const ShadeTrial::Batch trial = c.trial.next((int64_t)pn * sn, c.opt.opt_shade_per, records);
+  // A masked pass stays out of the trial (its batches have sizes of their own): the option, else the decided value, else 4.
+  const ShadeTrial::Batch trial = L.masked ? ShadeTrial::Batch{0, c.opt.opt_shade_per ? c.opt.opt_shade_per : (c.trial.phase >= 4 ? c.trial.per : 4)}
+                                           : c.trial.next((int64_t)pn * sn, c.opt.opt_shade_per, records);
   // Option camera_dedup: the batch's distinct camera rays -- one per (pixel, sample & 3), DevPaths::cam_dedup -- are generated and traced
   // once; bounce 0 still runs over all P slots and reads every slot's hit from its distinct ray.  The counting variant traces every
   // sample's camera ray: its contract is "equal to the oracle's walk".
@@ -325,18 +330,26 @@ static int render_batch(const ArtPassParams* p, const DevFrame& F, const TraceLa
   return 0;
 }
 
-// One Render_Pass of the current context: check, plan and allocate, then enqueue batch after batch.
-static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
+// What a render pass refuses on its parameters and the context's state, apart from the spp rule; changes nothing.
+static int check_render_pass(const ArtPassParams* p) {
   Ctx& c = g_ctx;
   if (check_pass(p)) return 1;
   if (p->render_type == ART_RT_DEBUG || p->render_type == ART_RT_WHITTED) return fail("debug render types go through art_debug_hit_pass");
   if (p->render_type < ART_PT_STUPID || p->render_type > ART_PT_MIS) return fail("unknown render_type");
   if (c.scene.n_inst > 0 && c.opt.trace_kernel != TRACE_COOP) return fail("an instanced scene renders through the record schedule only (option trace_kernel = 0)");
+  return 0;
+}
+static const char* const kSppRule = "with anti-aliasing on, spp must be a multiple of 4 (Generate4RayDirections order)";
+
+// One Render_Pass of the current context over the pixel list L: check, plan and allocate, then enqueue batch after batch.
+static int render_pass_list(const ArtPassParams* p, int32_t* spp_inout, const PixelList& L) {
+  Ctx& c = g_ctx;
+  if (check_render_pass(p)) return 1;
   const int per = p->aa_on ? 4 : 1;
   if (spp_inout) c.spp = *spp_inout;
-  if (p->aa_on && (c.spp % 4) != 0) return fail("with anti-aliasing on, spp must be a multiple of 4 (Generate4RayDirections order)");
+  if (p->aa_on && (c.spp % 4) != 0) return fail(kSppRule);
   const int S = p->vthreads * per;           // samples this pass
-  const int npix = c.npix_local;
+  const int npix = L.n;
   DevFrame F; make_frame(p, F);
   BatchPlan plan = {0, 0};
   if (npix > 0 && plan_and_allocate(p, npix, S, per, plan)) return 1;
@@ -349,7 +362,7 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   for (int px0 = 0; px0 < npix; px0 += plan.pc) {
     const int pn = std::min(plan.pc, npix - px0);
     for (int s0 = 0; s0 < S; s0 += plan.sc) {
-      if (render_batch(p, F, launch, px0, pn, s0, std::min(plan.sc, S - s0))) return 1;
+      if (render_batch(p, F, launch, L, px0, pn, s0, std::min(plan.sc, S - s0))) return 1;
     }
   }
   HIP_TRY(pass_timer.end());
@@ -357,6 +370,86 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
   c.spp += S;
   c.stats.samples += (uint64_t)npix * S;
   if (spp_inout) *spp_inout = c.spp;
+  return 0;
+}
+static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
+  Ctx& c = g_ctx;
+  return render_pass_list(p, spp_inout, PixelList{(const uint32_t*)c.b_pixmap.p, c.npix_local, false});
+}
+
+// ---- mask compaction and the masked pass (art_select.hip) --------------------------------------------------------------------------
+// b_select = the count word of the masked pass (its first 256 bytes) | one word per workgroup of 256 list entries.  Growing it (or
+// `also`) may wait: nothing enqueued may still use the old buffers.
+static int ensure_select_scratch(const StreamOrder& order, int n, DevBuf* also = nullptr, size_t also_bytes = 0) {
+  Ctx& c = g_ctx;
+  const size_t bytes = 256 + (size_t)select_blocks(n) * sizeof(uint32_t);
+  if (c.b_select.bytes >= bytes && (!also || also->bytes >= also_bytes)) return 0;
+  HIP_TRY(hipStreamSynchronize(c.stream));
+  if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
+  if (ensure(c.b_select, bytes)) return 1;
+  if (also && ensure(*also, also_bytes)) return 1;
+  return 0;
+}
+// the three launches over the context's pixel list (n = npix_local >= 1 entries) on st
+static void enqueue_compact(hipStream_t st, const uint8_t* mask1b, uint32_t* pixels_out, uint32_t* count_out) {
+  Ctx& c = g_ctx;
+  SelectArgs A;
+  A.mask = mask1b; A.pixmap = (const uint32_t*)c.b_pixmap.p; A.n = c.npix_local;
+  A.block_sums = (uint32_t*)((char*)c.b_select.p + 256); A.out = pixels_out;
+  launch_compact_mask(st, A, count_out);
+}
+
+int compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap, uint32_t* count_out, hipStream_t st) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_compact_mask_device";
+  if (!mask1b || !pixels_out || !count_out) return fail(name + ": null mask1b, pixels_out or count_out");
+  if (c.width <= 0) return fail(name + ": no viewport (art_resize)");
+  if ((int64_t)c.npix_local > (1ll << 28)) return fail(name + ": the pixel list holds more than 2^28 pixels");
+  if (cap < (int64_t)c.npix_local) return fail(name + ": cap " + std::to_string(cap) + " is smaller than the rank's pixel list (" + std::to_string(c.npix_local) + " pixels)");
+  if (ensure_device()) return 1;
+  if (check_device_ptr(mask1b, (size_t)c.width * (size_t)c.height, "mask1b") || check_device_ptr(pixels_out, 4 * (size_t)cap, "pixels_out") ||
+      check_device_ptr(count_out, 4, "count_out"))
+    return 1;
+  StreamOrder order(c, st);
+  if (c.npix_local > 0 && ensure_select_scratch(order, c.npix_local)) return 1;
+  if (order.enter()) return 1;
+  int rc = 0;
+  if (c.npix_local > 0) enqueue_compact(order.qs, mask1b, pixels_out, count_out);
+  else if (hipMemsetAsync(count_out, 0, 4, order.qs) != hipSuccess) rc = fail(name + ": hipMemsetAsync failed");
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
+// art_render_pass_masked on the current context (single device: the caller checked).  Everything is refused before the first launch.
+int render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* counts1u, int32_t* spp_inout, int64_t* pixels_out) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_render_pass_masked";
+  if (check_render_pass(p)) return 1;
+  if (p->aa_on && ((spp_inout ? *spp_inout : c.spp) % 4) != 0) return fail(kSppRule);
+  if (!mask1b) return fail(name + ": null mask1b");
+  if ((int64_t)c.npix_local > (1ll << 28)) return fail(name + ": the pixel list holds more than 2^28 pixels");
+  const size_t N = (size_t)c.width * (size_t)c.height;
+  if (check_device_ptr(mask1b, N, "mask1b") || (counts1u && check_device_ptr(counts1u, 4 * N, "counts1u"))) return 1;
+  uint32_t count = 0;
+  const uint32_t* list = nullptr;
+  if (c.npix_local > 0) {
+    StreamOrder order(c, nullptr);
+    if (ensure_select_scratch(order, c.npix_local, &c.b_masklist, (size_t)c.npix_local * sizeof(uint32_t))) return 1;
+    uint32_t* const d_count = (uint32_t*)c.b_select.p;
+    enqueue_compact(c.stream, mask1b, (uint32_t*)c.b_masklist.p, d_count);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&count, d_count, sizeof count, hipMemcpyDeviceToHost, c.stream));
+    HIP_TRY(hipStreamSynchronize(c.stream));               // the one wait: the host plans the batches from the list's length
+    if (count > (uint32_t)c.npix_local) return fail(name + ": internal: the compacted list is longer than the pixel list");
+    list = (const uint32_t*)c.b_masklist.p;
+  }
+  if (render_pass_list(p, spp_inout, PixelList{list, (int)count, true})) return 1;
+  if (counts1u && count > 0) {
+    launch_add_counts(c.stream, list, (int)count, counts1u, (uint32_t)(p->vthreads * (p->aa_on ? 4 : 1)));
+    HIP_TRY(hipGetLastError());
+  }
+  if (pixels_out) *pixels_out = (int64_t)count;
   return 0;
 }
 

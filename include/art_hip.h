@@ -532,6 +532,82 @@ int  art_temporal_motion_device(const ArtTemporalParams* p, const float* color3f
                                 const int32_t* id, const float* motion3f, const void* hist_in, void* hist_out, float* out3f, float* variance_out,
                                 float* length_out, void* hip_stream);
 
+/* ---- adaptive sampling ------------------------------------------------------------------------------
+ * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
+ * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
+ *
+ * Ordered stream compaction of a mask over this rank's pixel list.  mask1b: one byte per pixel of the art_resize frame, row-major, device
+ * memory; non-zero = selected.  With pixmap[0 .. npix_local) the rank's pixel list (art_set_shard; 32 x 32 tiles, tile after tile, rows
+ * inside a tile: csrc/art_host_scene.cpp build_pixmap), pixels_out receives the global pixel indices g = pixmap[i] (y * width + x) with
+ * mask1b[g] != 0, for i = 0 .. npix_local - 1 IN THAT ORDER -- the list a render pass walks, filtered, so a masked pass keeps the tile
+ * locality of a full one -- and *count_out (one device word) their number.  Words of pixels_out from *count_out on are not written.  The
+ * result is the same bytes on every run: three launches (per-workgroup counts, a scan of those counts, the scatter), no atomic decides
+ * a position and no workgroup waits for another.  cap: the words pixels_out holds.
+ * Stream-ordered exactly as art_render_aovs_device (NULL = the library's stream, hipStreamLegacy = the null stream; the call runs after
+ * everything the library has enqueued and before anything it enqueues later; the host waits only when the library's scratch of one word
+ * per 256 list entries has to grow); under art_init_devices it is device 0's list.  Refused before anything is launched, with
+ * art_last_error set: a null pointer, no art_resize, a list of more than 2^28 pixels, cap smaller than the rank's list (npix_local), any
+ * pointer that is host memory, another device's memory or too small (width * height bytes of mask, 4 * cap of pixels_out, 4 of count_out). */
+int  art_compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap, uint32_t* count_out, void* hip_stream);
+
+/* One Render_Pass over the selected pixels of this rank's list: art_render_pass restricted to mask1b (device memory, a byte per pixel of
+ * the frame, row-major, non-zero = selected).  The mask is compacted (as art_compact_mask_device does) into a list the library owns,
+ * THE HOST WAITS for the library's stream ONCE to read the list's length back (4 bytes: it plans the batches), and the pass then runs
+ * art_render_pass's batches over that list.  The RNG is keyed by pixel, sample index and bounce, so:
+ *   - the samples are those with indices spp .. spp + S - 1 (S = vthreads * (aa_on ? 4 : 1), spp = *spp_inout as art_render_pass reads
+ *     it), and *spp_inout advances by S WHATEVER the mask holds, also when it selects nothing;
+ *   - a selected pixel this rank owns receives exactly the colours the full pass at that spp would add, in the same order, into the accum
+ *     (the library's or art_bind_accum's) and into bound moments: bit for bit the full pass restricted to the mask;
+ *   - no word of any other pixel's accum or moments is written.
+ * The frame's pixels then no longer share one sample count.  counts1u (may be NULL): a caller-owned uint32 per pixel, row-major, device
+ * memory; a kernel of its own adds S to the word of every selected pixel this rank owns.  art_resize does not know the buffer: the caller
+ * zeroes it (and adds S itself after a full pass).  ArtStats::samples grows by (selected pixels) * S; rays and the stage statistics come
+ * out of the kernels as ever.  *pixels_out (may be NULL, host memory) = the number of selected pixels this rank owns.
+ * The shade stage's items-per-thread trial (option "shade_per" = 0) is neither advanced nor reset: a masked pass runs with the pinned
+ * option, else the decided value, else 4, and a later full pass behaves as if the masked one had not happened.  The picture never
+ * depends on that setting.  The call ends as art_render_pass does: it waits for the pass and reports lost paths.
+ * Refused before anything is launched (the accum, *spp_inout and counts1u stay as they were): everything art_render_pass refuses; a null
+ * mask1b; art_init_devices(n > 1) (as art_bind_moments); a mask1b or counts1u that is host memory, another device's memory or too small. */
+int  art_render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* counts1u, int32_t* spp_inout, int64_t* pixels_out);
+
+/* Per pixel: the mean colour, the variance of the mean's luminance, a relative error and the mask of the next masked pass, in one kernel
+ * (one lane per pixel).  Scene-independent like the denoisers: it needs an initialised device only and touches no accum buffer, spp,
+ * ArtStats, path state or scratch (it has none: the host never waits).  Stream order and pointer rules are art_temporal_device's.
+ * Inputs, device memory, row-major: accum3f (art_bind_accum's layout), moments2f {S1, S2} (art_bind_moments), counts1u = the samples
+ * behind each pixel (art_render_pass_masked).  Outputs, each may be NULL but not all: mean3f (3 floats), variance1f, error1f (1 float),
+ * mask1b (1 byte, 0 or 1).  mean3f may be accum3f itself; any other overlap is the caller's error.
+ * Refused before anything is launched, with art_last_error set: null p, accum3f, moments2f or counts1u; all four outputs NULL; width or
+ * height < 1 or width * height > 2^28; min_colours < 2; max_samples < 0; a threshold that is NaN; a lum_floor that is negative or not
+ * finite; any given pointer that is host memory, another device's memory or too small for its plane.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_adaptive.h is its one definition, compiled for the GPU and for the host).  Pixel q.  Except for
+ * the mean, operands are converted to binary64 first, every operation is rounded to binary64 in the order written (division and sqrt
+ * correctly rounded), and each stored float is rounded ONCE to binary32.
+ *   per = aa_on ? 4 : 1;   s = counts1u[q];   n = s / per (the colours: a quotient in binary64);   k = 1 / per.
+ *   mean3f = (1.0f / (float)s) * accum3f, channel-wise in binary32;  s = 0: mean3f = +0.0f.
+ *   s = 0 or n < 2:  variance1f = error1f = +infinity (art_denoise_svgf_var_device reads that as "no colour stop").
+ *   Otherwise, with S1, S2 the pixel's moments:
+ *     D = S2 - (S1 * S1) / n;   D0 = (D < 0) ? 0 : D (a NaN stays a NaN);   v = (D0 * (n / (n - 1))) / n;   m = (S1 / n) * k;
+ *     variance1f = (float)(v * (k * k))   -- the variance of the mean's luminance in the units of mean3f: what
+ *                                            art_denoise_svgf_var_device takes with scale = 1;
+ *     error1f = (float)((sqrt(v) * k) / (fabs(m) + lum_floor))   -- the standard error of the mean's luminance relative to it.
+ *     A variance1f or error1f that is a NaN is stored as the quiet NaN 0x7fc00000, whatever sign and payload the arithmetic gave it
+ *     (processors differ there); mean3f keeps what the binary32 product gives.
+ *   mask1b = (s < max_samples) && (n < min_colours || !(error1f <= threshold)) ? 1 : 0, the comparison on the stored binary32 error:
+ *   an error equal to the threshold is converged, a NaN error keeps the pixel selected until s reaches max_samples, and a zero counts
+ *   plane selects every pixel (with max_samples > 0).
+ * Quality: profiles/adaptive/quality.json holds the sweep the defaults of Backend.render_adaptive were chosen by. */
+typedef struct ArtAdaptiveParams {
+  int32_t width, height;
+  int32_t aa_on;             /* the passes' anti-aliasing: a colour is 4 samples with it, else 1 */
+  int32_t min_colours;       /* >= 2: a pixel with fewer colours is always selected */
+  int32_t max_samples;       /* >= 0: a pixel with this many samples is never selected */
+  float   threshold;         /* error1f <= threshold: the pixel is converged */
+  float   lum_floor;         /* >= 0, added to |mean luminance| in the error's denominator: dark pixels are not chased */
+} ArtAdaptiveParams;
+int  art_adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u,
+                                  float* mean3f, float* variance1f, float* error1f, uint8_t* mask1b, void* hip_stream);
+
 /* The camera of the uploaded scene: cam_pos and cam_matrix replace ArtSceneDesc's in every context under
  * art_init_devices, without a rebuild.  Stream-ordered on the library's stream (art_set_stream), like the other scene updates: work
  * enqueued before the call sees the old camera, work enqueued after it the new one.  Every later pass, AOV call and query gives, bit for
