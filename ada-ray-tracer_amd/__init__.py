@@ -135,6 +135,11 @@ class ArtTemporalParams(C.Structure):
                 ("scale", C.c_float), ("depth_tol", C.c_float), ("normal_min", C.c_float)]
 
 
+class ArtSvgfSpatialParams(C.Structure):
+    _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("radius", C.c_int32), ("normal_log2", C.c_int32), ("min_history", C.c_float),
+                ("sigma_depth", C.c_float)]
+
+
 class ArtAdaptiveParams(C.Structure):
     _fields_ = [("width", C.c_int32), ("height", C.c_int32), ("aa_on", C.c_int32), ("min_colours", C.c_int32), ("max_samples", C.c_int32),
                 ("threshold", C.c_float), ("lum_floor", C.c_float)]
@@ -228,6 +233,10 @@ SVGF_SIGMA_COLOR = 2.0
 TEMPORAL_MAX_HISTORY = 64
 TEMPORAL_DEPTH_TOL = 0.2
 TEMPORAL_NORMAL_MIN = 0.5
+# Backend.svgf_spatial_variance_torch's defaults: the best setting of profiles/svgf_spatial/quality.json (the sweep of profiles/svgf_spatial/quality.py)
+SVGF_SPATIAL_RADIUS = 1
+SVGF_SPATIAL_MIN_HISTORY = 8.0
+SVGF_SPATIAL_SIGMA_DEPTH = 0.0
 # Backend.render_adaptive's and adaptive_estimate_torch's defaults: the best setting of profiles/adaptive/quality.json (the sweep of profiles/adaptive/quality.py)
 ADAPTIVE_THRESHOLD = 0.1
 ADAPTIVE_LUM_FLOOR = 1.0
@@ -242,7 +251,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_set_camera",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_svgf_spatial_variance_device", "art_set_camera",
     "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device",
     "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
@@ -297,6 +306,7 @@ def load_library():
     L.art_denoise_svgf_var_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
     L.art_temporal_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 11
     L.art_temporal_motion_device.argtypes = [C.POINTER(ArtTemporalParams)] + [C.c_void_p] * 12
+    L.art_svgf_spatial_variance_device.argtypes = [C.POINTER(ArtSvgfSpatialParams)] + [C.c_void_p] * 4
     L.art_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
     L.art_temporal_history_bytes.restype = C.c_int64
     L.art_compact_mask_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
@@ -880,6 +890,42 @@ class Backend:
         _check(self.lib.art_temporal_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
                                             ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
         return out, var, length, new
+
+    def svgf_spatial_variance_torch(self, hist, variance, width, height, radius=SVGF_SPATIAL_RADIUS, min_history=SVGF_SPATIAL_MIN_HISTORY,
+                                    sigma_depth=SVGF_SPATIAL_SIGMA_DEPTH, normal_log2=7, out=None):
+        """SVGF's spatial variance estimate (art_svgf_spatial_variance_device; include/art_hip.h states the arithmetic): where a pixel's
+        history is shorter than min_history colours, or its variance is not finite, the variance comes from the luminance moments pooled
+        over the (2 * radius + 1)^2 window of the history; every other pixel keeps its word.  hist: temporal_torch's fourth result,
+        float32 [3, H, W, 4]; variance: its second, float32 [H, W]; width, height: the frame's size, which both must have.  out: float32
+        [H, W] or None (a new tensor); it may be `variance` itself.  Returns out, enqueued on torch.cuda.current_stream() without waiting
+        for it; it goes into denoise_svgf_torch(variance=...).  Every tensor is checked before any C call.  The defaults of radius,
+        min_history and sigma_depth are the best setting of the sweep in profiles/svgf_spatial/quality.json."""
+        torch = sys.modules.get("torch")
+        call = "svgf_spatial_variance_torch"
+        w, h = int(width), int(height)
+        if w < 1 or h < 1:
+            raise ArtError("%s: width and height must be at least 1, not %d x %d" % (call, w, h))
+        for name, x, shape in (("hist", hist, (3, h, w, 4)), ("variance", variance, (h, w)), ("out", out, (h, w))):
+            if x is None and name == "out":
+                continue
+            if torch is None or not isinstance(x, torch.Tensor):
+                raise ArtError("%s: %s: a torch tensor is required, not %s" % (call, name, type(x).__name__))
+            if x.dtype != torch.float32:
+                raise ArtError("%s: %s: dtype must be torch.float32, not %s" % (call, name, x.dtype))
+            if tuple(x.shape) != shape:
+                raise ArtError("%s: %s: shape must be %s, not %s" % (call, name, list(shape), tuple(x.shape)))
+            if not x.is_contiguous():
+                raise ArtError("%s: %s: the tensor must be contiguous" % (call, name))
+        for name, x in (("hist", hist), ("variance", variance), ("out", out)):
+            if x is not None and (x.device.type != "cuda" or x.device != hist.device):
+                raise ArtError("%s: %s: must be a GPU tensor on %s, not on %s"
+                               % (call, name, hist.device if hist.device.type == "cuda" else "the library's device", x.device))
+        if out is None:
+            out = torch.empty((h, w), dtype=torch.float32, device=hist.device)
+        p = ArtSvgfSpatialParams(w, h, int(radius), int(normal_log2), float(min_history), float(sigma_depth))
+        stream = torch.cuda.current_stream(hist.device).cuda_stream
+        _check(self.lib.art_svgf_spatial_variance_device(C.byref(p), hist.data_ptr(), variance.data_ptr(), out.data_ptr(), stream or HIP_STREAM_LEGACY))
+        return out
 
     def _frame_tensor(self, torch, call, name, x, dtype, elements, optional=False):
         """A plane of the adaptive calls, checked as bind_moments checks its tensor: a contiguous GPU tensor of `dtype` with at least

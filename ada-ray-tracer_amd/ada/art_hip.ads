@@ -242,6 +242,21 @@ package Art_Hip is
   function art_temporal_history_bytes (width, height : int) return long;
   pragma Import (C, art_temporal_history_bytes, "art_temporal_history_bytes");
 
+  --  SVGF's spatial variance estimate (include/art_hip.h ArtSvgfSpatialParams, 24 bytes, states the arithmetic): between
+  --  art_temporal_device and art_denoise_svgf_var_device.  hist is art_temporal_device's hist_out; variance_out1f may be variance_in1f
+  --  itself and must not overlap hist; all DEVICE memory.
+  type Art_Svgf_Spatial_Params is record
+    width, height : int;
+    radius        : int;     --  1 .. 3; 3 = the 7 x 7 window
+    normal_log2   : int;     --  0 .. 10
+    min_history   : C_float; --  a pixel with at least this many colours and a finite variance keeps its variance
+    sigma_depth   : C_float; --  <= 0: no depth stop
+  end record;
+  pragma Convention (C, Art_Svgf_Spatial_Params);
+  function art_svgf_spatial_variance_device (p : access constant Art_Svgf_Spatial_Params; hist, variance_in1f, variance_out1f : System.Address;
+                                             hip_stream : System.Address) return int;
+  pragma Import (C, art_svgf_spatial_variance_device, "art_svgf_spatial_variance_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

@@ -835,6 +835,28 @@ int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, c
   return rc;
 }
 
+// art_svgf_spatial_variance_device: one kernel over the caller's history and variance planes (art_svgf_spatial.h), in the queries' stream
+// order.  Like art_temporal_device it has no scratch, needs no scene and no viewport and takes no event pair.
+int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f, hipStream_t st) {
+  const std::string name = "art_svgf_spatial_variance_device";
+  SvgfSpatialArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = sv::params_from_abi(p, hist, variance_in1f, variance_out1f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_device_ptr(hist, 48 * N, "hist") || check_device_ptr(variance_in1f, 4 * N, "variance_in1f") || check_device_ptr(variance_out1f, 4 * N, "variance_out1f"))
+    return 1;
+  StreamOrder order(c, st);
+  if (order.enter()) return 1;
+  A.tiles_x = svgf_spatial_tiles_x(A.P.W);
+  A.hist = (const sv::Rec4*)hist; A.variance_in = variance_in1f; A.variance_out = variance_out1f;
+  launch_svgf_spatial(order.qs, A);
+  int rc = 0;
+  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
+  if (order.leave()) return 1;          // (also after a failed launch)
+  return rc;
+}
+
 void shutdown() {
   if (g_devs[0].device_ready && !use_dev(0)) { reset_reduce_info(); g_reduce_pairs.destroy(); }
   if (g_comms_ready) { for (int k = 0; k < g_ndev; ++k) (void)ncclCommDestroy(g_comms[k]); g_comms_ready = false; }
@@ -1066,6 +1088,11 @@ int art_adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3
                                  float* mean3f, float* variance1f, float* error1f, uint8_t* mask1b, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return adaptive_estimate_device(p, accum3f, moments2f, counts1u, mean3f, variance1f, error1f, mask1b, (hipStream_t)hip_stream);
+}
+
+int art_svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return svgf_spatial_variance_device(p, hist, variance_in1f, variance_out1f, (hipStream_t)hip_stream);
 }
 
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {

@@ -8,6 +8,7 @@
 #include "art_temporal.h"
 #include "art_motion.h"
 #include "art_adaptive.h"
+#include "art_svgf_spatial.h"
 
 namespace art {
 
@@ -175,6 +176,16 @@ struct AdaptiveArgs {
   float* mean; float* variance; float* error; uint8_t* mask;
 };
 void launch_adaptive_estimate(hipStream_t st, const AdaptiveArgs& A);
+
+// art_svgf_spatial_variance_device (art_svgf_spatial.hip, art_api.cpp svgf_spatial_variance_device): the history of art_temporal_device and
+// the caller's two variance planes (they may be one); tiles_x = svgf_spatial_tiles_x(P.W), the kernel's tiles per row of tiles
+struct SvgfSpatialArgs {
+  sv::Params P;
+  int32_t tiles_x;
+  const sv::Rec4* hist; const float* variance_in; float* variance_out;
+};
+int svgf_spatial_tiles_x(int width);
+void launch_svgf_spatial(hipStream_t st, const SvgfSpatialArgs& A);
 
 // refit of the CLOSEST mesh's tree in place (art_refit.hip, art_update.cpp art_refit_device)
 constexpr float kRefitMaxCoord = 1.0e18f;      // the GPU SAH builder's limit: a vertex coordinate beyond it (or not finite) is a bad vertex

@@ -532,6 +532,56 @@ int  art_temporal_motion_device(const ArtTemporalParams* p, const float* color3f
                                 const int32_t* id, const float* motion3f, const void* hist_in, void* hist_out, float* out3f, float* variance_out,
                                 float* length_out, void* hip_stream);
 
+/* SVGF's spatial variance estimate (Schied et al. 2017, section 4.2): where a pixel's history is short -- the
+ * first frame, a disocclusion, a restart on a silhouette -- the variance of art_temporal_device comes from one or two numbers, or is
+ * +infinity (fewer than two colours: "no colour stop" in art_denoise_svgf_var_device).  This call replaces it there by the variance of
+ * the luminance moments pooled over a (2 * radius + 1)^2 window of the history, weighted by the filter's normal and depth stops, and
+ * copies every other pixel's variance.  It goes between art_temporal_device and art_denoise_svgf_var_device.
+ * hist: art_temporal_device's hist_out of the frame (48 * width * height bytes, the layout stated there), read only.  variance_in1f,
+ * variance_out1f: one float per pixel, row-major; variance_out1f may BE variance_in1f (a pixel reads only its own word of it), it must
+ * not overlap hist.  Scene-independent like the denoisers: an initialised device only, no scratch (the host never waits), no ArtStats;
+ * stream order and pointer rules are art_temporal_device's.
+ * Refused before anything is launched, with art_last_error set: a null pointer; width or height < 1 or width * height > 2^28; radius
+ * outside 1 .. 3; normal_log2 outside 0 .. 10; a min_history or sigma_depth that is NaN; variance_out1f overlapping hist; a pointer
+ * that is host memory, another device's memory or too small for its plane.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_svgf_spatial.h is its one definition, compiled for the GPU and for the host).  Binary32, not
+ * contracted, in the order written, division correctly rounded, except where binary64 is named.  finite(v): neither NaN nor an infinity.
+ * Of pixel q the history holds n_q (plane 0's fourth word), m1_q, m2_q, z_q (plane 1's first three) and the normal N_q (plane 2's first
+ * three).  Centre p = (x, y).
+ *  LONG HISTORY: n_p >= min_history and finite(variance_in[p]) (a NaN n_p or min_history = +infinity fail):  variance_out[p] =
+ *   variance_in[p], the same word.  Nothing else is read for the pixel.
+ *  SHORT HISTORY, every other pixel:
+ *   Gradient, when sigma_depth > 0 (else 0): gx = 0.5f * (z(x1, y) - z(x0, y)), gy = 0.5f * (z(x, y1) - z(x, y0)) with x1 = min(x + 1,
+ *   width - 1), x0 = max(x - 1, 0), likewise y1, y0 -- art_denoise_device's gradient over the history's depth.  zfloor = 1e-3f * z_p + 1e-6f.
+ *   Taps: for dy = -radius .. radius outer, dx = -radius .. radius inner, q = p + (dx, dy).  A tap COUNTS when it is inside the frame,
+ *   n_q, m1_q, m2_q, z_q and the three words of N_q are finite, n_q > 0, and its weight w is not a NaN.  The centre's w is 1.0f (it
+ *   counts under the same tests).  Every other tap: w = wn * e, the normal and depth stops of art_denoise_device, with neither its spline
+ *   weight h nor a colour term:
+ *     wn = amax(dot(N_p, N_q), 0.0f) squared normal_log2 times (dot and amax as there: (ax * bx + ay * by) + az * bz; a NaN gives 0);
+ *     xz = fabsf(z_p - z_q) / (sigma_depth * (fabsf(gx * (float)dx) + fabsf(gy * (float)dy)) + zfloor), or 0.0f when sigma_depth <= 0;
+ *     t = -(double)xz;  e = 0.0f when t < -200, (float)exp_small(t) when t <= 0 (exp_small as there), else a NaN (t positive or NaN).
+ *   Pooling, in binary64 (operands converted first, each operation rounded to binary64), N = S1 = S2 = 0, per counted tap in that order:
+ *     k = w * n_q (exact);   N += k;   S1 += k * m1_q;   S2 += k * m2_q.
+ *   N < 2:  variance_out[p] = +infinity.  Otherwise
+ *     M1 = S1 / N;   M2 = S2 / N;   D = M2 - M1 * M1;   D0 = (D < 0) ? 0 : D (a NaN stays a NaN);
+ *     variance_out[p] = (float)((D0 * (N / (N - 1))) / n_p), the one rounding to binary32 -- the variance of the centre's mean luminance
+ *     (n_p as it stands, whatever the centre's own tests said).  A NaN is stored as the quiet NaN 0x7fc00000.
+ *   When only the centre counts, N = n_p, M1 = m1_p and M2 = m2_p exactly (k * m1_p is exact in binary64), so the result is step 6 of
+ *   art_temporal_device's arithmetic, bit for bit: a window that finds nothing changes nothing.
+ * A history made without a normal plane holds N = (0, 0, 0): wn is then 0 for every neighbour and only the centre counts; the same holds
+ * for a pixel that missed the scene.  Quality: profiles/svgf_spatial/quality.json holds the sweep the defaults of
+ * Backend.svgf_spatial_variance_torch were chosen by. */
+typedef struct ArtSvgfSpatialParams {
+  int32_t width, height;
+  int32_t radius;            /* 1..3; 3 = the 7 x 7 window */
+  int32_t normal_log2;       /* 0..10: the normal stop's power, as ArtSvgfParams */
+  float   min_history;       /* colours; a pixel with n >= min_history and a finite variance_in keeps variance_in */
+  float   sigma_depth;       /* the depth stop, as ArtSvgfParams; <= 0: off */
+} ArtSvgfSpatialParams;
+int  art_svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f,
+                                      void* hip_stream);
+
 /* ---- adaptive sampling ------------------------------------------------------------------------------
  * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
  * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
