@@ -697,90 +697,61 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
   return rc;
 }
 
-// art_denoise_device: the a-trous filter of art_denoise.h over the caller's planes, in a scratch of its own (b_denoise: two images, the
-// guide records and the depth gradients, 56 bytes per pixel) and the queries' stream order.  It needs no scene and no viewport and takes
-// no event pair: ArtStats and ArtStageStats do not see it.
-int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st) {
-  const std::string name = "art_denoise_device";
-  if (!p) return fail(name + ": null ArtDenoiseParams");
-  if (!color3f || !out3f) return fail(name + ": null color3f or out3f");
-  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return fail(name + ": width and height must be at least 1 and width * height at most 2^28");
-  if (p->iterations < 1 || p->iterations > 8) return fail(name + ": iterations must be 1 .. 8");
-  if (p->normal_log2 < 0 || p->normal_log2 > 10) return fail(name + ": normal_log2 must be 0 .. 10");
-  if (p->variant < 0 || p->variant > 2) return fail(name + ": variant must be 0 .. 2");
-  if (!std::isfinite(p->scale)) return fail(name + ": scale is not finite");
-  if (std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return fail(name + ": a sigma is NaN");
-  if (ensure_device()) return 1;
-  Ctx& c = g_ctx;
-  const size_t N = (size_t)p->width * (size_t)p->height;
-  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || (albedo3f && check_device_ptr(albedo3f, 12 * N, "albedo3f")) ||
-      (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) || (depth && check_device_ptr(depth, 4 * N, "depth")))
-    return 1;
-  StreamOrder order(c, st);
-  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2));
-  if (c.b_denoise.bytes < bytes) {        // growing it may wait: nothing enqueued may still use the old scratch
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
-    if (ensure(c.b_denoise, bytes)) return 1;
-  }
-  if (order.enter()) return 1;
-  DenoiseArgs A; std::memset(&A, 0, sizeof A);
-  A.P.W = p->width; A.P.H = p->height; A.P.normal_log2 = p->normal_log2; A.P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
-  A.P.has_normal = normal3f ? 1 : 0; A.P.has_depth = depth ? 1 : 0;
-  A.P.scale = p->scale; A.P.sigma_color = p->sigma_color; A.P.sigma_depth = p->sigma_depth;
-  A.n = (int32_t)N; A.color = color3f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f;
-  dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
-  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N);
-  launch_denoise(order.qs, A, p->iterations);      // (variant: one kernel exists, every tap from global memory; 0, 1 and 2 all select it)
+// The end of an image-space entry (the denoisers, art_temporal_device, art_adaptive_estimate_device, art_svgf_spatial_variance_device),
+// after its launches on order.qs.
+static int finish_launches(StreamOrder& order, const std::string& name) {
   int rc = 0;
   if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
   if (order.leave()) return 1;          // (also after a failed launch)
   return rc;
 }
 
-// art_denoise_svgf_device: the variance-guided filter of art_denoise.h's second half.  Scratch (b_denoise, shared with art_denoise_device:
-// both run in the queries' stream order): two images, the guide records, the depth plane and the depth gradients, 60 bytes per pixel.
-int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
-                        float* out3f, float* variance_out, hipStream_t st, bool variance_plane) {
-  const std::string name = variance_plane ? "art_denoise_svgf_var_device" : "art_denoise_svgf_device";
-  if (!p) return fail(name + ": null ArtSvgfParams");
-  if (!color3f || !out3f) return fail(name + ": null color3f or out3f");
-  if (!moments2f) return fail(name + (variance_plane ? ": null variance1f" : ": null moments2f"));
-  if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return fail(name + ": width and height must be at least 1 and width * height at most 2^28");
-  if (p->iterations < 1 || p->iterations > 8) return fail(name + ": iterations must be 1 .. 8");
-  if (p->normal_log2 < 0 || p->normal_log2 > 10) return fail(name + ": normal_log2 must be 0 .. 10");
-  if (!variance_plane && p->n_colours < 2) return fail(name + ": n_colours must be at least 2");
-  if (!std::isfinite(p->scale)) return fail(name + ": scale is not finite");
-  if (std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return fail(name + ": a sigma is NaN");
+// The three a-trous filters of art_denoise.h over the caller's planes (A.P and the planes are set, dn::params_from_abi has passed), in a
+// scratch of their own (b_denoise, shared: all run in the queries' stream order) and the queries' stream order.  Scratch per pixel: two
+// images, the guide records and the depth gradients, 56 bytes; the modes that carry a variance add the depth plane, 60 bytes.  They need
+// no scene and no viewport and take no event pair: ArtStats and ArtStageStats do not see them.
+static int run_denoise(const std::string& name, dn::Mode mode, DenoiseArgs& A, int iterations, hipStream_t st) {
   if (ensure_device()) return 1;
   Ctx& c = g_ctx;
-  const size_t N = (size_t)p->width * (size_t)p->height;
-  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(out3f, 12 * N, "out3f") || check_device_ptr(moments2f, (variance_plane ? 4 : 8) * N, variance_plane ? "variance1f" : "moments2f") ||
-      (albedo3f && check_device_ptr(albedo3f, 12 * N, "albedo3f")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
-      (depth && check_device_ptr(depth, 4 * N, "depth")) || (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")))
+  const bool v = dn::carries_variance(mode), plane = (mode == dn::Mode::SvgfVar);
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_device_ptr(A.color, 12 * N, "color3f") || check_device_ptr(A.out, 12 * N, "out3f") ||
+      (v && check_device_ptr(A.moments, (plane ? 4 : 8) * N, plane ? "variance1f" : "moments2f")) ||
+      (A.albedo && check_device_ptr(A.albedo, 12 * N, "albedo3f")) || (A.normal && check_device_ptr(A.normal, 12 * N, "normal3f")) ||
+      (A.depth && check_device_ptr(A.depth, 4 * N, "depth")) || (A.variance_out && check_device_ptr(A.variance_out, 4 * N, "variance_out")))
     return 1;
   StreamOrder order(c, st);
-  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2) + sizeof(float));
+  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2) + (v ? sizeof(float) : 0));
   if (c.b_denoise.bytes < bytes) {        // growing it may wait: nothing enqueued may still use the old scratch
     HIP_TRY(hipStreamSynchronize(c.stream));
     if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
     if (ensure(c.b_denoise, bytes)) return 1;
   }
   if (order.enter()) return 1;
-  SvgfArgs A; std::memset(&A, 0, sizeof A);
-  A.P.W = p->width; A.P.H = p->height; A.P.normal_log2 = p->normal_log2; A.P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
-  A.P.has_normal = normal3f ? 1 : 0; A.P.has_depth = depth ? 1 : 0;
-  A.P.scale = p->scale; A.P.sigma_color = p->sigma_color; A.P.sigma_depth = p->sigma_depth;
-  A.n = (int32_t)N; A.n_colours = p->n_colours;
-  A.color = color3f; A.moments = moments2f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f; A.variance_out = variance_out;
+  A.n = (int32_t)N;
   dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
-  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N); A.z = (float*)(A.grad + N);
-  if (variance_plane) launch_denoise_svgf_var(order.qs, A, p->iterations);      // (A.moments: the variance plane; A.n_colours is not read)
-  else launch_denoise_svgf(order.qs, A, p->iterations);
-  int rc = 0;
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
+  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N); A.z = v ? (float*)(A.grad + N) : nullptr;
+  launch_denoise(order.qs, mode, A, iterations);
+  return finish_launches(order, name);
+}
+
+int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st) {
+  const std::string name = "art_denoise_device";
+  DenoiseArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = dn::params_from_abi(p, color3f, albedo3f, normal3f, depth, out3f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  A.color = color3f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f;
+  return run_denoise(name, dn::Mode::Plain, A, p->iterations, st);      // (variant: one kernel exists, every tap from global memory; 0, 1 and 2 all select it)
+}
+
+// variance_plane: art_denoise_svgf_var_device, whose moments2f is the variance plane
+int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
+                        float* out3f, float* variance_out, hipStream_t st, bool variance_plane) {
+  const std::string name = variance_plane ? "art_denoise_svgf_var_device" : "art_denoise_svgf_device";
+  DenoiseArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = dn::params_from_abi(p, color3f, moments2f, albedo3f, normal3f, depth, out3f, variance_plane, A.P)) return fail(name + ": " + why);
+  A.n_colours = p->n_colours;
+  A.color = color3f; A.moments = moments2f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f; A.variance_out = variance_out;
+  return run_denoise(name, variance_plane ? dn::Mode::SvgfVar : dn::Mode::Svgf, A, p->iterations, st);
 }
 
 // art_temporal_device: one kernel over the caller's planes and histories (art_temporal.h), in the queries' stream order.  It has no scratch
@@ -805,10 +776,7 @@ int temporal_device(const ArtTemporalParams* p, const float* color3f, const floa
   A.n = (int32_t)N; A.color = color3f; A.moments = moments2f; A.normal = normal3f; A.depth = depth; A.id = id;
   A.hist_in = (const tp::Rec4*)hist_in; A.hist_out = (tp::Rec4*)hist_out; A.out = out3f; A.variance_out = variance_out; A.length_out = length_out;
   launch_temporal(order.qs, A);
-  int rc = 0;
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
+  return finish_launches(order, name);
 }
 
 // art_adaptive_estimate_device: one kernel over the caller's planes (art_adaptive.h), in the queries' stream order.  Like art_temporal_device
@@ -829,10 +797,7 @@ int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, c
   if (order.enter()) return 1;
   A.accum = accum3f; A.moments = moments2f; A.counts = counts1u; A.mean = mean3f; A.variance = variance1f; A.error = error1f; A.mask = mask1b;
   launch_adaptive_estimate(order.qs, A);
-  int rc = 0;
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
+  return finish_launches(order, name);
 }
 
 // art_svgf_spatial_variance_device: one kernel over the caller's history and variance planes (art_svgf_spatial.h), in the queries' stream
@@ -851,10 +816,7 @@ int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist
   A.tiles_x = svgf_spatial_tiles_x(A.P.W);
   A.hist = (const sv::Rec4*)hist; A.variance_in = variance_in1f; A.variance_out = variance_out1f;
   launch_svgf_spatial(order.qs, A);
-  int rc = 0;
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
+  return finish_launches(order, name);
 }
 
 void shutdown() {

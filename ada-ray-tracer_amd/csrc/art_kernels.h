@@ -121,30 +121,18 @@ struct AovMotionArgs : AovArgs {
 };
 void launch_aov_resolve_motion(hipStream_t st, const DevFrame& F, const DevScene& S, const AovMotionArgs& A);
 
-// art_denoise_device (art_denoise.hip, art_api.cpp denoise_device): the caller's planes (albedo / normal / depth nullptr: not given; out
-// may be color) and the library's scratch records of art_denoise.h, n = W * H of each
+// art_denoise_device, art_denoise_svgf_device and art_denoise_svgf_var_device (art_denoise.hip, art_api.cpp run_denoise): the caller's planes
+// (albedo / normal / depth / variance_out nullptr: not given; out may be color) and the library's scratch records of art_denoise.h, n = W * H
+// of each.  moments: the moments plane or, for dn::Mode::SvgfVar, the variance plane (n_colours is then not read).  dn::Mode::Plain leaves
+// n_colours, moments, variance_out and z zero: its kernels read none of them.
 struct DenoiseArgs {
-  dn::Params P;
-  int32_t n;
-  const float* color; const float* albedo; const float* normal; const float* depth;
-  float* out;
-  dn::Rec4* image[2]; dn::Rec4* guide; dn::Rec2* grad;
-};
-void launch_denoise(hipStream_t st, const DenoiseArgs& A, int iterations);      // the pack kernel and `iterations` filter launches
-
-// art_denoise_svgf_device (art_denoise.hip, art_api.cpp denoise_svgf_device): the same, with the moments plane, the optional variance
-// plane and the scratch layout of art_denoise.h's second half (the depth in a plane of its own)
-struct SvgfArgs {
   dn::Params P;
   int32_t n, n_colours;
   const float* color; const float* moments; const float* albedo; const float* normal; const float* depth;
   float* out; float* variance_out;
   dn::Rec4* image[2]; dn::Rec4* guide; float* z; dn::Rec2* grad;
 };
-void launch_denoise_svgf(hipStream_t st, const SvgfArgs& A, int iterations);
-// art_denoise_svgf_var_device: the same launches behind a pack kernel of its own, which reads A.moments as the variance plane (one float per
-// pixel) and ignores A.n_colours
-void launch_denoise_svgf_var(hipStream_t st, const SvgfArgs& A, int iterations);
+void launch_denoise(hipStream_t st, dn::Mode mode, const DenoiseArgs& A, int iterations);      // the mode's pack kernel and `iterations` filter launches
 
 // art_temporal_device (art_temporal.hip, art_api.cpp temporal_device): the caller's current planes (normal / depth / id nullptr: not given),
 // the two histories (hist_in nullptr: the first frame) and the optional outputs; n = W * H of the current frame

@@ -4,7 +4,7 @@
 // the host build cannot drift apart.
 //
 // The history is art_temporal_device's hist_out (art_temporal.h): three planes of 16-byte records, so a tap costs three 16-byte loads.
-// The stops are those of dn::atrous_pixel (art_denoise.h) without the spline and without the colour term.
+// The stops are the a-trous filters' own (dn::stop_weight, art_denoise.h), with no spline weight and no colour term.
 #pragma once
 #include <stdint.h>
 #include "art_hip.h"
@@ -48,18 +48,8 @@ ART_HD float pooled_variance(const Params& P, const Rec4* hist, int x, int y) {
   const size_t p = (size_t)y * (size_t)P.W + (size_t)x;
   const float n_p = hist[p].w;
   const Rec4 bp = hist[N + p], cp = hist[2 * N + p];
-  const float zp = bp.z;
-  const bool use_depth = P.sigma_depth > 0.0f;
-  float gx = 0.0f, gy = 0.0f;
-  if (use_depth) {
-    const int x1 = (x + 1 < P.W) ? x + 1 : P.W - 1, x0 = (x > 0) ? x - 1 : 0;
-    const int y1 = (y + 1 < P.H) ? y + 1 : P.H - 1, y0 = (y > 0) ? y - 1 : 0;
-    const size_t row = N + (size_t)y * (size_t)P.W;
-    gx = 0.5f * (hist[row + (size_t)x1].z - hist[row + (size_t)x0].z);
-    gy = 0.5f * (hist[N + (size_t)y1 * (size_t)P.W + (size_t)x].z - hist[N + (size_t)y0 * (size_t)P.W + (size_t)x].z);
-  }
-  const float zfloor = 1e-3f * zp + 1e-6f;
-  const f3 np = mk3(cp.x, cp.y, cp.z);
+  dn::Stops stops = {mk3(cp.x, cp.y, cp.z), 1, P.normal_log2, P.sigma_depth > 0.0f, bp.z, 0.0f, 0.0f, 1e-3f * bp.z + 1e-6f, P.sigma_depth};
+  if (stops.use_depth) dn::central_difference(P.W, P.H, x, y, [hist, N](size_t k) { return hist[N + k].z; }, stops.gx, stops.gy);
   double Ns = 0.0, S1 = 0.0, S2 = 0.0;
   for (int dy = -P.radius; dy <= P.radius; ++dy) {
     const int qy = y + dy;
@@ -75,19 +65,7 @@ ART_HD float pooled_variance(const Params& P, const Rec4* hist, int x, int y) {
       const Rec4 c = hist[2 * N + q];
       if (!(finite_f(c.x) && finite_f(c.y) && finite_f(c.z))) continue;
       float w = 1.0f;
-      if (dx != 0 || dy != 0) {
-        float wn = amax(dot(np, mk3(c.x, c.y, c.z)), 0.0f);
-        for (int j = 0; j < P.normal_log2; ++j) wn = wn * wn;
-        float xz = 0.0f;
-        if (use_depth) xz = fabsf(zp - b.z) / (P.sigma_depth * (fabsf(gx * (float)dx) + fabsf(gy * (float)dy)) + zfloor);
-        const double t = -(double)xz;
-        float e;
-        if (t < -200.0) e = 0.0f;
-        else if (t <= 0.0) e = (float)m1::exp_small(t);
-        else e = __builtin_bit_cast(float, 0x7fc00000u);        // t NaN (or positive: a negative depth): the tap is skipped below
-        w = wn * e;
-        if (w != w) continue;
-      }
+      if ((dx != 0 || dy != 0) && !dn::stop_weight(stops, 1.0f, mk3(c.x, c.y, c.z), b.z, (float)dx, (float)dy, 0.0f, w)) continue;
       const double k = (double)w * (double)nq;
       Ns += k; S1 += k * (double)b.x; S2 += k * (double)b.y;
     }

@@ -11,7 +11,7 @@
 //                once and is shared through L1 / L2 (a 1920 x 1080 history is 100 MB, the size of the Infinity Cache).  A tap
 //                of weight zero is not loaded: with cameras at rest one tap per pixel remains.  The new history leaves as three 16-byte
 //                stores per lane (a wave: 1 KB contiguous per plane); out3f leaves as three dword stores per lane at a stride of 12
-//                bytes (a wave's 768 bytes are contiguous, but k_atrous stages the same plane through LDS; the cost of not doing so
+//                bytes (a wave's 768 bytes are contiguous, but k_atrous<*, true> stages the same plane through LDS; the cost of not doing so
 //                here is unmeasured).  No LDS, no atomics, no barrier: every output has one owner.
 //
 // Compulsory bytes per pixel, every plane given: read 12 (colour) + 8 (moments) + 12 (normal) + 4 (depth) + 4 (id) + 48 (each history record

@@ -106,7 +106,7 @@ def fold_kstats(args):
         raise SystemExit("no *kernel_stats.csv under %s" % args.kstats)
     k = {}
     for r in csv.DictReader(open(files[0])):
-        name = r["Name"].replace("void ", "").replace("art::", "").split("(")[0]
+        name = r["Name"].replace("void ", "").replace("art::", "").rsplit("(", 1)[0]      # (the pack kernel's template argument holds a "(" too)
         if name.startswith("k_denoise_pack") or name.startswith("k_atrous"):
             e = k.setdefault(name, {"calls": 0, "total_ns": 0})
             e["calls"] += int(r["Calls"]); e["total_ns"] += int(r["TotalDurationNs"])

@@ -9,7 +9,8 @@ Workload: C4 (scenes.synthetic_scene(1000000, 4)) at 1920 x 1080, accum and mome
                   The bound variant adds 8 B read and 8 B written per pixel to the accumulate's rad reads (12 B per sample) and the
                   accum's 12 + 12 B.
   (c) kernel_ms   with --kstats DIR (a rocprofv3 --kernel-trace --stats run of `measure.py --device-only`): time per launch of
-                  k_svgf_pack, k_svgf_atrous<false>, k_svgf_atrous<true> next to the plain filter's kernels.
+                  k_denoise_pack<dn::Mode::Svgf>, k_atrous<true, false>, k_atrous<true, true> next to the plain filter's kernels
+                  (k_denoise_pack<dn::Mode::Plain>, k_atrous<false, false>, k_atrous<false, true>).
 
 usage: python profiles/svgf/measure.py --out DIR
        rocprofv3 --kernel-trace --stats --output-format csv -d DIR/trace -- python profiles/svgf/measure.py --device-only
@@ -101,8 +102,8 @@ def fold_kstats(args):
         raise SystemExit("no *kernel_stats.csv under %s" % args.kstats)
     k = {}
     for r in csv.DictReader(open(files[0])):
-        name = r["Name"].replace("void ", "").replace("art::", "").split("(")[0]
-        if name.startswith(("k_denoise_pack", "k_atrous", "k_svgf")):
+        name = r["Name"].replace("void ", "").replace("art::", "").rsplit("(", 1)[0]      # (a pack kernel's template argument holds a "(" too)
+        if name.startswith(("k_denoise_pack", "k_atrous")):
             e = k.setdefault(name, {"calls": 0, "total_ns": 0})
             e["calls"] += int(r["Calls"]); e["total_ns"] += int(r["TotalDurationNs"])
     res["kernel_ms"] = {key: v["total_ns"] * 1e-6 / max(1, v["calls"]) for key, v in k.items()}      # per launch

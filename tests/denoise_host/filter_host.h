@@ -1,0 +1,31 @@
+// TEST-ONLY: the driver of the a-trous filters on host arrays, pack -> iterate -> finish, through the product's own per-pixel text
+// (csrc/art_denoise.h) in the mode the kernels take.  P comes from dn::params_from_abi; pointers are host memory; out3f may be color3f.
+// moments, n_colours and variance_out are as DenoiseArgs' (csrc/art_kernels.h); dn::Mode::Plain reads none of them.
+#pragma once
+#include <vector>
+#include "../../ada-ray-tracer_amd/csrc/art_denoise.h"
+
+template <art::dn::Mode M>
+void filter_host(const art::dn::Params& P, int iterations, int32_t n_colours, const float* color3f, const float* moments, const float* albedo3f,
+                 const float* normal3f, const float* depth, float* out3f, float* variance_out) {
+  using namespace art;
+  constexpr bool V = dn::carries_variance(M);
+  const size_t N = (size_t)P.W * (size_t)P.H;
+  std::vector<dn::Rec4> image[2] = {std::vector<dn::Rec4>(N), std::vector<dn::Rec4>(N)}, guide(N);
+  std::vector<dn::Rec2> grad(N);
+  std::vector<float> z(V ? N : 1);
+  for (int y = 0; y < P.H; ++y)
+    for (int x = 0; x < P.W; ++x) {
+      const size_t q = (size_t)y * P.W + x;
+      dn::prepare_pixel<M>(P, n_colours, color3f, moments, albedo3f, normal3f, depth, x, y, image[0][q], guide[q], z[V ? q : 0], grad[q]);
+    }
+  for (int i = 0; i < iterations; ++i)
+    for (int y = 0; y < P.H; ++y)
+      for (int x = 0; x < P.W; ++x)
+        image[(i + 1) & 1][(size_t)y * P.W + x] = dn::atrous_pixel<V>(P, image[i & 1].data(), guide.data(), V ? z.data() : nullptr, grad.data(), x, y, i);
+  const std::vector<dn::Rec4>& last = image[iterations & 1];
+  for (size_t q = 0; q < N; ++q) {
+    dn::finish_pixel(P, albedo3f, q, last[q], out3f[3 * q], out3f[3 * q + 1], out3f[3 * q + 2]);
+    if (V && variance_out) variance_out[q] = last[q].w;
+  }
+}

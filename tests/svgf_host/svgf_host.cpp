@@ -7,38 +7,16 @@
 #include <cstring>
 #include <vector>
 #include "art_hip.h"
-#include "../../ada-ray-tracer_amd/csrc/art_denoise.h"
+#include "../denoise_host/filter_host.h"
 #include "../../ada-ray-tracer_amd/csrc/art_shade.h"
 
 using namespace art;
 
 extern "C" int sh_denoise_svgf(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f,
                                const float* depth, float* out3f, float* variance_out) {
-  if (!p || !color3f || !out3f || !moments2f || p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return 1;
-  if (p->iterations < 1 || p->iterations > 8 || p->normal_log2 < 0 || p->normal_log2 > 10 || p->n_colours < 2) return 1;
-  if (!std::isfinite(p->scale) || std::isnan(p->sigma_color) || std::isnan(p->sigma_depth)) return 1;
   dn::Params P;
-  P.W = p->width; P.H = p->height; P.normal_log2 = p->normal_log2; P.demod = (p->demodulate != 0 && albedo3f) ? 1 : 0;
-  P.has_normal = normal3f ? 1 : 0; P.has_depth = depth ? 1 : 0;
-  P.scale = p->scale; P.sigma_color = p->sigma_color; P.sigma_depth = p->sigma_depth;
-  const size_t N = (size_t)P.W * (size_t)P.H;
-  std::vector<dn::Rec4> image[2] = {std::vector<dn::Rec4>(N), std::vector<dn::Rec4>(N)}, guide(N);
-  std::vector<dn::Rec2> grad(N);
-  std::vector<float> z(N);
-  for (int y = 0; y < P.H; ++y)
-    for (int x = 0; x < P.W; ++x) {
-      const size_t q = (size_t)y * P.W + x;
-      dn::svgf_pack_pixel(P, p->n_colours, color3f, moments2f, albedo3f, normal3f, depth, x, y, image[0][q], guide[q], z[q], grad[q]);
-    }
-  for (int i = 0; i < p->iterations; ++i)
-    for (int y = 0; y < P.H; ++y)
-      for (int x = 0; x < P.W; ++x)
-        image[(i + 1) & 1][(size_t)y * P.W + x] = dn::svgf_atrous_pixel(P, image[i & 1].data(), guide.data(), z.data(), grad.data(), x, y, i);
-  const std::vector<dn::Rec4>& last = image[p->iterations & 1];
-  for (size_t q = 0; q < N; ++q) {
-    dn::finish_pixel(P, albedo3f, q, last[q], out3f[3 * q], out3f[3 * q + 1], out3f[3 * q + 2]);
-    if (variance_out) variance_out[q] = last[q].w;
-  }
+  if (dn::params_from_abi(p, color3f, moments2f, albedo3f, normal3f, depth, out3f, false, P)) return 1;      // (the library's own derivation and refusals)
+  filter_host<dn::Mode::Svgf>(P, p->iterations, p->n_colours, color3f, moments2f, albedo3f, normal3f, depth, out3f, variance_out);
   return 0;
 }
 
