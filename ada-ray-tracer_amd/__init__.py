@@ -369,23 +369,110 @@ t, normal [N, 3], uv [N, 2]: float32; is_hit, prim_type, prim_index, mat_id, mat
 HIP_STREAM_LEGACY = 1      # hipStreamLegacy: torch's default stream is the null stream (handle 0), and NULL means the library's stream to the C ABI
 
 
-def _query_tensors(torch, origins, dirs, tnear, tfar):
-    """Checks of the device queries that need no GPU: float32, [N, 3] rays, [N] intervals; everything made contiguous."""
-    def f32(name, x, shape):
-        if not isinstance(x, torch.Tensor):
-            raise ArtError("%s: a torch tensor is required, not %s" % (name, type(x).__name__))
-        if x.dtype != torch.float32:
-            raise ArtError("%s: dtype must be torch.float32, not %s" % (name, x.dtype))
-        if tuple(x.shape) != shape:
-            raise ArtError("%s: shape %s, expected %s" % (name, tuple(x.shape), shape))
-        return x.contiguous()
-    if not isinstance(origins, torch.Tensor) or origins.dim() != 2:
-        raise ArtError("origins: a [N, 3] float32 tensor is required")
-    n = origins.shape[0]
-    o = f32("origins", origins, (n, 3)); d = f32("dirs", dirs, (n, 3))
-    tn = None if tnear is None else f32("tnear", tnear, (n,))
-    tf = None if tfar is None else f32("tfar", tfar, (n,))
-    return o, d, tn, tf, n
+def _ptr(x):
+    return None if x is None else x.data_ptr()
+
+
+def _stream(torch, device):
+    """torch's current stream of `device`: what the torch-facing calls enqueue on, without waiting for it"""
+    return torch.cuda.current_stream(device)
+
+
+def _handle(stream):
+    """a torch.cuda.Stream as the C ABI takes it"""
+    return stream.cuda_stream or HIP_STREAM_LEGACY
+
+
+# One argument of a torch-facing call: label is what a refusal opens with ("denoise_torch: albedo"), dtype the name of a torch dtype
+# (None: any), rule an exact shape, a least number of elements, or (predicate, sentence) where the sentence's {} is the shape as it
+# came (None: any shape); an optional plane may be None.
+_Plane = collections.namedtuple("_Plane", "label x dtype rule optional", defaults=(None, None, False))
+
+
+def _expected(*shape):
+    """the exact shape in the words of the older wrappers (the ray queries, the vertex updates)"""
+    return (lambda x: tuple(x.shape) == shape, "shape {}, expected %s" % (shape,))
+
+
+def _check_planes(torch, planes, contiguous="refuse", kind="", tail=""):
+    """THE check of what a plane is -- a torch tensor, its dtype, its shape, its layout, in that order, plane after plane -- for
+    every torch-facing call.  contiguous: "refuse" a strided tensor (`tail` ends that sentence), "make" it contiguous as the older
+    wrappers do, or None (not looked at).  kind: what else the argument may be, ahead of "a torch tensor is required".  Where a
+    plane is (_check_devices) is not looked at.  Returns the tensors, None for an absent optional plane."""
+    checked = []
+    for p in planes:
+        x, rule = p.x, p.rule
+        if x is None and p.optional:
+            checked.append(None)
+            continue
+        if torch is None or not isinstance(x, torch.Tensor):
+            raise ArtError("%s: %sa torch tensor is required, not %s" % (p.label, kind, type(x).__name__))
+        if p.dtype is not None and x.dtype != getattr(torch, p.dtype):
+            raise ArtError("%s: dtype must be %s, not %s" % (p.label, getattr(torch, p.dtype), x.dtype))
+        if isinstance(rule, int):
+            rule = (lambda x, n=rule: x.numel() >= n, "the tensor holds {numel} elements, the frame needs %d" % rule)
+        elif rule is not None and not callable(rule[0]):
+            rule = (lambda x, shape=tuple(rule): tuple(x.shape) == shape, "shape must be %s, not {}" % list(rule))
+        if rule is not None and not rule[0](x):
+            raise ArtError("%s: %s" % (p.label, rule[1].format(tuple(x.shape), numel=x.numel())))
+        if contiguous == "make":
+            x = x.contiguous()
+        elif contiguous == "refuse" and not x.is_contiguous():
+            raise ArtError("%s: the tensor must be contiguous%s" % (p.label, tail))
+        checked.append(x)
+    return checked
+
+
+def _check_devices(planes, device=None, where=" on the library's device"):
+    """THE check of where the planes are: every one that is there on a GPU, and on `device` where one is given (the device of the
+    call's first tensor, which names it; `where` stands in while that is not a GPU, or with no device given)."""
+    for p in planes:
+        if p.x is not None and (p.x.device.type != "cuda" or (device is not None and p.x.device != device)):
+            raise ArtError("%s: must be a GPU tensor%s, not on %s"
+                           % (p.label, " on %s" % device if device is not None and device.type == "cuda" else where, p.x.device))
+
+
+def _frame_plane(torch, label, x, dtype, rule, optional=False, kind="", tail=""):
+    """A plane the library reads or writes from its first element on (bind_accum, bind_moments, the adaptive calls), in the order of
+    refusals those calls have: what it is, where it is, dtype and layout, its size last.  Returns its device address (None for an
+    absent optional plane)."""
+    if x is None and optional:
+        return None
+    _check_planes(torch, [_Plane(label, x)], None, kind)
+    _check_devices([_Plane(label, x)])
+    _check_planes(torch, [_Plane(label, x, dtype)], tail=tail)
+    _check_planes(torch, [_Plane(label, x, dtype, rule)])
+    return x.data_ptr()
+
+
+def _colour_frame(torch, call, color):
+    """color is what names the frame of the image-space calls: a tensor shaped [H, W, 3], ahead of every other check -> (H, W)"""
+    _check_planes(torch, [_Plane(call + ": color", color, None, (lambda x: x.dim() == 3 and x.shape[2] == 3 and x.numel() != 0,
+                                                                  "shape must be [H, W, 3], not {}"))], None)
+    return int(color.shape[0]), int(color.shape[1])
+
+
+def _image_plane(call, h, w, name, x, per, dtype="float32", optional=True):
+    """a plane of an H x W frame with `per` words per pixel; per = 2 is the moments, which may be flat and longer (bind_moments' tensor)"""
+    rule = (h, w, 3) if per == 3 else (h, w)
+    if per == 2:
+        rule = (lambda x: x.numel() >= 2 * h * w, "shape must hold at least %d elements ([H, W, 2]), not {}" % (2 * h * w))
+    return _Plane("%s: %s" % (call, name), x, dtype, rule, optional)
+
+
+def _only_aov_planes(call, keywords):
+    """the dict of render_aovs_torch may be given whole as keyword arguments: what a filter does not read of it is ignored"""
+    for name in keywords:
+        if name not in AOV_PLANES:
+            raise TypeError("%s: unexpected keyword argument %r" % (call, name))
+
+
+def _known_planes(call, want):
+    want = tuple(want)
+    for name in want:
+        if name not in AOV_PLANES:
+            raise ValueError("%s: unknown plane %r (known: %s)" % (call, name, ", ".join(AOV_PLANES)))
+    return want
 
 
 class SceneDesc:
@@ -497,9 +584,21 @@ class Backend:
         p.background = (C.c_float * 3)(*background); p.seed = seed; p.layout = layout
         return p
 
+    def _frame_shape(self, layout):
+        return (self.height, self.width) if layout == LAYOUT_ROW_MAJOR else (self.width, self.height)
+
+    def _get(self, entry, struct, *first):
+        """a struct the library fills in: art_get_...(first..., &struct)"""
+        x = struct()
+        _check(getattr(self.lib, entry)(*first, C.byref(x)))
+        return x
+
+    def _need_device(self):
+        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+
     def render_pass(self, params, spp, want_accum=True, want_screen=False):
         """Returns (accum or None, screen or None, new spp).  Arrays are [H,W,..] for ROW_MAJOR, [W,H,..] for ADA_XY."""
-        shape = (self.height, self.width) if params.layout == LAYOUT_ROW_MAJOR else (self.width, self.height)
+        shape = self._frame_shape(params.layout)
         accum = np.zeros(shape + (3,), np.float32) if want_accum else None
         screen = np.zeros(shape, np.uint32) if want_screen else None
         s = C.c_int32(spp)
@@ -512,14 +611,14 @@ class Backend:
         return s.value
 
     def debug_hit_pass(self, params):
-        shape = (self.height, self.width) if params.layout == LAYOUT_ROW_MAJOR else (self.width, self.height)
+        shape = self._frame_shape(params.layout)
         accum = np.zeros(shape + (3,), np.float32); screen = np.zeros(shape, np.uint32)
         prim = np.zeros(shape, np.int32); mat = np.zeros(shape, np.int32); ptype = np.zeros(shape, np.int32)
         _check(self.lib.art_debug_hit_pass(C.byref(params), _fp(accum), _up(screen), _ip(prim), _ip(mat), _ip(ptype)))
         return accum, screen, prim, mat, ptype
 
     def download(self, spp, layout=LAYOUT_ROW_MAJOR, want_screen=True):
-        shape = (self.height, self.width) if layout == LAYOUT_ROW_MAJOR else (self.width, self.height)
+        shape = self._frame_shape(layout)
         accum = np.zeros(shape + (3,), np.float32)
         screen = np.zeros(shape, np.uint32) if want_screen else None
         _check(self.lib.art_download(_fp(accum), _up(screen), layout, spp))
@@ -531,22 +630,7 @@ class Backend:
         the memory alive and large enough), or a contiguous float32 torch tensor on the library's GPU.  A tensor is checked before any
         C call, held here until the next bind_accum so that it cannot be collected while bound, and resize() refuses a frame it is
         too small for."""
-        held = None
-        if accum is not None and not isinstance(accum, int):
-            torch = sys.modules.get("torch")
-            if torch is None or not isinstance(accum, torch.Tensor):
-                raise ArtError("bind_accum: None, an integer device address or a torch tensor is required, not %s" % type(accum).__name__)
-            if accum.device.type != "cuda":
-                raise ArtError("bind_accum: must be a GPU tensor on the library's device, not on %s" % accum.device)
-            if accum.dtype != torch.float32:
-                raise ArtError("bind_accum: dtype must be torch.float32, not %s" % accum.dtype)
-            if not accum.is_contiguous():
-                raise ArtError("bind_accum: the tensor must be contiguous (the library writes row-major float3 from its first element on)")
-            if accum.numel() == 0:
-                raise ArtError("bind_accum: the tensor is empty")
-            held, accum = accum, accum.data_ptr()
-        _check(self.lib.art_bind_accum(accum))         # (a refused pointer keeps the previous binding, and the tensor held for it)
-        self._accum_tensor = held
+        self._bind("accum", accum, 3)
 
     def bind_moments(self, moments):
         """Let the render passes keep the luminance moments {S1, S2} of every pixel in caller-owned device memory (art_bind_moments; the
@@ -554,31 +638,25 @@ class Backend:
         moments, the default), an integer device address, or a contiguous float32 torch tensor on the library's GPU with at least
         2 * W * H elements for the frame the next resize() sets.  Checked before any C call, held until the next bind_moments and
         guarded by resize(), which refuses a frame the tensor is too small for, exactly as bind_accum's tensor."""
+        self._bind("moments", moments, 2)
+
+    def _bind(self, what, x, per):
+        """bind_accum / bind_moments: art_bind_<what>(x), holding the tensor x came as in _<what>_tensor"""
         held = None
-        if moments is not None and not isinstance(moments, int):
-            torch = sys.modules.get("torch")
-            if torch is None or not isinstance(moments, torch.Tensor):
-                raise ArtError("bind_moments: None, an integer device address or a torch tensor is required, not %s" % type(moments).__name__)
-            if moments.device.type != "cuda":
-                raise ArtError("bind_moments: must be a GPU tensor on the library's device, not on %s" % moments.device)
-            if moments.dtype != torch.float32:
-                raise ArtError("bind_moments: dtype must be torch.float32, not %s" % moments.dtype)
-            if not moments.is_contiguous():
-                raise ArtError("bind_moments: the tensor must be contiguous (the library writes row-major float2 from its first element on)")
-            if moments.numel() == 0:
-                raise ArtError("bind_moments: the tensor is empty")
-            held, moments = moments, moments.data_ptr()
-        _check(self.lib.art_bind_moments(moments))     # (a refused pointer keeps the previous binding, and the tensor held for it)
-        self._moments_tensor = held
+        if x is not None and not isinstance(x, int):
+            held = x
+            x = _frame_plane(sys.modules.get("torch"), "bind_" + what, x, "float32", (lambda t: t.numel() != 0, "the tensor is empty"),
+                             kind="None, an integer device address or ",
+                             tail=" (the library writes row-major float%d from its first element on)" % per)
+        _check(getattr(self.lib, "art_bind_" + what)(x))       # (a refused pointer keeps the previous binding, and the tensor held for it)
+        setattr(self, "_%s_tensor" % what, held)
 
     def synchronize(self):
         _check(self.lib.art_synchronize())
 
     def stage_stats(self):
         """the wavefront stages around the trace kernel: GPU ms per kind of kernel, items read / kept per bounce (device 0, cumulative)"""
-        st = ArtStageStats()
-        _check(self.lib.art_get_stage_stats(C.byref(st)))
-        return st
+        return self._get("art_get_stage_stats", ArtStageStats)
 
     def camera_rays_traced(self):
         """camera rays the render passes generated and traced since resize(): with option camera_dedup (default) each distinct ray of a
@@ -589,9 +667,7 @@ class Backend:
 
     def reduce_info(self):
         """what the multi-device path did: ranks of the RCCL communicator, GPU time of the reduces, GPU time of every device's passes"""
-        ri = ArtReduceInfo()
-        _check(self.lib.art_get_reduce_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_reduce_info", ArtReduceInfo)
 
     def trace_rays(self, origins, dirs, tfar=None, kernel=TRACE_COOP, want_stats=False):
         o = np.ascontiguousarray(origins, np.float32); d = np.ascontiguousarray(dirs, np.float32)
@@ -603,24 +679,25 @@ class Backend:
         return (out, st) if want_stats else out
 
     def _query(self, origins, dirs, tnear, tfar):
-        """Validated, contiguous inputs of a device query, and the HIP stream it runs on (torch's current stream of their device)."""
+        """Validated, contiguous inputs of a device query, and the HIP stream it runs on (torch's current stream of their device):
+        float32, [N, 3] rays, [N] intervals."""
         import torch
-        o, d, tn, tf, n = _query_tensors(torch, origins, dirs, tnear, tfar)
-        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
-        dev = o.device
-        for name, x in (("origins", o), ("dirs", d), ("tnear", tn), ("tfar", tf)):
-            if x is not None and (x.device.type != "cuda" or x.device != dev):
-                raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        return torch, o, d, tn, tf, n, stream or HIP_STREAM_LEGACY
+        if not isinstance(origins, torch.Tensor) or origins.dim() != 2:
+            raise ArtError("origins: a [N, 3] float32 tensor is required")
+        n = origins.shape[0]
+        planes = [_Plane("origins", origins, "float32", _expected(n, 3)), _Plane("dirs", dirs, "float32", _expected(n, 3)),
+                  _Plane("tnear", tnear, "float32", _expected(n), True), _Plane("tfar", tfar, "float32", _expected(n), True)]
+        o, d, tn, tf = _check_planes(torch, planes, "make")
+        self._need_device()
+        _check_devices(planes, o.device)
+        return torch, o, d, tn, tf, n, _handle(_stream(torch, o.device))
 
     def trace_rays_torch(self, origins, dirs, tnear=None, tfar=None, kernel=TRACE_COOP):
         """Closest hit of N rays held in torch tensors on the GPU (origins, dirs [N, 3] float32; tnear, tfar [N] or None), enqueued on
         torch.cuda.current_stream() without waiting for it.  Returns RayHits on the same device (art_trace_rays_device)."""
         torch, o, d, tn, tf, n, stream = self._query(origins, dirs, tnear, tfar)
         raw = torch.empty((n, 11), dtype=torch.int32, device=o.device)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        _check(self.lib.art_trace_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, raw.data_ptr() if n else None, kernel, stream))
+        _check(self.lib.art_trace_rays_device(_ptr(o), _ptr(d), _ptr(tn), _ptr(tf), n, raw.data_ptr() if n else None, kernel, stream))
         f = raw.view(torch.float32)
         return RayHits(f[:, 0], raw[:, 1], raw[:, 2], raw[:, 3], raw[:, 4], raw[:, 5], f[:, 6:9], f[:, 9:11], raw)
 
@@ -629,22 +706,13 @@ class Backend:
         rays and intervals (art_occluded_rays_device)."""
         torch, o, d, tn, tf, n, stream = self._query(origins, dirs, tnear, tfar)
         out = torch.empty((n,), dtype=torch.bool, device=o.device)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        _check(self.lib.art_occluded_rays_device(ptr(o), ptr(d), ptr(tn), ptr(tf), n, out.data_ptr() if n else None, stream))
+        _check(self.lib.art_occluded_rays_device(_ptr(o), _ptr(d), _ptr(tn), _ptr(tf), n, out.data_ptr() if n else None, stream))
         return out
 
-    def render_aovs_torch(self, params, want=tuple(AOV_PLANES)):
-        """First-hit feature buffers of the frame (art_render_aovs_device): a dict of torch tensors on the library's GPU, one per name in
-        `want` -- albedo, normal [H, W, 3] float32; depth, alpha [H, W] float32; prim_type, prim_index, mat [H, W] int32 -- allocated by
-        torch and enqueued on torch.cuda.current_stream() without waiting for it.  Of `params` only aa_on and background are read: with
-        aa_on a float plane is the mean of the pixel's four camera rays, the ids are those of ray 0.  An unknown name raises ValueError
-        before any call."""
-        want = tuple(want)
-        for name in want:
-            if name not in AOV_PLANES:
-                raise ValueError("render_aovs_torch: unknown plane %r (known: %s)" % (name, ", ".join(AOV_PLANES)))
-        import torch
-        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
+    def _aov_outputs(self, torch, want, motion=False):
+        """The planes of `want` for the frame of resize(), and "motion" if asked, allocated by torch on its current device: (dict,
+        the ArtAovBuffers that points at the planes of `want`, the device)"""
+        self._need_device()
         dev = torch.device("cuda", torch.cuda.current_device())
         h, w = getattr(self, "height", 0), getattr(self, "width", 0)
         out, buf = {}, ArtAovBuffers()
@@ -652,8 +720,20 @@ class Backend:
             field, per, integer = AOV_PLANES[name]
             out[name] = torch.empty((h, w, 3) if per == 3 else (h, w), dtype=torch.int32 if integer else torch.float32, device=dev)
             setattr(buf, field, out[name].data_ptr() or None)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.lib.art_render_aovs_device(C.byref(params), C.byref(buf), stream or HIP_STREAM_LEGACY))
+        if motion:
+            out["motion"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
+        return out, buf, dev
+
+    def render_aovs_torch(self, params, want=tuple(AOV_PLANES)):
+        """First-hit feature buffers of the frame (art_render_aovs_device): a dict of torch tensors on the library's GPU, one per name in
+        `want` -- albedo, normal [H, W, 3] float32; depth, alpha [H, W] float32; prim_type, prim_index, mat [H, W] int32 -- allocated by
+        torch and enqueued on torch.cuda.current_stream() without waiting for it.  Of `params` only aa_on and background are read: with
+        aa_on a float plane is the mean of the pixel's four camera rays, the ids are those of ray 0.  An unknown name raises ValueError
+        before any call."""
+        want = _known_planes("render_aovs_torch", want)
+        import torch
+        out, buf, dev = self._aov_outputs(torch, want)
+        _check(self.lib.art_render_aovs_device(C.byref(params), C.byref(buf), _handle(_stream(torch, dev))))
         return out
 
     def render_aovs_torch_motion(self, params, want=tuple(AOV_PLANES), cur_pos=None, prev_pos=None, prev_matrices=None):
@@ -663,25 +743,15 @@ class Backend:
         update earlier, float32 [nverts, 3] GPU tensors, both or neither.  Instanced scene: prev_matrices = the matrices one update
         earlier, float32 [n_instances, 12] (or [n, 3, 4]).  All None: the plane is zero.  `want` may be empty.  Every tensor is checked
         before any C call; what the library refuses (a wrong count, arrays of the other kind of scene) raises ArtError."""
-        want = tuple(want)
-        for name in want:
-            if name not in AOV_PLANES:
-                raise ValueError("render_aovs_torch_motion: unknown plane %r (known: %s)" % (name, ", ".join(AOV_PLANES)))
+        call = "render_aovs_torch_motion"
+        want = _known_planes(call, want)
         import torch
         src = ArtMotionSource()
         for name, x, last in (("cur_pos", cur_pos, 3), ("prev_pos", prev_pos, 3), ("prev_matrices", prev_matrices, 12)):
-            if x is None:
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise ArtError("render_aovs_torch_motion: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
-            if x.dtype != torch.float32:
-                raise ArtError("render_aovs_torch_motion: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
-            if x.dim() < 2 or x.numel() == 0 or x.numel() != x.shape[0] * last:
-                raise ArtError("render_aovs_torch_motion: %s: shape must be [n, %d], not %s" % (name, last, tuple(x.shape)))
-            if not x.is_contiguous():
-                raise ArtError("render_aovs_torch_motion: %s: the tensor must be contiguous" % name)
-            if x.device.type != "cuda":
-                raise ArtError("render_aovs_torch_motion: %s: must be a GPU tensor, not on %s" % (name, x.device))
+            rows = (lambda x, last=last: x.dim() >= 2 and x.numel() != 0 and x.numel() == x.shape[0] * last, "shape must be [n, %d], not {}" % last)
+            plane = [_Plane("%s: %s" % (call, name), x, "float32", rows, True)]
+            _check_planes(torch, plane)                     # (plane after plane: all of one before any of the next)
+            _check_devices(plane, where="")
         if (cur_pos is None) != (prev_pos is None):
             raise ArtError("render_aovs_torch_motion: cur_pos and prev_pos must both be given or both be None")
         if cur_pos is not None:
@@ -690,17 +760,9 @@ class Backend:
             src.cur_pos3f, src.prev_pos3f, src.nverts = cur_pos.data_ptr(), prev_pos.data_ptr(), int(cur_pos.shape[0])
         if prev_matrices is not None:
             src.prev_m12f, src.n_instances = prev_matrices.data_ptr(), int(prev_matrices.shape[0])
-        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
-        dev = torch.device("cuda", torch.cuda.current_device())
-        h, w = getattr(self, "height", 0), getattr(self, "width", 0)
-        out, buf = {}, ArtAovBuffers()
-        for name in want:
-            field, per, integer = AOV_PLANES[name]
-            out[name] = torch.empty((h, w, 3) if per == 3 else (h, w), dtype=torch.int32 if integer else torch.float32, device=dev)
-            setattr(buf, field, out[name].data_ptr() or None)
-        out["motion"] = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.lib.art_render_aovs_motion_device(C.byref(params), C.byref(buf), C.byref(src), out["motion"].data_ptr() or None, stream or HIP_STREAM_LEGACY))
+        out, buf, dev = self._aov_outputs(torch, want, motion=True)
+        _check(self.lib.art_render_aovs_motion_device(C.byref(params), C.byref(buf), C.byref(src), out["motion"].data_ptr() or None,
+                                                      _handle(_stream(torch, dev))))
         return out
 
     def denoise_torch(self, color, albedo=None, normal=None, depth=None, iterations=5, scale=1.0, sigma_color=4.0, sigma_depth=1.0,
@@ -713,36 +775,19 @@ class Backend:
         keyword arguments: its planes that the filter does not read (alpha, prim_type, prim_index, mat) are ignored.  The defaults
         of iterations, the sigmas and normal_log2 are starting values taken from the literature (Dammertz et al. 2010, SVGF), not
         tuned on this renderer."""
-        for name in other_planes:
-            if name not in AOV_PLANES:
-                raise TypeError("denoise_torch: unexpected keyword argument %r" % name)
+        call = "denoise_torch"
+        _only_aov_planes(call, other_planes)
         torch = sys.modules.get("torch")
-        planes = (("color", color, 3), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3))
-        if torch is None or not isinstance(color, torch.Tensor):
-            raise ArtError("denoise_torch: color: a torch tensor is required, not %s" % type(color).__name__)
-        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
-            raise ArtError("denoise_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
-        h, w = int(color.shape[0]), int(color.shape[1])
-        for name, x, per in planes:
-            if x is None:
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise ArtError("denoise_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
-            if x.dtype != torch.float32:
-                raise ArtError("denoise_torch: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
-            if tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
-                raise ArtError("denoise_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
-            if not x.is_contiguous():
-                raise ArtError("denoise_torch: %s: the tensor must be contiguous" % name)
-            if x.device.type != "cuda" or x.device != color.device:
-                raise ArtError("denoise_torch: %s: must be a GPU tensor on %s, not on %s"
-                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        h, w = _colour_frame(torch, call, color)
+        for name, x, per in (("color", color, 3), ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3)):
+            plane = [_image_plane(call, h, w, name, x, per)]
+            _check_planes(torch, plane)                     # (plane after plane: all of one before any of the next)
+            _check_devices(plane, color.device)
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.float32, device=color.device)
         p = ArtDenoiseParams(w, h, int(iterations), 1 if demodulate else 0, int(normal_log2), int(variant), float(scale), float(sigma_color), float(sigma_depth))
-        ptr = lambda x: None if x is None else x.data_ptr()
-        stream = torch.cuda.current_stream(color.device).cuda_stream
-        _check(self.lib.art_denoise_device(C.byref(p), ptr(color), ptr(albedo), ptr(normal), ptr(depth), ptr(out), stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_denoise_device(C.byref(p), _ptr(color), _ptr(albedo), _ptr(normal), _ptr(depth), _ptr(out),
+                                           _handle(_stream(torch, color.device))))
         return out
 
     def denoise_svgf_torch(self, color, moments=None, n_colours=0, albedo=None, normal=None, depth=None, iterations=SVGF_ITERATIONS, scale=1.0,
@@ -756,53 +801,26 @@ class Backend:
         defaults of iterations and sigma_color are the best setting of the sweep in profiles/svgf/quality.json.
         variance: float32 [H, W], given INSTEAD of moments and n_colours (art_denoise_svgf_var_device): the variance of each pixel's
         luminance estimate in the units of color before scale -- temporal_torch's second result, with scale = 1."""
-        for name in other_planes:
-            if name not in AOV_PLANES:
-                raise TypeError("denoise_svgf_torch: unexpected keyword argument %r" % name)
+        call = "denoise_svgf_torch"
+        _only_aov_planes(call, other_planes)
         torch = sys.modules.get("torch")
-        if torch is None or not isinstance(color, torch.Tensor):
-            raise ArtError("denoise_svgf_torch: color: a torch tensor is required, not %s" % type(color).__name__)
-        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
-            raise ArtError("denoise_svgf_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
-        h, w = int(color.shape[0]), int(color.shape[1])
+        h, w = _colour_frame(torch, call, color)
         if variance is not None and (moments is not None or n_colours):
             raise ArtError("denoise_svgf_torch: give moments (with n_colours) or variance, not both")
-        first = ("variance", variance, 1) if variance is not None else ("moments", moments, 2)
-        planes = (("color", color, 3), first, ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3),
-                  ("variance_out", variance_out, 1))
-        for name, x, per in planes:
-            if x is None and name != "moments":
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise ArtError("denoise_svgf_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
-            if x.dtype != torch.float32:
-                raise ArtError("denoise_svgf_torch: %s: dtype must be torch.float32, not %s" % (name, x.dtype))
-            if per == 2:
-                if x.numel() < 2 * h * w:
-                    raise ArtError("denoise_svgf_torch: moments: shape must hold at least %d elements ([H, W, 2]), not %s" % (2 * h * w, tuple(x.shape)))
-            elif tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
-                raise ArtError("denoise_svgf_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
-            if not x.is_contiguous():
-                raise ArtError("denoise_svgf_torch: %s: the tensor must be contiguous" % name)
-        for name, x, per in planes:                    # (the devices last: a wrong kind of argument is named before a wrong place)
-            if x is None:
-                continue
-            if x.device.type != "cuda" or x.device != color.device:
-                raise ArtError("denoise_svgf_torch: %s: must be a GPU tensor on %s, not on %s"
-                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        spread = ("variance", variance, 1) if variance is not None else ("moments", moments, 2)
+        planes = [_image_plane(call, h, w, name, x, per, optional=name != "moments")
+                  for name, x, per in (("color", color, 3), spread, ("albedo", albedo, 3), ("normal", normal, 3), ("depth", depth, 1), ("out", out, 3),
+                                       ("variance_out", variance_out, 1))]
+        _check_planes(torch, planes)
+        _check_devices(planes, color.device)               # (the devices last: a wrong kind of argument is named before a wrong place)
         if variance is None and int(n_colours) < 2:
             raise ArtError("denoise_svgf_torch: n_colours must be at least 2 (a variance needs two colours), not %s" % (n_colours,))
         if out is None:
             out = torch.empty((h, w, 3), dtype=torch.float32, device=color.device)
         p = ArtSvgfParams(w, h, int(iterations), 1 if demodulate else 0, int(normal_log2), int(n_colours), float(scale), float(sigma_color), float(sigma_depth))
-        ptr = lambda x: None if x is None else x.data_ptr()
-        stream = torch.cuda.current_stream(color.device).cuda_stream
-        if variance is not None:
-            _check(self.lib.art_denoise_svgf_var_device(C.byref(p), ptr(color), ptr(variance), ptr(albedo), ptr(normal), ptr(depth), ptr(out),
-                                                        ptr(variance_out), stream or HIP_STREAM_LEGACY))
-            return out
-        _check(self.lib.art_denoise_svgf_device(C.byref(p), ptr(color), ptr(moments), ptr(albedo), ptr(normal), ptr(depth), ptr(out), ptr(variance_out),
-                                                stream or HIP_STREAM_LEGACY))
+        entry = self.lib.art_denoise_svgf_device if variance is None else self.lib.art_denoise_svgf_var_device
+        _check(entry(C.byref(p), _ptr(color), _ptr(spread[1]), _ptr(albedo), _ptr(normal), _ptr(depth), _ptr(out), _ptr(variance_out),
+                     _handle(_stream(torch, color.device))))
         return out
 
     @staticmethod
@@ -828,35 +846,19 @@ class Backend:
         the best setting of the sweep in profiles/temporal/quality.json.
         motion: float32 [H, W, 3] or None -- the "motion" plane of render_aovs_torch_motion for this frame; given, the call is
         art_temporal_motion_device, which follows surfaces that moved (cur["motion"] is NOT read: the plane is named explicitly)."""
+        call = "temporal_torch"
         torch = sys.modules.get("torch")
         if not isinstance(cur, dict):
             raise ArtError("temporal_torch: cur: a dict of planes is required, not %s" % type(cur).__name__)
         color = cur.get("color")
-        if torch is None or not isinstance(color, torch.Tensor):
-            raise ArtError("temporal_torch: color: a torch tensor is required, not %s" % type(color).__name__)
-        if color.dim() != 3 or color.shape[2] != 3 or color.numel() == 0:
-            raise ArtError("temporal_torch: color: shape must be [H, W, 3], not %s" % (tuple(color.shape),))
-        h, w = int(color.shape[0]), int(color.shape[1])
-        planes = [("color", color, 3, torch.float32), ("moments", cur.get("moments"), 2, torch.float32), ("normal", cur.get("normal"), 3, torch.float32),
-                  ("depth", cur.get("depth"), 1, torch.float32), (id_plane, cur.get(id_plane) if id_plane else None, 1, torch.int32),
-                  ("history", history, 0, torch.float32), ("motion", motion, 3, torch.float32)]
-        for name, x, per, dtype in planes:
-            if x is None and name != "moments":
-                continue
-            if not isinstance(x, torch.Tensor):
-                raise ArtError("temporal_torch: %s: a torch tensor is required, not %s" % (name, type(x).__name__))
-            if x.dtype != dtype:
-                raise ArtError("temporal_torch: %s: dtype must be %s, not %s" % (name, dtype, x.dtype))
-            if per == 2:
-                if x.numel() < 2 * h * w:
-                    raise ArtError("temporal_torch: moments: shape must hold at least %d elements ([H, W, 2]), not %s" % (2 * h * w, tuple(x.shape)))
-            elif per == 0:
-                if x.dim() != 4 or x.shape[0] != 3 or x.shape[3] != 4 or x.numel() == 0:
-                    raise ArtError("temporal_torch: history: shape must be [3, H', W', 4], not %s" % (tuple(x.shape),))
-            elif tuple(x.shape) != ((h, w, 3) if per == 3 else (h, w)):
-                raise ArtError("temporal_torch: %s: shape must be %s, not %s" % (name, [h, w, 3] if per == 3 else [h, w], tuple(x.shape)))
-            if not x.is_contiguous():
-                raise ArtError("temporal_torch: %s: the tensor must be contiguous" % name)
+        h, w = _colour_frame(torch, call, color)
+        moments, normal, depth, ids = [cur.get(name) if name else None for name in ("moments", "normal", "depth", id_plane)]
+        whole = (lambda x: x.dim() == 4 and x.shape[0] == 3 and x.shape[3] == 4 and x.numel() != 0, "shape must be [3, H', W', 4], not {}")
+        planes = [_image_plane(call, h, w, "color", color, 3), _image_plane(call, h, w, "moments", moments, 2, optional=False),
+                  _image_plane(call, h, w, "normal", normal, 3), _image_plane(call, h, w, "depth", depth, 1),
+                  _image_plane(call, h, w, id_plane, ids, 1, "int32"), _Plane(call + ": history", history, "float32", whole, True),
+                  _image_plane(call, h, w, "motion", motion, 3)]
+        _check_planes(torch, planes)
         if history is not None and cam_prev is None:
             raise ArtError("temporal_torch: cam_prev: a history needs the camera it was rendered with")
         for name, cam in (("cam_cur", cam_cur), ("cam_prev", cam_prev if history is not None else None)):
@@ -864,10 +866,8 @@ class Backend:
                 raise ArtError("temporal_torch: %s: a camera is (cam_pos, cam_matrix)" % name)
         if cam_cur is None:
             raise ArtError("temporal_torch: cam_cur: a camera is (cam_pos, cam_matrix)")
-        for name, x, per, dtype in planes:
-            if x is not None and (x.device.type != "cuda" or x.device != color.device):
-                raise ArtError("temporal_torch: %s: must be a GPU tensor on %s, not on %s"
-                               % (name, color.device if color.device.type == "cuda" else "the library's device", x.device))
+        dev = color.device
+        _check_devices(planes, dev)                         # (after the cameras: what an argument is, is named before where it is)
         if int(n_colours) < 1:
             raise ArtError("temporal_torch: n_colours must be at least 1, not %s" % (n_colours,))
         p = ArtTemporalParams()
@@ -876,19 +876,13 @@ class Backend:
             p.prev = self.temporal_camera(cam_prev, int(history.shape[2]), int(history.shape[1]))
         p.n_colours, p.max_history = int(n_colours), int(max_history)
         p.scale, p.depth_tol, p.normal_min = float(scale), float(depth_tol), float(normal_min)
-        dev = color.device
         out = torch.empty((h, w, 3), dtype=torch.float32, device=dev)
         var = torch.empty((h, w), dtype=torch.float32, device=dev)
         length = torch.empty((h, w), dtype=torch.float32, device=dev)
         new = torch.empty((3, h, w, 4), dtype=torch.float32, device=dev)
-        ptr = lambda x: None if x is None else x.data_ptr()
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if motion is not None:
-            _check(self.lib.art_temporal_motion_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
-                                                       ptr(motion), ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
-            return out, var, length, new
-        _check(self.lib.art_temporal_device(C.byref(p), ptr(color), ptr(planes[1][1]), ptr(planes[2][1]), ptr(planes[3][1]), ptr(planes[4][1]),
-                                            ptr(history), ptr(new), ptr(out), ptr(var), ptr(length), stream or HIP_STREAM_LEGACY))
+        entry, moved = (self.lib.art_temporal_device, ()) if motion is None else (self.lib.art_temporal_motion_device, (_ptr(motion),))
+        _check(entry(C.byref(p), _ptr(color), _ptr(moments), _ptr(normal), _ptr(depth), _ptr(ids), *moved, _ptr(history), _ptr(new), _ptr(out),
+                     _ptr(var), _ptr(length), _handle(_stream(torch, dev))))
         return out, var, length, new
 
     def svgf_spatial_variance_torch(self, hist, variance, width, height, radius=SVGF_SPATIAL_RADIUS, min_history=SVGF_SPATIAL_MIN_HISTORY,
@@ -905,49 +899,21 @@ class Backend:
         w, h = int(width), int(height)
         if w < 1 or h < 1:
             raise ArtError("%s: width and height must be at least 1, not %d x %d" % (call, w, h))
-        for name, x, shape in (("hist", hist, (3, h, w, 4)), ("variance", variance, (h, w)), ("out", out, (h, w))):
-            if x is None and name == "out":
-                continue
-            if torch is None or not isinstance(x, torch.Tensor):
-                raise ArtError("%s: %s: a torch tensor is required, not %s" % (call, name, type(x).__name__))
-            if x.dtype != torch.float32:
-                raise ArtError("%s: %s: dtype must be torch.float32, not %s" % (call, name, x.dtype))
-            if tuple(x.shape) != shape:
-                raise ArtError("%s: %s: shape must be %s, not %s" % (call, name, list(shape), tuple(x.shape)))
-            if not x.is_contiguous():
-                raise ArtError("%s: %s: the tensor must be contiguous" % (call, name))
-        for name, x in (("hist", hist), ("variance", variance), ("out", out)):
-            if x is not None and (x.device.type != "cuda" or x.device != hist.device):
-                raise ArtError("%s: %s: must be a GPU tensor on %s, not on %s"
-                               % (call, name, hist.device if hist.device.type == "cuda" else "the library's device", x.device))
+        planes = [_Plane(call + ": hist", hist, "float32", (3, h, w, 4)), _Plane(call + ": variance", variance, "float32", (h, w)),
+                  _Plane(call + ": out", out, "float32", (h, w), True)]
+        _check_planes(torch, planes)
+        _check_devices(planes, hist.device)
         if out is None:
             out = torch.empty((h, w), dtype=torch.float32, device=hist.device)
         p = ArtSvgfSpatialParams(w, h, int(radius), int(normal_log2), float(min_history), float(sigma_depth))
-        stream = torch.cuda.current_stream(hist.device).cuda_stream
-        _check(self.lib.art_svgf_spatial_variance_device(C.byref(p), hist.data_ptr(), variance.data_ptr(), out.data_ptr(), stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_svgf_spatial_variance_device(C.byref(p), hist.data_ptr(), variance.data_ptr(), out.data_ptr(),
+                                                         _handle(_stream(torch, hist.device))))
         return out
-
-    def _frame_tensor(self, torch, call, name, x, dtype, elements, optional=False):
-        """A plane of the adaptive calls, checked as bind_moments checks its tensor: a contiguous GPU tensor of `dtype` with at least
-        `elements` elements.  Returns its device address (None for an absent optional plane)."""
-        if x is None and optional:
-            return None
-        if torch is None or not isinstance(x, torch.Tensor):
-            raise ArtError("%s: %s: a torch tensor is required, not %s" % (call, name, type(x).__name__))
-        if x.device.type != "cuda":
-            raise ArtError("%s: %s: must be a GPU tensor on the library's device, not on %s" % (call, name, x.device))
-        if x.dtype != dtype:
-            raise ArtError("%s: %s: dtype must be %s, not %s" % (call, name, dtype, x.dtype))
-        if not x.is_contiguous():
-            raise ArtError("%s: %s: the tensor must be contiguous" % (call, name))
-        if x.numel() < elements:
-            raise ArtError("%s: %s: the tensor holds %d elements, the frame needs %d" % (call, name, x.numel(), elements))
-        return x.data_ptr()
 
     def _mask_tensor(self, torch, call, mask):
         if torch is not None and isinstance(mask, torch.Tensor) and mask.dtype == torch.bool:
             mask = mask.view(torch.uint8)                   # (a bool tensor is one byte per element, 0 or 1)
-        return mask, self._frame_tensor(torch, call, "mask", mask, None if torch is None else torch.uint8, self.width * self.height)
+        return mask, _frame_plane(torch, call + ": mask", mask, "uint8", self.width * self.height)
 
     def compact_mask_torch(self, mask):
         """The selected pixels of this rank's list, in list order (art_compact_mask_device; include/art_hip.h): mask is a uint8 or bool GPU
@@ -959,8 +925,7 @@ class Backend:
         n = self.width * self.height
         pixels = torch.empty(n, dtype=torch.int32, device=mask.device)
         count = torch.empty(1, dtype=torch.int32, device=mask.device)
-        stream = torch.cuda.current_stream(mask.device).cuda_stream
-        _check(self.lib.art_compact_mask_device(mp, pixels.data_ptr(), n, count.data_ptr(), stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_compact_mask_device(mp, pixels.data_ptr(), n, count.data_ptr(), _handle(_stream(torch, mask.device))))
         return pixels, count
 
     def render_pass_masked(self, params, spp, mask, counts=None):
@@ -971,7 +936,7 @@ class Backend:
         Returns (new spp, pixels rendered)."""
         torch = sys.modules.get("torch")
         mask, mp = self._mask_tensor(torch, "render_pass_masked", mask)
-        cp = self._frame_tensor(torch, "render_pass_masked", "counts", counts, torch.int32, self.width * self.height, optional=True)
+        cp = _frame_plane(torch, "render_pass_masked: counts", counts, "int32", self.width * self.height, optional=True)
         s = C.c_int32(spp); k = C.c_int64(0)
         _check(self.lib.art_render_pass_masked(C.byref(params), mp, cp, C.byref(s), C.byref(k)))
         return s.value, k.value
@@ -987,9 +952,9 @@ class Backend:
         torch = sys.modules.get("torch")
         call = "adaptive_estimate_torch"
         w, h = self.width, self.height
-        ap = self._frame_tensor(torch, call, "accum", accum, None if torch is None else torch.float32, 3 * w * h)
-        mp = self._frame_tensor(torch, call, "moments", moments, torch.float32, 2 * w * h)
-        cp = self._frame_tensor(torch, call, "counts", counts, torch.int32, w * h)
+        ap = _frame_plane(torch, call + ": accum", accum, "float32", 3 * w * h)
+        mp = _frame_plane(torch, call + ": moments", moments, "float32", 2 * w * h)
+        cp = _frame_plane(torch, call + ": counts", counts, "int32", w * h)
         for name in want:
             if name not in ("mean", "variance", "error", "mask"):
                 raise ArtError("%s: want: unknown plane %r" % (call, name))
@@ -1006,9 +971,8 @@ class Backend:
             out["mask"] = torch.empty((h, w), dtype=torch.uint8, device=dev)
         p = ArtAdaptiveParams(w, h, 1 if aa_on else 0, int(ADAPTIVE_MIN_COLOURS if min_colours is None else min_colours), int(max_samples),
                               float(ADAPTIVE_THRESHOLD if threshold is None else threshold), float(ADAPTIVE_LUM_FLOOR if lum_floor is None else lum_floor))
-        ptr = lambda name: out[name].data_ptr() if name in out else None
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        _check(self.lib.art_adaptive_estimate_device(C.byref(p), ap, mp, cp, ptr("mean"), ptr("variance"), ptr("error"), ptr("mask"), stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_adaptive_estimate_device(C.byref(p), ap, mp, cp, *[_ptr(out.get(name)) for name in ("mean", "variance", "error", "mask")],
+                                                     _handle(_stream(torch, dev))))
         return out
 
     def render_adaptive(self, params, budget_samples, step_vthreads, threshold=None, lum_floor=None, min_colours=None, max_samples=1 << 30,
@@ -1055,23 +1019,21 @@ class Backend:
         if not isinstance(pos, torch.Tensor) or pos.dim() != 2:
             raise ArtError("pos: a [nverts, 3] float32 tensor is required")
         n = pos.shape[0]
+        planes = [_Plane("pos", pos, "float32", _expected(n, 3)), _Plane("nrm", nrm, "float32", _expected(n, 3), True)]
+        p, q = _check_planes(torch, planes, "make")
+        self._need_device()
+        _check_devices(planes, p.device)
+        return torch, p, q, n, _stream(torch, p.device)
 
-        def f32(name, x):
-            if not isinstance(x, torch.Tensor):
-                raise ArtError("%s: a torch tensor is required, not %s" % (name, type(x).__name__))
-            if x.dtype != torch.float32:
-                raise ArtError("%s: dtype must be torch.float32, not %s" % (name, x.dtype))
-            if tuple(x.shape) != (n, 3):
-                raise ArtError("%s: shape %s, expected %s" % (name, tuple(x.shape), (n, 3)))
-            return x.contiguous()
-        p = f32("pos", pos)
-        q = None if nrm is None else f32("nrm", nrm)
-        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
-        dev = p.device
-        for name, x in (("pos", p), ("nrm", q)):
-            if x is not None and (x.device.type != "cuda" or x.device != dev):
-                raise ArtError("%s: must be a GPU tensor on %s, not on %s" % (name, dev if dev.type == "cuda" else "the library's device", x.device))
-        return torch, p, q, n, torch.cuda.current_stream(dev)
+    @staticmethod
+    def _refuse_bad_vertices(torch, call, p, q, stream):
+        """check=True of the refits, before any launch; the ONE host synchronisation with the stream that it costs is here"""
+        with torch.cuda.stream(stream):
+            bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
+            badn = torch.zeros_like(bad) if q is None else (~torch.isfinite(q)).any(dim=1).sum()
+            counts = torch.stack([bad, badn]).tolist()                     # the one host synchronisation
+        if counts[0] or counts[1]:
+            raise ValueError("%s: %d vertex position(s) not finite or beyond 1e18 in magnitude, %d normal(s) not finite" % (call, *counts))
 
     def set_camera(self, cam_pos, cam_matrix=None):
         """Replace the camera of the uploaded scene without a rebuild (art_set_camera): cam_pos 3 floats, cam_matrix 16 floats row-major
@@ -1092,19 +1054,12 @@ class Backend:
         emptied on the GPU and the next synchronize fails with the count."""
         torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
         if check and n:
-            with torch.cuda.stream(stream):
-                bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
-                badn = torch.zeros_like(bad) if q is None else (~torch.isfinite(q)).any(dim=1).sum()
-                counts = torch.stack([bad, badn]).tolist()                     # the one host synchronisation
-            if counts[0] or counts[1]:
-                raise ValueError("refit_torch: %d vertex position(s) not finite or beyond 1e18 in magnitude, %d normal(s) not finite" % tuple(counts))
-        _check(self.lib.art_refit_device(p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+            self._refuse_bad_vertices(torch, "refit_torch", p, q, stream)
+        _check(self.lib.art_refit_device(p.data_ptr(), _ptr(q), n, _handle(stream)))
 
     def refit_info(self):
         """ArtRefitInfo: refits, refit_ms (GPU time of device 0's refit kernels), plan_ms, bad_vertices -- cumulative since the upload (waits)"""
-        ri = ArtRefitInfo()
-        _check(self.lib.art_get_refit_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_refit_info", ArtRefitInfo)
 
     def rebuild_torch(self, pos, nrm=None):
         """Build a new tree for the scene's CLOSEST mesh at new vertex positions, on the GPU (art_rebuild_device): the tree the next
@@ -1112,20 +1067,16 @@ class Backend:
         torch.cuda.current_stream(), but unlike a refit the call returns only when the tree is committed (the builders read counts
         back).  A bad vertex (not finite, beyond 1e18) fails the call with the count and leaves the scene unchanged."""
         torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
-        _check(self.lib.art_rebuild_device(p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_rebuild_device(p.data_ptr(), _ptr(q), n, _handle(stream)))
 
     def rebuild_info(self):
         """ArtRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
-        ri = ArtRebuildInfo()
-        _check(self.lib.art_get_rebuild_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_rebuild_info", ArtRebuildInfo)
 
     def tree_cost(self):
         """ArtTreeCost of the tree in HBM (device 0; waits): root_area and the surface-area expectation of node visits, leaf visits and
         triangle tests per line through the root.  Compare a refitted tree's figure with a rebuilt one's to decide when to rebuild."""
-        tc = ArtTreeCost()
-        _check(self.lib.art_get_tree_cost(C.byref(tc)))
-        return tc
+        return self._get("art_get_tree_cost", ArtTreeCost)
 
     def move_instances_torch(self, m, check=True):
         """Move the instances of an instanced scene (art_move_instances_device): m is a float32 tensor [n_instances, 3, 4] or
@@ -1136,31 +1087,24 @@ class Backend:
         check=False skips it: a bad matrix (also a singular one, which check=True does not look for) empties its instance on the GPU
         and the next synchronize fails with the count."""
         import torch
-        if not isinstance(m, torch.Tensor):
-            raise ArtError("m: a torch tensor is required, not %s" % type(m).__name__)
-        if m.dtype != torch.float32:
-            raise ArtError("m: dtype must be torch.float32, not %s" % m.dtype)
-        if not ((m.dim() == 3 and tuple(m.shape[1:]) == (3, 4)) or (m.dim() == 2 and m.shape[1] == 12)):
-            raise ArtError("m: shape %s, expected [n_instances, 3, 4] or [n_instances, 12]" % (tuple(m.shape),))
-        m = m.contiguous()
+        plane = _Plane("m", m, "float32", (lambda m: (m.dim() == 3 and tuple(m.shape[1:]) == (3, 4)) or (m.dim() == 2 and m.shape[1] == 12),
+                                           "shape {}, expected [n_instances, 3, 4] or [n_instances, 12]"))
+        m, = _check_planes(torch, [plane], "make")
         n = m.shape[0]
-        _check(self.lib.art_trace_rays_device(None, None, None, None, 0, None, TRACE_COOP, None))     # n = 0: "is there a device?"
-        if m.device.type != "cuda":
-            raise ArtError("m: must be a GPU tensor on the library's device, not on %s" % m.device)
-        stream = torch.cuda.current_stream(m.device)
+        self._need_device()
+        _check_devices([plane])
+        stream = _stream(torch, m.device)
         if check and n:
             with torch.cuda.stream(stream):
                 bad = int((~torch.isfinite(m.reshape(n, 12))).any(dim=1).sum().item())      # the one host synchronisation
             if bad:
                 raise ValueError("move_instances_torch: %d matrix(es) with an element that is not finite" % bad)
-        _check(self.lib.art_move_instances_device(m.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+        _check(self.lib.art_move_instances_device(m.data_ptr(), n, _handle(stream)))
 
     def move_info(self):
         """ArtMoveInfo: moves, move_ms (GPU time of device 0's move kernels), plan_ms, bad_matrices, repads (meshes whose boxes a move
         had to widen) -- cumulative since the upload (waits)"""
-        mi = ArtMoveInfo()
-        _check(self.lib.art_get_move_info(C.byref(mi)))
-        return mi
+        return self._get("art_get_move_info", ArtMoveInfo)
 
     def refit_mesh_torch(self, mesh, pos, nrm=None, check=True):
         """Deform mesh number `mesh` of an instanced scene (art_refit_mesh_device): pos, nrm float32 [nverts, 3] tensors on the library's
@@ -1172,29 +1116,22 @@ class Backend:
         emptied on the GPU and the next synchronize fails with the count."""
         torch, p, q, n, stream = self._vertex_tensors(pos, nrm)
         if check and n:
-            with torch.cuda.stream(stream):
-                bad = (~(p.abs() <= 1e18)).any(dim=1).sum()
-                badn = torch.zeros_like(bad) if q is None else (~torch.isfinite(q)).any(dim=1).sum()
-                counts = torch.stack([bad, badn]).tolist()                     # the one host synchronisation
-            if counts[0] or counts[1]:
-                raise ValueError("refit_mesh_torch: %d vertex position(s) not finite or beyond 1e18 in magnitude, %d normal(s) not finite" % tuple(counts))
-        _check(self.lib.art_refit_mesh_device(int(mesh), p.data_ptr(), None if q is None else q.data_ptr(), n, stream.cuda_stream or HIP_STREAM_LEGACY))
+            self._refuse_bad_vertices(torch, "refit_mesh_torch", p, q, stream)
+        _check(self.lib.art_refit_mesh_device(int(mesh), p.data_ptr(), _ptr(q), n, _handle(stream)))
 
     def mesh_refit_info(self):
         """ArtMeshRefitInfo: refits, refit_ms (GPU time of device 0's kernels), plan_ms, bad_vertices, repads (meshes whose boxes a mesh
         refit had to widen) -- cumulative since the upload (waits)"""
-        ri = ArtMeshRefitInfo()
-        _check(self.lib.art_get_mesh_refit_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_mesh_refit_info", ArtMeshRefitInfo)
 
     @staticmethod
     def _rebuild_stream(stream):
         """the stream a rebuild waits for: the caller's, else torch's current stream if torch is loaded and the GPU is in use, else the library's"""
         if stream is not None:
-            return stream.cuda_stream or HIP_STREAM_LEGACY
+            return _handle(stream)
         torch = sys.modules.get("torch")
         if torch is not None and torch.cuda.is_available() and torch.cuda.is_initialized():
-            return torch.cuda.current_stream().cuda_stream or HIP_STREAM_LEGACY
+            return _handle(torch.cuda.current_stream())
         return None
 
     def rebuild_instances(self, stream=None):
@@ -1207,17 +1144,13 @@ class Backend:
 
     def instance_rebuild_info(self):
         """ArtInstanceRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
-        ri = ArtInstanceRebuildInfo()
-        _check(self.lib.art_get_instance_rebuild_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_instance_rebuild_info", ArtInstanceRebuildInfo)
 
     def instance_tree_cost(self):
         """ArtTreeCost of the instance tree in HBM (device 0; waits): root_area and the surface-area expectation of node visits and of
         entry points entered (leaf_visits = tri_tests) per line through the root.  Compare the figure of a moved tree with a rebuilt
         one's to decide when to call rebuild_instances."""
-        tc = ArtTreeCost()
-        _check(self.lib.art_get_instance_tree_cost(C.byref(tc)))
-        return tc
+        return self._get("art_get_instance_tree_cost", ArtTreeCost)
 
     def rebuild_mesh(self, mesh, stream=None):
         """Build the tree of mesh number `mesh` of the uploaded instanced scene again, on the GPU, from its triangle records as the
@@ -1229,16 +1162,12 @@ class Backend:
 
     def mesh_rebuild_info(self):
         """ArtMeshRebuildInfo: rebuilds, gather_ms, build_ms (GPU time on device 0), host_ms (host time inside the calls) -- cumulative since the upload"""
-        ri = ArtMeshRebuildInfo()
-        _check(self.lib.art_get_mesh_rebuild_info(C.byref(ri)))
-        return ri
+        return self._get("art_get_mesh_rebuild_info", ArtMeshRebuildInfo)
 
     def mesh_tree_cost(self, mesh):
         """ArtTreeCost of mesh number `mesh`'s tree in HBM, in object space (device 0; waits).  Compare the figure of a refitted tree with
         the one at the last build to decide when to call rebuild_mesh."""
-        tc = ArtTreeCost()
-        _check(self.lib.art_get_mesh_tree_cost(int(mesh), C.byref(tc)))
-        return tc
+        return self._get("art_get_mesh_tree_cost", ArtTreeCost, int(mesh))
 
     def bvh_info(self):
         info = ArtBvhInfo()
@@ -1263,9 +1192,7 @@ class Backend:
         return out
 
     def stats(self):
-        st = ArtStats()
-        _check(self.lib.art_get_stats(C.byref(st)))
-        return st
+        return self._get("art_get_stats", ArtStats)
 
     def shutdown(self):
         self.lib.art_shutdown()
