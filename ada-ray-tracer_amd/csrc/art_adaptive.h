@@ -21,7 +21,7 @@ struct Params {
 };
 
 // ArtAdaptiveParams and which pointers are given -> the kernel's Params: every refusal that needs no device.  Returns nullptr, or why the
-// call is refused.  The library (art_api.cpp) and tests/adaptive_host both derive their Params here.
+// call is refused.  The library (art_device_entries.cpp) and tests/adaptive_host both derive their Params here.
 inline const char* params_from_abi(const ArtAdaptiveParams* p, const void* accum3f, const void* moments2f, const void* counts1u, const void* mean3f,
                                    const void* variance1f, const void* error1f, const void* mask1b, Params& P) {
   if (!p) return "null ArtAdaptiveParams";

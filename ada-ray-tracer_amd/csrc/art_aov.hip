@@ -13,7 +13,7 @@
 //                   art_render_aovs_motion_device is a template flag: a third float3 staged the same way, its per-hit arithmetic in
 //                   art_motion.h.
 //
-// Between the two the rays go through the render loop's own trace launch (art_api.cpp trace()).
+// Between the two the rays go through the render loop's own trace launch (art_render.cpp trace()).
 #include <hip/hip_runtime.h>
 #include <type_traits>
 #include "art_kernels.h"

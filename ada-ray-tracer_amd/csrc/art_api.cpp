@@ -8,6 +8,7 @@
 //   then resolve (gamma, clamp, pack) when the caller asks for the LDR image.
 //
 // The path state, the trace launch and that schedule itself: art_render.cpp (batch shape and shade trial: art_pass_plan.h).
+// The entries that work on the caller's device memory in the caller's stream order (ray queries, AOVs, denoisers, temporal, adaptive estimate): art_device_entries.cpp.
 // The device-side scene updates (art_refit_device, art_rebuild_device, art_move_instances_device, art_refit_mesh_device, art_rebuild_instance_tree_device, art_get_tree_cost): art_update.cpp.
 // There is no CPU fallback: every entry point that needs the GPU fails with art_last_error() set when
 // HIP reports no usable device.
@@ -450,61 +451,6 @@ int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host
   return 0;
 }
 
-int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st) {
-  Ctx& c = g_ctx;
-  if (!c.scene_ready) return fail("no scene uploaded");
-  if (n <= 0 || n > (1ll << 28) || !origins || !dirs || !out) return fail("art_trace_rays: bad arguments");
-  if (kernel != TRACE_COOP && kernel != TRACE_SIMPLE) return fail("art_trace_rays: unknown kernel");
-  const size_t N = (size_t)n;
-  if (ensure(c.b_rays, N * 12 * 4)) return 1;      // 7 N ray floats, N of padding, N 16-byte hit records
-  std::vector<float> soa(7 * N);
-  for (size_t i = 0; i < N; ++i) {
-    soa[i] = origins[3 * i]; soa[N + i] = origins[3 * i + 1]; soa[2 * N + i] = origins[3 * i + 2];
-    soa[3 * N + i] = dirs[3 * i]; soa[4 * N + i] = dirs[3 * i + 1]; soa[5 * N + i] = dirs[3 * i + 2];
-    soa[6 * N + i] = tfar ? tfar[i] : kInfinity;
-  }
-  float* d = (float*)c.b_rays.p;
-  HIP_TRY(hipMemcpyAsync(d, soa.data(), 7 * N * 4, hipMemcpyHostToDevice, c.stream));
-  HIP_TRY(hipMemsetAsync(d + 8 * N, 0xff, 4 * N * 4, c.stream));
-  if (st) HIP_TRY(hipMemsetAsync(c.d_counters + CNT_STATS, 0, 8 * sizeof(unsigned long long), c.stream));
-  DevPaths q; std::memset(&q, 0, sizeof q);
-  q.ray_ox = d; q.ray_oy = d + N; q.ray_oz = d + 2 * N; q.ray_dx = d + 3 * N; q.ray_dy = d + 4 * N; q.ray_dz = d + 5 * N; q.ray_tfar = d + 6 * N;
-  q.hit = (DevHit*)(d + 8 * N);                                      // 16-byte aligned: the buffer is, and 8 N floats precede it
-  const TraceLaunch launch = {c.stream, kernel, /*count_tests=*/st != nullptr, /*timed=*/st != nullptr};      // without stats: no events, no counter read-back (the per-ray seam)
-  if (trace(q, (int)n, launch)) return 1;
-  std::vector<DevHit> hits(N);
-  HIP_TRY(hipMemcpyAsync(hits.data(), d + 8 * N, N * sizeof(DevHit), hipMemcpyDeviceToHost, c.stream));
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  HIP_TRY(hipGetLastError());
-  HostScene& hs = c.host_scene;
-  if (hs.m_shade_stale) {                                            // a refit rewrote the normals in HBM (the stream is idle: synchronised above)
-    HIP_TRY(hipMemcpy(hs.m_shade.data(), c.b_m_shade.p, hs.m_shade.size() * sizeof(float), hipMemcpyDeviceToHost));
-    hs.m_shade_stale = false;
-  }
-  if (hs.inst_stale) {                                               // a move rewrote the matrices in HBM
-    HIP_TRY(hipMemcpy(hs.inst.data(), c.b_inst.p, hs.inst.size() * sizeof(DevInstance), hipMemcpyDeviceToHost));
-    hs.inst_stale = false;
-  }
-  bind_host_pointers(hs);
-  for (size_t i = 0; i < N; ++i) {
-    ArtHit& h = out[i];
-    const uint32_t key = hits[i].key;
-    h.t = hits[i].t; h.u = hits[i].u; h.v = hits[i].v;
-    if (key == KEY_MISS) { h.is_hit = 0; h.prim_type = -1; h.prim_index = -1; h.mat_id = -1; h.mat = -1; h.normal[0] = h.normal[1] = h.normal[2] = 0.0f; continue; }
-    const f3 o = mk3(origins[3 * i], origins[3 * i + 1], origins[3 * i + 2]), dd = mk3(dirs[3 * i], dirs[3 * i + 1], dirs[3 * i + 2]);
-    const Surface sf = surface_at(hs.hdr, o, dd, h.t, key, h.u, h.v);
-    const uint32_t cls = key & ~KEY_INDEX_MASK;
-    h.is_hit = 1; h.prim_index = (int32_t)(key & KEY_INDEX_MASK); h.mat_id = sf.mat_id; h.mat = sf.mat;
-    h.prim_type = (cls == KEY_CORNELL) ? 0 : (cls == KEY_SPHERE) ? 1 : (cls == KEY_QUAD) ? 3 : 2;
-    h.normal[0] = sf.normal.x; h.normal[1] = sf.normal.y; h.normal[2] = sf.normal.z;
-  }
-  if (st) {
-    if (synchronize()) return 1;
-    *st = c.stats;
-  }
-  return 0;
-}
-
 // c's tree as it lies in HBM (c's GPU is current), after its stream has drained: a refit on another stream is ordered before that
 static int fetch_tree(Ctx& c, std::vector<float>& nodes, std::vector<float>& tris) {
   const Bvh8& b = c.host_scene.bvh;
@@ -524,299 +470,6 @@ int fetch_host_bvh(std::vector<float>& nodes, std::vector<float>& tris, int& wid
   if (c.host_scene.tree_in_hbm_only() && b.nodes.empty()) return use_dev(0) || fetch_tree(c, nodes, tris);
   nodes = b.nodes; tris = b.tris;
   return 0;
-}
-
-// ---- device-resident ray queries (art_trace_rays_device / art_occluded_rays_device) ----------------------------------------------
-// A caller's buffer must be device memory of this context's GPU, and (where HIP knows the allocation) hold `bytes` from `p` on.
-int check_device_ptr(const void* p, size_t bytes, const char* what) {
-  Ctx& c = g_ctx;
-  hipPointerAttribute_t at;
-  std::memset(&at, 0, sizeof at);
-  if (hipPointerGetAttributes(&at, p) != hipSuccess) { (void)hipGetLastError(); return fail(std::string(what) + " is not device memory (hipPointerGetAttributes failed)"); }
-  if (at.type != hipMemoryTypeDevice) return fail(std::string(what) + " is not device memory (host or unregistered pointer)");
-  if (at.device != c.device) return fail(std::string(what) + " is memory of device " + std::to_string(at.device) + ", the library runs on device " + std::to_string(c.device));
-  hipDeviceptr_t base = nullptr; size_t size = 0;
-  if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)p) == hipSuccess) {
-    if ((const char*)p + bytes > (const char*)base + size) return fail(std::string(what) + " is smaller than the query needs (" + std::to_string(bytes) + " bytes)");
-  } else (void)hipGetLastError();       // (memory HIP cannot size, e.g. a virtual-memory mapping: the type and the device were checked)
-  return 0;
-}
-
-// The scratch of one slice of S rays: b_query = counter sink (256 B) | 7 SoA floats + the shadow minimum per ray | the hit records, and
-// what the trace launch needs of b_queue and b_ovf.  Growing it may wait: nothing enqueued may still use the old buffers.
-static int ensure_query_scratch(const StreamOrder& order, size_t S, bool coop) {
-  Ctx& c = g_ctx;
-  int entries; bool ovf; stack_plan(entries, ovf);
-  const size_t q_bytes = 256 + S * (8 * 4 + sizeof(DevHit));
-  const bool grow = c.b_query.bytes < q_bytes || (coop && c.b_queue.bytes < (S + kRecSlack) * kTraceRecBytes) || (coop && ovf && c.b_ovf.bytes < S * sizeof(int));
-  if (!grow) return 0;
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
-  if (ensure(c.b_query, q_bytes)) return 1;
-  if (coop && ensure(c.b_queue, (S + kRecSlack) * kTraceRecBytes)) return 1;
-  if (coop && ovf && ensure(c.b_ovf, S * sizeof(int))) return 1;
-  return 0;
-}
-
-// hits (closest hit) or occluded (occlusion): n rays in slices of query_slice, every launch on the stream `st` names (StreamOrder).
-// The scratch (b_query, b_queue, b_ovf) is shared with the render passes on the context stream: on another stream the query waits
-// for what the context stream holds, and the context stream waits for the query.
-int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st) {
-  Ctx& c = g_ctx;
-  const char* name = hits ? "art_trace_rays_device" : "art_occluded_rays_device";
-  if (ensure_device()) return 1;
-  if (n < 0 || n > 0x7fffffffll) return fail(std::string(name) + ": n must be 0 .. 2^31 - 1");
-  if (kernel != TRACE_COOP && kernel != TRACE_SIMPLE) return fail(std::string(name) + ": unknown kernel");
-  if (n == 0) return 0;
-  if (!c.scene_ready) return fail("no scene uploaded");
-  if (!o3 || !d3 || (!hits && !occluded)) return fail(std::string(name) + ": null ray or output buffer");
-  const size_t N = (size_t)n;
-  if (check_device_ptr(o3, 12 * N, "origins") || check_device_ptr(d3, 12 * N, "dirs") || (tnear && check_device_ptr(tnear, 4 * N, "tnear")) ||
-      (tfar && check_device_ptr(tfar, 4 * N, "tfar")) || (hits && check_device_ptr(hits, sizeof(ArtHit) * N, "hits_out")) ||
-      (occluded && check_device_ptr(occluded, N, "occluded_out")))
-    return 1;
-  StreamOrder order(c, st);
-  const hipStream_t qs = order.qs;
-  const size_t S = (size_t)std::min<int64_t>(n, c.opt.query_slice);
-  const bool coop = (kernel == TRACE_COOP);
-  if (ensure_query_scratch(order, S, coop)) return 1;
-  if (order.enter()) return 1;
-  char* base = (char*)c.b_query.p;
-  unsigned long long* sink = (unsigned long long*)base;
-  float* f = (float*)(base + 256);
-  DevHit* dh = (DevHit*)(f + 8 * S);                                 // 16-byte aligned: 256 + 32 S bytes
-  const TraceLaunch launch = {qs, kernel, /*count_tests=*/false, /*timed=*/false, nullptr, nullptr, /*live_rays=*/sink};
-  int rc = 0;
-  for (size_t s0 = 0; s0 < N && !rc; s0 += S) {
-    const int m = (int)std::min(S, N - s0);
-    QueryArgs Q; std::memset(&Q, 0, sizeof Q);
-    Q.n = m; Q.o3 = o3 + 3 * s0; Q.d3 = d3 + 3 * s0; Q.tnear = tnear ? tnear + s0 : nullptr; Q.tfar = tfar ? tfar + s0 : nullptr;
-    Q.ox = f; Q.oy = f + S; Q.oz = f + 2 * S; Q.dx = f + 3 * S; Q.dy = f + 4 * S; Q.dz = f + 5 * S; Q.tf = f + 6 * S;
-    Q.shm = occluded ? f + 7 * S : nullptr; Q.hit = dh;
-    Q.out = hits ? (uint32_t*)(hits + s0) : nullptr; Q.occluded = occluded ? occluded + s0 : nullptr;
-    launch_query_pack(qs, Q);
-    DevPaths q; std::memset(&q, 0, sizeof q);
-    q.ray_ox = Q.ox; q.ray_oy = Q.oy; q.ray_oz = Q.oz; q.ray_dx = Q.dx; q.ray_dy = Q.dy; q.ray_dz = Q.dz; q.ray_tfar = Q.tf; q.hit = dh;
-    q.sh_min_t = Q.shm; q.P = 0;                                     // occlusion: every ray is a shadow ray (shadow_begin = 0)
-    rc = trace(q, m, launch);
-    if (rc) break;
-    if (hits) launch_query_finalize(qs, c.scene, Q);
-    else launch_query_occluded(qs, Q);
-    if (hipGetLastError() != hipSuccess) rc = fail(std::string(name) + ": kernel launch failed");
-  }
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
-}
-
-// art_render_aovs_device: the whole frame's camera rays (k per pixel) in slices of whole pixels, k * pixels <= query_slice, through the
-// queries' scratch and stream order; per slice k_aov_raygen, the render loop's trace launch, k_aov_resolve.  Like a query it counts its
-// rays into the scratch's sink and takes no event pair: ArtStats and ArtStageStats do not see it.
-// motion3f (art_render_aovs_motion_device): the resolve's MOTION instantiation also writes the motion plane from src (art_motion.h); the
-// flat mesh's index triples are the refit plan's, which is built here where no refit has (the one time the host waits).
-int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st, const ArtMotionSource* src, float* motion3f) {
-  Ctx& c = g_ctx;
-  const std::string name = motion3f ? "art_render_aovs_motion_device" : "art_render_aovs_device";
-  static const ArtAovBuffers no_planes = ArtAovBuffers();
-  if (!p) return fail(name + ": null ArtPassParams");
-  if (!out && motion3f) out = &no_planes;
-  if (!out) return fail(name + ": null ArtAovBuffers");
-  if (!motion3f && !out->albedo3f && !out->normal3f && !out->depth && !out->alpha && !out->prim_type && !out->prim_index && !out->mat) return fail(name + ": no plane is wanted (all seven pointers are null)");
-  if (motion3f && !src) return fail(name + ": motion3f needs an ArtMotionSource (null src)");
-  if (!c.scene_ready) return fail(name + ": no scene uploaded");
-  if (c.host_scene.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which has no camera");
-  if (c.width <= 0) return fail(name + ": no viewport (art_resize)");
-  const int kernel = c.opt.trace_kernel;
-  if (c.scene.n_inst > 0 && kernel != TRACE_COOP) return fail(name + ": an instanced scene is traced through the record schedule only (option trace_kernel = 0)");
-  const bool instanced = c.scene.n_inst > 0;
-  const bool flat_src = motion3f && (src->cur_pos3f || src->prev_pos3f), inst_src = motion3f && src->prev_m12f;
-  if (motion3f) {
-    if ((src->cur_pos3f != nullptr) != (src->prev_pos3f != nullptr)) return fail(name + ": cur_pos3f and prev_pos3f must both be given or both be null");
-    if (flat_src && instanced) return fail(name + ": vertex arrays are given but the scene is instanced (its motion comes from prev_m12f)");
-    if (inst_src && !instanced) return fail(name + ": prev_m12f is given but the scene is not instanced (its motion comes from cur_pos3f and prev_pos3f)");
-    if (flat_src && c.host_scene.m_nverts == 0) return fail(name + ": vertex arrays are given but the scene has no ART_MESH_CLOSEST mesh");
-    if (flat_src && src->nverts != c.host_scene.m_nverts) return fail(name + ": nverts " + std::to_string(src->nverts) + " differs from the uploaded mesh's " + std::to_string(c.host_scene.m_nverts));
-    if (inst_src && src->n_instances != c.scene.n_inst) return fail(name + ": n_instances " + std::to_string(src->n_instances) + " differs from the uploaded count " + std::to_string(c.scene.n_inst));
-  }
-  if (ensure_device()) return 1;
-  const int64_t npix = (int64_t)c.width * c.height;
-  const size_t N = (size_t)npix;
-  if (motion3f && (check_device_ptr(motion3f, 12 * N, "motion3f") ||
-                   (flat_src && (check_device_ptr(src->cur_pos3f, 12 * (size_t)src->nverts, "cur_pos3f") || check_device_ptr(src->prev_pos3f, 12 * (size_t)src->nverts, "prev_pos3f"))) ||
-                   (inst_src && check_device_ptr(src->prev_m12f, 48 * (size_t)src->n_instances, "prev_m12f"))))
-    return 1;
-  if ((out->albedo3f && check_device_ptr(out->albedo3f, 12 * N, "albedo3f")) || (out->normal3f && check_device_ptr(out->normal3f, 12 * N, "normal3f")) ||
-      (out->depth && check_device_ptr(out->depth, 4 * N, "depth")) || (out->alpha && check_device_ptr(out->alpha, 4 * N, "alpha")) ||
-      (out->prim_type && check_device_ptr(out->prim_type, 4 * N, "prim_type")) || (out->prim_index && check_device_ptr(out->prim_index, 4 * N, "prim_index")) ||
-      (out->mat && check_device_ptr(out->mat, 4 * N, "mat")))
-    return 1;
-  ArtPassParams pp = ArtPassParams();   // only aa_on and background are the caller's
-  pp.aa_on = p->aa_on; std::memcpy(pp.background, p->background, 12);
-  DevFrame F; make_frame(&pp, F);
-  const int k = F.aa_on ? 4 : 1;
-  const int64_t ns = std::min<int64_t>(npix, std::max<int64_t>(1, c.opt.query_slice / k));      // pixels per slice
-  const size_t S = (size_t)(ns * k);                                                            // its rays: at most 2^28 (query_slice), or k
-  StreamOrder order(c, st);
-  const hipStream_t qs = order.qs;
-  const bool coop = (kernel == TRACE_COOP);
-  if (ensure_query_scratch(order, S, coop)) return 1;
-  mo::Source ms; std::memset(&ms, 0, sizeof ms);
-  if (flat_src) {
-    if (ensure_refit_plan()) return 1;
-    ms.idx = (const int32_t*)c.refit.b_idx.p; ms.cur = src->cur_pos3f; ms.prev = src->prev_pos3f;
-    if (!ms.idx) return fail(name + ": internal: the refit plan holds no index triples");
-  }
-  if (instanced && motion3f) { ms.inst = c.scene.inst; ms.prev_m = src->prev_m12f; ms.inst_shift = c.scene.inst_shift; }
-  if (order.enter()) return 1;
-  char* base = (char*)c.b_query.p;
-  unsigned long long* sink = (unsigned long long*)base;
-  float* f = (float*)(base + 256);
-  DevHit* dh = (DevHit*)(f + 8 * S);
-  const TraceLaunch launch = {qs, kernel, /*count_tests=*/false, /*timed=*/false, nullptr, nullptr, /*live_rays=*/sink};
-  int rc = 0;
-  for (int64_t p0 = 0; p0 < npix && !rc; p0 += ns) {
-    const int n = (int)std::min<int64_t>(ns, npix - p0);
-    AovMotionArgs A; std::memset((void*)&A, 0, sizeof A);      // (its AovArgs part is all the launches without the plane see)
-    A.motion = motion3f ? motion3f + 3 * p0 : nullptr; A.src = ms;
-    A.n = n; A.k = k; A.pixel0 = (uint32_t)p0;
-    A.ox = f; A.oy = f + S; A.oz = f + 2 * S; A.dx = f + 3 * S; A.dy = f + 4 * S; A.dz = f + 5 * S; A.tf = f + 6 * S; A.hit = dh;
-    A.albedo = out->albedo3f ? out->albedo3f + 3 * p0 : nullptr; A.normal = out->normal3f ? out->normal3f + 3 * p0 : nullptr;
-    A.depth = out->depth ? out->depth + p0 : nullptr; A.alpha = out->alpha ? out->alpha + p0 : nullptr;
-    A.prim_type = out->prim_type ? out->prim_type + p0 : nullptr; A.prim_index = out->prim_index ? out->prim_index + p0 : nullptr;
-    A.mat = out->mat ? out->mat + p0 : nullptr;
-    launch_aov_raygen(qs, F, c.scene, A);
-    DevPaths q; std::memset(&q, 0, sizeof q);
-    q.ray_ox = A.ox; q.ray_oy = A.oy; q.ray_oz = A.oz; q.ray_dx = A.dx; q.ray_dy = A.dy; q.ray_dz = A.dz; q.ray_tfar = A.tf; q.hit = dh;
-    q.P = 0;                                                         // (no shadow minima: every ray is a closest-hit query)
-    rc = trace(q, k * n, launch);
-    if (rc) break;
-    if (motion3f) launch_aov_resolve_motion(qs, F, c.scene, A);
-    else launch_aov_resolve(qs, F, c.scene, A);
-    if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  }
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
-}
-
-// The end of an image-space entry (the denoisers, art_temporal_device, art_adaptive_estimate_device, art_svgf_spatial_variance_device),
-// after its launches on order.qs.
-static int finish_launches(StreamOrder& order, const std::string& name) {
-  int rc = 0;
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
-}
-
-// The three a-trous filters of art_denoise.h over the caller's planes (A.P and the planes are set, dn::params_from_abi has passed), in a
-// scratch of their own (b_denoise, shared: all run in the queries' stream order) and the queries' stream order.  Scratch per pixel: two
-// images, the guide records and the depth gradients, 56 bytes; the modes that carry a variance add the depth plane, 60 bytes.  They need
-// no scene and no viewport and take no event pair: ArtStats and ArtStageStats do not see them.
-static int run_denoise(const std::string& name, dn::Mode mode, DenoiseArgs& A, int iterations, hipStream_t st) {
-  if (ensure_device()) return 1;
-  Ctx& c = g_ctx;
-  const bool v = dn::carries_variance(mode), plane = (mode == dn::Mode::SvgfVar);
-  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
-  if (check_device_ptr(A.color, 12 * N, "color3f") || check_device_ptr(A.out, 12 * N, "out3f") ||
-      (v && check_device_ptr(A.moments, (plane ? 4 : 8) * N, plane ? "variance1f" : "moments2f")) ||
-      (A.albedo && check_device_ptr(A.albedo, 12 * N, "albedo3f")) || (A.normal && check_device_ptr(A.normal, 12 * N, "normal3f")) ||
-      (A.depth && check_device_ptr(A.depth, 4 * N, "depth")) || (A.variance_out && check_device_ptr(A.variance_out, 4 * N, "variance_out")))
-    return 1;
-  StreamOrder order(c, st);
-  const size_t bytes = N * (3 * sizeof(dn::Rec4) + sizeof(dn::Rec2) + (v ? sizeof(float) : 0));
-  if (c.b_denoise.bytes < bytes) {        // growing it may wait: nothing enqueued may still use the old scratch
-    HIP_TRY(hipStreamSynchronize(c.stream));
-    if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
-    if (ensure(c.b_denoise, bytes)) return 1;
-  }
-  if (order.enter()) return 1;
-  A.n = (int32_t)N;
-  dn::Rec4* r4 = (dn::Rec4*)c.b_denoise.p;
-  A.image[0] = r4; A.image[1] = r4 + N; A.guide = r4 + 2 * N; A.grad = (dn::Rec2*)(r4 + 3 * N); A.z = v ? (float*)(A.grad + N) : nullptr;
-  launch_denoise(order.qs, mode, A, iterations);
-  return finish_launches(order, name);
-}
-
-int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st) {
-  const std::string name = "art_denoise_device";
-  DenoiseArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = dn::params_from_abi(p, color3f, albedo3f, normal3f, depth, out3f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
-  A.color = color3f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f;
-  return run_denoise(name, dn::Mode::Plain, A, p->iterations, st);      // (variant: one kernel exists, every tap from global memory; 0, 1 and 2 all select it)
-}
-
-// variance_plane: art_denoise_svgf_var_device, whose moments2f is the variance plane
-int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
-                        float* out3f, float* variance_out, hipStream_t st, bool variance_plane) {
-  const std::string name = variance_plane ? "art_denoise_svgf_var_device" : "art_denoise_svgf_device";
-  DenoiseArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = dn::params_from_abi(p, color3f, moments2f, albedo3f, normal3f, depth, out3f, variance_plane, A.P)) return fail(name + ": " + why);
-  A.n_colours = p->n_colours;
-  A.color = color3f; A.moments = moments2f; A.albedo = albedo3f; A.normal = normal3f; A.depth = depth; A.out = out3f; A.variance_out = variance_out;
-  return run_denoise(name, variance_plane ? dn::Mode::SvgfVar : dn::Mode::Svgf, A, p->iterations, st);
-}
-
-// art_temporal_device: one kernel over the caller's planes and histories (art_temporal.h), in the queries' stream order.  It has no scratch
-// (so nothing can make the host wait), needs no scene and no viewport and takes no event pair: ArtStats and ArtStageStats do not see it.
-int temporal_device(const ArtTemporalParams* p, const float* color3f, const float* moments2f, const float* normal3f, const float* depth, const int32_t* id,
-                    const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out, hipStream_t st, const float* motion3f, const char* call) {
-  const std::string name = call;
-  TemporalArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = tp::params_from_abi(p, color3f, moments2f, normal3f, depth, id, hist_in, hist_out, A.P, motion3f)) return fail(name + ": " + why);      // (before the device is looked for)
-  if (ensure_device()) return 1;
-  Ctx& c = g_ctx;
-  const size_t N = (size_t)A.P.cur.W * (size_t)A.P.cur.H, NP = (size_t)A.P.prev.W * (size_t)A.P.prev.H;
-  if (check_device_ptr(color3f, 12 * N, "color3f") || check_device_ptr(moments2f, 8 * N, "moments2f") || check_device_ptr(hist_out, 48 * N, "hist_out") ||
-      (hist_in && check_device_ptr(hist_in, 48 * NP, "hist_in")) || (normal3f && check_device_ptr(normal3f, 12 * N, "normal3f")) ||
-      (depth && check_device_ptr(depth, 4 * N, "depth")) || (id && check_device_ptr(id, 4 * N, "id")) || (out3f && check_device_ptr(out3f, 12 * N, "out3f")) ||
-      (variance_out && check_device_ptr(variance_out, 4 * N, "variance_out")) || (length_out && check_device_ptr(length_out, 4 * N, "length_out")) ||
-      (motion3f && check_device_ptr(motion3f, 12 * N, "motion3f")))
-    return 1;
-  StreamOrder order(c, st);
-  if (order.enter()) return 1;
-  A.motion = motion3f; A.has_motion = motion3f ? 1 : 0;
-  A.n = (int32_t)N; A.color = color3f; A.moments = moments2f; A.normal = normal3f; A.depth = depth; A.id = id;
-  A.hist_in = (const tp::Rec4*)hist_in; A.hist_out = (tp::Rec4*)hist_out; A.out = out3f; A.variance_out = variance_out; A.length_out = length_out;
-  launch_temporal(order.qs, A);
-  return finish_launches(order, name);
-}
-
-// art_adaptive_estimate_device: one kernel over the caller's planes (art_adaptive.h), in the queries' stream order.  Like art_temporal_device
-// it has no scratch, needs no scene and no viewport and takes no event pair.
-int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u, float* mean3f, float* variance1f,
-                             float* error1f, uint8_t* mask1b, hipStream_t st) {
-  const std::string name = "art_adaptive_estimate_device";
-  AdaptiveArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = ad::params_from_abi(p, accum3f, moments2f, counts1u, mean3f, variance1f, error1f, mask1b, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
-  if (ensure_device()) return 1;
-  Ctx& c = g_ctx;
-  const size_t N = (size_t)A.P.n;
-  if (check_device_ptr(accum3f, 12 * N, "accum3f") || check_device_ptr(moments2f, 8 * N, "moments2f") || check_device_ptr(counts1u, 4 * N, "counts1u") ||
-      (mean3f && check_device_ptr(mean3f, 12 * N, "mean3f")) || (variance1f && check_device_ptr(variance1f, 4 * N, "variance1f")) ||
-      (error1f && check_device_ptr(error1f, 4 * N, "error1f")) || (mask1b && check_device_ptr(mask1b, N, "mask1b")))
-    return 1;
-  StreamOrder order(c, st);
-  if (order.enter()) return 1;
-  A.accum = accum3f; A.moments = moments2f; A.counts = counts1u; A.mean = mean3f; A.variance = variance1f; A.error = error1f; A.mask = mask1b;
-  launch_adaptive_estimate(order.qs, A);
-  return finish_launches(order, name);
-}
-
-// art_svgf_spatial_variance_device: one kernel over the caller's history and variance planes (art_svgf_spatial.h), in the queries' stream
-// order.  Like art_temporal_device it has no scratch, needs no scene and no viewport and takes no event pair.
-int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f, hipStream_t st) {
-  const std::string name = "art_svgf_spatial_variance_device";
-  SvgfSpatialArgs A; std::memset(&A, 0, sizeof A);
-  if (const char* why = sv::params_from_abi(p, hist, variance_in1f, variance_out1f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
-  if (ensure_device()) return 1;
-  Ctx& c = g_ctx;
-  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
-  if (check_device_ptr(hist, 48 * N, "hist") || check_device_ptr(variance_in1f, 4 * N, "variance_in1f") || check_device_ptr(variance_out1f, 4 * N, "variance_out1f"))
-    return 1;
-  StreamOrder order(c, st);
-  if (order.enter()) return 1;
-  A.tiles_x = svgf_spatial_tiles_x(A.P.W);
-  A.hist = (const sv::Rec4*)hist; A.variance_in = variance_in1f; A.variance_out = variance_out1f;
-  launch_svgf_spatial(order.qs, A);
-  return finish_launches(order, name);
 }
 
 void shutdown() {
@@ -945,7 +598,7 @@ int art_bind_accum(void* device_accum_rowmajor) {
   std::lock_guard<std::mutex> lk(g_mu);
   SINGLE_DEVICE_ONLY("art_bind_accum");
   // (the frame may not be known yet, so only the kind of memory and its device are checked: a refused pointer leaves the binding as it was)
-  if (device_accum_rowmajor && (ensure_device() || check_device_ptr(device_accum_rowmajor, 0, "art_bind_accum: device_accum_rowmajor"))) return 1;
+  if (device_accum_rowmajor && (ensure_device() || check_planes({{device_accum_rowmajor, 0, "art_bind_accum: device_accum_rowmajor"}}))) return 1;
   g_ctx.ext_accum = (float*)device_accum_rowmajor;
   return 0;
 }
@@ -953,7 +606,7 @@ int art_bind_moments(void* device_moments_rowmajor) {
   std::lock_guard<std::mutex> lk(g_mu);
   SINGLE_DEVICE_ONLY("art_bind_moments");
   // (as art_bind_accum: only the kind of memory and its device can be checked here; a refused pointer leaves the binding as it was)
-  if (device_moments_rowmajor && (ensure_device() || check_device_ptr(device_moments_rowmajor, 0, "art_bind_moments: device_moments_rowmajor"))) return 1;
+  if (device_moments_rowmajor && (ensure_device() || check_planes({{device_moments_rowmajor, 0, "art_bind_moments: device_moments_rowmajor"}}))) return 1;
   g_ctx.ext_moments = (float*)device_moments_rowmajor;
   return 0;
 }

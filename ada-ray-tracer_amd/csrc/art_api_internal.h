@@ -2,6 +2,8 @@
 // g_data in embree_connect.cpp:12-22 and the package-level variables of ray_tracer.ads:20-33,106-109).
 #pragma once
 #include <hip/hip_runtime.h>
+#include <array>
+#include <initializer_list>
 #include <mutex>
 #include <string>
 #include <vector>
@@ -202,7 +204,6 @@ int upload(DevBuf& b, const std::vector<T>& v) {
   HIP_TRY(hipMemcpy(b.p, v.data(), b.bytes, hipMemcpyHostToDevice));
   return 0;
 }
-int check_device_ptr(const void* p, size_t bytes, const char* what);
 int check_tree_limits(int width, int64_t n_nodes, int64_t n_tris, bool flat, bool gpu_built, bool have_qnodes, int stack);
 struct GpuBvh;
 void free_tree(GpuBvh& g);                                             // a built tree nobody adopted (current device: the tree's)
@@ -221,6 +222,26 @@ void release_updates(Ctx& c);         // the plans go with the scene (upload, re
 void destroy_updates(Ctx& c);         // shutdown
 void reset_update_info();             // the figures are cumulative since the last upload
 int sync_updates();                   // art_synchronize, current context, stream idle: fold the event pairs and counters, report a bad update once
+// ---- what the device-resident entries share (art_device_entries.cpp) ----
+// A caller's plane: device memory of the current context's GPU that holds `bytes` from p on.  check_planes reports the first of a list
+// that is not; a null p is skipped (a required plane is refused as null before its list is checked).
+struct DevPlane { const void* p; size_t bytes; const char* what; };
+int check_planes(std::initializer_list<DevPlane> planes);
+// Scratch an entry wants at least this large (buf null: an unused place).  grow_idle allocates what is too small, after waiting for the
+// context stream and, where it is another, the caller's: nothing enqueued may still use the old buffer.
+struct Grow { DevBuf* buf = nullptr; size_t bytes = 0; };
+using GrowList = std::array<Grow, 3>;
+int grow_idle(const StreamOrder& order, const GrowList& want);
+int end_ordered(StreamOrder& order, const char* name, int rc);      // rc, else the failed launch under the entry's name; then leave()
+// One call in the caller's stream order, after the entry's refusals: grow while idle, enter(), body(qs) enqueues on qs and returns rc, the
+// launch check, leave() -- also after a failed body.
+template <class Body>
+int ordered_call(const char* name, hipStream_t st, const GrowList& grow, Body&& body) {
+  StreamOrder order(g_ctx, st);
+  if (grow_idle(order, grow) || order.enter()) return 1;
+  return end_ordered(order, name, body(order.qs));
+}
+// ---- contexts, scene, frame (art_api.cpp) ----
 int ensure_device();
 int upload_scene(const ArtSceneDesc* d);
 int resize(int w, int h);
@@ -228,6 +249,7 @@ int build_shard();                    // the current context's pixel list (rank,
 inline float* accum_ptr() { return g_ctx.ext_accum ? g_ctx.ext_accum : (float*)g_ctx.b_accum.p; }
 int download_from(const float* acc_dev, float* accum_host, uint32_t* screen_host, int layout, int spp);
 int synchronize_one();                // the current context: wait for its stream, fold its event pairs and counters, report lost paths
+int synchronize();                    // every context: synchronize_one, then device 0's reduce events
 extern const bool g_debug_addr;       // ART_DEBUG_ADDR is set: device addresses of the path state and the shade trial's verdict on stderr
 extern bool g_multi_api;              // the process came up through art_init_devices: passes carry host-clock marks (Ctx::PassClock)
 void clock_cb(void* p);               // hipLaunchHostFunc: *(double*)p = the host clock, ms

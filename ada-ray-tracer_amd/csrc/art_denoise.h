@@ -247,7 +247,7 @@ ART_HD Rec4 svgf_atrous_pixel(const Params& P, const Rec4* image, const Rec4* gu
 }
 
 // ---- the ABI's parameters and the pointers -> Params: every refusal that needs no device.  Each returns nullptr, or why the call is
-// refused.  The library (art_api.cpp) and the host builds under tests/ both derive their Params here.
+// refused.  The library (art_device_entries.cpp) and the host builds under tests/ both derive their Params here.
 template <class Abi>      // ArtDenoiseParams or ArtSvgfParams: what the two have in common
 inline const char* frame_refusal(const Abi* p) {
   if (p->width < 1 || p->height < 1 || (int64_t)p->width * p->height > (1ll << 28)) return "width and height must be at least 1 and width * height at most 2^28";

@@ -1,4 +1,4 @@
-// art_kernels.h -- launch interface between the host driver (art_api.cpp, art_render.cpp) and art_kernels.hip.
+// art_kernels.h -- launch interface between the host driver (art_api.cpp, art_render.cpp, art_device_entries.cpp) and art_kernels.hip.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "art_shade.h"
@@ -99,7 +99,7 @@ void launch_query_pack(hipStream_t st, const QueryArgs& Q);
 void launch_query_finalize(hipStream_t st, const DevScene& S, const QueryArgs& Q);
 void launch_query_occluded(hipStream_t st, const QueryArgs& Q);
 
-// first-hit feature buffers (art_aov.hip, art_api.cpp render_aovs): one slice of n whole pixels, k camera rays each, in the queries'
+// first-hit feature buffers (art_aov.hip, art_device_entries.cpp render_aovs): one slice of n whole pixels, k camera rays each, in the queries'
 // scratch.  Ray s of local pixel l lies at slot s * n + l (samples first, like a render batch).  The planes are the caller's, advanced
 // to the slice's first pixel; nullptr: not wanted.
 struct AovArgs {
@@ -121,7 +121,7 @@ struct AovMotionArgs : AovArgs {
 };
 void launch_aov_resolve_motion(hipStream_t st, const DevFrame& F, const DevScene& S, const AovMotionArgs& A);
 
-// art_denoise_device, art_denoise_svgf_device and art_denoise_svgf_var_device (art_denoise.hip, art_api.cpp run_denoise): the caller's planes
+// art_denoise_device, art_denoise_svgf_device and art_denoise_svgf_var_device (art_denoise.hip, art_device_entries.cpp run_denoise): the caller's planes
 // (albedo / normal / depth / variance_out nullptr: not given; out may be color) and the library's scratch records of art_denoise.h, n = W * H
 // of each.  moments: the moments plane or, for dn::Mode::SvgfVar, the variance plane (n_colours is then not read).  dn::Mode::Plain leaves
 // n_colours, moments, variance_out and z zero: its kernels read none of them.
@@ -134,7 +134,7 @@ struct DenoiseArgs {
 };
 void launch_denoise(hipStream_t st, dn::Mode mode, const DenoiseArgs& A, int iterations);      // the mode's pack kernel and `iterations` filter launches
 
-// art_temporal_device (art_temporal.hip, art_api.cpp temporal_device): the caller's current planes (normal / depth / id nullptr: not given),
+// art_temporal_device (art_temporal.hip, art_device_entries.cpp temporal_device): the caller's current planes (normal / depth / id nullptr: not given),
 // the two histories (hist_in nullptr: the first frame) and the optional outputs; n = W * H of the current frame
 struct TemporalArgs {
   tp::Params P;
@@ -157,7 +157,7 @@ int select_blocks(int n);
 void launch_compact_mask(hipStream_t st, const SelectArgs& A, uint32_t* count_out);      // three launches: count, scan (one workgroup), scatter
 void launch_add_counts(hipStream_t st, const uint32_t* list, int n, uint32_t* counts, uint32_t samples);   // counts[list[i]] += samples, i < n
 
-// art_adaptive_estimate_device (art_adaptive.hip, art_api.cpp adaptive_estimate_device): the caller's planes, outputs nullptr where not wanted
+// art_adaptive_estimate_device (art_adaptive.hip, art_device_entries.cpp adaptive_estimate_device): the caller's planes, outputs nullptr where not wanted
 struct AdaptiveArgs {
   ad::Params P;
   const float* accum; const float* moments; const uint32_t* counts;
@@ -165,7 +165,7 @@ struct AdaptiveArgs {
 };
 void launch_adaptive_estimate(hipStream_t st, const AdaptiveArgs& A);
 
-// art_svgf_spatial_variance_device (art_svgf_spatial.hip, art_api.cpp svgf_spatial_variance_device): the history of art_temporal_device and
+// art_svgf_spatial_variance_device (art_svgf_spatial.hip, art_device_entries.cpp svgf_spatial_variance_device): the history of art_temporal_device and
 // the caller's two variance planes (they may be one); tiles_x = svgf_spatial_tiles_x(P.W), the kernel's tiles per row of tiles
 struct SvgfSpatialArgs {
   sv::Params P;

@@ -8,7 +8,7 @@
 //                      contiguous bytes.
 //   k_query_occluded   one byte per ray: the hit record holds a hit.
 //
-// Between pack and finalize the rays go through the render loop's own trace launch (art_api.cpp trace(): k_analytic + k_trace_coop,
+// Between pack and finalize the rays go through the render loop's own trace launch (art_render.cpp trace(): k_analytic + k_trace_coop,
 // or k_trace_simple); occlusion runs every ray as a shadow ray of that launch (shadow_begin = 0, sh_min = 0), so the early exit of
 // the shadow rule applies.
 #include <hip/hip_runtime.h>
@@ -50,7 +50,7 @@ __global__ __launch_bounds__(kQueryBlock) void k_query_pack(const QueryArgs Q) {
   if (Q.shm) Q.shm[i] = 0.0f;                                    // occlusion: every hit is a far hit of the shadow rule
 }
 
-// DevHit -> ArtHit (art_api.cpp trace_rays, the host loop after the download, on the device)
+// DevHit -> ArtHit (art_device_entries.cpp trace_rays, the host loop after the download, on the device)
 __global__ __launch_bounds__(kQueryBlock) void k_query_finalize(const DevScene S, const QueryArgs Q) {
   constexpr int W = kArtHitWords;
   __shared__ uint32_t s_out[W * kQueryBlock];                    // a lane's record at a stride of 11 dwords (odd: no bank conflict)

@@ -378,18 +378,8 @@ static int render_pass_one(const ArtPassParams* p, int32_t* spp_inout) {
 }
 
 // ---- mask compaction and the masked pass (art_select.hip) --------------------------------------------------------------------------
-// b_select = the count word of the masked pass (its first 256 bytes) | one word per workgroup of 256 list entries.  Growing it (or
-// `also`) may wait: nothing enqueued may still use the old buffers.
-static int ensure_select_scratch(const StreamOrder& order, int n, DevBuf* also = nullptr, size_t also_bytes = 0) {
-  Ctx& c = g_ctx;
-  const size_t bytes = 256 + (size_t)select_blocks(n) * sizeof(uint32_t);
-  if (c.b_select.bytes >= bytes && (!also || also->bytes >= also_bytes)) return 0;
-  HIP_TRY(hipStreamSynchronize(c.stream));
-  if (order.other()) HIP_TRY(hipStreamSynchronize(order.qs));
-  if (ensure(c.b_select, bytes)) return 1;
-  if (also && ensure(*also, also_bytes)) return 1;
-  return 0;
-}
+// b_select = the count word of the masked pass (its first 256 bytes) | one word per workgroup of 256 list entries
+static size_t select_bytes(int n) { return 256 + (size_t)select_blocks(n) * sizeof(uint32_t); }
 // the three launches over the context's pixel list (n = npix_local >= 1 entries) on st
 static void enqueue_compact(hipStream_t st, const uint8_t* mask1b, uint32_t* pixels_out, uint32_t* count_out) {
   Ctx& c = g_ctx;
@@ -407,18 +397,12 @@ int compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap
   if ((int64_t)c.npix_local > (1ll << 28)) return fail(name + ": the pixel list holds more than 2^28 pixels");
   if (cap < (int64_t)c.npix_local) return fail(name + ": cap " + std::to_string(cap) + " is smaller than the rank's pixel list (" + std::to_string(c.npix_local) + " pixels)");
   if (ensure_device()) return 1;
-  if (check_device_ptr(mask1b, (size_t)c.width * (size_t)c.height, "mask1b") || check_device_ptr(pixels_out, 4 * (size_t)cap, "pixels_out") ||
-      check_device_ptr(count_out, 4, "count_out"))
-    return 1;
-  StreamOrder order(c, st);
-  if (c.npix_local > 0 && ensure_select_scratch(order, c.npix_local)) return 1;
-  if (order.enter()) return 1;
-  int rc = 0;
-  if (c.npix_local > 0) enqueue_compact(order.qs, mask1b, pixels_out, count_out);
-  else if (hipMemsetAsync(count_out, 0, 4, order.qs) != hipSuccess) rc = fail(name + ": hipMemsetAsync failed");
-  if (hipGetLastError() != hipSuccess) rc = fail(name + ": kernel launch failed");
-  if (order.leave()) return 1;          // (also after a failed launch)
-  return rc;
+  if (check_planes({{mask1b, (size_t)c.width * (size_t)c.height, "mask1b"}, {pixels_out, 4 * (size_t)cap, "pixels_out"}, {count_out, 4, "count_out"}})) return 1;
+  return ordered_call(name.c_str(), st, GrowList{Grow{c.npix_local > 0 ? &c.b_select : nullptr, select_bytes(c.npix_local)}}, [&](hipStream_t qs) {
+    if (c.npix_local > 0) enqueue_compact(qs, mask1b, pixels_out, count_out);
+    else if (hipMemsetAsync(count_out, 0, 4, qs) != hipSuccess) return fail(name + ": hipMemsetAsync failed");
+    return 0;
+  });
 }
 
 // art_render_pass_masked on the current context (single device: the caller checked).  Everything is refused before the first launch.
@@ -430,12 +414,11 @@ int render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* 
   if (!mask1b) return fail(name + ": null mask1b");
   if ((int64_t)c.npix_local > (1ll << 28)) return fail(name + ": the pixel list holds more than 2^28 pixels");
   const size_t N = (size_t)c.width * (size_t)c.height;
-  if (check_device_ptr(mask1b, N, "mask1b") || (counts1u && check_device_ptr(counts1u, 4 * N, "counts1u"))) return 1;
+  if (check_planes({{mask1b, N, "mask1b"}, {counts1u, 4 * N, "counts1u"}})) return 1;
   uint32_t count = 0;
   const uint32_t* list = nullptr;
   if (c.npix_local > 0) {
-    StreamOrder order(c, nullptr);
-    if (ensure_select_scratch(order, c.npix_local, &c.b_masklist, (size_t)c.npix_local * sizeof(uint32_t))) return 1;
+    if (grow_idle(StreamOrder(c, nullptr), GrowList{Grow{&c.b_select, select_bytes(c.npix_local)}, Grow{&c.b_masklist, (size_t)c.npix_local * sizeof(uint32_t)}})) return 1;
     uint32_t* const d_count = (uint32_t*)c.b_select.p;
     enqueue_compact(c.stream, mask1b, (uint32_t*)c.b_masklist.p, d_count);
     HIP_TRY(hipGetLastError());

@@ -23,7 +23,7 @@ struct Params {
 };
 
 // ArtSvgfSpatialParams and the pointers -> the kernel's Params: every refusal that needs no device.  Returns nullptr, or why the call is
-// refused.  The library (art_api.cpp) and tests/svgf_spatial_host both derive their Params here.
+// refused.  The library (art_device_entries.cpp) and tests/svgf_spatial_host both derive their Params here.
 inline const char* params_from_abi(const ArtSvgfSpatialParams* p, const void* hist, const void* variance_in1f, const void* variance_out1f, Params& P) {
   if (!p) return "null ArtSvgfSpatialParams";
   if (!hist || !variance_in1f || !variance_out1f) return "null hist, variance_in1f or variance_out1f";

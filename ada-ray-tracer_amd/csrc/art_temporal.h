@@ -61,7 +61,7 @@ inline bool camera_from_abi(const float* cam_pos, const float* cam_matrix, int32
 
 // ArtTemporalParams and which pointers are given -> the kernel's Params: every refusal that needs no device, the two cameras, and the rule
 // of step 3 (no reprojection without depth, without history, or between cameras that are the same words).  Returns nullptr, or why the
-// call is refused.  The library (art_api.cpp) and tests/temporal_host both derive their Params here.
+// call is refused.  The library (art_device_entries.cpp) and tests/temporal_host both derive their Params here.
 // motion3f: art_temporal_motion_device's plane (nullptr: art_temporal_device's rules, word for word).
 inline const char* params_from_abi(const ArtTemporalParams* p, const void* color3f, const void* moments2f, const void* normal3f, const void* depth, const void* id,
                                    const void* hist_in, const void* hist_out, Params& P, const void* motion3f = nullptr) {

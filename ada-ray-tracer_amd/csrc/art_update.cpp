@@ -91,19 +91,20 @@ static int report_bad(UpdateLane& L, const char* head, const char* tail) {
 }
 
 // ---- one update on every context --------------------------------------------------------------------------------------------------
-// The driver of refit and move, after the kind's own refusals.  Every check comes before the first launch: the caller's buffers (srcs),
+// The driver of refit and move, after the kind's own refusals.  Every check comes before the first launch: the caller's buffers (planes),
 // then every context's plan (plan(), with that context current).  Device 0 runs `work` on the caller's stream, ordered against its context
 // stream; every other context waits for the caller's stream, copies the sources from device 0 into its lane's stage (one after the other; a
 // null source keeps its place), runs `work` on its own stream, and the caller's stream waits for it -- so the caller may overwrite its
 // buffers after whatever it enqueues next.  mark() notes on the host that the scene changes.
-struct PeerSrc { const void* p; size_t bytes; const char* what; };
 template <typename Lane, typename Plan, typename Mark, typename Work>
-static int run_update(const std::string& call, hipStream_t st, Lane lane, const std::vector<PeerSrc>& srcs, Plan plan, Mark mark, Work work) {
+static int run_update(const std::string& call, hipStream_t st, Lane lane, std::initializer_list<DevPlane> planes, Plan plan, Mark mark, Work work) {
   Ctx& c0 = g_devs[0];
   Dev0Guard guard;
   if (use_dev(0)) return 1;
+  if (check_planes(planes)) return 1;
+  const DevPlane* const srcs = planes.begin();
   std::vector<const void*> at;
-  for (const PeerSrc& x : srcs) { if (x.p && check_device_ptr(x.p, x.bytes, x.what)) return 1; at.push_back(x.p); }
+  for (const DevPlane& x : planes) at.push_back(x.p);
   for (int k = 0; k < g_ndev; ++k) { if (use_dev(k) || plan()) return 1; }
   if (use_dev(0)) return 1;
   StreamOrder order(c0, st);
@@ -119,7 +120,7 @@ static int run_update(const std::string& call, hipStream_t st, Lane lane, const 
     UpdateLane& L = lane(c);
     bool ok = hipStreamWaitEvent(c.stream, lane(c0).ready_ev, 0) == hipSuccess;
     char* stage = (char*)L.b_stage.p;
-    for (size_t i = 0; i < srcs.size(); stage += srcs[i].bytes, ++i) {
+    for (size_t i = 0; i < planes.size(); stage += srcs[i].bytes, ++i) {
       at[i] = srcs[i].p ? stage : nullptr;
       if (ok && srcs[i].p) ok = hipMemcpyPeerAsync(stage, c.device, srcs[i].p, c0.device, srcs[i].bytes, c.stream) == hipSuccess;
     }
@@ -721,7 +722,7 @@ int rebuild_device(const float* pos, const float* nrm, int64_t nverts, hipStream
   if (hs.m_idx.size() / 3 < 2) return fail("art_rebuild_device: a mesh of fewer than two triangles has no GPU-built tree; art_refit_device moves it");
   if (bp.builder == 0) bp.builder = 3;                                    // the host builder's tree, from the GPU binned-SAH builder
   const size_t bytes = 12 * (size_t)nverts;
-  if (check_device_ptr(pos, bytes, "pos3f") || (nrm && check_device_ptr(nrm, bytes, "nrm3f"))) return 1;      // (against g_ctx: context 0, which every call leaves current)
+  if (check_planes({{pos, bytes, "pos3f"}, {nrm, bytes, "nrm3f"}})) return 1;      // (against g_ctx: context 0, which every call leaves current)
   return run_rebuild<PendingTree>(t0, st, g_rebuild_info,
       [](int) { return 0; },
       [&](int k, hipStream_t s, PendingTree& t, float* gather_ms) {
