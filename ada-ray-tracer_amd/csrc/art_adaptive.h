@@ -70,4 +70,16 @@ ART_HD Out adaptive_pixel(const Params& P, const float* accum, const float* mome
 }
 
 }  // namespace ad
+
+// ---- launch interface (art_adaptive.hip); hipcc only: the g++ builds of the tests take the per-pixel text above and nothing else
+#if defined(__HIPCC__)
+// art_adaptive_estimate_device (art_adaptive.hip, art_device_entries.cpp adaptive_estimate_device): the caller's planes, outputs nullptr where not wanted
+struct AdaptiveArgs {
+  ad::Params P;
+  const float* accum; const float* moments; const uint32_t* counts;
+  float* mean; float* variance; float* error; uint8_t* mask;
+};
+void launch_adaptive_estimate(hipStream_t st, const AdaptiveArgs& A);
+#endif
+
 }  // namespace art

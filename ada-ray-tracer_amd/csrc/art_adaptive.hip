@@ -12,7 +12,6 @@
 // (profiles/adaptive/measure.py is the script): the kernel runs at the rate of its 45 bytes per pixel.
 #include <hip/hip_runtime.h>
 #include "art_adaptive.h"
-#include "art_kernels.h"
 
 namespace art {
 

@@ -16,7 +16,9 @@
 // Between the two the rays go through the render loop's own trace launch (art_render.cpp trace()).
 #include <hip/hip_runtime.h>
 #include <type_traits>
-#include "art_kernels.h"
+#include "art_query.h"
+#include "art_motion.h"
+#include "art_shade.h"
 
 namespace art {
 

@@ -26,6 +26,7 @@
 #include <vector>
 
 #include "art_api_internal.h"
+#include "art_frame.h"
 #include "art_lbvh.h"
 
 namespace art {

@@ -10,7 +10,8 @@
 #include "../../include/art_hip.h"
 #include "art_event_pairs.h"
 #include "art_host_scene.h"
-#include "art_kernels.h"
+#include "art_move.h"
+#include "art_trace.h"
 #include "art_pass_plan.h"
 
 namespace art {

@@ -285,4 +285,21 @@ inline const char* params_from_abi(const ArtSvgfParams* p, const void* color3f, 
 }
 
 }  // namespace dn
+
+// ---- launch interface (art_denoise.hip); hipcc only: the g++ builds of the tests take the per-pixel text above and nothing else
+#if defined(__HIPCC__)
+// art_denoise_device, art_denoise_svgf_device and art_denoise_svgf_var_device (art_denoise.hip, art_device_entries.cpp run_denoise): the caller's planes
+// (albedo / normal / depth / variance_out nullptr: not given; out may be color) and the library's scratch records of art_denoise.h, n = W * H
+// of each.  moments: the moments plane or, for dn::Mode::SvgfVar, the variance plane (n_colours is then not read).  dn::Mode::Plain leaves
+// n_colours, moments, variance_out and z zero: its kernels read none of them.
+struct DenoiseArgs {
+  dn::Params P;
+  int32_t n, n_colours;
+  const float* color; const float* moments; const float* albedo; const float* normal; const float* depth;
+  float* out; float* variance_out;
+  dn::Rec4* image[2]; dn::Rec4* guide; float* z; dn::Rec2* grad;
+};
+void launch_denoise(hipStream_t st, dn::Mode mode, const DenoiseArgs& A, int iterations);      // the mode's pack kernel and `iterations` filter launches
+#endif
+
 }  // namespace art

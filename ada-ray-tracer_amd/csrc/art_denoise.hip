@@ -21,7 +21,6 @@
 #define ART_F64_CONST_FREE      // m1::exp_small's coefficients as plain literals: no asm pin in these kernels (the value is the literal's either way)
 #include <hip/hip_runtime.h>
 #include "art_denoise.h"
-#include "art_kernels.h"
 
 namespace art {
 

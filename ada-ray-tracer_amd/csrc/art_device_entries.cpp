@@ -15,6 +15,13 @@
 #include <vector>
 
 #include "art_api_internal.h"
+#include "art_adaptive.h"
+#include "art_denoise.h"
+#include "art_motion.h"
+#include "art_query.h"
+#include "art_shade.h"      // surface_at: trace_rays finishes its hit records on the host
+#include "art_svgf_spatial.h"
+#include "art_temporal.h"
 
 namespace art {
 

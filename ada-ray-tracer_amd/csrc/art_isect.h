@@ -150,7 +150,7 @@ ART_HD void isect_bf_mesh(f3 o, f3 d, f3 rcp, const DevScene& s, Cand& best) {
   if (any) cand_take(best, ht, KEY_BFTRI | tri_id, hu, hv);
 }
 
-// ---- BVH8 traversal, one ray per caller (the cooperative 8-lane kernel lives in art_kernels.hip).
+// ---- BVH8 traversal, one ray per caller (the cooperative 8-lane kernel lives in art_trace.hip).
 // Published order (DESIGN.md "Traversal order"): pop; drop if entry.tmin > best.t; inner node: test
 // the valid children against [max(.,0), min(., best.t)], sort hits ascending by
 // key = (bits(tmin) & ~7) | slot, push far-to-near; leaf: test its triangles in storage order.

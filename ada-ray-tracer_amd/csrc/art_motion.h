@@ -67,3 +67,17 @@ ART_HD float mean4(float v0, float v1, float v2, float v3) { return (((v0 + v1) 
 
 }  // namespace mo
 }  // namespace art
+
+// ---- launch interface (art_aov.hip's resolve with the motion plane); hipcc only: the g++ builds of the tests take the per-pixel text above and nothing else
+#if defined(__HIPCC__)
+#include "art_query.h"
+namespace art {
+// art_render_aovs_motion_device: the same slice with the motion plane (3 floats per pixel, advanced to the slice; never nullptr here) and
+// what its deltas are made from (art_motion.h).  A type of its own, so that the kernels without the plane keep their arguments.
+struct AovMotionArgs : AovArgs {
+  float* motion;
+  mo::Source src;
+};
+void launch_aov_resolve_motion(hipStream_t st, const DevFrame& F, const DevScene& S, const AovMotionArgs& A);
+}  // namespace art
+#endif

@@ -73,7 +73,7 @@
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
-#include "art_kernels.h"
+#include "art_move.h"
 #include "art_refit_node.h"
 
 namespace art {

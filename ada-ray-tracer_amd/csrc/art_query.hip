@@ -12,7 +12,8 @@
 // or k_trace_simple); occlusion runs every ray as a shadow ray of that launch (shadow_begin = 0, sh_min = 0), so the early exit of
 // the shadow rule applies.
 #include <hip/hip_runtime.h>
-#include "art_kernels.h"
+#include "art_query.h"
+#include "art_shade.h"
 
 namespace art {
 

@@ -14,7 +14,8 @@
 
 #include <algorithm>
 
-#include "art_kernels.h"
+#include "art_rebuild.h"
+#include "art_refit.h"      // kRefitMaxCoord
 
 namespace art {
 

@@ -16,7 +16,7 @@
 #include <algorithm>
 
 #include "art_bvh.h"
-#include "art_kernels.h"
+#include "art_refit.h"
 #include "art_refit_node.h"
 
 namespace art {

@@ -16,7 +16,7 @@
 #include <hip/hip_runtime.h>
 
 #include "art_bvh.h"
-#include "art_kernels.h"
+#include "art_refit.h"
 #include "art_qnode.h"
 
 namespace art {

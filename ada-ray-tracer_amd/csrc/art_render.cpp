@@ -12,6 +12,9 @@
 #include <string>
 
 #include "art_api_internal.h"
+#include "art_frame.h"
+#include "art_select.h"
+#include "art_stages.h"
 
 namespace art {
 

@@ -27,7 +27,7 @@ struct DevSphere { float x, y, z, r; };
 // closest hit of a ray, one 16-byte record: every producer writes it and every consumer reads it with ONE 16-byte access
 struct alignas(16) DevHit { float t; uint32_t key; float u, v; };
 
-// one 16-byte quarter of a 64-byte trace record (art_kernels.h): what the cooperative trace kernel starts a ray from
+// one 16-byte quarter of a 64-byte trace record (art_trace.h): what the cooperative trace kernel starts a ray from
 struct alignas(16) Rec4 { float x, y, z, w; };
 // Which rays a work item of a bank owns a trace record for (round 3: the wavefront stages write the records themselves, at positions
 // given by the item index -- no queue, no atomics, no separate pass over the rays):
@@ -145,7 +145,7 @@ struct DevPaths {
   // Record schedule (round 5): a SHADOW ray's result is ONE word, sh_t[item] = t of the closest hit the search ended with, or -1 (none) --
   // Compute_Shadow only asks whether that t lies above 10 eps (ray_tracer.adb:122), so the 16-byte record (key, u, v) was 12 bytes
   // written by the stage, 12 read by the next one and a 16-byte store of the trace kernel for nothing.  The record names the word by
-  // kShadowWord | item (art_kernels.h TraceArgs::sh_t).  nullptr: the plain layout, shadow hits at hit[P + item].
+  // kShadowWord | item (art_trace.h TraceArgs::sh_t).  nullptr: the plain layout, shadow hits at hit[P + item].
   float* sh_t;
   // per-path
   float* prev_pdf;              // MatSample.pdf of the previous bounce

@@ -22,7 +22,7 @@
 //   k_add_counts      counts[list[i]] += samples for the n entries of a compacted list: the entries are distinct, so every word has one
 //                     writer.
 #include <hip/hip_runtime.h>
-#include "art_kernels.h"
+#include "art_select.h"
 
 namespace art {
 

@@ -381,7 +381,7 @@ ART_HD Cand analytic_bound(const DevScene& s, const StageCtx& cx, f3 o, f3 d, f3
 ART_HD size_t rec_slot(int mode, int w, bool shadow_ray) { return (mode == REC_BOTH) ? 2 * (size_t)w + (shadow_ray ? 1u : 0u) : (size_t)w; }
 
 // One ray of an output item: its hit record (the starting bound: what stands if the BVH finds nothing nearer) and its 64-byte trace
-// record (art_kernels.h) -- everything k_analytic does for the plain layout, done where the ray is born.  shm >= 0: a shadow ray under
+// record (art_trace.h) -- everything k_analytic does for the plain layout, done where the ray is born.  shm >= 0: a shadow ray under
 // the visibility rule (art_isect.h shadow_rule).  A ray that does not exist (live = false) or is already decided leaves a record whose
 // bound is negative: the trace kernel takes it and retires it at once.
 struct TraceRec { Rec4 r0, r1, r2, r3; };

@@ -87,4 +87,18 @@ ART_HD float spatial_pixel(const Params& P, const Rec4* hist, const float* varia
 }
 
 }  // namespace sv
+
+// ---- launch interface (art_svgf_spatial.hip); hipcc only: the g++ builds of the tests take the per-pixel text above and nothing else
+#if defined(__HIPCC__)
+// art_svgf_spatial_variance_device (art_svgf_spatial.hip, art_device_entries.cpp svgf_spatial_variance_device): the history of art_temporal_device and
+// the caller's two variance planes (they may be one); tiles_x = svgf_spatial_tiles_x(P.W), the kernel's tiles per row of tiles
+struct SvgfSpatialArgs {
+  sv::Params P;
+  int32_t tiles_x;
+  const sv::Rec4* hist; const float* variance_in; float* variance_out;
+};
+int svgf_spatial_tiles_x(int width);
+void launch_svgf_spatial(hipStream_t st, const SvgfSpatialArgs& A);
+#endif
+
 }  // namespace art

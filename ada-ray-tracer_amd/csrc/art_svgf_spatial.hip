@@ -16,7 +16,6 @@
 // travel: 16 more.  Short history: each record of the three planes once, 48, plus the same 8.
 #include <hip/hip_runtime.h>
 #include "art_svgf_spatial.h"
-#include "art_kernels.h"
 
 namespace art {
 

@@ -194,4 +194,21 @@ ART_HD Out temporal_pixel(const Params& P, const float* color, const float* mome
 }
 
 }  // namespace tp
+
+// ---- launch interface (art_temporal.hip); hipcc only: the g++ builds of the tests take the per-pixel text above and nothing else
+#if defined(__HIPCC__)
+// art_temporal_device (art_temporal.hip, art_device_entries.cpp temporal_device): the caller's current planes (normal / depth / id nullptr: not given),
+// the two histories (hist_in nullptr: the first frame) and the optional outputs; n = W * H of the current frame
+struct TemporalArgs {
+  tp::Params P;
+  int32_t n;
+  int32_t has_motion;              // art_temporal_motion_device with a motion plane: the MOTION instantiation runs (the word lies in what was padding)
+  const float* color; const float* moments; const float* normal; const float* depth; const int32_t* id;
+  const tp::Rec4* hist_in; tp::Rec4* hist_out;
+  float* out; float* variance_out; float* length_out;
+  const float* motion;             // art_temporal_motion_device: 3 floats per pixel of the current frame; else nullptr
+};
+void launch_temporal(hipStream_t st, const TemporalArgs& A);      // A.has_motion selects the motion variant of the kernel
+#endif
+
 }  // namespace art

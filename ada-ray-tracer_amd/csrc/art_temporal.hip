@@ -22,7 +22,6 @@
 // workgroup's taps inside a handful of history rows.
 #include <hip/hip_runtime.h>
 #include "art_temporal.h"
-#include "art_kernels.h"
 
 namespace art {
 

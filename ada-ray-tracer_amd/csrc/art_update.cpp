@@ -17,6 +17,8 @@
 #include <vector>
 
 #include "art_api_internal.h"
+#include "art_rebuild.h"
+#include "art_refit.h"
 #include "art_lbvh.h"
 #include "art_renumber.h"
 

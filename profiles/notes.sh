@@ -1,6 +1,6 @@
 #!/bin/bash
 # Code-object notes (VGPRs, SGPRs, spills, LDS, scratch) of every kernel in a hipcc object or shared library.
-# usage: bash profiles/notes.sh ada-ray-tracer_amd/build/art_kernels.hip.o [name filter]
+# usage: bash profiles/notes.sh ada-ray-tracer_amd/build/art_trace.hip.o [name filter]
 O=$1; F=${2:-.}
 T=$(mktemp -d -p "${TMPDIR:-/tmp}")
 B=/opt/rocm/lib/llvm/bin

@@ -54,7 +54,7 @@ def main():
     occ = bench["roofline"]["wave_occupancy"]
     asm = "/tmp/art_kernels_mix.s"
     subprocess.check_call(["/opt/rocm/bin/hipcc"] + FLAGS + ["-I" + os.path.join(ROOT, "include"), "--cuda-device-only", "-S",
-                                                              os.path.join(ROOT, "ada-ray-tracer_amd", "csrc", "art_kernels.hip"), "-o", asm], stderr=subprocess.DEVNULL)
+                                                              os.path.join(ROOT, "ada-ray-tracer_amd", "csrc", "art_trace.hip"), "-o", asm], stderr=subprocess.DEVNULL)
     lines = open(asm).read().split("\n")
     start = next(i for i, l in enumerate(lines) if l.startswith(KERNEL + ":"))
     end = next(i for i in range(start, len(lines)) if "s_endpgm" in lines[i])

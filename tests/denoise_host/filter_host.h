@@ -1,6 +1,6 @@
 // TEST-ONLY: the driver of the a-trous filters on host arrays, pack -> iterate -> finish, through the product's own per-pixel text
 // (csrc/art_denoise.h) in the mode the kernels take.  P comes from dn::params_from_abi; pointers are host memory; out3f may be color3f.
-// moments, n_colours and variance_out are as DenoiseArgs' (csrc/art_kernels.h); dn::Mode::Plain reads none of them.
+// moments, n_colours and variance_out are as DenoiseArgs' (csrc/art_denoise.h); dn::Mode::Plain reads none of them.
 #pragma once
 #include <vector>
 #include "../../ada-ray-tracer_amd/csrc/art_denoise.h"

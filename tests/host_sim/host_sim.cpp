@@ -122,7 +122,7 @@ extern "C" int hs_render(const ArtSceneDesc* sd, const ArtPassParams* p, int w, 
   if (g_fold_dense) {
 #pragma omp parallel for
     for (int s = 0; s < P; ++s) resolve_last_shadow(q, s, D - 1);
-    for (int k = D - 1; k >= 0; --k) {                     // art_kernels.hip launch_fold_levels: odd levels -> term, even levels -> rad
+    for (int k = D - 1; k >= 0; --k) {                     // art_stages.hip launch_fold_levels: odd levels -> term, even levels -> rad
       float* cur[3] = {(k & 1) ? q.term_r : q.rad_r, (k & 1) ? q.term_g : q.rad_g, (k & 1) ? q.term_b : q.rad_b};
       const float* nxt[3] = {(k & 1) ? q.rad_r : q.term_r, (k & 1) ? q.rad_g : q.term_g, (k & 1) ? q.rad_b : q.term_b};
 #pragma omp parallel for

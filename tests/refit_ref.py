@@ -17,7 +17,7 @@ import numpy as np
 F = np.float32
 INFLATE_REL = F(8.0e-6)      # BvhBuildParams::inflate_rel (art_bvh.h)
 INFLATE_ABS = F(1.0e-6)      # BvhBuildParams::inflate_abs
-MAX_COORD = F(1.0e18)        # kRefitMaxCoord (art_kernels.h)
+MAX_COORD = F(1.0e18)        # kRefitMaxCoord (art_refit.h)
 MAX_LEAF_TRIS = 8            # kMaxLeafTris (art_scene.h)
 TINY = F(1.401298464e-45)    # the smallest positive binary32 value
 

@@ -25,7 +25,7 @@ import numpy as np
 import refit_ref
 from refit_ref import F, levels, next_dn, next_up, pad_box, quantise      # noqa: F401  (next_dn / next_up: the pad rule's, through pad_box)
 
-MAX_REACH = 1.0e18           # kMoveMaxReach (art_kernels.h)
+MAX_REACH = 1.0e18           # kMoveMaxReach (art_move.h)
 NODE_BASE, TRI_BASE, SHADE_BASE, ROOT_ENTRY, QROOT, INST = 24, 25, 26, 27, 28, 29      # DevInstance words (m: 0..11, minv: 12..23)
 ARRAYS = ("inst", "tlas_nodes", "tlas_tris", "blas_nodes", "blas_tris", "qnodes", "mesh_pad", "mesh_box", "mesh_base", "node_mesh")
 INF = F(np.inf)
