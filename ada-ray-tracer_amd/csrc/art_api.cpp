@@ -625,7 +625,8 @@ int art_reduce(void) {
 
 int art_download(float* accum_host, uint32_t* screen_host, int32_t layout, int32_t spp) {
   std::lock_guard<std::mutex> lk(g_mu);
-  if (spp <= 0) return fail("art_download: spp must be positive");
+  // 1 / spp scales the resolve only: without a screen spp is not read; with one, spp <= 0 would divide by zero or negate the picture
+  if (screen_host && spp <= 0) return fail("art_download: spp must be positive to resolve a screen, got " + std::to_string(spp));
   return download(accum_host, screen_host, layout, spp);
 }
 

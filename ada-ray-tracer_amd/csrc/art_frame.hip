@@ -27,13 +27,6 @@ __global__ __launch_bounds__(256) void k_to_xmajor_u32(const uint32_t* src_rowma
   const int x = i / h, y = i - x * h;
   dst_xmajor[i] = src_rowmajor[(size_t)y * w + x];
 }
-__global__ __launch_bounds__(256) void k_from_xmajor_f3(const float* src_xmajor, float* dst_rowmajor, int w, int h) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= w * h) return;
-  const int x = i / h, y = i - x * h;
-  const size_t s = (size_t)y * w + x;
-  dst_rowmajor[3 * s] = src_xmajor[3 * (size_t)i]; dst_rowmajor[3 * s + 1] = src_xmajor[3 * (size_t)i + 1]; dst_rowmajor[3 * s + 2] = src_xmajor[3 * (size_t)i + 2];
-}
 
 // 48-byte triangle records -> 64-byte padded records for the 4-wide trace kernel
 __global__ __launch_bounds__(256) void k_pad_tris(const float* __restrict__ src, float* __restrict__ dst, int n) {
@@ -61,9 +54,6 @@ void launch_to_xmajor_f3(hipStream_t st, const float* src, float* dst, int w, in
 }
 void launch_to_xmajor_u32(hipStream_t st, const uint32_t* src, uint32_t* dst, int w, int h) {
   hipLaunchKernelGGL(k_to_xmajor_u32, dim3(blocks_for(w * h)), dim3(256), 0, st, src, dst, w, h);
-}
-void launch_from_xmajor_f3(hipStream_t st, const float* src, float* dst, int w, int h) {
-  hipLaunchKernelGGL(k_from_xmajor_f3, dim3(blocks_for(w * h)), dim3(256), 0, st, src, dst, w, h);
 }
 
 void launch_pad_tris(hipStream_t st, const float* src, float* dst, int n) {

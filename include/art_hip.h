@@ -221,6 +221,12 @@ int  art_bind_accum(void* device_accum_rowmajor);        /* NULL: back to the in
  * the moments alone.  The accum a pass writes is the same, bit for bit, with and without moments bound. */
 int  art_bind_moments(void* device_moments_rowmajor);   /* NULL: none (the default) */
 void* art_accum_device(void);
+/* Read the framebuffer back (after a reduce in multi-device mode): accum_host and / or screen_host, either may be NULL, in `layout`.
+ * The screen is the resolve of the accum as it lies there, whatever wrote it: per channel min((accum * (1.0f / spp)) ** 0.5, 1) * 255
+ * rounded to the nearest integer, a tie away from zero, packed R | G << 8 | B << 16; a negative or NaN sum gives 255.  spp is read for
+ * the screen only.  With screen_host != NULL, spp <= 0 is refused before anything is launched ("art_download: spp must be positive ..."):
+ * the host buffers and the framebuffer stay untouched.  (The reference never resolves at zero samples: Render_Pass counts the pass's
+ * samples before it divides.)  With screen_host == NULL any spp is accepted. */
 int  art_download(float* accum_host, uint32_t* screen_host, int32_t layout, int32_t spp);
 int  art_synchronize(void);
 

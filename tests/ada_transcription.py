@@ -510,13 +510,62 @@ def path_trace(scn, kind, o, d, prev, level, uniforms, max_depth):
         return add(explicit, mulv(w, nxt))
 
 
-def eye_ray_direction(x, y, ox, oy, width, height):
-    """ray_tracer.adb:61-97: ox = oy = 0.5 (no AA) or the 1/3, 2/3 offsets; fov = pi/2"""
-    fov = f(np.float64(np.pi) / 2.0)
+def eye_ray_z(width, fov=None):
+    """res.z of ray_tracer.adb:67: -float(width) / safe_tan(fov / 2.0); fov = Pi / 2.0 in the Ada text"""
+    fov = f(np.float64(np.pi) / 2.0) if fov is None else f(fov)
     half = fov / f(2)
     tan_half = f(np.tan(np.float64(half)))                       # safe_tan: |x| /= pi/2 here
-    r = (f(x) + ox - (f(width) / f(2)), f(y) + oy - (f(height) / f(2)), -f(width) / tan_half)
+    return -f(width) / tan_half
+
+
+def eye_ray_direction(x, y, ox, oy, width, height, z=None):
+    """ray_tracer.adb:61-97: ox = oy = 0.5 (no AA) or the 1/3, 2/3 offsets; fov = pi/2 unless another res.z is given.  x and y may be
+    integer arrays: every operation is then the same binary32 operation per element"""
+    z = eye_ray_z(width) if z is None else f(z)
+    x, y = np.asarray(x).astype(np.float32)[()], np.asarray(y).astype(np.float32)[()]
+    r = (x + ox - (f(width) / f(2)), y + oy - (f(height) / f(2)), z)
     return normalize(r)
+
+
+AA_OFFSETS = ((f(1) / f(3), f(1) / f(3)), (f(1) / f(3), f(2) / f(3)), (f(2) / f(3), f(1) / f(3)), (f(2) / f(3), f(2) / f(3)))   # Generate4RayDirections: res(0..3)
+
+
+# ================================================================================================ the LDR frame
+# ray_tracer.adb:279-291 (normC, the gamma, the store), :19-38 (ToneMapping), :41-57 (ColorToUnsigned_32), ray_tracer.ads:32 (g_gamma)
+G_GAMMA = f(2)
+
+
+def to_unsigned_32(v):
+    """Unsigned_32(v) of a Float, RM 4.6(33): the nearest integer, a tie away from zero.  v + 0.5 is exact in binary64 for every binary32
+    below 2^32, so the floor of that sum is the rule itself, not an approximation of it.  Below -0.5 the Ada text raises Constraint_Error
+    and it has no NaN; both give 0 here, as (-0.5, 0.5) does"""
+    if not v > 0:
+        return 0
+    return int(np.floor(np.float64(v) + 0.5))
+
+
+def tone_mapping(v):
+    return (amin(v[0], f(1)), amin(v[1], f(1)), amin(v[2], f(1)))
+
+
+def color_to_unsigned_32(c):
+    r, g, b = c[0] * f(255), c[1] * f(255), c[2] * f(255)
+    return to_unsigned_32(r) | (to_unsigned_32(g) << 8) | (to_unsigned_32(b) << 16)
+
+
+def resolve_channel(a, norm_c):
+    """one channel from the accumulated sum to the value that is converted: the product with normC, the gamma, the clamp, the scale"""
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        return amin(power(norm_c * a, f(1) / G_GAMMA), f(1)) * f(255)
+
+
+def resolve(acc, norm_c):
+    """screen_buffer(x, y) of an accumulated colour: a negative or NaN sum has no answer in the Ada text ("**" raises Argument_Error);
+    numpy's sqrt gives NaN there and min(NaN, 1.0) -- `if a < b then a else b` -- gives 1.0"""
+    with np.errstate(invalid="ignore", over="ignore", under="ignore"):
+        rgb = scale(norm_c, acc)
+        rgb = tuple(power(c, f(1) / G_GAMMA) for c in rgb)
+    return color_to_unsigned_32(tone_mapping(rgb))
 
 
 # ================================================================================================ the pyramid's transform chain

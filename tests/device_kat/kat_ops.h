@@ -42,10 +42,16 @@ enum Op : int {
   OP_SLAB,              // o, d, lo, hi, tbest -> slab_setup: inv, noi; slab_interval: tmn, tmx
   OP_CAND_WINS,         // t, key, best.t, best.key -> 0 / 1
   OP_SINCOS_F64,        // x -> m1::sincos((double)x) before its rounding to binary32: s low, high word, c low, high word
+  // the two ends of a picture: the camera ray and the LDR frame
+  OP_CAMERA_DIR,        // pixel, sample (as words) -> camera_dir                        params: CameraParams
+  OP_RESOLVE,           // accum r, g, b, norm_c -> resolve_pixel (the packed word)
+  OP_ROUND_U32,         // v (below 2^32: a larger value has no uint32_t) -> ada_round_u32 (as a word)
+  OP_COLOUR_LUM,        // r, g, b -> colour_lum
   OP_COUNT
 };
 
 struct OpShape { int in_words, out_words, param_bytes; };
+struct CameraParams { int32_t width, height, aa_on; float cam_z; float cam_matrix[16]; };     // what camera_dir reads of DevFrame / DevScene
 
 ART_HD OpShape op_shape(int op) {
   switch (op) {
@@ -76,6 +82,10 @@ ART_HD OpShape op_shape(int op) {
     case OP_SLAB:                return {13, 8, 0};
     case OP_CAND_WINS:           return {4, 1, 0};
     case OP_SINCOS_F64:          return {1, 4, 0};
+    case OP_CAMERA_DIR:          return {2, 3, (int)sizeof(CameraParams)};
+    case OP_RESOLVE:             return {4, 1, 0};
+    case OP_ROUND_U32:           return {1, 1, 0};
+    case OP_COLOUR_LUM:          return {3, 1, 0};
     default:                     return {0, 0, 0};
   }
 }
@@ -169,6 +179,18 @@ ART_HD void run_item(int op, const float* in, float* out, const void* params) {
       return;
     }
     case OP_SINCOS_F64: { double sd, cd; m1::sincos((double)in[0], sd, cd); put_f64(out, sd); put_f64(out + 2, cd); return; }
+    case OP_CAMERA_DIR: {
+      const CameraParams* c = (const CameraParams*)params;
+      DevFrame fr; memset(&fr, 0, sizeof fr);
+      DevScene s; memset(&s, 0, sizeof s);
+      fr.width = c->width; fr.height = c->height; fr.aa_on = c->aa_on; fr.cam_z = c->cam_z;
+      for (int k = 0; k < 16; ++k) s.cam_matrix[k] = c->cam_matrix[k];
+      put3(out, camera_dir(fr, s, word(in[0]), word(in[1])));
+      return;
+    }
+    case OP_RESOLVE: { out[0] = as_float(resolve_pixel(ld3(in), in[3])); return; }
+    case OP_ROUND_U32: { out[0] = as_float(ada_round_u32(in[0])); return; }
+    case OP_COLOUR_LUM: { out[0] = colour_lum(ld3(in)); return; }
     default: return;
   }
 }

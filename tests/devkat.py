@@ -11,6 +11,7 @@ import hostsim
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIGHT_BYTES, MATERIAL_BYTES = 76, 40           # sizeof(DevLight), sizeof(DevMaterial) = the ABI's ArtLight / ArtMaterial
+CAMERA_BYTES = 80                              # sizeof(kat::CameraParams): width, height, aa_on, cam_z, cam_matrix[16]
 
 OPS = {name: (k,) + shape for k, (name, shape) in enumerate([
     ("sincos", (1, 2, 0)), ("tan", (1, 2, 0)), ("apow", (2, 1, 0)), ("sqrt", (1, 1, 0)), ("rcp", (1, 1, 0)), ("div", (2, 1, 0)),
@@ -19,7 +20,8 @@ OPS = {name: (k,) + shape for k, (name, shape) in enumerate([
     ("light_sample", (5, 10, LIGHT_BYTES)), ("light_eval_pdf", (7, 1, LIGHT_BYTES)), ("sphere_light_pdf", (3, 1, LIGHT_BYTES)),
     ("pdf_area_to_solid", (3, 1, 0)), ("bsdf_sample", (8, 8, MATERIAL_BYTES)), ("bsdf_eval", (9, 4, MATERIAL_BYTES)),
     ("tri_raw", (15, 4, 0)), ("sphere", (10, 2, 0)), ("cornell", (6, 5, 24)), ("quad", (6, 2, LIGHT_BYTES)), ("slab", (13, 8, 0)),
-    ("cand_wins", (4, 1, 0)), ("sincos_f64", (1, 4, 0))])}
+    ("cand_wins", (4, 1, 0)), ("sincos_f64", (1, 4, 0)),
+    ("camera_dir", (2, 3, CAMERA_BYTES)), ("resolve", (4, 1, 0)), ("round_u32", (1, 1, 0)), ("colour_lum", (3, 1, 0))])}
 
 _dev = None
 _sig = [C.c_int, C.c_longlong, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int]

@@ -11,7 +11,7 @@ import kat_inputs as ki
 f = np.float32
 T = lambda a: tuple(f(c) for c in a)
 NO_TRANSCRIPTION = {"tan": "the Ada text calls the run-time library's Tan; mpmath checks atan_m1 on the CPU",
-                    "sqrt": None, "rcp": None, "div": None,      # numpy's own binary32 operation IS the reference: see expect()
+                    "sqrt": None, "rcp": None, "div": None, "colour_lum": None,      # numpy's own binary32 operations ARE the reference: see expect()
                     "sincos_f64": "ART-M1 internals: the binary64 sine and cosine before the single rounding, host build only",
                     "log_pos": "ART-M1 internals: checked against mpmath on the CPU", "exp_small": "ART-M1 internals: checked against mpmath on the CPU",
                     "slab": "this backend's own slab arithmetic, not reference code: host build only"}
@@ -83,11 +83,31 @@ def expect(op, case, i):
     if op == "quad":
         h = ada.intersect_flat_light(T(x[:3]), T(x[3:6]), L)
         return (_w([h["t"], _key(ki.KEY_QUAD)]), None) if h["is_hit"] else (_w([ki.FLT_MAX, _key(ki.KEY_MISS)]), None)
+    if op == "resolve": return np.array([ada.resolve(T(x[:3]), x[3])], np.uint32), None
+    if op == "round_u32": return np.array([ada.to_unsigned_32(x[0])], np.uint32), None
+    if op == "colour_lum": return _w([(f(0.2126) * x[0] + f(0.7152) * x[1]) + f(0.0722) * x[2]]), None      # include/art_hip.h, art_bind_moments: binary32, not contracted
     if op == "cand_wins":
         w = case.words[i]
         t, bt = x[0], x[2]
         return _w([1.0 if (t < bt) or (t == bt and w[3] != ki.KEY_MISS and w[1] < w[3]) else 0.0]), None
     return None
+
+
+def camera_expected(case, n):
+    """camera_dir of the first n items of a camera Case, all at once: the transcription's functions on binary32 arrays, which are the same
+    binary32 operations per element.  Sample s takes res(s mod 4) of Generate4RayDirections; without AA every sample is EyeRayDirection."""
+    d = case.pdesc
+    W, H = d["width"], d["height"]
+    pix, smp = case.words[:n, 0].astype(np.int64), case.words[:n, 1].astype(np.int64)
+    x, y = pix % W, pix // W
+    if d["aa_on"]:
+        off = np.array(ada.AA_OFFSETS, np.float32)[smp % 4]
+        ox, oy = off[:, 0], off[:, 1]
+    else:
+        ox = oy = f(0.5)
+    r = ada.eye_ray_direction(x, y, ox, oy, W, H, d["cam_z"])
+    out = ada.normalize(ada.mat_mul_point(d["matrix"], r))
+    return np.stack([np.broadcast_to(c, (n,)) for c in out], axis=1).astype(np.float32).view(np.uint32)
 
 
 _expected = {}
@@ -110,6 +130,9 @@ RAISING_SETS = {"phong_0"}            # cosPower 0: a lobe cosine clamped to 0 i
 
 
 def _transcribe_case(op, case):
+    if op == "camera_dir":
+        n = case.n_transcribed()
+        return case, np.arange(n), camera_expected(case, n), np.ones((n, 3), bool)
     idx, rows, masks = [], [], []
     for i in range(case.n_transcribed()):
         if i in case.no_ref:
@@ -143,7 +166,7 @@ def expected_table(op):
 
 def differing(op, got, want, mask=None):
     """items of got (n x words) that differ from want under the rule: both NaN, or the same bits (binary64 halves: the same bits)"""
-    if op in ("log_pos", "exp_small", "sincos_f64"):
+    if op in ("log_pos", "exp_small", "sincos_f64", "resolve", "round_u32"):      # (and integers: the same bits)
         bad = got != want
     else:
         bad = ~((got == want) | (np.isnan(got.view(np.float32)) & np.isnan(want.view(np.float32))))
@@ -170,6 +193,7 @@ def assert_matches_transcription(op, run):
 def assert_coverage(op, outputs):
     """outputs: [(case, output words)] of one side.  Asserts, from inputs and outputs, that the op's branches all occurred."""
     fl = lambda w: w.view(np.float32)
+    _assert_picture_ends_coverage(op, outputs)
     if op == "bsdf_sample":
         seen = set(); tir = 0
         for case, out in outputs:
@@ -242,6 +266,50 @@ def assert_coverage(op, outputs):
             d2 = ((p - np.array(L["center"], np.float32)) ** 2).sum(axis=1)
             inside = d2 - float(L["radius"]) ** 2 < 1e-4
             assert inside[:case.n_edge].any() and (~inside[:case.n_edge]).any() and inside[case.n_edge:].any(), "sphere light: points inside and outside"
+
+
+MIN_BOUNDARIES = 250            # of the 255 rises of the byte, both sides must occur among the inputs
+
+
+def boundaries_reached(in_words, out_bytes):
+    """the bytes k for which two inputs one ulp apart (positive, finite) give k and k + 1"""
+    keep = in_words < 0x7F800000
+    w, first = np.unique(in_words[keep], return_index=True)
+    b = out_bytes[keep][first].astype(np.int64)
+    adj = (w[1:].astype(np.int64) == w[:-1].astype(np.int64) + 1) & (b[1:] == b[:-1] + 1)
+    return set(b[:-1][adj].tolist())
+
+
+def assert_boundary_coverage(op, case, out):
+    """resolve: per norm_c, on the red channel; round_u32: on its one input"""
+    if op == "round_u32":
+        groups = [("", case.words[:, 0], out[:, 0])]
+    else:
+        groups = [("norm_c %r: " % float(np.uint32(nw).view(np.float32)), case.words[case.words[:, 3] == nw, 0], out[case.words[:, 3] == nw, 0] & 255)
+                  for nw in np.unique(case.words[:case.n_edge, 3])]
+    for name, w, b in groups:
+        got = boundaries_reached(w, b) & set(range(255))
+        assert len(got) >= MIN_BOUNDARIES, "%s: %sboth sides of only %d of the 255 rounding boundaries occur" % (op, name, len(got))
+    return min(len(boundaries_reached(w, b) & set(range(255))) for _, w, b in groups)
+
+
+def _assert_picture_ends_coverage(op, outputs):
+    fl = lambda w: w.view(np.float32)
+    if op in ("resolve", "round_u32"):
+        (case, out), = outputs
+        assert_boundary_coverage(op, case, out)
+        edge = out[:case.n_edge, 0]
+        top = (edge == 0x00FFFFFF) if op == "resolve" else (edge == int(ki.ROUND_TOP))
+        assert top.any() and (edge == 0).any(), "%s: the two ends of the range must occur among the edges" % op
+    elif op == "camera_dir":
+        for case, out in outputs:
+            d = case.pdesc
+            pix, smp = case.words[:case.n_edge, 0], case.words[:case.n_edge, 1]
+            assert (pix == 0).any() and (pix == d["width"] * d["height"] - 1).any(), "camera: the first and the last pixel must occur"
+            first = out[:case.n_edge][pix == 0]
+            distinct = len({tuple(r) for r in first.tolist()})
+            assert (smp[pix == 0] >= 4).any() and distinct == (4 if d["aa_on"] else 1), "camera/%s: pixel 0 has %d distinct rays" % (case.label, distinct)
+            assert np.isfinite(fl(out)).all(), "camera/%s: a ray is not finite" % case.label
 
 
 def run_all(op, run):

@@ -5,6 +5,10 @@ hipcc for gfx950 with the product's flags (tests/device_kat, one item per lane) 
   * the independent Ada transcription (tests/ada_transcription.py) on the edge lists and the first 1000 random items, under the same rule.
 The inputs (tests/kat_inputs.py) sit where this arithmetic can go wrong: special-case exponents of apow one ulp either side, the k-rounding
 boundaries of sincos, denormal operands of sqrt and division, glass at the critical angle, det at the 1e-25 clamp of the triangle test.
+The last four ops are the two ends of a picture: camera_dir per pixel and sample (frames from 1x1 to 4096x2160, rotated and moved cameras,
+narrow and wide fields of view) and resolve_pixel / ada_round_u32 / colour_lum (NaN, infinities, negative sums, and for every byte the
+input at which it rises and its neighbours one ulp either side); camera_dir and the resolve are also held to float64 references
+(tests/test_device_kat_host.py assert_float64).
 A device / host difference means a build flag (-ffp-contract=off, correctly rounded divide / sqrt, denormals kept) is no longer honoured
 for that function, or an optimisation changed the operation order.  tests/test_device_kat_host.py is the CPU leg (transcription, mpmath)."""
 import numpy as np
@@ -13,6 +17,7 @@ import pytest
 import devkat
 import kat_inputs as ki
 import kat_refs
+import test_device_kat_host as host_leg
 
 pytestmark = pytest.mark.gpu
 
@@ -38,3 +43,4 @@ def test_device_build_equals_host_build_and_transcription(art, op):
     assert n_items > 0
     kat_refs.assert_matches_transcription(op, dev)
     kat_refs.assert_coverage(op, kat_refs.run_all(op, dev))
+    host_leg.assert_float64(op, dev)               # camera_dir, resolve: the float64 references, within twice the transcription's own deviation
