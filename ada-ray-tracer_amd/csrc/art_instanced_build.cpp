@@ -7,6 +7,8 @@
 #include <cstring>
 #include <utility>
 
+#include "art_tree_walk.h"
+
 namespace art {
 
 static bool invert_3x4(const float m[12], float out[12]) {     // world -> object in binary64, rounded once
@@ -184,9 +186,10 @@ bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vect
       if ((o.entry & 15) != 0 || transforms > 2.0e8) { closed.push_back(o); continue; }      // a leaf, or the budget is spent: stays as it is
       const float* nd = &T.blas_nodes[((size_t)R.node_base + (size_t)(o.entry >> 4)) * (size_t)node_floats(4)];
       for (int j = 0; j < 4; ++j) {
-        const int32_t rj = __builtin_bit_cast(int32_t, nd[4 * j + 3]);
+        int32_t rj, cj;
+        slot_words(nd, 4, j, rj, cj);
         if (rj < 0) continue;
-        Open c; c.inst = o.inst; c.entry = (rj << 4) | __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+        Open c; c.inst = o.inst; c.entry = (rj << 4) | cj;
         world_box(inst_m[(size_t)o.inst], [&](auto&& take) {       // the corners of every triangle below the child
           walk.assign(1, c.entry);
           while (!walk.empty()) {
@@ -200,8 +203,9 @@ bool build_two_level_host(const std::vector<InstMeshIn>& meshes, const std::vect
             } else {
               const float* n2 = &T.blas_nodes[((size_t)R.node_base + (size_t)(e >> 4)) * (size_t)node_floats(4)];
               for (int k = 0; k < 4; ++k) {
-                const int32_t rk = __builtin_bit_cast(int32_t, n2[4 * k + 3]);
-                if (rk >= 0) walk.push_back((rk << 4) | __builtin_bit_cast(int32_t, n2[16 + 4 * k + 3]));
+                int32_t rk, ck;
+                slot_words(n2, 4, k, rk, ck);
+                if (rk >= 0) walk.push_back((rk << 4) | ck);
               }
             }
           }
@@ -341,33 +345,16 @@ bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& e
   // (deepest level first)
   P.node_mesh.assign((size_t)n_blas, -1); P.blas_tight.assign(6 * (size_t)n_blas, 0.0f);
   P.blas_level_off.assign(1, 0); P.mesh_level_first.assign(1, 0);
+  TreeFault fault = TreeFault::none;
   {
-    std::vector<int32_t> cur, next;
-    for (size_t mi = 0; mi < nm; ++mi) {
-      cur.assign(1, P.mesh_base[3 * mi]); P.node_mesh[(size_t)P.mesh_base[3 * mi]] = (int32_t)mi;
-      while (!cur.empty()) {
-        next.clear();
-        for (const int32_t g : cur) {
-          const float* nd = &T.blas_nodes[(size_t)g * NF];
-          for (int j = 0; j < W; ++j) {
-            const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
-            if (ref < 0) continue;
-            if (cnt > 0) {
-              if (P.mesh_base[3 * mi + 1] >= 0 && (cnt > kMaxLeafTris || (int64_t)ref + cnt > mesh_recs[mi])) { err = "move plan: a leaf outside its mesh's records"; return false; }
-              continue;
-            }
-            const int64_t c = (int64_t)P.mesh_base[3 * mi] + ref;
-            if (ref >= mesh_nodes[mi] || P.node_mesh[(size_t)c] >= 0) { err = "move plan: a mesh's nodes do not form a tree"; return false; }
-            P.node_mesh[(size_t)c] = (int32_t)mi; next.push_back((int32_t)c);
-          }
-        }
-        P.blas_levels.insert(P.blas_levels.end(), cur.begin(), cur.end());
-        P.blas_level_off.push_back((int)P.blas_levels.size());
-        cur.swap(next);
-      }
+    for (size_t mi = 0; mi < nm && fault == TreeFault::none; ++mi) {          // (a mesh nobody shows has no records: its leaves are not bounded)
+      fault = walk_levels(T.blas_nodes.data(), W, P.mesh_base[3 * mi], mesh_nodes[mi], P.mesh_base[3 * mi + 1] >= 0 ? mesh_recs[mi] : -1, kMaxLeafTris,
+                          P.blas_levels, P.blas_level_off, [&](int32_t g) { P.node_mesh[(size_t)g] = (int32_t)mi; });
       P.mesh_level_first.push_back((int)P.blas_level_off.size() - 1);
     }
-    if ((int64_t)P.blas_levels.size() != n_blas) { err = "move plan: unreachable nodes in a mesh's tree"; return false; }
+    if (fault == TreeFault::none && (int64_t)P.blas_levels.size() != n_blas) fault = TreeFault::unreachable_nodes;      // (nodes before the first mesh's)
+    static const char* const wrong[] = {nullptr, "a leaf outside its mesh's records", "a mesh's nodes do not form a tree", "unreachable nodes in a mesh's tree"};
+    if (fault != TreeFault::none) { err = std::string("move plan: ") + wrong[(int)fault]; return false; }
     for (int L = (int)P.blas_level_off.size() - 2; L >= 0; --L)          // (a mesh's levels lie one after the other: deepest first inside every mesh)
       for (int k = P.blas_level_off[(size_t)L]; k < P.blas_level_off[(size_t)L + 1]; ++k) {
         const int32_t g = P.blas_levels[(size_t)k], mi = P.node_mesh[(size_t)g];
@@ -376,7 +363,8 @@ bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& e
         for (int a = 0; a < 3; ++a) { b[a] = INFINITY; b[a + 3] = -INFINITY; }
         if (P.mesh_base[3 * (size_t)mi + 1] < 0) continue;                       // (a mesh nobody shows is never re-padded)
         for (int j = 0; j < W; ++j) {
-          const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
+          int32_t ref, cnt;
+          slot_words(nd, W, j, ref, cnt);
           if (ref < 0) continue;
           if (cnt > 0) {
             for (int r = 0; r < cnt; ++r) {
@@ -412,8 +400,9 @@ bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& e
         if (ref < 0 || ref >= mesh_nodes[(size_t)R.mesh] || found.size() + walk.size() > (size_t)n_rec + (size_t)n_blas) { err = "move plan: an entry point outside its mesh's tree"; return false; }
         const float* nd = &T.blas_nodes[((size_t)R.node_base + (size_t)ref) * NF];
         for (int j = 0; j < W; ++j) {
-          const int32_t rj = __builtin_bit_cast(int32_t, nd[4 * j + 3]);
-          if (rj >= 0) walk.push_back((rj << 4) | __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]));
+          int32_t rj, cj;
+          slot_words(nd, W, j, rj, cj);
+          if (rj >= 0) walk.push_back((rj << 4) | cj);
         }
       }
       std::sort(found.begin(), found.end());
@@ -435,24 +424,9 @@ bool build_move_plan_host(const TwoLevelHost& T, MovePlanHost& P, std::string& e
     P.proxy_rec[(size_t)id] = (int32_t)r;
   }
   for (size_t e = 0; e < n_entry; ++e) if (P.proxy_rec[e] < 0) { err = "move plan: an entry point without a proxy"; return false; }
-  std::vector<uint8_t> seen((size_t)n_tlas, 0);
-  P.tlas_levels.assign(1, 0); P.tlas_level_off.assign(1, 0); seen[0] = 1;
-  for (size_t b = 0; b < P.tlas_levels.size();) {
-    const size_t e = P.tlas_levels.size();
-    for (size_t i = b; i < e; ++i) {
-      const float* nd = &T.tlas.nodes[(size_t)P.tlas_levels[i] * NF];
-      for (int j = 0; j < W; ++j) {
-        const int32_t ref = __builtin_bit_cast(int32_t, nd[4 * j + 3]), cnt = __builtin_bit_cast(int32_t, nd[16 + 4 * j + 3]);
-        if (ref < 0) continue;
-        if (cnt > 0) { if (cnt > kMaxLeafTris || (int64_t)ref + cnt > n_proxy) { err = "move plan: an instance tree leaf outside the proxies"; return false; } continue; }
-        if (ref >= n_tlas || seen[(size_t)ref]) { err = "move plan: the instance tree's nodes do not form a tree"; return false; }
-        seen[(size_t)ref] = 1; P.tlas_levels.push_back(ref);
-      }
-    }
-    P.tlas_level_off.push_back((int)e);
-    b = e;
-  }
-  if ((int64_t)P.tlas_levels.size() != n_tlas) { err = "move plan: unreachable nodes in the instance tree"; return false; }
+  static const char* const tlas_wrong[] = {nullptr, "an instance tree leaf outside the proxies", "the instance tree's nodes do not form a tree", "unreachable nodes in the instance tree"};
+  fault = walk_levels(T.tlas.nodes.data(), W, 0, n_tlas, n_proxy, kMaxLeafTris, P.tlas_levels, P.tlas_level_off, [](int32_t) {});
+  if (fault != TreeFault::none) { err = std::string("move plan: ") + tlas_wrong[(int)fault]; return false; }
   return true;
 }
 

@@ -14,24 +14,10 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "art_lbvh.h"
-#include "art_qnode.h"
+#include "art_gpu_build.h"
 
 namespace art {
 namespace {
-
-#define LB_TRY(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return false; } \
-  } while (0)
-
-__device__ __forceinline__ int enc(float f) { const int i = __float_as_int(f); return i >= 0 ? i : i ^ 0x7fffffff; }   // order-preserving
-__host__ __device__ __forceinline__ float dec(int i) { const int j = i >= 0 ? i : i ^ 0x7fffffff; return __builtin_bit_cast(float, j); }
 
 __global__ __launch_bounds__(256) void k_prep(const float* __restrict__ tri9, int n, float4* __restrict__ blo, float4* __restrict__ bhi, int* scene /*6 encoded*/) {
   __shared__ int s[6];
@@ -287,15 +273,13 @@ __global__ __launch_bounds__(128) void k_collapse(Lbvh T, const Item* __restrict
   const int stack_here = it.stack_before + nc - 1;
   atomicMax(max_stack, stack_here + 1);
   float* nd = nodes + (size_t)it.n8 * (size_t)node_floats(width);
-  const int hb = 4 * width;
   for (int j = 0; j < width; ++j) {
     int ref = -1, cnt = 0;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    float l[3] = {0, 0, 0}, h[3] = {0, 0, 0};
     if (j < nc) {
       const int id = ch[j];
       const float4 l4 = lo_of(id), h4 = hi_of(id);
-      const float l[3] = {l4.x, l4.y, l4.z}, h[3] = {h4.x, h4.y, h4.z};
-      pad_child_box(l, h, inflate_rel, inflate_abs, lo, hi);
+      l[0] = l4.x; l[1] = l4.y; l[2] = l4.z; h[0] = h4.x; h[1] = h4.y; h[2] = h4.z;
       const int c = count_of(id);
       if (c <= max_leaf) { ref = first_of(id); cnt = c; }
       else {
@@ -306,8 +290,7 @@ __global__ __launch_bounds__(128) void k_collapse(Lbvh T, const Item* __restrict
         } else { ref = -1; atomicExch(overflow, 1); }
       }
     }
-    nd[4 * j + 0] = lo[0]; nd[4 * j + 1] = lo[1]; nd[4 * j + 2] = lo[2]; nd[4 * j + 3] = __int_as_float(ref);
-    nd[hb + 4 * j + 0] = hi[0]; nd[hb + 4 * j + 1] = hi[1]; nd[hb + 4 * j + 2] = hi[2]; nd[hb + 4 * j + 3] = __int_as_float(cnt);
+    write_wide_slot(nd, width, j, j < nc, l, h, inflate_rel, inflate_abs, ref, cnt);
   }
 }
 
@@ -322,17 +305,6 @@ __global__ __launch_bounds__(256) void k_quantise_nodes(float* __restrict__ node
   for (int k = 0; k < 32; ++k) nodes[(size_t)i * 32 + k] = nd[k];
   qnodes[i] = q;
 }
-
-struct Scratch {
-  std::vector<void*> ptrs;
-  ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
-  template <typename T> bool get(T** p, size_t count, std::string& err) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { err = std::string("hipMalloc: ") + hipGetErrorString(e); return false; }
-    ptrs.push_back(q); *p = (T*)q; return true;
-  }
-};
 
 }  // namespace
 
@@ -352,21 +324,19 @@ bool build_bvh8_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hipSt
       !S.get(&parent, 2 * (size_t)n, err) || !S.get(&flag, n, err) || !S.get(&counters, 8, err) || !S.get(&child, n, err) || !S.get(&range, n, err) ||
       !S.get(&qa, n, err) || !S.get(&qb, n, err))
     return false;
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;   // released on every return path
-  LB_TRY(hipEventCreate(&ev.a)); LB_TRY(hipEventCreate(&ev.b));
-  const hipEvent_t e0 = ev.a, e1 = ev.b;
-  LB_TRY(hipEventRecord(e0, st));
+  BuildEvents ev;
+  if (!ev.start(st, err)) return false;
   const int h_scene[6] = {0x7fffffff, 0x7fffffff, 0x7fffffff, (int)0x80000000, (int)0x80000000, (int)0x80000000};
-  LB_TRY(hipMemcpyAsync(scene, h_scene, sizeof h_scene, hipMemcpyHostToDevice, st));
-  LB_TRY(hipMemsetAsync(flag, 0, (size_t)n * sizeof(int), st));
+  BUILD_TRY(hipMemcpyAsync(scene, h_scene, sizeof h_scene, hipMemcpyHostToDevice, st));
+  BUILD_TRY(hipMemsetAsync(flag, 0, (size_t)n * sizeof(int), st));
   const int nb = (n + 255) / 256;
   hipLaunchKernelGGL(k_prep, dim3(nb), dim3(256), 0, st, d_tri9, n, blo, bhi, scene);
   hipLaunchKernelGGL(k_morton, dim3(nb), dim3(256), 0, st, blo, bhi, n, scene, keys, vals);
   size_t tmp_bytes = 0;
-  LB_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, n, 0, 30, st));
+  BUILD_TRY(hipcub::DeviceRadixSort::SortPairs(nullptr, tmp_bytes, keys, keys2, vals, vals2, n, 0, 30, st));
   void* tmp = nullptr;
   if (!S.get((char**)&tmp, tmp_bytes, err)) return false;
-  LB_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys2, vals, vals2, n, 0, 30, st));
+  BUILD_TRY(hipcub::DeviceRadixSort::SortPairs(tmp, tmp_bytes, keys, keys2, vals, vals2, n, 0, 30, st));
   hipLaunchKernelGGL(k_gather_boxes, dim3(nb), dim3(256), 0, st, blo, bhi, vals2, n, llo, lhi);
   Lbvh T; T.n = n; T.keys = keys2; T.child = child; T.parent = parent; T.range = range; T.nlo = nlo; T.nhi = nhi; T.llo = llo; T.lhi = lhi; T.flag = flag;
   const uint32_t* tri_order = vals2;          // triangle of every leaf position
@@ -379,10 +349,10 @@ bool build_bvh8_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hipSt
         !S.get(&llo2, n, err) || !S.get(&lhi2, n, err) || !S.get(&order2, n, err))
       return false;
     size_t scan_bytes = 0;
-    LB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep, pos, n, st));
+    BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, scan_bytes, keep, pos, n, st));
     void* scan_tmp = nullptr;
     if (!S.get((char**)&scan_tmp, scan_bytes, err)) return false;
-    LB_TRY(hipMemsetAsync(parent, 0xff, 2 * (size_t)n * sizeof(int), st));          // -1: no parent (the root keeps it)
+    BUILD_TRY(hipMemsetAsync(parent, 0xff, 2 * (size_t)n * sizeof(int), st));          // -1: no parent (the root keeps it)
     PlocOut O; O.child = child; O.parent = parent; O.count = count; O.nlo = nlo; O.nhi = nhi; O.n = n;
     hipLaunchKernelGGL(k_ploc_init, dim3(nb), dim3(256), 0, st, n, llo, lhi, cid, clo, chi);
     const int radius = std::max(1, prm.ploc_radius);
@@ -391,11 +361,11 @@ bool build_bvh8_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hipSt
       const int mb = (m + 255) / 256;
       hipLaunchKernelGGL(k_ploc_nn, dim3(mb), dim3(256), 0, st, m, radius, clo, chi, nn);
       hipLaunchKernelGGL(k_ploc_keep, dim3(mb), dim3(256), 0, st, m, nn, keep);
-      LB_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, keep, pos, m, st));
+      BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(scan_tmp, scan_bytes, keep, pos, m, st));
       int last[2];
-      LB_TRY(hipMemcpyAsync(&last[0], pos + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      LB_TRY(hipMemcpyAsync(&last[1], keep + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-      LB_TRY(hipStreamSynchronize(st));
+      BUILD_TRY(hipMemcpyAsync(&last[0], pos + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+      BUILD_TRY(hipMemcpyAsync(&last[1], keep + (m - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+      BUILD_TRY(hipStreamSynchronize(st));
       const int m_new = last[0] + last[1];
       if (m_new >= m || m_new < 1) { err = "internal: PLOC round made no progress"; return false; }   // the closest pair is always mutual
       hipLaunchKernelGGL(k_ploc_merge, dim3(mb), dim3(256), 0, st, m, base, nn, keep, pos, cid, clo, chi, cid2, clo2, chi2, O);
@@ -415,41 +385,32 @@ bool build_bvh8_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hipSt
   }
   // triangle records in leaf order
   const size_t tri_bytes = (size_t)n * kTriFloats * sizeof(float);
-  LB_TRY(hipMalloc(&out.tris, tri_bytes));
+  BUILD_TRY(hipMalloc(&out.tris, tri_bytes));
   hipLaunchKernelGGL(k_emit_tris, dim3(nb), dim3(256), 0, st, d_tri9, tri_order, n, out.tris);
   // collapse, one launch per level of the wide tree.  Every wide node opens at least one inner node of the binary tree (n - 1 of them), so
   // at most n - 1 wide nodes can appear; with max_leaf = 1 a balanced tree really needs ~2n/3 (n/2 + 2 was too small: ADVICE r1).
   const size_t node_cap = (size_t)n;
-  LB_TRY(hipMalloc(&out.nodes, node_cap * (size_t)node_floats(prm.width) * sizeof(float)));
+  BUILD_TRY(hipMalloc(&out.nodes, node_cap * (size_t)node_floats(prm.width) * sizeof(float)));
   const int h_cnt[4] = {0, 1, 1, 0};    // [0] next-queue length, [1] node count (root = 0 taken), [2] max stack, [3] node capacity overflow
-  LB_TRY(hipMemcpyAsync(counters, h_cnt, sizeof h_cnt, hipMemcpyHostToDevice, st));
+  BUILD_TRY(hipMemcpyAsync(counters, h_cnt, sizeof h_cnt, hipMemcpyHostToDevice, st));
   const Item root = {root_id, 0, 0};
-  LB_TRY(hipMemcpyAsync(qa, &root, sizeof root, hipMemcpyHostToDevice, st));
+  BUILD_TRY(hipMemcpyAsync(qa, &root, sizeof root, hipMemcpyHostToDevice, st));
   int n_in = 1, levels = 0;
   Item *in = qa, *nx = qb;
   while (n_in > 0) {
     hipLaunchKernelGGL(k_collapse, dim3((n_in + 127) / 128), dim3(128), 0, st, T, in, n_in, nx, counters, counters + 1, counters + 2, counters + 3, (int)node_cap,
                        out.nodes, prm.width, max_leaf, prm.inflate_rel, prm.inflate_abs);
     int h[4];
-    LB_TRY(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, st));
-    LB_TRY(hipStreamSynchronize(st));
+    BUILD_TRY(hipMemcpyAsync(h, counters, sizeof h, hipMemcpyDeviceToHost, st));
+    BUILD_TRY(hipStreamSynchronize(st));
     n_in = h[0]; out.n_nodes = h[1]; out.max_stack = h[2];
     if (h[3] != 0 || (size_t)out.n_nodes > node_cap) { err = "internal: LBVH node capacity exceeded"; return false; }
-    LB_TRY(hipMemsetAsync(counters, 0, sizeof(int), st));
+    BUILD_TRY(hipMemsetAsync(counters, 0, sizeof(int), st));
     std::swap(in, nx);
     if (++levels > 64) { err = "internal: LBVH collapse did not terminate"; return false; }
   }
-  if (prm.width == 4 && prm.quantise) {
-    LB_TRY(hipMalloc(&out.qnodes, (size_t)out.n_nodes * kQNodeBytes));
-    launch_quantise_nodes(st, out.nodes, out.n_nodes, out.qnodes);
-  }
-  LB_TRY(hipEventRecord(e1, st));
-  LB_TRY(hipEventSynchronize(e1));
-  float ms = 0.0f;
-  LB_TRY(hipEventElapsedTime(&ms, e0, e1));
-  LB_TRY(hipGetLastError());
-  out.n_tris = n; out.build_ms = ms; if (prm.builder != 2) out.levels = levels;
-  return true;
+  if (prm.builder != 2) out.levels = levels;
+  return finish_gpu_build(prm, st, ev, n, out, err);
 }
 
 }  // namespace art

@@ -6,9 +6,10 @@
 // (1 to kMaxLeafTris records); tests/renumber_check.cpp tests it on the CPU.
 #pragma once
 #include <cstdint>
-#include <cstring>
 #include <string>
 #include <vector>
+
+#include "art_tree_walk.h"
 
 namespace art {
 
@@ -18,42 +19,31 @@ namespace art {
 inline bool renumber_built_tree(const float* nodes, int64_t N, int64_t n_recs, int max_leaf, const std::string& what, std::vector<int32_t>& node_map,
                                 std::vector<int32_t>& rec_map, std::vector<int32_t>& levels, std::vector<int>& level_off, std::string& err) {
   if (N < 1 || N > 0x7fffffff || n_recs < 0 || n_recs > 0x7fffffff) { err = "the built " + what + " is empty or too large"; return false; }
+  levels.clear(); level_off.clear();                                       // (walked in the builder's numbers; the levels hold the new ones below)
+  const TreeFault fault = walk_levels(nodes, 4, 0, N, n_recs, max_leaf, levels, level_off, [](int32_t) {});
+  if (fault == TreeFault::leaf_outside_records) { err = "the built " + what + " has a leaf outside its records"; return false; }
+  if (fault == TreeFault::child_out_of_range_or_twice) { err = "the built " + what + "'s nodes do not form a tree"; return false; }
+  if (fault == TreeFault::unreachable_nodes) { err = "unreachable nodes in the built " + what; return false; }
   node_map.assign((size_t)N, -1); rec_map.assign((size_t)n_recs, -1);
-  auto words = [&](int32_t n, int j, int32_t& ref, int32_t& cnt) { std::memcpy(&ref, &nodes[(size_t)n * 32 + 4 * j + 3], 4); std::memcpy(&cnt, &nodes[(size_t)n * 32 + 16 + 4 * j + 3], 4); };
   std::vector<int32_t> todo(1, 0);
-  int64_t next_node = 1, next_rec = 0;
+  int32_t next_node = 1, next_rec = 0;
   node_map[0] = 0;
-  while (!todo.empty()) {
+  while (!todo.empty()) {                                                  // (a tree, and every leaf inside the records: the walk has checked it)
     const int32_t n = todo.back(); todo.pop_back();
     for (int j = 0; j < 4; ++j) {
       int32_t ref, cnt;
-      words(n, j, ref, cnt);
+      slot_words(nodes + (size_t)n * 32, 4, j, ref, cnt);
       if (ref < 0) continue;
-      if (cnt != 0) {
-        if (cnt < 1 || cnt > max_leaf || (int64_t)ref + cnt > n_recs) { err = "the built " + what + " has a leaf outside its records"; return false; }
-        for (int32_t r = 0; r < cnt; ++r) {
-          if (rec_map[(size_t)ref + (size_t)r] >= 0) { err = "a record of the built " + what + " is named twice"; return false; }
-          rec_map[(size_t)ref + (size_t)r] = (int32_t)next_rec++;
-        }
-        continue;
+      if (cnt < 0) { err = "the built " + what + " has a leaf outside its records"; return false; }
+      if (cnt == 0) { node_map[(size_t)ref] = next_node++; todo.push_back(ref); continue; }
+      for (int32_t r = 0; r < cnt; ++r) {
+        if (rec_map[(size_t)ref + (size_t)r] >= 0) { err = "a record of the built " + what + " is named twice"; return false; }
+        rec_map[(size_t)ref + (size_t)r] = next_rec++;
       }
-      if (ref >= N || node_map[(size_t)ref] >= 0) { err = "the built " + what + "'s nodes do not form a tree"; return false; }
-      node_map[(size_t)ref] = (int32_t)next_node++; todo.push_back(ref);
     }
   }
-  if (next_node != N) { err = "unreachable nodes in the built " + what; return false; }
   if (next_rec != n_recs) { err = "a record without a leaf in the built " + what; return false; }
-  std::vector<int32_t> cur(1, 0), next;                                    // (the builder's numbers; the levels hold the new ones)
-  levels.clear(); level_off.assign(1, 0);
-  while (!cur.empty()) {
-    next.clear();
-    for (const int32_t n : cur) {
-      levels.push_back(node_map[(size_t)n]);
-      for (int j = 0; j < 4; ++j) { int32_t ref, cnt; words(n, j, ref, cnt); if (ref >= 0 && cnt == 0) next.push_back(ref); }
-    }
-    level_off.push_back((int)levels.size());
-    cur.swap(next);
-  }
+  for (int32_t& n : levels) n = node_map[(size_t)n];
   return true;
 }
 

@@ -25,32 +25,15 @@
 #include <hip/hip_runtime.h>
 #include <hipcub/hipcub.hpp>
 
-#include <algorithm>
-#include <string>
-#include <vector>
-
-#include "art_lbvh.h"
-#include "art_qnode.h"
+#include "art_gpu_build.h"
 
 namespace art {
 namespace {
-
-#define SB_TRY(expr)                                                                          \
-  do {                                                                                        \
-    hipError_t _e = (expr);                                                                   \
-    if (_e != hipSuccess) { err = std::string(#expr) + ": " + hipGetErrorString(_e); return false; } \
-  } while (0)
 
 constexpr int kChunk = 2048;              // references per chunk workgroup (256 threads x 8); a node with more references is "big"
 constexpr int kRounds = kChunk / 256;
 constexpr int kBinWords = 8;              // per bin: lo.xyz, hi.xyz (encoded), count, pad
 constexpr int kMaxBins = 64;
-
-// order-preserving float <-> int (min / max of encodings = min / max of the floats; -0 sorts below +0, which no result depends on)
-__host__ __device__ __forceinline__ int enc(float f) { const int i = __builtin_bit_cast(int, f); return i >= 0 ? i : i ^ 0x7fffffff; }
-__host__ __device__ __forceinline__ float dec(int i) { return __builtin_bit_cast(float, i >= 0 ? i : i ^ 0x7fffffff); }
-constexpr int kEncPosInf = 0x7f800000;            // enc(+inf): identity of a minimum
-constexpr int kEncNegInf = (int)0x807fffffu;      // enc(-inf): identity of a maximum
 
 struct SahCost { int nb, max_leaf, max_depth, width; float node_cost, leaf_base, tri_cost; };
 __device__ __forceinline__ float leaf_cost(const SahCost& P, int n) { return P.leaf_base + P.tri_cost * (float)n; }   // BvhBuildParams::leaf_cost
@@ -489,16 +472,14 @@ __global__ __launch_bounds__(128) void k_col_emit(Nodes N, const Item* __restric
   const int stack_here = it.stack_before + K.nc - 1;
   atomicMax(max_stack, stack_here + 1);
   float* nd = nodes + (size_t)it.n8 * (size_t)node_floats(width);
-  const int hb = 4 * width;
   int inner_k = 0;
   for (int j = 0; j < width; ++j) {
     int ref = -1, cnt = 0;
-    float lo[3] = {0, 0, 0}, hi[3] = {0, 0, 0};
+    float l[3] = {0, 0, 0}, h[3] = {0, 0, 0};
     if (j < K.nc) {
       const int id = K.ch[j];
       const int4 l4 = N.blo[id], h4 = N.bhi[id];
-      const float l[3] = {dec(l4.x), dec(l4.y), dec(l4.z)}, h[3] = {dec(h4.x), dec(h4.y), dec(h4.z)};
-      pad_child_box(l, h, inflate_rel, inflate_abs, lo, hi);
+      l[0] = dec(l4.x); l[1] = dec(l4.y); l[2] = dec(l4.z); h[0] = dec(h4.x); h[1] = dec(h4.y); h[2] = dec(h4.z);
       if (N.child[id].x < 0) { ref = l4.w; cnt = h4.w; }                           // leaf: first reference position = first triangle record
       else {
         const int slot = off[q] + inner_k; ++inner_k;
@@ -507,21 +488,9 @@ __global__ __launch_bounds__(128) void k_col_emit(Nodes N, const Item* __restric
         next_items[slot] = nx;
       }
     }
-    nd[4 * j + 0] = lo[0]; nd[4 * j + 1] = lo[1]; nd[4 * j + 2] = lo[2]; nd[4 * j + 3] = __int_as_float(ref);
-    nd[hb + 4 * j + 0] = hi[0]; nd[hb + 4 * j + 1] = hi[1]; nd[hb + 4 * j + 2] = hi[2]; nd[hb + 4 * j + 3] = __int_as_float(cnt);
+    write_wide_slot(nd, width, j, j < K.nc, l, h, inflate_rel, inflate_abs, ref, cnt);
   }
 }
-
-struct Scratch {
-  std::vector<void*> ptrs;
-  ~Scratch() { for (void* p : ptrs) (void)hipFree(p); }
-  template <typename T> bool get(T** p, size_t count, std::string& err) {
-    void* q = nullptr;
-    hipError_t e = hipMalloc(&q, std::max<size_t>(count, 1) * sizeof(T));
-    if (e != hipSuccess) { err = std::string("hipMalloc: ") + hipGetErrorString(e); return false; }
-    ptrs.push_back(q); *p = (T*)q; return true;
-  }
-};
 
 }  // namespace
 
@@ -548,30 +517,29 @@ bool build_bvh_sah_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hi
       !S.get(&items[0], n, err) || !S.get(&items[1], n, err) || !S.get(&kids, n, err) || !S.get(&n_inner, n, err) || !S.get(&inner_off, n, err))
     return false;
   size_t tmp_a = 0, tmp_b = 0;
-  SB_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tmp_a, flags, offs, S4Sum(), S4{0, 0, 0, 0}, (int)max_active, st));
-  SB_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, n_inner, inner_off, n, st));
+  BUILD_TRY(hipcub::DeviceScan::ExclusiveScan(nullptr, tmp_a, flags, offs, S4Sum(), S4{0, 0, 0, 0}, (int)max_active, st));
+  BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(nullptr, tmp_b, n_inner, inner_off, n, st));
   void* tmp = nullptr;
   const size_t tmp_bytes = std::max(tmp_a, tmp_b);
   if (!S.get((char**)&tmp, tmp_bytes, err)) return false;
 
-  struct Events { hipEvent_t a = nullptr, b = nullptr; ~Events() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); } } ev;
-  SB_TRY(hipEventCreate(&ev.a)); SB_TRY(hipEventCreate(&ev.b));
-  SB_TRY(hipEventRecord(ev.a, st));
+  BuildEvents ev;
+  if (!ev.start(st, err)) return false;
 
   // root
   {
     const int4 h_root[4] = {{kEncPosInf, kEncPosInf, kEncPosInf, 0}, {kEncNegInf, kEncNegInf, kEncNegInf, n}, {kEncPosInf, kEncPosInf, kEncPosInf, 0}, {kEncNegInf, kEncNegInf, kEncNegInf, 0}};
-    SB_TRY(hipMemcpyAsync(N.blo, &h_root[0], sizeof(int4), hipMemcpyHostToDevice, st)); SB_TRY(hipMemcpyAsync(N.bhi, &h_root[1], sizeof(int4), hipMemcpyHostToDevice, st));
-    SB_TRY(hipMemcpyAsync(N.clo, &h_root[2], sizeof(int4), hipMemcpyHostToDevice, st)); SB_TRY(hipMemcpyAsync(N.chi, &h_root[3], sizeof(int4), hipMemcpyHostToDevice, st));
-    SB_TRY(hipMemsetAsync(misc, 0, 8 * sizeof(int), st));
+    BUILD_TRY(hipMemcpyAsync(N.blo, &h_root[0], sizeof(int4), hipMemcpyHostToDevice, st)); BUILD_TRY(hipMemcpyAsync(N.bhi, &h_root[1], sizeof(int4), hipMemcpyHostToDevice, st));
+    BUILD_TRY(hipMemcpyAsync(N.clo, &h_root[2], sizeof(int4), hipMemcpyHostToDevice, st)); BUILD_TRY(hipMemcpyAsync(N.chi, &h_root[3], sizeof(int4), hipMemcpyHostToDevice, st));
+    BUILD_TRY(hipMemsetAsync(misc, 0, 8 * sizeof(int), st));
     hipLaunchKernelGGL(k_refs, dim3((n + 255) / 256), dim3(256), 0, st, d_tri9, n, rlo[0], rhi[0], N, misc);
     Act a0; a0.node = 0; a0.big_slot = (n > kChunk) ? 0 : -1; a0.chunk0 = (n > kChunk) ? 0 : -1; a0.pad = 0;
-    SB_TRY(hipMemcpyAsync(act[0], &a0, sizeof a0, hipMemcpyHostToDevice, st));
+    BUILD_TRY(hipMemcpyAsync(act[0], &a0, sizeof a0, hipMemcpyHostToDevice, st));
     if (n > kChunk) {
       std::vector<int2> c0((size_t)(n + kChunk - 1) / kChunk);
       for (size_t k = 0; k < c0.size(); ++k) c0[k] = make_int2(0, (int)k);
-      SB_TRY(hipMemcpyAsync(chunk[0], c0.data(), c0.size() * sizeof(int2), hipMemcpyHostToDevice, st));
-      SB_TRY(hipStreamSynchronize(st));                                            // c0 is a local
+      BUILD_TRY(hipMemcpyAsync(chunk[0], c0.data(), c0.size() * sizeof(int2), hipMemcpyHostToDevice, st));
+      BUILD_TRY(hipStreamSynchronize(st));                                            // c0 is a local
     }
   }
   int m = 1, n_chunks = (n > kChunk) ? (n + kChunk - 1) / kChunk : 0, n_big = (n > kChunk) ? 1 : 0, n_nodes2 = 1, level = 0;
@@ -591,18 +559,18 @@ bool build_bvh_sah_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hi
     }
     hipLaunchKernelGGL(k_eval, dim3((m + 3) / 4), dim3(256), eval_lds, st, A, m);
     size_t tb = tmp_bytes;
-    SB_TRY(hipcub::DeviceScan::ExclusiveScan(tmp, tb, flags, offs, S4Sum(), S4{0, 0, 0, 0}, m, st));
+    BUILD_TRY(hipcub::DeviceScan::ExclusiveScan(tmp, tb, flags, offs, S4Sum(), S4{0, 0, 0, 0}, m, st));
     hipLaunchKernelGGL(k_commit, dim3((m + 255) / 256), dim3(256), 0, st, A, m);
     if (n_chunks > 0) {
       hipLaunchKernelGGL(k_part_count, dim3(n_chunks), dim3(256), 0, st, A);
       tb = tmp_bytes;
-      SB_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, chunk_cnt, chunk_off, n_chunks, st));
+      BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, chunk_cnt, chunk_off, n_chunks, st));
       hipLaunchKernelGGL(k_part_write, dim3(n_chunks), dim3(256), 0, st, A);
     }
     S4 t; int h_misc[8];
-    SB_TRY(hipMemcpyAsync(&t, totals, sizeof t, hipMemcpyDeviceToHost, st));
-    SB_TRY(hipMemcpyAsync(h_misc, misc, sizeof h_misc, hipMemcpyDeviceToHost, st));      // the error words travel with every level's round trip
-    SB_TRY(hipStreamSynchronize(st));
+    BUILD_TRY(hipMemcpyAsync(&t, totals, sizeof t, hipMemcpyDeviceToHost, st));
+    BUILD_TRY(hipMemcpyAsync(h_misc, misc, sizeof h_misc, hipMemcpyDeviceToHost, st));      // the error words travel with every level's round trip
+    BUILD_TRY(hipStreamSynchronize(st));
     if (h_misc[0]) { err = "non-finite triangle vertex, or a coordinate beyond 1e18 (box extents and the node quantisation need headroom in binary32)"; return false; }
     if (h_misc[2]) { err = "internal: GPU SAH partition does not match its bins"; return false; }
     n_nodes2 += 2 * t.s; m = t.a; n_chunks = t.c; n_big = t.b;
@@ -610,28 +578,28 @@ bool build_bvh_sah_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hi
     if (++level > 4096) { err = "internal: GPU SAH build did not terminate"; return false; }
   }
   // triangle records: position p of the final reference order
-  SB_TRY(hipMalloc(&out.tris, (size_t)n * kTriFloats * sizeof(float)));
+  BUILD_TRY(hipMalloc(&out.tris, (size_t)n * kTriFloats * sizeof(float)));
   hipLaunchKernelGGL(k_emit_tris, dim3((n_nodes2 + 255) / 256), dim3(256), 0, st, N, n_nodes2, rlo[0], rlo[1], d_tri9, out.tris);
   // collapse.  Every wide node opens at least one inner BVH2 node, so there are at most n - 1 of them.
   const size_t node_cap = (size_t)n;
-  SB_TRY(hipMalloc(&out.nodes, node_cap * (size_t)node_floats(prm.width) * sizeof(float)));
+  BUILD_TRY(hipMalloc(&out.nodes, node_cap * (size_t)node_floats(prm.width) * sizeof(float)));
   const Item root = {0, 0, 0, 0};
-  SB_TRY(hipMemcpyAsync(items[0], &root, sizeof root, hipMemcpyHostToDevice, st));
+  BUILD_TRY(hipMemcpyAsync(items[0], &root, sizeof root, hipMemcpyHostToDevice, st));
   int* max_stack = misc + 1;
   const int one = 1;
-  SB_TRY(hipMemcpyAsync(max_stack, &one, sizeof one, hipMemcpyHostToDevice, st));
+  BUILD_TRY(hipMemcpyAsync(max_stack, &one, sizeof one, hipMemcpyHostToDevice, st));
   int n_items = 1, n_wide = 1, wlevels = 0;
   while (n_items > 0) {
     const int cur = wlevels & 1;
     hipLaunchKernelGGL(k_col_pick, dim3((n_items + 127) / 128), dim3(128), 0, st, N, items[cur], n_items, prm.width, kids, n_inner);
     size_t tb = tmp_bytes;
-    SB_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, n_inner, inner_off, n_items, st));
+    BUILD_TRY(hipcub::DeviceScan::ExclusiveSum(tmp, tb, n_inner, inner_off, n_items, st));
     hipLaunchKernelGGL(k_col_emit, dim3((n_items + 127) / 128), dim3(128), 0, st, N, items[cur], n_items, prm.width, kids, inner_off, n_wide, items[cur ^ 1], max_stack,
                        out.nodes, prm.inflate_rel, prm.inflate_abs);
     int last[2];
-    SB_TRY(hipMemcpyAsync(&last[0], inner_off + (n_items - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    SB_TRY(hipMemcpyAsync(&last[1], n_inner + (n_items - 1), sizeof(int), hipMemcpyDeviceToHost, st));
-    SB_TRY(hipStreamSynchronize(st));
+    BUILD_TRY(hipMemcpyAsync(&last[0], inner_off + (n_items - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    BUILD_TRY(hipMemcpyAsync(&last[1], n_inner + (n_items - 1), sizeof(int), hipMemcpyDeviceToHost, st));
+    BUILD_TRY(hipStreamSynchronize(st));
     n_items = last[0] + last[1];
     n_wide += n_items;
     if ((size_t)n_wide > node_cap) { err = "internal: GPU SAH wide-node count out of bounds"; return false; }   // checked before the next level writes
@@ -640,21 +608,12 @@ bool build_bvh_sah_gpu(const float* d_tri9, int n, const BvhBuildParams& prm, hi
   out.n_nodes = n_wide;
   {
     int h_ms = 1;
-    SB_TRY(hipMemcpyAsync(&h_ms, max_stack, sizeof(int), hipMemcpyDeviceToHost, st));
-    SB_TRY(hipStreamSynchronize(st));
+    BUILD_TRY(hipMemcpyAsync(&h_ms, max_stack, sizeof(int), hipMemcpyDeviceToHost, st));
+    BUILD_TRY(hipStreamSynchronize(st));
     out.max_stack = h_ms;
   }
-  if (prm.width == 4 && prm.quantise) {
-    SB_TRY(hipMalloc(&out.qnodes, (size_t)out.n_nodes * kQNodeBytes));
-    launch_quantise_nodes(st, out.nodes, out.n_nodes, out.qnodes);
-  }
-  SB_TRY(hipEventRecord(ev.b, st));
-  SB_TRY(hipEventSynchronize(ev.b));
-  float ms = 0.0f;
-  SB_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-  SB_TRY(hipGetLastError());
-  out.n_tris = n; out.build_ms = ms; out.levels = level;
-  return true;
+  out.levels = level;
+  return finish_gpu_build(prm, st, ev, n, out, err);
 }
 
 }  // namespace art

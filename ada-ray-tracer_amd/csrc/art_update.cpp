@@ -183,30 +183,11 @@ static int build_refit_plan(const HostScene& hs) {
   std::vector<float> nodes((size_t)N * NF);
   HIP_TRY(hipStreamSynchronize(c.stream));
   HIP_TRY(hipMemcpy(nodes.data(), c.b_nodes.p, nodes.size() * 4, hipMemcpyDeviceToHost));
-  std::vector<int32_t> order;
-  order.reserve((size_t)N);
-  order.push_back(0);
-  R.level_off.assign(1, 0);
-  for (size_t b = 0; b < order.size();) {                       // breadth first: level L = order[level_off[L] .. level_off[L + 1])
-    const size_t e = order.size();
-    for (size_t i = b; i < e; ++i) {
-      const float* nd = &nodes[(size_t)order[i] * NF];
-      for (int j = 0; j < W; ++j) {
-        int32_t ref, cnt;
-        std::memcpy(&ref, nd + 4 * j + 3, 4); std::memcpy(&cnt, nd + 4 * W + 4 * j + 3, 4);
-        if (ref < 0) continue;
-        if (cnt > 0) {
-          if (cnt > kMaxLeafTris || (int64_t)ref + cnt > (int64_t)c.scene.n_tris) return fail("art_refit_device: internal: a leaf outside the triangle records");
-          continue;
-        }
-        if (ref >= N || order.size() >= (size_t)N) return fail("art_refit_device: internal: the uploaded nodes do not form a tree");
-        order.push_back(ref);
-      }
-    }
-    R.level_off.push_back((int)e);
-    b = e;
-  }
-  if (order.size() != (size_t)N) return fail("art_refit_device: internal: unreachable nodes in the uploaded tree");
+  std::vector<int32_t> order;                                   // breadth first: level L = order[level_off[L] .. level_off[L + 1])
+  R.level_off.clear();
+  static const char* const wrong[] = {nullptr, "a leaf outside the triangle records", "the uploaded nodes do not form a tree", "unreachable nodes in the uploaded tree"};
+  const TreeFault fault = walk_levels(nodes.data(), W, 0, N, c.scene.n_tris, kMaxLeafTris, order, R.level_off, [](int32_t) {});
+  if (fault != TreeFault::none) return fail(std::string("art_refit_device: internal: ") + wrong[(int)fault]);
   if (upload(R.b_idx, hs.m_idx) || upload(R.b_levels, order) || ensure(R.b_tight, (size_t)N * 6 * sizeof(float)) || ensure(R.b_bad, 2 * sizeof(unsigned long long)))
     return 1;
   HIP_TRY(hipMemset(R.b_bad.p, 0, 2 * sizeof(unsigned long long)));
@@ -282,6 +263,13 @@ struct PlanImage {
   int upload_to(DevBuf& b) const { return upload(b, img); }
 };
 
+// a context's arrays in HBM have the sizes of the two-level build the host keeps (build_move_plan, export_two_level)
+static bool arrays_are_the_kept_builds(const Ctx& c, const TwoLevelHost& T) {
+  const size_t n_entry = T.entry.size(), n_tlas = (size_t)T.tlas.n_nodes, n_blas = T.blas_nodes.size() / 32;
+  return c.b_inst.bytes == n_entry * sizeof(DevInstance) && c.b_qnodes.bytes == (n_tlas + n_blas) * kQNodeBytes && c.b_tlas_nodes.bytes == n_tlas * 128 &&
+         c.b_blas_nodes.bytes == n_blas * 128 && c.b_tlas_tris.bytes == n_entry * kTriBytes && c.b_blas_tris.bytes == T.blas_tris.size() * 4;
+}
+
 // The plan of the current context, from the two-level build the upload kept and before either call has changed anything: MovePlanHost's
 // constant arrays and the meshes' index triples in one buffer, what the kernels maintain in another (the tight boxes, the meshes' boxes
 // and pads, the matrices in force), and MoveArgs pointing into both and into the scene's arrays.  `call` builds it; its info takes the time.
@@ -293,9 +281,7 @@ static int build_move_plan(const HostScene& hs, const std::string& call, double&
   std::string err;
   if (!build_move_plan_host(hs.two, H, err)) return fail(call + ": " + err);
   const size_t n_entry = hs.two.entry.size(), n_inst = hs.two.inst.size(), nm = (size_t)H.n_mesh, n_tlas = (size_t)hs.two.tlas.n_nodes, n_blas = H.node_mesh.size();
-  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
-      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != hs.two.blas_tris.size() * 4)
-    return fail(call + ": internal: the arrays in HBM are not the kept build's");
+  if (!arrays_are_the_kept_builds(c, hs.two)) return fail(call + ": internal: the arrays in HBM are not the kept build's");
   if (hs.inst.size() != n_entry || hs.mesh_nverts.size() != nm || hs.mesh_idx_off.size() != nm + 1 || c.b_qtris.bytes != hs.two.blas_tris.size() / kTriFloats * (size_t)kQTriBytes)
     return fail(call + ": internal: the host scene is not the kept build's");
   PlanImage img, work;                                                     // the constant arrays | what the kernels maintain
@@ -510,9 +496,7 @@ int export_two_level(ArtTwoLevelInfo* info, const ArtTwoLevelBuffers* buf) {
   const TwoLevelHost& T = hs.two;
   const size_t n_entry = T.entry.size(), n_inst = T.inst.size(), nm = T.mesh_pad_abs.size(), n_tlas = (size_t)T.tlas.n_nodes;
   const size_t n_blas = T.blas_nodes.size() / 32, n_rec = T.blas_tris.size() / kTriFloats;
-  if (c.b_inst.bytes != n_entry * sizeof(DevInstance) || c.b_qnodes.bytes != (n_tlas + n_blas) * kQNodeBytes || c.b_tlas_nodes.bytes != n_tlas * 128 ||
-      c.b_blas_nodes.bytes != n_blas * 128 || c.b_tlas_tris.bytes != n_entry * kTriBytes || c.b_blas_tris.bytes != n_rec * kTriBytes)
-    return fail(name + ": internal: the arrays in HBM are not the kept build's");
+  if (!arrays_are_the_kept_builds(c, T)) return fail(name + ": internal: the arrays in HBM are not the kept build's");
   const Ctx::MovePlan& P = c.move;
   std::memset(info, 0, sizeof *info);
   info->n_inst = (int32_t)n_inst; info->n_entry = (int32_t)n_entry; info->n_mesh = (int32_t)nm; info->n_tlas_nodes = (int32_t)n_tlas;

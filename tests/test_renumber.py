@@ -8,15 +8,24 @@ import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "..", "ada-ray-tracer_amd", "csrc")
-COMMON = ["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I", os.path.join(HERE, "..", "include"),
-          os.path.join(HERE, "renumber_check.cpp"), os.path.join(CSRC, "art_bvh.cpp"), "-lpthread"]
+COMMON = ["g++", "-std=c++17", "-Wall", "-Werror", "-Wno-unknown-pragmas", "-ffp-contract=off", "-I", os.path.join(HERE, "..", "include")]
+FLAGS = [["-O2"], ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined", "-static-libasan", "-static-libubsan"]]
 
 
-@pytest.mark.parametrize("flags", [["-O2"], ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined",
-                                             "-static-libasan", "-static-libubsan"]], ids=["plain", "sanitizers"])
-def test_renumbering_gives_the_host_builders_tree(tmp_path, flags):
-    exe = str(tmp_path / "renumber_check")
-    subprocess.check_call(COMMON + flags + ["-o", exe])
+def build_and_run(tmp_path, flags, sources, says):
+    exe = str(tmp_path / "check")
+    subprocess.check_call(COMMON + sources + ["-lpthread"] + flags + ["-o", exe])
     env = dict(os.environ, ASAN_OPTIONS="detect_leaks=1:abort_on_error=0", UBSAN_OPTIONS="print_stacktrace=1:halt_on_error=1")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
-    assert r.returncode == 0 and r.stdout.startswith("renumber ok"), r.stdout + r.stderr
+    assert r.returncode == 0 and r.stdout.startswith(says), r.stdout + r.stderr
+
+
+@pytest.mark.parametrize("flags", FLAGS, ids=["plain", "sanitizers"])
+def test_renumbering_gives_the_host_builders_tree(tmp_path, flags):
+    build_and_run(tmp_path, flags, [os.path.join(HERE, "renumber_check.cpp"), os.path.join(CSRC, "art_bvh.cpp")], "renumber ok")
+
+
+@pytest.mark.parametrize("flags", FLAGS, ids=["plain", "sanitizers"])
+def test_the_level_walk_on_hand_made_packets_and_against_levels_by_recursion(tmp_path, flags):
+    """csrc/art_tree_walk.h, the one breadth-first walk of the refit plan, the move plan and the renumbering: tests/tree_walk_check.cpp"""
+    build_and_run(tmp_path, flags, [os.path.join(HERE, "tree_walk_check.cpp"), os.path.join(CSRC, "art_bvh.cpp"), os.path.join(CSRC, "art_instanced_build.cpp")], "tree walk ok")
