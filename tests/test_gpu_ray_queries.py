@@ -143,6 +143,11 @@ def _shadow_rays(backend, sd, n, seed):
     h = conv.hits_to_arrays(backend.trace_rays(o, d))
     hit = np.nonzero(h[1] == 1)[0]
     p = (o[hit] + h[0][hit][:, None] * d[hit]).astype(np.float32)
+    return _shadow_rays_from(sd, p, rng)
+
+
+def _shadow_rays_from(sd, p, rng):
+    """The shadow rays of the surface points p [m, 3] (float32), wherever they come from."""
     L = sd.desc.lights
     samples = []
     for i in range(sd.desc.n_lights):
