@@ -17,6 +17,8 @@ import sys
 
 import numpy as np
 
+from . import radiance      # art_radiance_rays_device: ArtRadianceParams and Backend.radiance_rays_torch
+
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 ROOT = os.path.dirname(PKG_DIR)
 LIB_PATH = os.environ.get("ART_LIB", os.path.join(PKG_DIR, "libart_hip.so"))   # ART_LIB: A/B builds of the same source
@@ -252,7 +254,7 @@ EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_svgf_spatial_variance_device", "art_set_camera",
-    "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device",
+    "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device", "art_radiance_rays_device",
     "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
     "art_refit_mesh_device", "art_get_mesh_refit_info",
@@ -312,6 +314,7 @@ def load_library():
     L.art_compact_mask_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_render_pass_masked.argtypes = [C.POINTER(ArtPassParams), C.c_void_p, C.c_void_p, i32p, C.POINTER(C.c_int64)]
     L.art_adaptive_estimate_device.argtypes = [C.POINTER(ArtAdaptiveParams)] + [C.c_void_p] * 8
+    L.art_radiance_rays_device.argtypes = [C.POINTER(radiance.ArtRadianceParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_refit_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
     L.art_get_refit_info.argtypes = [C.POINTER(ArtRefitInfo)]
     L.art_rebuild_device.argtypes = [C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p]
@@ -533,7 +536,7 @@ class SceneDesc:
         self.desc = d
 
 
-class Backend:
+class Backend(radiance.RadianceQueries):
     """One process-wide backend instance (the C library is a singleton, like g_data / ray_tracer.ads globals)."""
 
     def __init__(self, device=-1, devices=None):

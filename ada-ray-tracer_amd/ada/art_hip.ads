@@ -269,6 +269,20 @@ package Art_Hip is
   function art_render_pass_masked (p : access constant Art_Pass_Params; mask1b, counts1u : System.Address; spp_inout : access int;
                                    pixels_out : access long) return int;
   pragma Import (C, art_render_pass_masked, "art_render_pass_masked");
+  --  Radiance along the caller's rays (include/art_hip.h states the contract): `samples` paths per ray with the integrator render_type
+  --  selects, added into radiance3f (and moments2f, may be Null_Address).  All arrays are DEVICE memory; keys1u may be Null_Address
+  --  (ray i has RNG key i).  Runs on the library's stream and waits at the end, as art_render_pass_masked does (ArtRadianceParams, 24 bytes).
+  type Art_Radiance_Params is record
+    render_type : int;          --  ART_PT_STUPID | ART_PT_SHADOW | ART_PT_MIS
+    max_depth   : int;          --  1 .. 16
+    samples     : int;          --  >= 1
+    sample_base : Unsigned_32;
+    seed        : Unsigned_64;
+  end record;
+  pragma Convention (C, Art_Radiance_Params);
+  function art_radiance_rays_device (p : access constant Art_Radiance_Params; origins3f, dirs3f, keys1u : System.Address;
+                                     n : Interfaces.Integer_64; radiance3f, moments2f : System.Address) return int;
+  pragma Import (C, art_radiance_rays_device, "art_radiance_rays_device");
   --  Per pixel: mean colour, variance of the mean's luminance, relative error and the next mask (ArtAdaptiveParams, 28 bytes).  The four
   --  outputs may each be Null_Address, but not all.
   type Art_Adaptive_Params is record

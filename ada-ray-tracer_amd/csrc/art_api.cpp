@@ -701,6 +701,14 @@ int art_render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32
   return synchronize();
 }
 
+int art_radiance_rays_device(const ArtRadianceParams* p, const float* origins3f, const float* dirs3f, const uint32_t* keys1u, int64_t n,
+                             float* radiance3f, float* moments2f) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  SINGLE_DEVICE_ONLY("art_radiance_rays_device");
+  if (radiance_rays(p, origins3f, dirs3f, keys1u, n, radiance3f, moments2f)) return 1;
+  return synchronize();
+}
+
 int art_adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u,
                                  float* mean3f, float* variance1f, float* error1f, uint8_t* mask1b, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0

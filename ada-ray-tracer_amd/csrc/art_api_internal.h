@@ -103,7 +103,7 @@ struct Ctx {
   DevBuf b_accum, b_screen, b_stage, b_pixmap, b_paths, b_rays, b_ids, b_queue, b_ovf;
   DevBuf b_query;                              // device-resident ray queries: SoA rays + shadow minima + hit records of one slice, and a counter sink
   DevBuf b_denoise;                            // art_denoise_device: its working images, guide records and depth gradients (art_denoise.h)
-  DevBuf b_select, b_masklist;                 // mask compaction (art_select.hip): a count word (256 B) + one word per 256 list entries | the masked pass's pixel list; both only grow, like b_pixmap
+  DevBuf b_select, b_masklist;                 // mask compaction (art_select.hip): a count word (256 B) + one word per 256 list entries | the masked pass's pixel list, or the iota keys of art_radiance_rays_device; both only grow, like b_pixmap
   hipEvent_t q_ev[2] = {nullptr, nullptr};     // ... their ordering with the context stream when they run on another stream (library -> query, query -> library)
   // art_refit_device (art_refit.hip): the plan is built on the first refit after an upload (the upload drops it); per context, because
   // the GPU builders may number the nodes differently on every device
@@ -275,6 +275,7 @@ void make_frame(const ArtPassParams* p, DevFrame& f);
 int render_pass_device(const ArtPassParams* p, int32_t* spp_inout);
 int compact_mask_device(const uint8_t* mask1b, uint32_t* pixels_out, int64_t cap, uint32_t* count_out, hipStream_t st);
 int render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* counts1u, int32_t* spp_inout, int64_t* pixels_out);   // single device (the caller checked), no synchronize
+int radiance_rays(const ArtRadianceParams* p, const float* origins3f, const float* dirs3f, const uint32_t* keys1u, int64_t n, float* radiance3f, float* moments2f);   // single device (the caller checked), no synchronize
 int adaptive_estimate_device(const ArtAdaptiveParams* p, const float* accum3f, const float* moments2f, const uint32_t* counts1u, float* mean3f, float* variance1f,
                              float* error1f, uint8_t* mask1b, hipStream_t st);
 int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f, hipStream_t st);

@@ -13,6 +13,7 @@
 
 #include "art_api_internal.h"
 #include "art_frame.h"
+#include "art_radiance.h"
 #include "art_select.h"
 #include "art_stages.h"
 
@@ -236,7 +237,11 @@ static int plan_and_allocate(const ArtPassParams* p, int npix, int S, int per, B
 // bank b & 1 and writes the survivors densely into the other bank.  d_live[0] / d_live[32]: the banks' item counts.  Every stage leaves
 // its rays as trace records in its output bank (round 3), at positions given by the item index; the trace kernel reads them from there
 // in item order.  cam_dedup: DevPaths::cam_dedup (0: every slot's camera ray is traced); cam_n: camera rays the batch generates and traces.
-static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const TraceLaunch& launch, DevPaths bank[2], int sn, int cam_dedup, int cam_n, ShadeTrial::Batch tb) {
+// rays != nullptr (art_radiance_rays_device): the two ends of the batch are art_radiance.hip's -- raygen reads the caller's rays, bounce 0 reads
+// them from bank 0 (synth0 = 0: the stage's non-camera instantiation), the fold's result goes to the caller's planes -- and the frame's
+// counters (ArtStageStats' batches and items) stay as they are.
+static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const TraceLaunch& launch, DevPaths bank[2], int sn, int cam_dedup, int cam_n, ShadeTrial::Batch tb,
+                                const RayBatch* rays = nullptr) {
   Ctx& c = g_ctx;
   const int trial = tb.trial, shade_per = tb.shade_per;
   if (!c.d_live) HIP_TRY(hipMalloc(&c.d_live, 32 * 18 * sizeof(int)));          // d_live[32 k]: items of level k (the input set of bounce k), k = 1 .. max_depth <= 16
@@ -247,7 +252,8 @@ static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const
   q.cam_dedup = cam_dedup;
   DevPaths qgen = q; qgen.P = cam_n;               // raygen's slots: [0, cam_n) are the distinct rays (slot = (sample & 3 within the batch) * pn + pixel)
   if (!c.d_items) { HIP_TRY(hipMalloc(&c.d_items, 32 * sizeof(unsigned long long))); HIP_TRY(hipMemsetAsync(c.d_items, 0, 32 * sizeof(unsigned long long), c.stream)); }
-  { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(2))); launch_raygen(c.stream, F, c.scene, qgen); }
+  { EventPairs::Timer t; HIP_TRY(c.stage_pairs.begin(t, c.stream, ev_tag(2)));
+    if (rays) launch_raygen_rays(c.stream, c.scene, qgen, *rays); else launch_raygen(c.stream, F, c.scene, qgen); }
   launch_bump(c.stream, c.d_counters + CNT_RAYS, rays_b, (unsigned long long)q.P);      // ArtStats::rays: one camera query per sample (the reference's Find_Closest_Hit calls), however many were traced
   { const RecordQueue rq = {cam_n, nullptr, 1}; TraceLaunch t = launch; t.records = &rq; if (trace(q, cam_n, t)) return 1; }
   for (int b = 0; b < p->max_depth; ++b) {
@@ -278,9 +284,11 @@ static int render_batch_records(const ArtPassParams* p, const DevFrame& F, const
   launch_resolve_last(c.stream, bank[last], c.d_live + 32 * p->max_depth, p->max_depth - 1);
   if (bank[last].fold_dense) launch_fold_levels(c.stream, F, bank[last], p->max_depth, c.d_live);
   else launch_fold(c.stream, F, bank[last]);
-  if (c.ext_moments) launch_accumulate_moments(c.stream, F, q, sn, accum_ptr(), c.ext_moments);
+  if (rays) launch_accumulate_rays(c.stream, q, sn, *rays);
+  else if (c.ext_moments) launch_accumulate_moments(c.stream, F, q, sn, accum_ptr(), c.ext_moments);
   else launch_accumulate(c.stream, F, q, sn, accum_ptr());
   HIP_TRY(fold_timer.end());
+  if (rays) return 0;
   launch_acc_items(c.stream, c.d_live, p->max_depth, q.P, c.d_items);
   c.stage.batches += 1;
   return 0;
@@ -305,15 +313,28 @@ static int render_batch_plain(const ArtPassParams* p, const DevFrame& F, const T
 }
 
 // A pixel list a pass walks: the context's own (b_pixmap, npix_local), or the compacted list of a masked pass.
-struct PixelList { const uint32_t* pixels; int n; bool masked; };
+// rays != nullptr (art_radiance_rays_device): the list is the caller's n rays -- `pixels` their RNG keys (nullptr: ray i has key i, which
+// only a pass of ONE ray chunk may leave to DevPaths::pixmap's identity), rays->sample_base the sample index of the call's first path
+// instead of the frame's spp, the planes those of the call.  Such a pass reads and writes nothing of the frame.
+struct RaySource { RayBatch all; uint32_t sample_base; };
+struct PixelList { const uint32_t* pixels; int n; bool masked; const RaySource* rays = nullptr; };
 
 // The batch of samples [s0, s0 + sn) of the pixels [px0, px0 + pn) of the pixel list L.
 static int render_batch(const ArtPassParams* p, const DevFrame& F, const TraceLaunch& launch, const PixelList& L, int px0, int pn, int s0, int sn) {
   Ctx& c = g_ctx;
   const bool records = (c.opt.trace_kernel == TRACE_COOP);
   DevPaths bank[2]; std::memset(bank, 0, sizeof bank);
-  for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = L.pixels + px0; b.sample_base = (uint32_t)(c.spp + s0); }
+  for (DevPaths& b : bank) { b.P = pn * sn; b.npix = pn; b.pixmap = L.pixels ? L.pixels + px0 : nullptr; b.sample_base = (L.rays ? L.rays->sample_base : (uint32_t)c.spp) + (uint32_t)s0; }
   carve(bank, bank[0].P, p->max_depth, records);
+  if (L.rays) {                                    // the caller's rays: the record schedule (checked by the entry), nothing synthesised, nothing shared
+    for (DevPaths& b : bank) b.synth0 = 0;
+    const RayBatch& A = L.rays->all;
+    const RayBatch R = {A.origins3f + 3 * (size_t)px0, A.dirs3f + 3 * (size_t)px0, A.radiance3f + 3 * (size_t)px0, A.moments2f ? A.moments2f + 2 * (size_t)px0 : nullptr};
+    const ShadeTrial::Batch per = {0, c.opt.opt_shade_per ? c.opt.opt_shade_per : (c.trial.phase >= 4 ? c.trial.per : 4)};      // out of the trial, as a masked pass
+    if (render_batch_records(p, F, launch, bank, sn, 0, bank[0].P, per, &R)) return 1;
+    HIP_TRY(hipGetLastError());
+    return 0;
+  }
   // items per thread of the shade stage for this batch: the option, the measured choice, or a trial (art_pass_plan.h ShadeTrial).
   // Nothing here waits for the GPU: a trial batch only tags its shade launches' event pairs, and the next call that synchronises
   // anyway reads them (collect_timing) -- Render_Pass releases all its workers before it waits for any (ray_tracer.adb:271-277).
@@ -345,23 +366,33 @@ static int check_render_pass(const ArtPassParams* p) {
 static const char* const kSppRule = "with anti-aliasing on, spp must be a multiple of 4 (Generate4RayDirections order)";
 
 // One Render_Pass of the current context over the pixel list L: check, plan and allocate, then enqueue batch after batch.
-static int render_pass_list(const ArtPassParams* p, int32_t* spp_inout, const PixelList& L) {
+// With a ray source (PixelList::rays; its entry, radiance_rays, has made the checks) the pass is the same plan and the same batches, and
+// nothing of the frame: spp, ArtStats::samples and pass_ms stay as they are.
+static int render_pass_list(const ArtPassParams* p, int32_t* spp_inout, const PixelList& L0) {
   Ctx& c = g_ctx;
-  if (check_render_pass(p)) return 1;
+  const bool frame = (L0.rays == nullptr);
+  if (frame && check_render_pass(p)) return 1;
   const int per = p->aa_on ? 4 : 1;
-  if (spp_inout) c.spp = *spp_inout;
-  if (p->aa_on && (c.spp % 4) != 0) return fail(kSppRule);
+  if (frame && spp_inout) c.spp = *spp_inout;
+  if (frame && p->aa_on && (c.spp % 4) != 0) return fail(kSppRule);
   const int S = p->vthreads * per;           // samples this pass
-  const int npix = L.n;
+  const int npix = L0.n;
   DevFrame F; make_frame(p, F);
   BatchPlan plan = {0, 0};
   if (npix > 0 && plan_and_allocate(p, npix, S, per, plan)) return 1;
+  PixelList L = L0;
+  if (!frame && !L.pixels && npix > 0 && plan.pc < npix) {
+    // rays without keys in more than one ray chunk: a chunk past ray 0 needs its keys spelled out (b_masklist: a list scratch of this stream)
+    if (grow_idle(StreamOrder(c, nullptr), GrowList{Grow{&c.b_masklist, (size_t)npix * sizeof(uint32_t)}})) return 1;
+    launch_iota_keys(c.stream, (uint32_t*)c.b_masklist.p, npix);
+    L.pixels = (const uint32_t*)c.b_masklist.p;
+  }
   EventPairs::Timer pass_timer;
-  HIP_TRY(c.pass_pairs.begin(pass_timer, c.stream));
+  if (frame) HIP_TRY(c.pass_pairs.begin(pass_timer, c.stream));
   struct Uncounted { EventPairs::Timer& t; ~Uncounted() { t.cancel(); } } uncounted{pass_timer};      // a pass that fails midway never enters pass_ms
   const TraceLaunch launch = pass_launch();
   Ctx::PassClock* clock = nullptr;
-  if (g_multi_api) { clock = new Ctx::PassClock; c.pass_clock.push_back(clock); HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t0)); }
+  if (g_multi_api && frame) { clock = new Ctx::PassClock; c.pass_clock.push_back(clock); HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t0)); }
   for (int px0 = 0; px0 < npix; px0 += plan.pc) {
     const int pn = std::min(plan.pc, npix - px0);
     for (int s0 = 0; s0 < S; s0 += plan.sc) {
@@ -370,6 +401,7 @@ static int render_pass_list(const ArtPassParams* p, int32_t* spp_inout, const Pi
   }
   HIP_TRY(pass_timer.end());
   if (clock) HIP_TRY(hipLaunchHostFunc(c.stream, clock_cb, &clock->t1));
+  if (!frame) return 0;
   c.spp += S;
   c.stats.samples += (uint64_t)npix * S;
   if (spp_inout) *spp_inout = c.spp;
@@ -437,6 +469,31 @@ int render_pass_masked(const ArtPassParams* p, const uint8_t* mask1b, uint32_t* 
   }
   if (pixels_out) *pixels_out = (int64_t)count;
   return 0;
+}
+
+// art_radiance_rays_device on the current context (single device: the caller checked).  Every refusal comes before the first launch, and
+// those that need no GPU before the device is looked for.  The pass is render_pass_list's over the caller's rays: no anti-aliasing, one
+// "virtual thread" per sample, no background.
+int radiance_rays(const ArtRadianceParams* p, const float* origins3f, const float* dirs3f, const uint32_t* keys1u, int64_t n, float* radiance3f, float* moments2f) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_radiance_rays_device";
+  if (!p) return fail(name + ": null ArtRadianceParams");
+  if (p->render_type == ART_RT_DEBUG || p->render_type == ART_RT_WHITTED) return fail(name + ": debug render types have no radiance (ART_PT_STUPID, ART_PT_SHADOW or ART_PT_MIS)");
+  if (p->render_type < ART_PT_STUPID || p->render_type > ART_PT_MIS) return fail(name + ": unknown render_type");
+  if (p->max_depth < 1 || p->max_depth > 16) return fail(name + ": max_depth must be 1..16");
+  if (p->samples < 1) return fail(name + ": samples must be >= 1");
+  if (n < 0 || n > (1ll << 28)) return fail(name + ": n must be 0 .. 2^28");
+  if (n == 0) return 0;
+  if (!origins3f || !dirs3f || !radiance3f) return fail(name + ": null origins3f, dirs3f or radiance3f");
+  if (!c.scene_ready) return fail(name + ": no scene uploaded (art_upload_scene)");
+  if (c.opt.trace_kernel != TRACE_COOP) return fail(name + ": the cooperative record schedule only (option trace_kernel = 0)");
+  if (ensure_device()) return 1;
+  const size_t N = (size_t)n;
+  if (check_planes({{origins3f, 12 * N, "origins3f"}, {dirs3f, 12 * N, "dirs3f"}, {keys1u, 4 * N, "keys1u"}, {radiance3f, 12 * N, "radiance3f"}, {moments2f, 8 * N, "moments2f"}})) return 1;
+  ArtPassParams pp = ArtPassParams();      // (background: zero, and never read without anti-aliasing)
+  pp.render_type = p->render_type; pp.aa_on = 0; pp.max_depth = p->max_depth; pp.vthreads = p->samples; pp.seed = p->seed; pp.layout = ART_LAYOUT_ROW_MAJOR;
+  const RaySource src = {RayBatch{origins3f, dirs3f, radiance3f, moments2f}, p->sample_base};
+  return render_pass_list(&pp, nullptr, PixelList{keys1u, (int)n, true, &src});
 }
 
 // One Render_Pass on every device of the process: each GPU renders the pixel tiles it owns into its own accum buffer, asynchronously on

@@ -251,6 +251,46 @@ int  art_trace_rays_device(const float* origins3f, const float* dirs3f, const fl
 int  art_occluded_rays_device(const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n,
                               uint8_t* occluded_out, void* hip_stream);
 
+/* Radiance queries: path-trace rays of the caller's choosing -- "how much light arrives along this ray" -- with the render passes'
+ * integrators, stages and trace kernel.  Every pointer is device memory of the device the library runs on: origins3f / dirs3f float3
+ * arrays (12 bytes per ray), keys1u one uint32 per ray or NULL, radiance3f float3 per ray, moments2f float2 per ray or NULL.
+ * Per-path value.  Ray i is the first ray of `samples` independent paths; path k is what PathTrace (ray_tracer-integrators.adb:82-301,
+ *   the integrator render_type selects: ART_PT_STUPID, ART_PT_SHADOW or ART_PT_MIS, to max_depth 1..16) returns for a ray that leaves
+ *   origins3f[i] along dirs3f[i].  It starts as a camera sample does: previous pdf 1, previous bounce specular, unbounded -- so a ray that
+ *   meets a light face-on returns its emittance (ART_PT_SHADOW: 0, as for a camera ray) and a miss returns 0.  The background colour
+ *   plays no part, as it plays none for one sample of a pass without anti-aliasing.
+ * RNG key.  The counter-based RNG is keyed by (seed, key_i, sample_base + k, bounce): key_i = keys1u[i], or i when keys1u is NULL; it
+ *   stands where a render pass has the pixel index y * width + x.  With the camera rays of a W x H frame without anti-aliasing as the
+ *   rays, key_i = i and the frame's spp as sample_base, the path values are those art_render_pass adds to pixel i, bit for bit.
+ * Direction.  Used as given: the library does not normalise it (the integrators assume unit length, as camera rays have).
+ * Outputs.  radiance3f[3 i ..] is read-modify-write: for k = 0 .. samples - 1 in that order, out = s_k + out per channel, in binary32,
+ *   not contracted.  The caller zeroes the buffer first; calling again with sample_base advanced by `samples` refines it, and two calls of
+ *   m samples leave the bits one call of 2 m leaves.  The result does not depend on how the call is cut into batches (option
+ *   batch_paths).  moments2f, if given, takes the luminance sums of art_bind_moments' formula, one colour being one path value, in the
+ *   same order and also read-modify-write:  l = (0.2126f * r + 0.7152f * g) + 0.0722f * b;  S1 = l + S1;  S2 = l * l + S2.
+ *   A path value that is not finite poisons its ray's sums, as it poisons a pixel.
+ * Refusals, each before anything is launched and with art_last_error set: a null p; a render type other than the three integrators;
+ *   max_depth outside 1..16; samples < 1; n outside 0 .. 2^28; (n == 0 then succeeds and launches nothing;) a null origins3f, dirs3f or
+ *   radiance3f; no uploaded scene; option trace_kernel = 1 (only the cooperative record schedule has the stages); a pointer that is not
+ *   device memory of the library's device or is smaller than n rays need.  Single device: refused after art_init_devices(n > 1).  No
+ *   viewport is needed (art_resize); flat and instanced scenes both work.
+ * What the call leaves alone: the frame's accum, a bound accum and bound moments, spp, art_get_camera_rays_traced, the shade stage's
+ *   items-per-thread trial (the call uses the decided value, as art_render_pass_masked does), ArtStageStats' batches and items, and
+ *   ArtStats::samples and pass_ms.  ArtStats::rays, trace_ms and trace_launches DO count the call's rays and trace launches, and
+ *   ArtStageStats' stage times its raygen, shade and fold launches; a lost path (ArtStats::lost_paths) fails the call.
+ * Stream and waiting.  As art_render_pass_masked: everything runs on the library's stream (art_set_stream) and the call returns when
+ *   its work is done, so the outputs are complete on return.  Inputs (rays, keys, and the planes' previous contents) written by work on
+ *   ANOTHER stream must be complete before the call: synchronise that stream, or make the library's stream wait for it, first. */
+typedef struct ArtRadianceParams {
+  int32_t  render_type;   /* ART_PT_STUPID | ART_PT_SHADOW | ART_PT_MIS */
+  int32_t  max_depth;     /* 1..16 */
+  int32_t  samples;       /* >= 1: paths per ray in this call */
+  uint32_t sample_base;   /* RNG sample index of the call's first path */
+  uint64_t seed;
+} ArtRadianceParams;
+int  art_radiance_rays_device(const ArtRadianceParams* p, const float* origins3f, const float* dirs3f, const uint32_t* keys1u /* or NULL */, int64_t n,
+                              float* radiance3f, float* moments2f /* or NULL */);
+
 /* First-hit feature buffers of the frame: what a denoiser, a segmentation mask or a compositing step wants
  * next to the radiance.  Every pointer of ArtAovBuffers is device memory of the library's device (device 0 under art_init_devices),
  * row-major (pixel (x, y) at y*width + x) whatever p->layout says; NULL = that plane is not wanted and costs nothing.
