@@ -257,6 +257,42 @@ package Art_Hip is
                                              hip_stream : System.Address) return int;
   pragma Import (C, art_svgf_spatial_variance_device, "art_svgf_spatial_variance_device");
 
+  --  The display transform (include/art_hip.h states the arithmetic): an exposure from the histogram of log2 luminance, kept in a state
+  --  of art_exposure_state_bytes bytes of DEVICE memory that the caller zeroes once (ArtExposureParams, 44 bytes), and the HDR plane as
+  --  8-bit screen words (ArtDisplayParams, 36 bytes).  color3f is row-major DEVICE memory; screen1u and ldr3f are written in `layout`
+  --  (ART_LAYOUT_ADA_XY: screen_buffer (x, y) as it is); exposure_state, and one of screen1u and ldr3f, may be Null_Address.
+  ART_CURVE_REFERENCE : constant := 0;  ART_CURVE_LINEAR : constant := 1;  ART_CURVE_REINHARD : constant := 2;  ART_CURVE_ACES : constant := 3;
+  ART_TRANSFER_SQRT : constant := 0;    ART_TRANSFER_SRGB : constant := 1; ART_TRANSFER_GAMMA22 : constant := 2;
+  type Art_Exposure_Params is record
+    width, height : int;
+    scale         : C_float;  --  the factor on color3f, e.g. 1 / spp
+    min_log2, max_log2 : C_float;            --  the histogram's range of log2 luminance; -12 and 4
+    low_fraction, high_fraction : C_float;   --  the ranks the mean is taken over; 0.5 and 0.95
+    key           : C_float;  --  0.18
+    adapt         : C_float;  --  (0, 1]; 1 jumps to the target
+    min_exposure, max_exposure : C_float;
+  end record;
+  pragma Convention (C, Art_Exposure_Params);
+  type Art_Display_Params is record
+    width, height : int;
+    scale         : C_float;
+    exposure      : C_float;  --  used when exposure_state is Null_Address
+    curve         : int;      --  ART_CURVE_...; ART_CURVE_REFERENCE gives the words of art_download
+    transfer      : int;      --  ART_TRANSFER_...
+    white         : C_float;  --  ART_CURVE_REINHARD's white point
+    dither        : int;      --  0 or 1
+    layout        : int;      --  ART_LAYOUT_...
+  end record;
+  pragma Convention (C, Art_Display_Params);
+  function art_exposure_state_bytes return long;
+  pragma Import (C, art_exposure_state_bytes, "art_exposure_state_bytes");
+  function art_auto_exposure_device (p : access constant Art_Exposure_Params; color3f, state : System.Address;
+                                     hip_stream : System.Address) return int;
+  pragma Import (C, art_auto_exposure_device, "art_auto_exposure_device");
+  function art_display_device (p : access constant Art_Display_Params; color3f, exposure_state, screen1u, ldr3f : System.Address;
+                               hip_stream : System.Address) return int;
+  pragma Import (C, art_display_device, "art_display_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

@@ -720,6 +720,18 @@ int art_svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* 
   return svgf_spatial_variance_device(p, hist, variance_in1f, variance_out1f, (hipStream_t)hip_stream);
 }
 
+int64_t art_exposure_state_bytes(void) { return 4 * (4 + 256); }      // (the header's layout: four words and the 256 bins)
+
+int art_auto_exposure_device(const ArtExposureParams* p, const float* color3f, void* state, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return auto_exposure_device(p, color3f, state, (hipStream_t)hip_stream);
+}
+
+int art_display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return display_device(p, color3f, exposure_state, screen1u, ldr3f, (hipStream_t)hip_stream);
+}
+
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
   return 48 * (int64_t)width * height;

@@ -1,7 +1,8 @@
 // art_device_entries.cpp -- the entries of the C ABI (include/art_hip.h) that work on the caller's device memory in the caller's stream
 // order: art_trace_rays_device and art_occluded_rays_device (art_query.hip), art_render_aovs_device and art_render_aovs_motion_device
 // (art_aov.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
-// art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip); with them art_trace_rays, the
+// art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip), art_auto_exposure_device and
+// art_display_device (art_display.hip); with them art_trace_rays, the
 // host-pointer query the device ones are held to.  What they share is written once: the check of a list of the caller's planes
 // (check_planes), growing a scratch while nothing uses it (grow_idle), and the ordered call (ordered_call, art_api_internal.h).  An entry
 // is its own refusals, its plane list, its size arithmetic and its launches; art_render.cpp's mask compaction uses the same pieces.
@@ -17,6 +18,7 @@
 #include "art_api_internal.h"
 #include "art_adaptive.h"
 #include "art_denoise.h"
+#include "art_display.h"
 #include "art_motion.h"
 #include "art_query.h"
 #include "art_shade.h"      // surface_at: trace_rays finishes its hit records on the host
@@ -338,6 +340,36 @@ int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist
   A.tiles_x = svgf_spatial_tiles_x(A.P.W);
   A.hist = (const sv::Rec4*)hist; A.variance_in = variance_in1f; A.variance_out = variance_out1f;
   return ordered_call(name.c_str(), st, GrowList{}, [&](hipStream_t qs) { launch_svgf_spatial(qs, A); return 0; });
+}
+
+// art_auto_exposure_device: the state's histogram is zeroed on the stream, then two kernels over the caller's plane and state
+// (art_display.h); no scratch.
+int auto_exposure_device(const ArtExposureParams* p, const float* color3f, void* state, hipStream_t st) {
+  const std::string name = "art_auto_exposure_device";
+  ExposureArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = dp::params_from_abi(p, color3f, state, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_planes({{color3f, 12 * N, "color3f"}, {state, 4 * (size_t)dp::kStateWords, "state"}})) return 1;
+  A.n = (int32_t)N; A.color = color3f; A.state = (uint32_t*)state;
+  return ordered_call(name.c_str(), st, GrowList{}, [&](hipStream_t qs) {
+    HIP_TRY(hipMemsetAsync(A.state + 4, 0, 4 * (size_t)dp::kBins, qs));
+    launch_auto_exposure(qs, A);
+    return 0;
+  });
+}
+
+// art_display_device: one kernel over the caller's planes (art_display.h); no scratch.
+int display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f, hipStream_t st) {
+  const std::string name = "art_display_device";
+  DisplayArgs A; std::memset(&A, 0, sizeof A);
+  if (const char* why = dp::params_from_abi(p, color3f, exposure_state, screen1u, ldr3f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_planes({{color3f, 12 * N, "color3f"}, {exposure_state, 4 * (size_t)dp::kStateWords, "exposure_state"}, {screen1u, 4 * N, "screen1u"}, {ldr3f, 12 * N, "ldr3f"}}))
+    return 1;
+  A.color = color3f; A.state = (const uint32_t*)exposure_state; A.screen = screen1u; A.ldr = ldr3f;
+  return ordered_call(name.c_str(), st, GrowList{}, [&](hipStream_t qs) { launch_display(qs, A); return 0; });
 }
 
 }  // namespace art

@@ -628,6 +628,94 @@ typedef struct ArtSvgfSpatialParams {
 int  art_svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist, const float* variance_in1f, float* variance_out1f,
                                       void* hip_stream);
 
+/* ---- the display transform ----------------------------------------------------------------------------
+ * The tail of the image-space pipeline: a float3 HDR plane in the caller's device memory becomes an exposure (art_auto_exposure_device)
+ * and then 8-bit screen words (art_display_device).  Scene-independent like the denoisers: an initialised device only, no viewport, no
+ * scratch (the host never waits), no ArtStats; stream order and pointer rules are art_temporal_device's.  color3f is row-major, three
+ * floats per pixel, and is only read.
+ *
+ * THE ARITHMETIC of both calls (the contract; csrc/art_display.h is its one definition, compiled for the GPU and for the host).
+ * Binary32, not contracted, in the order written, division and sqrtf correctly rounded, except where binary64 is named; there operands
+ * are converted first and every operation is rounded to binary64.  finite(v): neither NaN nor an infinity.  amin(a, b) = (a < b) ? a : b,
+ * amax(a, b) = (a >= b) ? a : b, aclamp(v, lo, hi) = amin(amax(v, lo), hi) (a NaN v gives lo).  log_pos, exp_small and apow are ART-M1's
+ * (csrc/art_math.h: + - * / in binary64 and one rounding), the functions art_denoise_device and the render passes use.
+ *
+ * AUTO-EXPOSURE.  state: art_exposure_state_bytes() = 1040 bytes of device memory, 4-byte aligned, that the caller zeroes once:
+ *   word 0  float    exposure    the factor art_display_device multiplies by
+ *   word 1  float    mean_log2   the trimmed mean of log2 luminance the last counted frame gave
+ *   word 2  uint32   counted     pixels of the last call that had a luminance to count (N below)
+ *   word 3  uint32   frames      calls so far that counted at least one pixel; 0 = fresh
+ *   words 4 .. 259   uint32      the histogram of the last call, bin 0 .. 255
+ *  Histogram.  The 256 bin words are set to zero on the stream, then every pixel adds 1 to one bin (integer adds only: per-workgroup
+ *  counters in LDS, then integer adds into the state, so the words do not depend on scheduling).  Of pixel p:
+ *   r = color[3p] * scale, g, b likewise;   l = (0.2126f * r + 0.7152f * g) + 0.0722f * b      (art_bind_moments' luminance)
+ *   not finite(l), or l <= 0:  bin 0 (not counted).  Otherwise, in binary64 throughout (nothing is rounded to binary32):
+ *   L = log_pos((double)l) * 0x1.71547652b82fep+0;   t = ((L - min_log2) / (max_log2 - min_log2)) * 254.0;
+ *   bin = 1 + (t < 0 ? 0 : t >= 253 ? 253 : (int)floor(t)).      Bin 255 stays 0.
+ *  Exposure, one fixed-order walk in binary64 after the histogram.  c_i = bin i's word, i = 1 .. 254; N = their sum (an integer, exact);
+ *   a = (double)low_fraction * N;  b = (double)high_fraction * N;  W = S = cum = 0;  for i = 1 .. 254 in turn:
+ *     lo = cum;  hi = cum + c_i;  o = (hi < b ? hi : b) - (lo > a ? lo : a);  centre_i = min_log2 + ((i - 1 + 0.5) / 254.0) * (max_log2 - min_log2);
+ *     if o > 0:  W += o;  S += o * centre_i.     cum = hi.
+ *   (o is the part of bin i's ranks [lo, hi) inside [a, b): a bin that straddles an end is counted in part.)
+ *   N == 0 (or W not > 0):  exposure = frames ? exposure : 1.0f;  mean_log2 = frames ? mean_log2 : 0.0f;  counted = 0;  frames stays.
+ *   Otherwise:  m = (float)(S / W), the one rounding to binary32;  target = aclamp(key * apow(2.0f, -m), min_exposure, max_exposure);
+ *     exposure = frames ? prev + (target - prev) * adapt : target  (prev = the state's exposure);  mean_log2 = m;  counted = N;
+ *     frames = frames + 1 (it stops at 2^32 - 1).
+ * Refused before anything is launched, with art_last_error set: a null p, color3f or state; width or height < 1 or width * height > 2^28;
+ * a scale that is not finite; min_log2 or max_log2 not finite, outside -126 .. 127, or min_log2 >= max_log2; a fraction outside [0, 1] or
+ * NaN, or low_fraction >= high_fraction; key, min_exposure or max_exposure not finite or <= 0, or min_exposure > max_exposure; adapt
+ * outside (0, 1] or NaN; state overlapping color3f; a pointer that is host memory, another device's memory or too small. */
+typedef struct ArtExposureParams {
+  int32_t width, height;
+  float   scale;               /* the factor on color3f, e.g. 1 / spp for an accum plane */
+  float   min_log2, max_log2;  /* the histogram's range of log2 luminance; -12 and 4 */
+  float   low_fraction, high_fraction;   /* the ranks of the counted pixels the mean is taken over; 0.5 and 0.95 */
+  float   key;                 /* the middle grey the trimmed mean is mapped to; 0.18 */
+  float   adapt;               /* (0, 1]: 1 jumps to the target, less moves from the previous exposure towards it by that fraction */
+  float   min_exposure, max_exposure;
+} ArtExposureParams;
+int64_t art_exposure_state_bytes(void);
+int  art_auto_exposure_device(const ArtExposureParams* p, const float* color3f, void* state, void* hip_stream);
+
+/* DISPLAY.  One lane per pixel (x, y), p = y * width + x, of the row-major color3f; the pixel's outputs go to element p of screen1u and
+ * ldr3f with ART_LAYOUT_ROW_MAJOR and to element x * height + y with ART_LAYOUT_ADA_XY (the constants of art_download).  screen1u (one
+ * word per pixel) and ldr3f (three floats per pixel) may each be NULL, not both.  exposure_state: the state of art_auto_exposure_device,
+ * whose word 0 is then the exposure (read on the device: no host round trip), or NULL = p->exposure.
+ *  ART_CURVE_REFERENCE:  screen = resolve_pixel(color[p], scale), the reference's resolve (ray_tracer.adb:281-291) as art_download runs
+ *   it, word for word: exposure, transfer, dither and white are not read, and ldr3f must be NULL (the curve defines screen words only).
+ *  Every other curve, per channel c of the pixel:
+ *   k = scale * e (e = the exposure; once per pixel);   x = c * k;   not finite(x) or not x > 0:  x = +0;   x = amin(x, 0x1p+60f);
+ *   ART_CURVE_LINEAR    v = x
+ *   ART_CURVE_REINHARD  v = (x * (1.0f + x / (white * white))) / (1.0f + x)
+ *   ART_CURVE_ACES      v = (x * (2.51f * x + 0.03f)) / (x * (2.43f * x + 0.59f) + 0.14f)
+ *   v = aclamp(v, 0.0f, 1.0f);
+ *   ART_TRANSFER_SQRT   u = sqrtf(v)
+ *   ART_TRANSFER_SRGB   u = (v < 0.0031308f) ? 12.92f * v : 1.055f * apow(v, 0x1.aaaaaap-2f) - 0.055f          (0x1.aaaaaap-2f = 1 / 2.4)
+ *   ART_TRANSFER_GAMMA22  u = apow(v, 0x1.d1745ep-2f)                                                           (0x1.d1745ep-2f = 1 / 2.2)
+ *   ldr3f receives u.   s = u * 255.0f;
+ *   dither 0:  q = ada_round_u32(s) = (s > 0) ? trunc(s) + ((s - trunc(s) >= 0.5f) ? 1 : 0) : 0          (the reference's rounding)
+ *   dither 1:  q = trunc(s + ((float)B[y & 3][x & 3] + 0.5f) / 16.0f),  B = {{0, 8, 2, 10}, {12, 4, 14, 6}, {3, 11, 1, 9}, {15, 7, 13, 5}}
+ *   q = min(q, 255);   screen = q_r | q_g << 8 | q_b << 16.
+ *  No input produces anything but 0 .. 255 per channel and a finite u in [0, 1.0000001].
+ * Refused before anything is launched, with art_last_error set: a null p or color3f; screen1u and ldr3f both NULL; width or height < 1 or
+ * width * height > 2^28; a scale that is not finite; an unknown curve, transfer or layout; dither other than 0 or 1; white not finite or
+ * <= 0; without a state an exposure that is not finite or < 0; ldr3f with ART_CURVE_REFERENCE; an output overlapping color3f, the
+ * other output or exposure_state (every lane reads the state's first word while others store); a pointer that is host memory, another device's memory or too small. */
+enum { ART_CURVE_REFERENCE = 0, ART_CURVE_LINEAR = 1, ART_CURVE_REINHARD = 2, ART_CURVE_ACES = 3 };
+enum { ART_TRANSFER_SQRT = 0, ART_TRANSFER_SRGB = 1, ART_TRANSFER_GAMMA22 = 2 };
+typedef struct ArtDisplayParams {
+  int32_t width, height;
+  float   scale;               /* the factor on color3f, e.g. 1 / spp for an accum plane */
+  float   exposure;            /* used when exposure_state is NULL */
+  int32_t curve;               /* ART_CURVE_... */
+  int32_t transfer;            /* ART_TRANSFER_... */
+  float   white;               /* the white point of ART_CURVE_REINHARD: x = white maps to 1 */
+  int32_t dither;              /* 0: round to nearest; 1: the 4 x 4 ordered dither */
+  int32_t layout;              /* ART_LAYOUT_ROW_MAJOR or ART_LAYOUT_ADA_XY, of screen1u and ldr3f */
+} ArtDisplayParams;
+int  art_display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f,
+                        void* hip_stream);
+
 /* ---- adaptive sampling ------------------------------------------------------------------------------
  * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
  * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
