@@ -18,6 +18,7 @@ import sys
 import numpy as np
 
 from . import radiance      # art_radiance_rays_device: ArtRadianceParams and Backend.radiance_rays_torch
+from . import aov_rays      # art_aovs_rays_device, art_camera_rays_device: their structs, Backend.aovs_rays_torch and camera_rays_torch
 from . import display       # art_auto_exposure_device, art_display_device: their structs and constants, Backend.exposure_state, auto_exposure_torch, display_torch
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -254,7 +255,7 @@ class HitCpp(C.Structure):
 EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
-    "art_trace_rays_device", "art_occluded_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_svgf_spatial_variance_device", "art_set_camera",
+    "art_trace_rays_device", "art_occluded_rays_device", "art_aovs_rays_device", "art_camera_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_svgf_spatial_variance_device", "art_set_camera",
     "art_exposure_state_bytes", "art_auto_exposure_device", "art_display_device",
     "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device", "art_radiance_rays_device",
     "art_refit_device", "art_get_refit_info",
@@ -303,6 +304,8 @@ def load_library():
     L.art_trace_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_int32, C.c_void_p]
     L.art_occluded_rays_device.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     L.art_render_aovs_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.c_void_p]
+    L.art_aovs_rays_device.argtypes = [C.POINTER(aov_rays.ArtAovRaysParams)] + [C.c_void_p] * 4 + [C.c_int64, C.POINTER(aov_rays.ArtAovRayBuffers), C.c_void_p]
+    L.art_camera_rays_device.argtypes = [C.POINTER(ArtPassParams), C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_render_aovs_motion_device.argtypes = [C.POINTER(ArtPassParams), C.POINTER(ArtAovBuffers), C.POINTER(ArtMotionSource), C.c_void_p, C.c_void_p]
     L.art_denoise_device.argtypes = [C.POINTER(ArtDenoiseParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_denoise_svgf_device.argtypes = [C.POINTER(ArtSvgfParams)] + [C.c_void_p] * 8
@@ -542,7 +545,7 @@ class SceneDesc:
         self.desc = d
 
 
-class Backend(radiance.RadianceQueries, display.DisplayCalls):
+class Backend(radiance.RadianceQueries, display.DisplayCalls, aov_rays.AovRayCalls):
     """One process-wide backend instance (the C library is a singleton, like g_data / ray_tracer.ads globals)."""
 
     def __init__(self, device=-1, devices=None):

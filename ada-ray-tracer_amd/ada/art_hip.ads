@@ -154,6 +154,29 @@ package Art_Hip is
                                    hip_stream : System.Address) return int;
   pragma Import (C, art_render_aovs_device, "art_render_aovs_device");
 
+  --  The same buffers along the caller's rays (include/art_hip.h states the contract; ArtAovRaysParams 16 bytes, ArtAovRayBuffers 64):
+  --  rays are group-major, element g of a plane owns rays g * group .. g * group + group - 1.  origins3f, dirs3f, tnear, tfar and every
+  --  component of the buffers are DEVICE memory; tnear, tfar and unwanted planes may be Null_Address.  Needs no viewport.
+  type Art_Aov_Rays_Params is record
+    group      : int;                               --  1 .. 16
+    background : Float3_C;
+  end record;
+  pragma Convention (C, Art_Aov_Rays_Params);
+  type Art_Aov_Ray_Buffers is record
+    albedo3f, normal3f, position3f : System.Address;   --  3 C floats per group
+    depth, alpha                   : System.Address;   --  1 C float per group
+    prim_type, prim_index, mat     : System.Address;   --  1 int per group: Art_Hit's fields for the group's ray 0
+  end record;
+  pragma Convention (C, Art_Aov_Ray_Buffers);
+  function art_aovs_rays_device (p : access constant Art_Aov_Rays_Params; origins3f, dirs3f, tnear, tfar : System.Address;
+                                 n_rays : Interfaces.Integer_64; buffers : access constant Art_Aov_Ray_Buffers;
+                                 hip_stream : System.Address) return int;
+  pragma Import (C, art_aovs_rays_device, "art_aovs_rays_device");
+  --  The frame's camera rays into DEVICE memory: ray s of pixel q at q * K + s, K = 4 with p.aa_on, else 1; 3 C floats per ray in each array.
+  function art_camera_rays_device (p : access constant Art_Pass_Params; origins3f, dirs3f : System.Address;
+                                   hip_stream : System.Address) return int;
+  pragma Import (C, art_camera_rays_device, "art_camera_rays_device");
+
   --  The same call with a motion plane (3 C floats per pixel, DEVICE memory): where each pixel's surface point was one scene update ago
   --  minus where it is (include/art_hip.h ArtMotionSource, 40 bytes, states the arithmetic).  Flat scene: cur_pos3f and prev_pos3f, both or
   --  neither; instanced scene: prev_m12f; Null_Address: nothing moved.  buffers may be null when motion3f is given.

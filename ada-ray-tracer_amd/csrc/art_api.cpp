@@ -659,6 +659,18 @@ int art_render_aovs_motion_device(const ArtPassParams* p, const ArtAovBuffers* o
   return render_aovs(p, out, (hipStream_t)hip_stream, motion3f ? src : nullptr, motion3f);
 }
 
+int art_aovs_rays_device(const ArtAovRaysParams* p, const float* origins3f, const float* dirs3f, const float* tnear, const float* tfar, int64_t n_rays,
+                         const ArtAovRayBuffers* out, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);
+  SINGLE_DEVICE_ONLY("art_aovs_rays_device");
+  return aovs_rays(p, origins3f, dirs3f, tnear, tfar, n_rays, out, (hipStream_t)hip_stream);
+}
+
+int art_camera_rays_device(const ArtPassParams* p, float* origins3f, float* dirs3f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like art_render_aovs_device, on device 0
+  return camera_rays(p, origins3f, dirs3f, (hipStream_t)hip_stream);
+}
+
 int art_denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, void* hip_stream) {
   std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
   return denoise_device(p, color3f, albedo3f, normal3f, depth, out3f, (hipStream_t)hip_stream);

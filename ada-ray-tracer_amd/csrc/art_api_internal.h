@@ -285,7 +285,9 @@ int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host,
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);
 int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st, const ArtMotionSource* src = nullptr, float* motion3f = nullptr);   // motion3f: art_render_aovs_motion_device
-int ensure_refit_plan();              // the current context's refit plan exists (art_update.cpp); its b_idx holds the flat mesh's index triples
+int aovs_rays(const ArtAovRaysParams* p, const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, const ArtAovRayBuffers* out, hipStream_t st);   // single device (the caller checked)
+int camera_rays(const ArtPassParams* p, float* o3, float* d3, hipStream_t st);
+int ensure_refit_plan();             // the current context's refit plan exists (art_update.cpp); its b_idx holds the flat mesh's index triples
 int denoise_device(const ArtDenoiseParams* p, const float* color3f, const float* albedo3f, const float* normal3f, const float* depth, float* out3f, hipStream_t st);
 int denoise_svgf_device(const ArtSvgfParams* p, const float* color3f, const float* moments2f, const float* albedo3f, const float* normal3f, const float* depth,
                         float* out3f, float* variance_out, hipStream_t st, bool variance_plane = false);      // variance_plane: art_denoise_svgf_var_device, moments2f is variance1f

@@ -1,6 +1,6 @@
 // art_device_entries.cpp -- the entries of the C ABI (include/art_hip.h) that work on the caller's device memory in the caller's stream
 // order: art_trace_rays_device and art_occluded_rays_device (art_query.hip), art_render_aovs_device and art_render_aovs_motion_device
-// (art_aov.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
+// (art_aov.hip), art_aovs_rays_device and art_camera_rays_device (art_aov_rays.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
 // art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip), art_auto_exposure_device and
 // art_display_device (art_display.hip); with them art_trace_rays, the
 // host-pointer query the device ones are held to.  What they share is written once: the check of a list of the caller's planes
@@ -252,6 +252,73 @@ int render_aovs(const ArtPassParams* p, const ArtAovBuffers* out, hipStream_t st
     }
     return 0;
   });
+}
+
+// art_aovs_rays_device: the caller's rays in slices of whole groups, k * groups <= query_slice (at least one group), through the queries'
+// scratch and stream order; per slice k_aov_rays_pack, the render loop's trace launch, k_aov_rays_resolve.  No viewport is needed.
+int aovs_rays(const ArtAovRaysParams* p, const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, const ArtAovRayBuffers* out, hipStream_t st) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_aovs_rays_device";
+  if (!p) return fail(name + ": null ArtAovRaysParams");
+  if (!out) return fail(name + ": null ArtAovRayBuffers");
+  if (!out->albedo3f && !out->normal3f && !out->position3f && !out->depth && !out->alpha && !out->prim_type && !out->prim_index && !out->mat)
+    return fail(name + ": no plane is wanted (all eight pointers are null)");
+  if (p->group < 1 || p->group > 16) return fail(name + ": group must be 1..16");
+  if (n < 0 || n > 0x7fffffffll) return fail(name + ": n_rays must be 0 .. 2^31 - 1");
+  if (n % p->group != 0) return fail(name + ": n_rays " + std::to_string(n) + " is not a multiple of group " + std::to_string(p->group));
+  if (n == 0) return 0;
+  if (!o3 || !d3) return fail(name + ": null origins3f or dirs3f");
+  if (!c.scene_ready) return fail(name + ": no scene uploaded");
+  const int kernel = c.opt.trace_kernel;
+  if (c.scene.n_inst > 0 && kernel != TRACE_COOP) return fail(name + ": an instanced scene is traced through the record schedule only (option trace_kernel = 0)");
+  if (ensure_device()) return 1;
+  const int k = p->group;
+  const size_t N = (size_t)n, G = N / (size_t)k;
+  if (check_planes({{o3, 12 * N, "origins3f"}, {d3, 12 * N, "dirs3f"}, {tnear, 4 * N, "tnear"}, {tfar, 4 * N, "tfar"}, {out->albedo3f, 12 * G, "albedo3f"},
+                    {out->normal3f, 12 * G, "normal3f"}, {out->position3f, 12 * G, "position3f"}, {out->depth, 4 * G, "depth"}, {out->alpha, 4 * G, "alpha"},
+                    {out->prim_type, 4 * G, "prim_type"}, {out->prim_index, 4 * G, "prim_index"}, {out->mat, 4 * G, "mat"}}))
+    return 1;
+  const size_t ns = std::min<size_t>(G, (size_t)std::max<int64_t>(1, c.opt.query_slice / k));     // groups per slice
+  const size_t S = ns * (size_t)k;                                                                // its rays: at most 2^28 (query_slice), or k
+  return ordered_call(name.c_str(), st, QuerySlice::scratch(S, kernel == TRACE_COOP), [&](hipStream_t qs) {
+    const QuerySlice sl(S);
+    const TraceLaunch launch = sl.launch(qs, kernel);
+    for (size_t g0 = 0; g0 < G; g0 += ns) {
+      const size_t r0 = g0 * (size_t)k;
+      AovRaysArgs A; std::memset(&A, 0, sizeof A);
+      A.n = (int)std::min(ns, G - g0); A.k = k;
+      A.o3 = o3 + 3 * r0; A.d3 = d3 + 3 * r0; A.tnear = tnear ? tnear + r0 : nullptr; A.tfar = tfar ? tfar + r0 : nullptr;
+      A.ox = sl.ox; A.oy = sl.oy; A.oz = sl.oz; A.dx = sl.dx; A.dy = sl.dy; A.dz = sl.dz; A.tf = sl.tf; A.hit = sl.hit;
+      std::memcpy(A.background, p->background, 12);
+      A.albedo = out->albedo3f ? out->albedo3f + 3 * g0 : nullptr; A.normal = out->normal3f ? out->normal3f + 3 * g0 : nullptr;
+      A.position = out->position3f ? out->position3f + 3 * g0 : nullptr;
+      A.depth = out->depth ? out->depth + g0 : nullptr; A.alpha = out->alpha ? out->alpha + g0 : nullptr;
+      A.prim_type = out->prim_type ? out->prim_type + g0 : nullptr; A.prim_index = out->prim_index ? out->prim_index + g0 : nullptr;
+      A.mat = out->mat ? out->mat + g0 : nullptr;
+      launch_aov_rays_pack(qs, A);
+      if (trace(sl.paths(/*shadow_minima=*/false), k * A.n, launch)) return 1;
+      launch_aov_rays_resolve(qs, c.scene, A);
+    }
+    return 0;
+  });
+}
+
+// art_camera_rays_device: one kernel into the caller's two arrays; no scratch.  It refuses where render_aovs refuses.
+int camera_rays(const ArtPassParams* p, float* o3, float* d3, hipStream_t st) {
+  Ctx& c = g_ctx;
+  const std::string name = "art_camera_rays_device";
+  if (!p) return fail(name + ": null ArtPassParams");
+  if (!o3 || !d3) return fail(name + ": null origins3f or dirs3f");
+  if (!c.scene_ready) return fail(name + ": no scene uploaded");
+  if (c.host_scene.gcore_seam) return fail(name + ": the scene was committed through gcore_commit_scene, which has no camera");
+  if (c.width <= 0) return fail(name + ": no viewport (art_resize)");
+  if (ensure_device()) return 1;
+  ArtPassParams pp = ArtPassParams();   // only aa_on is the caller's
+  pp.aa_on = p->aa_on;
+  DevFrame F; make_frame(&pp, F);
+  const int64_t n = (int64_t)c.width * c.height * (F.aa_on ? 4 : 1);
+  if (check_planes({{o3, 12 * (size_t)n, "origins3f"}, {d3, 12 * (size_t)n, "dirs3f"}})) return 1;
+  return ordered_call(name.c_str(), st, GrowList{}, [&](hipStream_t qs) { launch_camera_rays(qs, F, c.scene, o3, d3, n); return 0; });
 }
 
 // ---- the image-space entries: they need no scene and no viewport --------------------------------------------------------------------

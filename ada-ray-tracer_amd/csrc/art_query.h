@@ -1,4 +1,5 @@
-// art_query.h -- launch interface of art_query.hip (device-resident ray queries) and art_aov.hip (first-hit feature buffers).
+// art_query.h -- launch interface of art_query.hip (device-resident ray queries) art_aov.hip (first-hit feature buffers) and
+// art_aov_rays.hip (feature buffers along the caller's rays, the frame's camera rays).
 #pragma once
 #include <hip/hip_runtime.h>
 #include "art_scene.h"
@@ -36,5 +37,24 @@ struct AovArgs {
 };
 void launch_aov_raygen(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
 void launch_aov_resolve(hipStream_t st, const DevFrame& F, const DevScene& S, const AovArgs& A);
+
+// feature buffers along the caller's rays (art_aov_rays.hip, art_device_entries.cpp aovs_rays): one slice of n whole groups, k rays each
+// (the caller's rays g * k .. g * k + k - 1 of group g), in the queries' scratch.  Ray s of local group g lies at slot s * n + g, as in
+// AovArgs.  o3 / d3 / tnear / tfar and the planes are the caller's, advanced to the slice's first ray and group; nullptr: not given, not wanted.
+struct AovRaysArgs {
+  int32_t n, k;                       // groups of the slice | rays per group: 1..16
+  const float* o3; const float* d3;   // float3 AoS
+  const float* tnear; const float* tfar;   // nullptr: 0 / kInfinity
+  float *ox, *oy, *oz, *dx, *dy, *dz, *tf;  // SoA slots of the trace launch, k * n of each (tf < 0: a dead ray)
+  DevHit* hit;
+  float background[3];
+  float* albedo; float* normal; float* position;   // 3 floats per group
+  float* depth; float* alpha;
+  int32_t* prim_type; int32_t* prim_index; int32_t* mat;
+};
+void launch_aov_rays_pack(hipStream_t st, const AovRaysArgs& A);
+void launch_aov_rays_resolve(hipStream_t st, const DevScene& S, const AovRaysArgs& A);
+// the frame's camera rays (art_camera_rays_device): n = K * width * height rays, ray s of pixel q at q * K + s, K = 4 with F.aa_on, else 1
+void launch_camera_rays(hipStream_t st, const DevFrame& F, const DevScene& S, float* o3, float* d3, int64_t n);
 
 }  // namespace art

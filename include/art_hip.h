@@ -325,6 +325,65 @@ typedef struct ArtAovBuffers {
 } ArtAovBuffers;
 int  art_render_aovs_device(const ArtPassParams* p, const ArtAovBuffers* out, void* hip_stream);
 
+/* Feature buffers along rays of the caller's choosing: what art_render_aovs_device gives the built-in
+ * pinhole camera, for a camera the caller builds -- a fisheye, a panorama, a thin lens, a lightmap texel grid, a probe grid -- next to the
+ * radiance art_radiance_rays_device returns for the same rays.  Every pointer is device memory of the device the library runs on:
+ * origins3f / dirs3f float3 arrays (12 bytes per ray), tnear / tfar one float per ray or NULL (0 / Float'Last), the planes of
+ * ArtAovRayBuffers one element per GROUP; a NULL plane is not wanted and costs nothing.
+ * Grouping.  Rays are group-major: with K = p->group, 1..16, output element g owns rays g*K .. g*K + K - 1; n_rays is a multiple of K.
+ *   K stands where a pixel has its 4 anti-aliasing rays.
+ * The hit.  h_s is the ArtHit art_trace_rays_device returns for ray s of the group with the same tnear / tfar: its interval rule (the
+ *   ray traced is o + t0 d bounded by tfar - t0, an empty interval is a miss, a hit's t is t0 + t'), its trace launch under the option
+ *   "trace_kernel" as it stands, and so every kind of primitive: spheres, the Cornell box, rect lights, the REFERENCE_BF mesh, the
+ *   CLOSEST mesh or the instances.  The direction is used as given: the library does not normalise it.
+ * Per-ray values, with o_s and d_s the ray as the caller gave it:
+ *   hit:   depth_s = h_s.t   normal_s = h_s.normal   albedo_s = albedo of materials[h_s.mat]   hit_s = 1   position_s = o_s + h_s.t * d_s
+ *   miss:  depth_s = 0       normal_s = (0, 0, 0)    albedo_s = p->background                  hit_s = 0   position_s = (0, 0, 0)
+ *   The albedo of a material is art_render_aovs_device's table.  position_s is taken per component in binary32, one multiply then one
+ *   add, not contracted.  A sphere's normal is taken at the hit point of the ray's own origin, as h_s.normal is.
+ * The float planes (albedo3f, normal3f, position3f, depth, alpha -- alpha is the plane of hit_s) hold
+ *   (((v_0 + v_1) + ...) + v_{K-1}) / (float)K:  a left fold in binary32, not contracted, then one correctly rounded division.  K = 1 gives
+ *   v_0; K = 4 gives art_render_aovs_device's (...) * 0.25f word for word (a division by 4 is the same exact scaling).
+ * The id planes prim_type, prim_index and mat are those of h_0, -1 on a miss; instanced scenes report instance << shift | triangle.
+ * With the rays of art_camera_rays_device, group = its K, no bounds and the same background, the seven shared planes are
+ *   art_render_aovs_device's, bit for bit.
+ * The rays are traced in slices of whole groups, K * groups <= the option "query_slice" (at least one group), in the queries' scratch.
+ * Stream-ordered exactly as art_trace_rays_device: NULL = the library's stream, hipStreamLegacy = the null stream; the call runs after
+ *   everything the library has enqueued and before anything it enqueues later, so a refit, move or rebuild enqueued before it is seen;
+ *   the host waits only when the scratch has to grow.  It touches neither the accum buffer, spp, the path state, ArtStats nor
+ *   ArtStageStats, and it needs no viewport (art_resize).
+ * Refused before anything is launched, with art_last_error set: a null p or out; all eight planes NULL; group outside 1..16; n_rays
+ *   negative, above 2^31 - 1 or not a multiple of group (n_rays == 0 then succeeds and launches nothing); null origins3f or dirs3f; no
+ *   uploaded scene; an instanced scene with the option "trace_kernel" 1; a call after art_init_devices(n > 1); any given pointer that is
+ *   host memory, another device's memory or too small. */
+typedef struct ArtAovRaysParams {
+  int32_t group;                   /* K: rays per output element, 1..16 */
+  float   background[3];           /* the albedo of a ray that hits nothing */
+} ArtAovRaysParams;
+typedef struct ArtAovRayBuffers {  /* device memory, one element per GROUP; NULL = not wanted, costs nothing */
+  float*   albedo3f;               /* 3 floats per group */
+  float*   normal3f;               /* 3 */
+  float*   position3f;             /* 3: the mean of the rays' hit points, (0, 0, 0) for a ray that hits nothing */
+  float*   depth;                  /* 1 */
+  float*   alpha;                  /* 1: share of the group's rays that hit anything */
+  int32_t* prim_type;              /* ArtHit::prim_type of ray 0, -1 miss */
+  int32_t* prim_index;             /* ArtHit::prim_index of ray 0 */
+  int32_t* mat;                    /* ArtHit::mat of ray 0 */
+} ArtAovRayBuffers;
+int  art_aovs_rays_device(const ArtAovRaysParams* p, const float* origins3f, const float* dirs3f,
+                          const float* tnear /* or NULL */, const float* tfar /* or NULL */, int64_t n_rays,
+                          const ArtAovRayBuffers* out, void* hip_stream);
+
+/* The frame's own camera rays, into the caller's device memory: what art_render_aovs_device and the render passes trace, for a caller
+ * who wants to change them (jitter for depth of field, a crop, a warp) and hand them to art_aovs_rays_device and
+ * art_radiance_rays_device.  Of p only aa_on is read.  K = 4 with aa_on, else 1; ray s of pixel q = y*width + x is written at q*K + s:
+ * origins3f and dirs3f hold 3 * K * width * height floats each.  The origin is cam_pos; the direction is the one a render pass traces
+ * for sample s of q (the Generate4RayDirections offset of s through the camera matrix, normalised): one device function serves all three.
+ * Stream-ordered as art_aovs_rays_device; there is no scratch, so the host never waits.  Device 0 under art_init_devices.
+ * Refused before anything is launched, where art_render_aovs_device refuses: a null p or a null array, no scene, no art_resize, a scene
+ * committed through gcore_commit_scene, a pointer that is host memory, another device's memory or too small. */
+int  art_camera_rays_device(const ArtPassParams* p, float* origins3f, float* dirs3f, void* hip_stream);
+
 /* The feature buffers plus a MOTION plane: where each pixel's surface point was one scene update ago, for
  * art_temporal_motion_device to follow geometry that art_refit_device or art_move_instances_device moved.  ONE trace of the camera rays
  * serves all planes: it is art_render_aovs_device's trace, with its slices, its stream rules and its refusals.  out may be NULL, or have
