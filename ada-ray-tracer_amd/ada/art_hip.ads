@@ -316,6 +316,30 @@ package Art_Hip is
                                hip_stream : System.Address) return int;
   pragma Import (C, art_display_device, "art_display_device");
 
+  --  Guided upsampling of a low-resolution render (include/art_hip.h states the arithmetic): lo_color3f at lo_width x lo_height becomes
+  --  out3f at width x height under the feature buffers of both resolutions (Art_Upsample_Guides: DEVICE memory, Null_Address = not
+  --  given, each plane on both sides or on neither).  fallback1b (one byte per hi pixel, may be Null_Address): 0 guided, 1 unguided, 2 black.
+  type Art_Upsample_Jitter is array (0 .. 1) of C_float;
+  pragma Convention (C, Art_Upsample_Jitter);
+  type Art_Upsample_Params is record
+    width, height       : int;      --  the output frame
+    lo_width, lo_height : int;      --  the input frame; 1 .. width and 1 .. height
+    footprint           : int;      --  2 or 4
+    demodulate          : int;      --  1: divide by the lo albedo, multiply by the hi albedo
+    normal_log2         : int;      --  0 .. 10
+    scale               : C_float;  --  the factor on lo_color3f, e.g. 1 / spp
+    sigma_depth         : C_float;  --  <= 0: no depth stop
+    jitter              : Art_Upsample_Jitter;  --  sub-pixel offset of the lo samples, each in (-0.5, 0.5)
+  end record;
+  pragma Convention (C, Art_Upsample_Params);
+  type Art_Upsample_Guides is record
+    albedo3f, normal3f, depth, id : System.Address;
+  end record;
+  pragma Convention (C, Art_Upsample_Guides);
+  function art_upsample_device (p : access constant Art_Upsample_Params; lo_color3f : System.Address; lo, hi : access constant Art_Upsample_Guides;
+                                out3f, fallback1b : System.Address; hip_stream : System.Address) return int;
+  pragma Import (C, art_upsample_device, "art_upsample_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

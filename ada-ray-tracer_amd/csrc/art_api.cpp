@@ -744,6 +744,12 @@ int art_display_device(const ArtDisplayParams* p, const float* color3f, const vo
   return display_device(p, color3f, exposure_state, screen1u, ldr3f, (hipStream_t)hip_stream);
 }
 
+int art_upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const ArtUpsampleGuides* lo, const ArtUpsampleGuides* hi, float* out3f, uint8_t* fallback1b,
+                        void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return upsample_device(p, lo_color3f, lo, hi, out3f, fallback1b, (hipStream_t)hip_stream);
+}
+
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
   return 48 * (int64_t)width * height;

@@ -775,6 +775,71 @@ typedef struct ArtDisplayParams {
 int  art_display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f,
                         void* hip_stream);
 
+/* ---- guided upsampling of a low-resolution render ------------------------------------------------------
+ * Joint bilateral upsampling (Kopf et al. 2007): a colour plane traced at lo_width x lo_height ("lo") becomes a width x height picture
+ * ("hi"), every hi pixel a weighted mean of the lo pixels around it, the weights stopped at edges by feature buffers given at BOTH
+ * resolutions (ArtUpsampleGuides: the planes of art_render_aovs_device at the two viewports; id is any of its int32 planes).  With
+ * demodulation the lo colour is divided by the lo albedo before the mean and the result multiplied by the hi albedo, so albedo detail
+ * comes back at full resolution.  Every pointer is device memory of the library's device, row-major, float3 / float / int32 per pixel;
+ * each guide is given on both sides or on neither.  fallback1b (may be NULL): one byte per hi pixel, 0 = the guides reconstructed the
+ * pixel, 1 = no tap passed the stops and the pixel is the unguided mean, 2 = no tap had a finite colour and the pixel is black; its
+ * non-zero bytes are what art_compact_mask_device selects, for one art_render_pass_masked over the pixels the guides could not fill.
+ * The call needs an initialised device only, no scene and no viewport; it does not touch the accum buffer, spp, ArtStats or
+ * ArtStageStats.  Its scratch is the denoisers' (32 bytes per lo pixel).  Stream order is art_denoise_device's: NULL = the library's
+ * stream, hipStreamLegacy = the null stream; the host waits only when the scratch has to grow.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_upsample.h is its one definition, compiled for the GPU and for the host).  All operations are
+ * binary32, not contracted, in the order written, division correctly rounded, except where binary64 is named.  amax(a, b) = (a >= b) ? a
+ * : b.  finite(v): neither NaN nor an infinity.  W, H = width, height; LW, LH = lo_width, lo_height; p = (x, y) a hi pixel, q a lo pixel.
+ * Mapping, per hi pixel:
+ *   sx = (float)LW / (float)W;   u = ((float)x + 0.5f) * sx - (0.5f + jitter[0]);   i0 = floorf(u);   fx = u - i0.
+ *   sy = (float)LH / (float)H;   v = ((float)y + 0.5f) * sy - (0.5f + jitter[1]);   j0 = floorf(v);   fy = v - j0.
+ * Taps.  footprint 2: a = 0, 1 with kx(a) = (a == 0) ? 1.0f - fx : fx.   footprint 4: a = -1 .. 2 with the tent
+ *   kx(a) = amax(0.0f, 1.0f - fabsf((float)a - fx) / 2.0f).   ky(b) likewise from fy.   h = ky(b) * kx(a) (not normalised: the sum of the
+ *   weights is divided out).  The tap (a, b) reads the lo pixel q = (min(max(i0 + a, 0), LW - 1), min(max(j0 + b, 0), LH - 1)): an index
+ *   outside the lo frame is clamped to it and keeps its weight.  Its offset from p in hi pixels is that of the unclamped position:
+ *   ox = ((float)a - fx) / sx,  oy = ((float)b - fy) / sy.   The taps run with b outer and a inner, each in rising order.
+ * Preparation, once per lo pixel:   c(q) = scale * lo_color(q);   with demodulation c(q) = c(q) / amax(albedo_lo(q), 1e-3f).
+ *   q is BAD IN COLOUR when a channel of c(q) is not finite; BAD IN GUIDES when a given lo normal component or its given lo depth is
+ *   not finite (albedo and id do not count).
+ * Of the hi pixel:   n_p, z_p its given normal and depth;   gx = 0.5f * (z(x1, y) - z(x0, y)) with x1 = min(x + 1, W - 1), x0 = max(x - 1,
+ *   0), gy likewise in y: art_denoise_device's gradient, over the hi depth.   p is BAD when a given component of n_p or z_p is not
+ *   finite, and BACKGROUND when normals are given and n_p == (0, 0, 0) exactly (a miss as art_render_aovs_device writes it).
+ * Guided walk (left folds):  acc = 0, wsum = 0; each tap that is not skipped adds, in tap order,  acc += w * c(q);  wsum += w.
+ *   A bad p skips every tap.  A tap is skipped when q is bad in colour or bad in guides, or when both id planes are given and
+ *   id_lo(q) != id_hi(p).
+ *   p background:  a tap counts only where n_q == (0, 0, 0) exactly, with w = h (no normal and no depth term; the id stop stays).
+ *   otherwise:  wn = amax(dot(n_p, n_q), 0.0f), dot = (px * qx + py * qy) + pz * qz, then wn = wn * wn, normal_log2 times; no normals: wn = 1.
+ *     xz = fabsf(z_p - z_q) / (sigma_depth * (fabsf(gx * ox) + fabsf(gy * oy)) + (1e-3f * z_p + 1e-6f));  no depth, or sigma_depth <= 0: xz = 0.
+ *     t = -((double)xz + 0.0);   e = 0.0f when t < -200, else (float)exp_small(t) when t <= 0, else NaN;   w = (h * wn) * e;   a w that is
+ *     NaN skips the tap.  This is art_denoise_device's tap weight with no colour term (exp_small as stated there), called, not retyped.
+ * Result:   wsum > 0:  out = acc / wsum, fallback 0.   Otherwise the same taps are walked again with w = h, skipping only the taps that
+ *   are bad in colour:  wsum > 0:  out = acc / wsum, fallback 1;  else out = (0, 0, 0), fallback 2.
+ *   With demodulation out = out * amax(albedo_hi(p), 1e-3f) at the end.
+ * With no guide given the result is the plain bilinear (footprint 2) or tent (footprint 4) interpolation of the finite lo pixels.
+ * No finite input of moderate size (no overflow of a sum, unit or zero normals, a finite hi albedo) produces a value that is not
+ * finite: non-finite lo pixels are never read as taps, and non-finite hi guides lead to the unguided mean.
+ * Refused before the device is looked for, with art_last_error set: a null p, lo_color3f, lo, hi or out3f; width or height < 1 or
+ * width * height > 2^28; lo_width outside 1 .. width or lo_height outside 1 .. height; footprint other than 2 or 4; normal_log2 outside
+ * 0..10; a scale that is not finite; a sigma_depth that is NaN; a jitter outside (-0.5, 0.5) or NaN; a guide given on one side only;
+ * demodulate without albedo.  Then: any given pointer that is host memory, another device's memory or too small for its plane; out3f
+ * or fallback1b overlapping an input plane or each other. */
+typedef struct ArtUpsampleParams {
+  int32_t width, height;         /* the output ("hi") frame, row-major */
+  int32_t lo_width, lo_height;   /* the input ("lo") frame; 1 <= lo_width <= width, 1 <= lo_height <= height */
+  int32_t footprint;             /* 2: the 2 x 2 bilinear taps; 4: 4 x 4 taps under a tent of half-width 2 lo pixels */
+  int32_t demodulate;            /* 1 and both albedo planes given: filter colour / albedo_lo, multiply by albedo_hi */
+  int32_t normal_log2;           /* 0..10, as ArtDenoiseParams */
+  float   scale;                 /* lo colour is multiplied by this first (1/spp for an accum) */
+  float   sigma_depth;           /* <= 0: no depth stop */
+  float   jitter[2];             /* sub-pixel offset of the lo samples, in lo pixels, each in (-0.5, 0.5) */
+} ArtUpsampleParams;
+typedef struct ArtUpsampleGuides {   /* device memory; NULL = not given */
+  const float* albedo3f; const float* normal3f; const float* depth; const int32_t* id;
+} ArtUpsampleGuides;
+int  art_upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const ArtUpsampleGuides* lo, const ArtUpsampleGuides* hi,
+                         float* out3f, uint8_t* fallback1b /* or NULL */, void* hip_stream);
+
 /* ---- adaptive sampling ------------------------------------------------------------------------------
  * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
  * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
