@@ -340,6 +340,28 @@ package Art_Hip is
                                 out3f, fallback1b : System.Address; hip_stream : System.Address) return int;
   pragma Import (C, art_upsample_device, "art_upsample_device");
 
+  --  Temporal super-resolution (include/art_hip.h states the arithmetic): a jittered lo frame (lo_color3f, lo_moments2f at lo_width x
+  --  lo_height) is accumulated into a history at t.cur's size; t.cur and t.prev are the UNJITTERED cameras.  Guides: DEVICE memory,
+  --  Null_Address = not given, normal / depth / id on both sides or on neither, motion3f on the hi side only.  The histories are
+  --  art_temporal_device's.  out3f, variance_out, length_out and fallback1b (0 filled, 1 unguided, 2 zero) may be Null_Address.
+  type Art_Temporal_Upsample_Guides is record
+    normal3f, depth, id, motion3f : System.Address;
+  end record;
+  pragma Convention (C, Art_Temporal_Upsample_Guides);
+  type Art_Temporal_Upsample_Params is record
+    t                   : Art_Temporal_Params;
+    lo_width, lo_height : int;
+    jitter              : Art_Upsample_Jitter;  --  this frame's offset of the lo samples, each in (-0.5, 0.5)
+    radius              : C_float;  --  (0, min (width / lo_width, height / lo_height)], in hi pixels
+    min_confidence      : C_float;  --  (0, 1]
+  end record;
+  pragma Convention (C, Art_Temporal_Upsample_Params);
+  function art_temporal_upsample_device (p : access constant Art_Temporal_Upsample_Params; lo_color3f, lo_moments2f : System.Address;
+                                         lo, hi : access constant Art_Temporal_Upsample_Guides;
+                                         hist_in, hist_out, out3f, variance_out, length_out, fallback1b : System.Address;
+                                         hip_stream : System.Address) return int;
+  pragma Import (C, art_temporal_upsample_device, "art_temporal_upsample_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

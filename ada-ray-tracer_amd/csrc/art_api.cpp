@@ -750,6 +750,13 @@ int art_upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, con
   return upsample_device(p, lo_color3f, lo, hi, out3f, fallback1b, (hipStream_t)hip_stream);
 }
 
+int art_temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo_color3f, const float* lo_moments2f, const ArtTemporalUpsampleGuides* lo,
+                                 const ArtTemporalUpsampleGuides* hi, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
+                                 uint8_t* fallback1b, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return temporal_upsample_device(p, lo_color3f, lo_moments2f, lo, hi, hist_in, hist_out, out3f, variance_out, length_out, fallback1b, (hipStream_t)hip_stream);
+}
+
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
   return 48 * (int64_t)width * height;

@@ -282,6 +282,9 @@ int svgf_spatial_variance_device(const ArtSvgfSpatialParams* p, const void* hist
 int auto_exposure_device(const ArtExposureParams* p, const float* color3f, void* state, hipStream_t st);
 int display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f, hipStream_t st);
 int upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const ArtUpsampleGuides* lo, const ArtUpsampleGuides* hi, float* out3f, uint8_t* fallback1b, hipStream_t st);
+int temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo_color3f, const float* lo_moments2f, const ArtTemporalUpsampleGuides* lo,
+                             const ArtTemporalUpsampleGuides* hi, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
+                             uint8_t* fallback1b, hipStream_t st);
 int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);
 int query_rays(const float* o3, const float* d3, const float* tnear, const float* tfar, int64_t n, ArtHit* hits, uint8_t* occluded, int kernel, hipStream_t st);

@@ -2,7 +2,7 @@
 // order: art_trace_rays_device and art_occluded_rays_device (art_query.hip), art_render_aovs_device and art_render_aovs_motion_device
 // (art_aov.hip), art_aovs_rays_device and art_camera_rays_device (art_aov_rays.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
 // art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip), art_auto_exposure_device and
-// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip); with them art_trace_rays, the
+// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip), art_temporal_upsample_device (art_temporal_upsample.hip); with them art_trace_rays, the
 // host-pointer query the device ones are held to.  What they share is written once: the check of a list of the caller's planes
 // (check_planes), growing a scratch while nothing uses it (grow_idle), and the ordered call (ordered_call, art_api_internal.h).  An entry
 // is its own refusals, its plane list, its size arithmetic and its launches; art_render.cpp's mask compaction uses the same pieces.
@@ -24,6 +24,7 @@
 #include "art_shade.h"      // surface_at: trace_rays finishes its hit records on the host
 #include "art_svgf_spatial.h"
 #include "art_temporal.h"
+#include "art_temporal_upsample.h"
 #include "art_upsample.h"
 
 namespace art {
@@ -460,6 +461,34 @@ int upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const A
   return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, 2 * NL * sizeof(us::Rec4)}}, [&](hipStream_t qs) {
     A.lo_c = (us::Rec4*)c.b_denoise.p; A.lo_g = A.lo_c + NL;
     launch_upsample(qs, A);
+    return 0;
+  });
+}
+
+// art_temporal_upsample_device: the pack kernel over the lo frame into the denoisers' scratch (b_denoise: three records per lo pixel),
+// then one kernel over the hi frame and the two histories (art_temporal_upsample.h).
+int temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo_color3f, const float* lo_moments2f, const ArtTemporalUpsampleGuides* lo,
+                             const ArtTemporalUpsampleGuides* hi, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
+                             uint8_t* fallback1b, hipStream_t st) {
+  const std::string name = "art_temporal_upsample_device";
+  TemporalUpsampleArgs A; std::memset((void*)&A, 0, sizeof A);
+  if (const char* why = tu::params_from_abi(p, lo_color3f, lo_moments2f, lo, hi, hist_in, hist_out, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.T.cur.W * (size_t)A.P.T.cur.H, NP = (size_t)A.P.T.prev.W * (size_t)A.P.T.prev.H, NL = (size_t)A.P.LW * (size_t)A.P.LH;
+  if (check_planes({{lo_color3f, 12 * NL, "lo_color3f"}, {lo_moments2f, 8 * NL, "lo_moments2f"}, {lo->normal3f, 12 * NL, "lo normal3f"}, {lo->depth, 4 * NL, "lo depth"},
+                    {lo->id, 4 * NL, "lo id"}, {hi->normal3f, 12 * N, "hi normal3f"}, {hi->depth, 4 * N, "hi depth"}, {hi->id, 4 * N, "hi id"},
+                    {hi->motion3f, 12 * N, "hi motion3f"}, {hist_in, 48 * NP, "hist_in"}, {hist_out, 48 * N, "hist_out"}, {out3f, 12 * N, "out3f"},
+                    {variance_out, 4 * N, "variance_out"}, {length_out, 4 * N, "length_out"}, {fallback1b, N, "fallback1b"}}))
+    return 1;
+  if (const char* why = tu::overlap_refusal(A.P, lo_color3f, lo_moments2f, lo, hi, hist_in, hist_out, out3f, variance_out, length_out, fallback1b)) return fail(name + ": " + why);
+  A.lo_color = lo_color3f; A.lo_moments = lo_moments2f; A.lo_normal = lo->normal3f; A.lo_depth = lo->depth; A.lo_id = lo->id;
+  A.normal = hi->normal3f; A.depth = hi->depth; A.id = hi->id; A.motion = hi->motion3f;
+  A.hist_in = (const tu::Rec4*)hist_in; A.hist_out = (tu::Rec4*)hist_out;
+  A.out = out3f; A.variance_out = variance_out; A.length_out = length_out; A.fallback = fallback1b;
+  return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, 3 * NL * sizeof(tu::Rec4)}}, [&](hipStream_t qs) {
+    A.lo_a = (tu::Rec4*)c.b_denoise.p; A.lo_b = A.lo_a + NL; A.lo_c = A.lo_b + NL;
+    launch_temporal_upsample(qs, A);
     return 0;
   });
 }

@@ -840,6 +840,81 @@ typedef struct ArtUpsampleGuides {   /* device memory; NULL = not given */
 int  art_upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const ArtUpsampleGuides* lo, const ArtUpsampleGuides* hi,
                          float* out3f, uint8_t* fallback1b /* or NULL */, void* hip_stream);
 
+/* ---- temporal super-resolution: jittered lo frames accumulated into a hi history -------------------------
+ * Each frame is traced at lo_width x lo_height ("lo") with the lo grid moved by a sub-pixel jitter, and every lo sample is put into a
+ * history at t.cur.width x t.cur.height ("hi") at the place it was taken: art_temporal_device's accumulation, fed by art_upsample_device's
+ * mapping.  Over a few frames every hi pixel has been sampled near its own centre.  lo_color3f and lo_moments2f are the lo frame's colour
+ * and luminance moments (art_bind_accum / art_bind_moments at the lo viewport; t.scale and t.n_colours as in art_temporal_device).  The
+ * guides (ArtTemporalUpsampleGuides: normal, depth, an int32 id plane) are given at BOTH resolutions or at neither -- the lo ones traced
+ * with the jittered camera, the hi ones with the unjittered camera; motion3f is the hi frame's plane of art_render_aovs_motion_device
+ * (lo->motion3f must be NULL).  t.cur and t.prev are the UNJITTERED cameras at the HI size.  The histories are art_temporal_device's,
+ * word for word, at the hi size (art_temporal_history_bytes(width, height), three planes of 16-byte records): hist_out and variance_out
+ * feed art_svgf_spatial_variance_device, art_denoise_svgf_var_device and a later art_temporal_device unchanged.  out3f, variance_out,
+ * length_out and fallback1b may each be NULL.  fallback1b: one byte per hi pixel, 0 = filled by counting samples or by the history,
+ * 1 = no history and no sample passed the tests, the pixel is the unguided mean of the lo samples around it, 2 = none of them had a finite
+ * colour, the record is zero; its non-zero bytes are a mask for art_compact_mask_device / art_render_pass_masked.
+ * Scene-independent, stream-ordered like art_upsample_device, no ArtStats.  The call USES LIBRARY SCRATCH (the denoisers', 48 bytes per
+ * lo pixel): the host waits only when that scratch has to grow.  Albedo demodulation is NOT in this call: divide the lo colour by the lo
+ * albedo before it and multiply out3f by the hi albedo after it.
+ * Compulsory traffic: 137 bytes per hi pixel (149 with motion3f) and 136 per lo pixel: 171 per hi pixel at a ratio of 2.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_temporal_upsample.h is its one definition, compiled for the GPU and for the host).  Binary32,
+ * not contracted, in the order written, division and sqrtf correctly rounded, except where binary64 is named.  dot, finite, n_cur and the
+ * cameras are art_temporal_device's; amax(a, b) = (a >= b) ? a : b.  W, H = t.cur.width, t.cur.height; LW, LH = lo_width, lo_height.
+ * Preparation, once per lo pixel q:  c(q) = scale * lo_color(q);  m1(q) = S1 / n_cur;  m2(q) = S2 / n_cur.  q is BAD IN COLOUR when a
+ *   channel of c, m1 or m2 is not finite; BAD IN GUIDES when a given lo normal component or its given lo depth is not finite.
+ * Of the hi pixel p = (x, y):  z, id, N = the hi guides (+0.0f, 0, (0, 0, 0) where a plane is not given).  p is BAD when its given depth or
+ *   a given normal component is not finite; p is a MISS when depth is given and !(z > 0).
+ * A. This frame.
+ *   sx = (float)LW / (float)W;  u = ((float)x + 0.5f) * sx - (0.5f + jitter[0]);  i0 = floorf(u);  fx = u - i0;  likewise sy, v, j0, fy
+ *   (art_upsample_device's mapping).  The taps t = 0..3 in art_temporal_device's order: (a, b) = (t & 1, t >> 1) at lo pixel
+ *   q = (i0 + a, j0 + b).  A tap outside the lo frame is SKIPPED, not clamped.
+ *   dx = ((float)a - fx) / sx;  dy = ((float)b - fy) / sy   (the sample's offset from the pixel centre, in hi pixels);
+ *   k = amax(0.0f, 1.0f - fabsf(dx) / radius) * amax(0.0f, 1.0f - fabsf(dy) / radius)      (the narrow weight);
+ *   h = (a ? fx : 1.0f - fx) * (b ? fy : 1.0f - fy)                                            (the wide weight).
+ *   A tap COUNTS when it is inside the lo frame; q is neither bad in colour nor bad in guides; p is not bad; with ids, id_lo(q) == id;
+ *   and, for a p that is not a miss: with normals, dot(N, N_lo(q)) >= normal_min; with depth, fabsf(z_lo(q) - z) <= depth_tol * z;
+ *   for a p that is a miss, instead of those two: !(z_lo(q) > 0) (a hi miss counts lo misses only).
+ *   Left folds in tap order, each from 0:  over the counting taps with k > 0:  K += k;  Ck += k * c(q), likewise M1k, M2k;
+ *   over the counting taps with h > 0:  Hs += h;  Ch += h * c(q), likewise M1h, M2h;
+ *   over the taps inside the lo frame that are not bad in colour, with h > 0:  Us += h;  Cu += h * c(q), likewise M1u, M2u.
+ *   kappa = (K < 1.0f) ? K : 1.0f;   n_eff = kappa * n_cur.   (radius <= min(W / LW, H / LH): the 2 x 2 taps hold every sample the tent
+ *   reaches, and K <= 1 up to rounding.)
+ * B. History.  art_temporal_device's steps 2 to 4 on the hi guides, t.cur and t.prev, word for word (with motion3f:
+ *   art_temporal_motion_device's three changes of step 3): (hist, n_h), or NO HISTORY.
+ * C. Combine.
+ *   History and K > 0:   c = Ck / K, m1 = M1k / K, m2 = M2k / K;   cap = (float)max_history - n_eff;   f = (n_h > cap) ? cap / n_h : 1.0f;
+ *     n = n_eff + f * n_h;   a = n_eff / n;   b = 1.0f - a;   colour = a * c + b * hist.colour;   m1 = a * m1 + b * hist.m1;   m2 likewise
+ *     (art_temporal_device's step 5 with n_eff for n_cur).
+ *   History and K == 0:  colour, m1, m2 = hist's;   f = (n_h > (float)max_history) ? (float)max_history / n_h : 1.0f;   n = f * n_h.
+ *   No history and Hs > 0:   colour = Ch / Hs, m1 = M1h / Hs, m2 = M2h / Hs;   n = n_cur * amax(kappa, min_confidence).
+ *   No history, Hs == 0 and Us > 0:   colour = Cu / Us, m1 = M1u / Us, m2 = M2u / Us;   n = n_cur * min_confidence;   fallback = 1.
+ *   None of these:   colour, m1, m2, n = 0;   fallback = 2.  (No later frame counts a record with n = 0.)      Otherwise fallback = 0.
+ * D. Outputs: art_temporal_device's step 6.  hist_out: plane 0 {colour, n}, plane 1 {m1, m2, z, id}, plane 2 {N, 0} -- the HI guides.
+ *   out3f = colour, length_out = n, variance_out = +infinity where n < 2, else the binary64 expression of step 6.
+ * With lo size == hi size, jitter 0 and inputs that are finite and pass their own pixel's tests, u = x exactly, only tap (0, 0) has a
+ * weight, k = h = 1, and the call gives art_temporal_device's (art_temporal_motion_device's) bits for every radius (a colour of -0.0f
+ * comes out as +0.0f: it went through 0 + 1 * c).
+ * Refused before anything is launched, with art_last_error set: a null p, lo_color3f, lo_moments2f, lo, hi or hist_out; a guide given on
+ * one side only; lo->motion3f not NULL; everything art_temporal_device refuses for t at the hi size (with hi->motion3f as the motion
+ * plane); lo_width outside 1 .. width or lo_height outside 1 .. height; a jitter outside (-0.5, 0.5) or NaN; radius outside
+ * (0, min((float)W / (float)LW, (float)H / (float)LH)] or NaN; min_confidence outside (0, 1] or NaN.  Then: any given pointer that is host
+ * memory, another device's memory or too small for its plane; an output overlapping an input plane or another output. */
+typedef struct ArtTemporalUpsampleGuides {   /* device memory; NULL = not given */
+  const float* normal3f; const float* depth; const int32_t* id; const float* motion3f;
+} ArtTemporalUpsampleGuides;
+typedef struct ArtTemporalUpsampleParams {
+  ArtTemporalParams t;        /* cur / prev: the UNJITTERED cameras at the HI size; n_colours, max_history, scale, depth_tol, normal_min as in art_temporal_device */
+  int32_t lo_width, lo_height;
+  float   jitter[2];          /* offset of this frame's lo samples, in lo pixels, inside (-0.5, 0.5): art_upsample_device's convention */
+  float   radius;             /* half-width in HI pixels of the tent a lo sample is splatted with */
+  float   min_confidence;     /* in (0, 1]: the history length, as a share of n_colours, of a pixel filled without history */
+} ArtTemporalUpsampleParams;
+int  art_temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo_color3f, const float* lo_moments2f,
+                                  const ArtTemporalUpsampleGuides* lo, const ArtTemporalUpsampleGuides* hi,
+                                  const void* hist_in /* or NULL */, void* hist_out, float* out3f, float* variance_out, float* length_out,
+                                  uint8_t* fallback1b, void* hip_stream);
+
 /* ---- adaptive sampling ------------------------------------------------------------------------------
  * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
  * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
