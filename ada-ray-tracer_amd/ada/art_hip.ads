@@ -362,6 +362,24 @@ package Art_Hip is
                                          hip_stream : System.Address) return int;
   pragma Import (C, art_temporal_upsample_device, "art_temporal_upsample_device");
 
+  --  Firefly suppression ahead of temporal accumulation (include/art_hip.h states the arithmetic): a pixel whose luminance exceeds
+  --  gain * (the rank-th largest luminance among its neighbours) + floor is scaled down to that limit, its moments with it.  Planes:
+  --  DEVICE memory; moments2f and moments_out2f are both given or both Null_Address; id and clamped1b (0 kept, 1 clamped, 2 not finite)
+  --  may be Null_Address.  out3f may be color3f and moments_out2f may be moments2f.  out3f holds the SCALED colour.
+  type Art_Firefly_Params is record
+    width, height : int;
+    radius        : int;      --  1 or 2
+    rank          : int;      --  1 .. 4
+    min_count     : int;      --  rank .. (2 * radius + 1) ** 2 - 1
+    scale         : C_float;  --  the factor on color3f, e.g. 1 / spp
+    gain          : C_float;  --  finite, >= 1
+    floor         : C_float;  --  finite, >= 0
+  end record;
+  pragma Convention (C, Art_Firefly_Params);
+  function art_firefly_device (p : access constant Art_Firefly_Params; color3f, moments2f, id, out3f, moments_out2f, clamped1b : System.Address;
+                               hip_stream : System.Address) return int;
+  pragma Import (C, art_firefly_device, "art_firefly_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

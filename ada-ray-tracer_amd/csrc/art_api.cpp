@@ -757,6 +757,12 @@ int art_temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float
   return temporal_upsample_device(p, lo_color3f, lo_moments2f, lo, hi, hist_in, hist_out, out3f, variance_out, length_out, fallback1b, (hipStream_t)hip_stream);
 }
 
+int art_firefly_device(const ArtFireflyParams* p, const float* color3f, const float* moments2f, const int32_t* id, float* out3f, float* moments_out2f, uint8_t* clamped1b,
+                       void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return firefly_device(p, color3f, moments2f, id, out3f, moments_out2f, clamped1b, (hipStream_t)hip_stream);
+}
+
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
   return 48 * (int64_t)width * height;

@@ -2,7 +2,7 @@
 // order: art_trace_rays_device and art_occluded_rays_device (art_query.hip), art_render_aovs_device and art_render_aovs_motion_device
 // (art_aov.hip), art_aovs_rays_device and art_camera_rays_device (art_aov_rays.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
 // art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip), art_auto_exposure_device and
-// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip), art_temporal_upsample_device (art_temporal_upsample.hip); with them art_trace_rays, the
+// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip), art_temporal_upsample_device (art_temporal_upsample.hip), art_firefly_device (art_firefly.hip); with them art_trace_rays, the
 // host-pointer query the device ones are held to.  What they share is written once: the check of a list of the caller's planes
 // (check_planes), growing a scratch while nothing uses it (grow_idle), and the ordered call (ordered_call, art_api_internal.h).  An entry
 // is its own refusals, its plane list, its size arithmetic and its launches; art_render.cpp's mask compaction uses the same pieces.
@@ -19,6 +19,7 @@
 #include "art_adaptive.h"
 #include "art_denoise.h"
 #include "art_display.h"
+#include "art_firefly.h"
 #include "art_motion.h"
 #include "art_query.h"
 #include "art_shade.h"      // surface_at: trace_rays finishes its hit records on the host
@@ -489,6 +490,27 @@ int temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo
   return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, 3 * NL * sizeof(tu::Rec4)}}, [&](hipStream_t qs) {
     A.lo_a = (tu::Rec4*)c.b_denoise.p; A.lo_b = A.lo_a + NL; A.lo_c = A.lo_b + NL;
     launch_temporal_upsample(qs, A);
+    return 0;
+  });
+}
+
+// art_firefly_device: the key kernel over the frame into the denoisers' scratch (b_denoise: one float per pixel), then the window kernel
+// over 16 x 16 tiles (art_firefly.h).
+int firefly_device(const ArtFireflyParams* p, const float* color3f, const float* moments2f, const int32_t* id, float* out3f, float* moments_out2f, uint8_t* clamped1b, hipStream_t st) {
+  const std::string name = "art_firefly_device";
+  FireflyArgs A; std::memset((void*)&A, 0, sizeof A);
+  if (const char* why = fi::params_from_abi(p, color3f, moments2f, out3f, moments_out2f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_planes({{color3f, 12 * N, "color3f"}, {moments2f, 8 * N, "moments2f"}, {id, 4 * N, "id"}, {out3f, 12 * N, "out3f"}, {moments_out2f, 8 * N, "moments_out2f"},
+                    {clamped1b, N, "clamped1b"}}))
+    return 1;
+  if (const char* why = fi::overlap_refusal(A.P, color3f, moments2f, id, out3f, moments_out2f, clamped1b)) return fail(name + ": " + why);
+  A.color = color3f; A.moments = moments2f; A.id = id; A.out = out3f; A.moments_out = moments_out2f; A.clamped = clamped1b;
+  return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, N * sizeof(float)}}, [&](hipStream_t qs) {
+    A.keys = (float*)c.b_denoise.p;
+    launch_firefly(qs, A);
     return 0;
   });
 }

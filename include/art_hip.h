@@ -915,6 +915,59 @@ int  art_temporal_upsample_device(const ArtTemporalUpsampleParams* p, const floa
                                   const void* hist_in /* or NULL */, void* hist_out, float* out3f, float* variance_out, float* length_out,
                                   uint8_t* fallback1b, void* hip_stream);
 
+/* ---- firefly suppression ahead of temporal accumulation ------------------------------------------------
+ * A path that finds the light through a specular chain puts one pixel far above its neighbours; blended into a history it glows for
+ * max_history frames and inflates the variance the filters are guided by.  This call takes such outliers out of the FRAME, before
+ * art_temporal_device: a pixel whose luminance exceeds a limit made from the rank-th largest luminance among its neighbours is scaled
+ * down to that limit, its moments with it.  It goes between the render pass and art_temporal_device / art_temporal_upsample_device.
+ * color3f (3 floats per pixel), moments2f ({S1, S2} per pixel in art_bind_moments' convention, or NULL), id (an int32 plane, e.g.
+ * ArtAovBuffers::prim_index, or NULL: every neighbour counts), out3f, moments_out2f (NULL if and only if moments2f is NULL) and
+ * clamped1b (one byte per pixel, or NULL): row-major device memory of the library's device.  out3f may BE color3f and moments_out2f
+ * may BE moments2f (the same address): the window reads a key plane in the library's scratch, never the colour, and a pixel reads its
+ * own words before it writes them.  An output plane that overlaps any other plane in any other way is refused.
+ * The call needs an initialised device only, no scene and no viewport; it does not touch the accum buffer, spp, ArtStats or
+ * ArtStageStats.  Its scratch is the denoisers' (4 bytes per pixel).  Stream order is art_denoise_device's: NULL = the library's
+ * stream, hipStreamLegacy = the null stream; the host waits only when the scratch has to grow.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_firefly.h is its one definition, compiled for the GPU and for the host).  All operations are
+ * binary32, not contracted, in the order written, division correctly rounded.  amax(a, b) = (a >= b) ? a : b.  finite(v): neither NaN
+ * nor an infinity.  lum3(r, g, b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b, the filters' luminance.  QNAN = the word 0x7fc00000.
+ * Key, per pixel q:   c(q) = scale * color(q) per channel;   l(q) = lum3(c(q)).   q is BAD when a channel of c(q) or l(q) is not
+ *   finite.   key(q) = l(q), or QNAN for a bad pixel.
+ * Neighbours of p = (x, y):   the q = (x + dx, y + dy) with |dx| <= radius, |dy| <= radius, q != p, that lie inside the frame and are
+ *   not bad; with id given only those with id(q) == id(p).   count = how many there are.
+ * Limit:   m = the rank-th largest of the neighbours' keys (equal keys each take a place; it is a function of the values alone, so no
+ *   order of visiting changes it; -infinity when count < rank, which min_count keeps from being used).
+ *   T = amax(gain * m + (floor + 0.0f), 0.0f)    (the + 0.0f makes a floor of -0.0f a +0.0f: T never carries the sign of a zero key).
+ * Result:
+ *   p bad:                                   out = c(p),  moments_out = moments,  clamped = 2   (the later calls repair such pixels)
+ *   count < min_count,  or  !(l(p) > T):     out = c(p),  moments_out = moments,  clamped = 0
+ *   otherwise:   f = T / l(p);   out = f * c(p) per channel;   moments_out = (f * S1, (f * f) * S2);   clamped = 1
+ *     -- every sample of the pixel scaled by f, so art_temporal_device sees moments consistent with the colour it is given.
+ *   "moments_out = moments" copies the two words as they are.  Every word of out3f that is a NaN, and every word of moments_out2f
+ *   that is computed (clamped = 1) and is a NaN, is stored as QNAN (processors differ in the sign and payload they give one).
+ * Since l(p) > T >= 0 at a clamped pixel, 0 <= f < 1: no finite input produces an output that is not finite, and the call never
+ * raises a value.  A frame of equal keys is left alone at gain 1 (l > T is false), and so is a black frame at floor 0.
+ * The non-zero bytes of clamped1b are what art_compact_mask_device selects: one art_render_pass_masked over the clamped (and bad)
+ * pixels gives them more samples where that is wanted.  out3f holds the SCALED colour: the calls after this one take scale = 1.
+ * Refused before the device is looked for, with art_last_error set: a null p, color3f or out3f; moments_out2f given without moments2f
+ * or moments2f without moments_out2f; width or height < 1 or width * height > 2^28; radius other than 1 or 2; rank outside 1 .. 4;
+ * min_count outside rank .. (2 * radius + 1)^2 - 1; a scale that is not finite; a gain that is not finite or below 1; a floor that is
+ * not finite or below 0.  Then: any given pointer that is host memory, another device's memory or too small for its plane; an output
+ * plane overlapping another plane (other than out3f == color3f and moments_out2f == moments2f). */
+typedef struct ArtFireflyParams {
+  int32_t width, height;
+  int32_t radius;            /* 1 or 2: the 3 x 3 or the 5 x 5 window */
+  int32_t rank;              /* 1..4: the limit comes from the rank-th largest neighbour (2 lets one neighbouring firefly pass) */
+  int32_t min_count;         /* rank .. (2 * radius + 1)^2 - 1: a pixel with fewer neighbours is left alone */
+  float   scale;             /* colour is multiplied by this first (1 / spp for an accum buffer) */
+  float   gain;              /* finite, >= 1: how far above the rank-th neighbour a pixel may stand */
+  float   floor;             /* finite, >= 0: added to the limit, so dark surroundings do not clamp to black */
+} ArtFireflyParams;
+int  art_firefly_device(const ArtFireflyParams* p, const float* color3f, const float* moments2f /* or NULL */, const int32_t* id /* or NULL */,
+                        float* out3f, float* moments_out2f /* NULL iff moments2f is NULL */, uint8_t* clamped1b /* or NULL */,
+                        void* hip_stream);
+
 /* ---- adaptive sampling ------------------------------------------------------------------------------
  * Three calls: a byte mask over the frame is compacted into a pixel list, a render pass runs over the pixels of a mask only, and one
  * kernel turns accum, moments and per-pixel sample counts into the mean, its variance, a relative error and the next mask.
