@@ -22,6 +22,7 @@ from . import aov_rays      # art_aovs_rays_device, art_camera_rays_device: thei
 from . import display       # art_auto_exposure_device, art_display_device: their structs and constants, Backend.exposure_state, auto_exposure_torch, display_torch
 from . import upsample      # art_upsample_device: its structs and Backend.upsample_torch
 from . import firefly       # art_firefly_device: its struct, its defaults and Backend.firefly_torch
+from . import bloom         # art_bloom_device: its struct, its defaults and Backend.bloom_torch
 from . import temporal_upsample      # art_temporal_upsample_device: its structs, Backend.temporal_upsample_torch, jitter_sequence, jittered_camera
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -259,7 +260,7 @@ EXPORTED_SYMBOLS = [
     "art_init", "art_init_devices", "art_device_count", "art_reduce", "art_get_reduce_info", "art_set_stream", "art_upload_scene", "art_resize", "art_set_shard", "art_render_pass",
     "art_debug_hit_pass", "art_bind_accum", "art_bind_moments", "art_accum_device", "art_download", "art_synchronize", "art_trace_rays",
     "art_trace_rays_device", "art_occluded_rays_device", "art_aovs_rays_device", "art_camera_rays_device", "art_render_aovs_device", "art_render_aovs_motion_device", "art_denoise_device", "art_denoise_svgf_device", "art_denoise_svgf_var_device", "art_temporal_device", "art_temporal_motion_device", "art_temporal_history_bytes", "art_svgf_spatial_variance_device", "art_set_camera",
-    "art_exposure_state_bytes", "art_auto_exposure_device", "art_display_device", "art_upsample_device", "art_temporal_upsample_device", "art_firefly_device",
+    "art_exposure_state_bytes", "art_auto_exposure_device", "art_display_device", "art_upsample_device", "art_temporal_upsample_device", "art_firefly_device", "art_bloom_device",
     "art_compact_mask_device", "art_render_pass_masked", "art_adaptive_estimate_device", "art_radiance_rays_device",
     "art_refit_device", "art_get_refit_info",
     "art_rebuild_device", "art_get_rebuild_info", "art_get_tree_cost", "art_move_instances_device", "art_get_move_info",
@@ -324,6 +325,7 @@ def load_library():
     L.art_upsample_device.argtypes = [C.POINTER(upsample.ArtUpsampleParams), C.c_void_p, C.POINTER(upsample.ArtUpsampleGuides), C.POINTER(upsample.ArtUpsampleGuides),
                                       C.c_void_p, C.c_void_p, C.c_void_p]
     L.art_firefly_device.argtypes = [C.POINTER(firefly.ArtFireflyParams)] + [C.c_void_p] * 7
+    L.art_bloom_device.argtypes = [C.POINTER(bloom.ArtBloomParams)] + [C.c_void_p] * 5
     L.art_temporal_upsample_device.argtypes = [C.POINTER(temporal_upsample.params_struct()), C.c_void_p, C.c_void_p, C.POINTER(temporal_upsample.ArtTemporalUpsampleGuides),
                                                C.POINTER(temporal_upsample.ArtTemporalUpsampleGuides)] + [C.c_void_p] * 7
     L.art_temporal_history_bytes.argtypes = [C.c_int32, C.c_int32]
@@ -553,7 +555,7 @@ class SceneDesc:
         self.desc = d
 
 
-class Backend(radiance.RadianceQueries, display.DisplayCalls, aov_rays.AovRayCalls, upsample.UpsampleCalls, temporal_upsample.TemporalUpsampleCalls, firefly.FireflyCalls):
+class Backend(radiance.RadianceQueries, display.DisplayCalls, aov_rays.AovRayCalls, upsample.UpsampleCalls, temporal_upsample.TemporalUpsampleCalls, firefly.FireflyCalls, bloom.BloomCalls):
     """One process-wide backend instance (the C library is a singleton, like g_data / ray_tracer.ads globals)."""
 
     def __init__(self, device=-1, devices=None):

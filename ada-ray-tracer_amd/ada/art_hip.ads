@@ -380,6 +380,27 @@ package Art_Hip is
                                hip_stream : System.Address) return int;
   pragma Import (C, art_firefly_device, "art_firefly_device");
 
+  --  Bloom ahead of the display transform (include/art_hip.h states the arithmetic): the frame is filtered down a pyramid of halved
+  --  levels, the levels are blended back up with scatter, and the result B is mixed in: out = s + strength * (B - s).  Planes: DEVICE
+  --  memory, three floats per pixel; exposure_state (the state of art_auto_exposure_device) may be Null_Address = the record's
+  --  exposure; out3f and bloom3f (B alone) may each be Null_Address, not both; out3f may be color3f.  out3f holds the SCALED colour.
+  type Art_Bloom_Params is record
+    width, height : int;
+    levels        : int;      --  1 .. 8
+    karis         : int;      --  0 / 1: the first downsample weights its five boxes by 1 / (1 + luminance)
+    variant       : int;      --  0: the small levels in one workgroup; 1: one launch per level; the same words
+    scale         : C_float;  --  the factor on color3f, e.g. 1 / spp
+    exposure      : C_float;  --  used when exposure_state is Null_Address; only the threshold reads it
+    threshold     : C_float;  --  finite, >= 0: the soft threshold on exposure * luminance
+    knee          : C_float;  --  finite, >= 0
+    scatter       : C_float;  --  0 .. 1
+    strength      : C_float;  --  0 .. 1
+  end record;
+  pragma Convention (C, Art_Bloom_Params);
+  function art_bloom_device (p : access constant Art_Bloom_Params; color3f, exposure_state, out3f, bloom3f : System.Address;
+                             hip_stream : System.Address) return int;
+  pragma Import (C, art_bloom_device, "art_bloom_device");
+
   --  Adaptive sampling (include/art_hip.h states the contracts and the arithmetic).  mask1b: one byte per pixel of the frame, row-major,
   --  DEVICE memory, non-zero = selected.  art_compact_mask_device: the selected pixels of this rank's list, in list order, into pixels_out
   --  (cap words, DEVICE memory) and their number into count_out (one DEVICE word).

@@ -763,6 +763,11 @@ int art_firefly_device(const ArtFireflyParams* p, const float* color3f, const fl
   return firefly_device(p, color3f, moments2f, id, out3f, moments_out2f, clamped1b, (hipStream_t)hip_stream);
 }
 
+int art_bloom_device(const ArtBloomParams* p, const float* color3f, const void* exposure_state, float* out3f, float* bloom3f, void* hip_stream) {
+  std::lock_guard<std::mutex> lk(g_mu);          // like the ray queries, on device 0
+  return bloom_device(p, color3f, exposure_state, out3f, bloom3f, (hipStream_t)hip_stream);
+}
+
 int64_t art_temporal_history_bytes(int32_t width, int32_t height) {
   if (width < 1 || height < 1 || (int64_t)width * height > (1ll << 28)) return 0;
   return 48 * (int64_t)width * height;

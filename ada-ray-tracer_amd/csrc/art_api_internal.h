@@ -285,6 +285,7 @@ int upsample_device(const ArtUpsampleParams* p, const float* lo_color3f, const A
 int temporal_upsample_device(const ArtTemporalUpsampleParams* p, const float* lo_color3f, const float* lo_moments2f, const ArtTemporalUpsampleGuides* lo,
                              const ArtTemporalUpsampleGuides* hi, const void* hist_in, void* hist_out, float* out3f, float* variance_out, float* length_out,
                              uint8_t* fallback1b, hipStream_t st);
+int bloom_device(const ArtBloomParams* p, const float* color3f, const void* exposure_state, float* out3f, float* bloom3f, hipStream_t st);
 int firefly_device(const ArtFireflyParams* p, const float* color3f, const float* moments2f, const int32_t* id, float* out3f, float* moments_out2f, uint8_t* clamped1b, hipStream_t st);
 int debug_pass(const ArtPassParams* p, float* accum_host, uint32_t* screen_host, int32_t* prim_index, int32_t* mat_id, int32_t* prim_type);
 int trace_rays(const float* origins, const float* dirs, const float* tfar, int64_t n, ArtHit* out, int kernel, ArtStats* st);

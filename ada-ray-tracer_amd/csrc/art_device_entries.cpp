@@ -2,7 +2,7 @@
 // order: art_trace_rays_device and art_occluded_rays_device (art_query.hip), art_render_aovs_device and art_render_aovs_motion_device
 // (art_aov.hip), art_aovs_rays_device and art_camera_rays_device (art_aov_rays.hip), the three a-trous filters (art_denoise.hip), art_temporal_device and art_temporal_motion_device (art_temporal.hip),
 // art_adaptive_estimate_device (art_adaptive.hip), art_svgf_spatial_variance_device (art_svgf_spatial.hip), art_auto_exposure_device and
-// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip), art_temporal_upsample_device (art_temporal_upsample.hip), art_firefly_device (art_firefly.hip); with them art_trace_rays, the
+// art_display_device (art_display.hip), art_upsample_device (art_upsample.hip), art_temporal_upsample_device (art_temporal_upsample.hip), art_firefly_device (art_firefly.hip), art_bloom_device (art_bloom.hip); with them art_trace_rays, the
 // host-pointer query the device ones are held to.  What they share is written once: the check of a list of the caller's planes
 // (check_planes), growing a scratch while nothing uses it (grow_idle), and the ordered call (ordered_call, art_api_internal.h).  An entry
 // is its own refusals, its plane list, its size arithmetic and its launches; art_render.cpp's mask compaction uses the same pieces.
@@ -17,6 +17,7 @@
 
 #include "art_api_internal.h"
 #include "art_adaptive.h"
+#include "art_bloom.h"
 #include "art_denoise.h"
 #include "art_display.h"
 #include "art_firefly.h"
@@ -511,6 +512,24 @@ int firefly_device(const ArtFireflyParams* p, const float* color3f, const float*
   return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, N * sizeof(float)}}, [&](hipStream_t qs) {
     A.keys = (float*)c.b_denoise.p;
     launch_firefly(qs, A);
+    return 0;
+  });
+}
+
+// art_bloom_device: the pyramid in the denoisers' scratch (b_denoise: one 16-byte record per texel of levels 1 .. M), the downsamples,
+// the tail or the per-level blends, the mix (art_bloom.h).
+int bloom_device(const ArtBloomParams* p, const float* color3f, const void* exposure_state, float* out3f, float* bloom3f, hipStream_t st) {
+  const std::string name = "art_bloom_device";
+  BloomArgs A; std::memset((void*)&A, 0, sizeof A);
+  if (const char* why = bl::params_from_abi(p, color3f, exposure_state, out3f, bloom3f, A.P)) return fail(name + ": " + why);      // (before the device is looked for)
+  if (ensure_device()) return 1;
+  Ctx& c = g_ctx;
+  const size_t N = (size_t)A.P.W * (size_t)A.P.H;
+  if (check_planes({{color3f, 12 * N, "color3f"}, {exposure_state, bl::kStateBytes, "exposure_state"}, {out3f, 12 * N, "out3f"}, {bloom3f, 12 * N, "bloom3f"}})) return 1;
+  A.color = color3f; A.state = (const uint32_t*)exposure_state; A.out = out3f; A.bloom = bloom3f;
+  return ordered_call(name.c_str(), st, GrowList{Grow{&c.b_denoise, (size_t)A.P.off[A.P.made + 1] * sizeof(bl::Rec4)}}, [&](hipStream_t qs) {
+    A.pyr = (bl::Rec4*)c.b_denoise.p;
+    launch_bloom(qs, A);
     return 0;
   });
 }

@@ -775,6 +775,68 @@ typedef struct ArtDisplayParams {
 int  art_display_device(const ArtDisplayParams* p, const float* color3f, const void* exposure_state, uint32_t* screen1u, float* ldr3f,
                         void* hip_stream);
 
+/* ---- bloom: the glare of bright pixels, ahead of the display transform --------------------------------
+ * art_display_device clips a light to a flat white disc; the cue for "brighter than white" is the light a lens scatters around such
+ * pixels.  This call makes it (Jimenez 2014): the frame is filtered down a pyramid of halved levels, the levels are blended
+ * back up into each other, and the result is mixed into the frame.  It goes between the filters and art_auto_exposure_device /
+ * art_display_device.  color3f, out3f and bloom3f (each three floats per pixel, row-major; out3f and bloom3f may each be NULL, not
+ * both) are device memory of the library's device; exposure_state is the state of art_auto_exposure_device, whose word 0 is then the
+ * exposure e (read on the device), or NULL = p->exposure.  out3f may BE color3f: a pixel reads its own words before it writes them and
+ * every neighbour is read from the pyramid.  An output that overlaps anything in any other way is refused.  bloom3f receives the
+ * scattered light alone.  Scene-independent like the denoisers: an initialised device only, no viewport; the accum buffer, spp,
+ * ArtStats and ArtStageStats are not touched.  The pyramid is 16-byte records {r, g, b, +0} in the denoisers' scratch (about 5.4 bytes
+ * per frame pixel); stream order and pointer rules are art_firefly_device's: the host waits only when the scratch has to grow.
+ *
+ * THE ARITHMETIC (the contract; csrc/art_bloom.h is its one definition, compiled for the GPU and for the host).  All operations are
+ * binary32, not contracted, in the order written, division correctly rounded; an operation on a texel is that operation on each of its
+ * three channels.  finite, amin, amax, aclamp: the display section's (amax(a, b) = (a >= b) ? a : b gives b when a is a NaN, amin
+ * likewise).  lum3(r, g, b) = (0.2126f * r + 0.7152f * g) + 0.0722f * b.  clampi(i, n) = i < 0 ? 0 : i > n - 1 ? n - 1 : i.
+ * Read, per channel c of pixel p:   s = scale * c;   not finite(s) or not s > 0:  s = +0;   s = amin(s, 0x1p+60f)      (display's rule).
+ *   s(p) is the pixel's three channels after it: finite and not negative for every input, and so is everything below.
+ * Prefilter.   threshold == 0 and knee == 0:  L0(p) = s(p), no arithmetic, and the exposure is never read.   Otherwise
+ *   l = e * lum3(s(p));    not finite(l) or not l > 0:  f = +0;   otherwise
+ *   q = aclamp(l - (threshold - knee), 0.0f, 2.0f * knee);   soft = knee > 0 ? (q * q) / (4.0f * knee) : +0;
+ *   c = amax(soft, amax(l - threshold, 0.0f));   f = amin(c / l, 1.0f);         L0(p) = f * s(p)           (the quadratic soft knee)
+ * Levels.   w_0 = width, h_0 = height;   w_(k+1) = (w_k + 1) >> 1, h likewise;   levels 1 .. M are made, M = the smaller of `levels`
+ *   and the first k >= 1 with w_k = h_k = 1.   D_0 = L0 (never stored).
+ * Down, texel (x, y) of level k + 1 from level k:   t[i][j] = D_k(clampi(2 x - 2 + j, w_k), clampi(2 y - 2 + i, h_k)), i, j = 0 .. 5
+ *   (i the row);   the quad mean Q(a, b) = ((t[b][a] + t[b][a+1]) + (t[b+1][a] + t[b+1][a+1])) * 0.25f;
+ *   inner = (Q(1,1) + Q(3,1)) + (Q(1,3) + Q(3,3));   edge = (Q(2,0) + Q(0,2)) + (Q(4,2) + Q(2,4));   corner = (Q(0,0) + Q(4,0)) + (Q(0,4) + Q(4,4));
+ *   D_(k+1)(x, y) = (0.125f * (inner + Q(2,2)) + 0.0625f * edge) + 0.03125f * corner
+ *   -- Jimenez's 13 taps: 0.125 centre, 0.125 x 4 inner, 0.0625 x 4 edge, 0.03125 x 4 corner, which sum to 1.
+ *   With karis = 1, for k = 0 only, the five boxes of the same quads instead:
+ *   g_0 = inner * 0.25f;   g_1 = ((Q(0,0) + Q(2,0)) + (Q(0,2) + Q(2,2))) * 0.25f;   g_2 = ((Q(2,0) + Q(4,0)) + (Q(2,2) + Q(4,2))) * 0.25f;
+ *   g_3 = ((Q(0,2) + Q(2,2)) + (Q(0,4) + Q(2,4))) * 0.25f;   g_4 = ((Q(2,2) + Q(4,2)) + (Q(2,4) + Q(4,4))) * 0.25f;
+ *   k_0 = 0.5f / (1.0f + lum3(g_0));   k_n = 0.125f / (1.0f + lum3(g_n)), n = 1 .. 4;   K = ((k_1 + k_2) + (k_3 + k_4)) + k_0;
+ *   D_1(x, y) = ((((k_1 * g_1) + (k_2 * g_2)) + ((k_3 * g_3) + (k_4 * g_4))) + (k_0 * g_0)) / K     (one hot pixel does not own its box)
+ * Up.   up(S, ws, hs)(x, y), the 2 x bilinear rule from a level S of ws x hs texels:   xn = x >> 1;   xf = clampi(x odd ? xn + 1 : xn - 1, ws);
+ *   yn, yf likewise with hs;   top = 0.75f * S(xn, yn) + 0.25f * S(xf, yn);   bot = 0.75f * S(xn, yf) + 0.25f * S(xf, yf);
+ *   up = 0.75f * top + 0.25f * bot      (an even coordinate lies a quarter past its source texel's near edge: the far one is the one before).
+ *   U_M = D_M;   U_k(x, y) = D_k(x, y) + scatter * (up(U_(k+1), w_(k+1), h_(k+1))(x, y) - D_k(x, y)),  k = M - 1 .. 1, in place over D_k.
+ * Mix, per pixel p = (x, y):   B = up(U_1, w_1, h_1)(x, y);   bloom3f(p) = B;   out3f(p) = s(p) + strength * (B - s(p)).
+ * No atomics and no workgroup waits for another: every texel is a function of the level above or below it alone, so no word depends
+ * on scheduling or on `variant`.  strength = 0 gives out3f = s, word for word; with threshold = knee = 0 and karis = 0 the sum of
+ * bloom3f is the sum of s up to rounding wherever no level's taps are clamped at an edge (both filters spread every texel with a total
+ * weight of 1), and a constant frame of a value with a short mantissa comes out constant.
+ * Refused before anything is launched, with art_last_error set: a null p or color3f; out3f and bloom3f both NULL; width or height < 1
+ * or width * height > 2^28; levels outside 1 .. 8; karis or variant other than 0 or 1; a scale that is not finite; a threshold or knee
+ * that is not finite or < 0; a scatter or strength outside [0, 1] or NaN; without a state an exposure that is not finite or < 0; an
+ * output overlapping color3f (other than out3f == color3f), the other output or exposure_state; a pointer that is host memory,
+ * another device's memory or too small. */
+typedef struct ArtBloomParams {
+  int32_t width, height;
+  int32_t levels;      /* 1..8 pyramid levels below the frame; levels that would follow a 1 x 1 level are not made */
+  int32_t karis;       /* 0 / 1: weight the first downsample's five boxes by 1 / (1 + luminance) so one hot pixel does not flicker */
+  int32_t variant;     /* 0: small levels in one workgroup; 1: one launch per level.  Same words either way */
+  float   scale;       /* the factor on color3f, e.g. 1 / spp */
+  float   exposure;    /* used when exposure_state is NULL; only the threshold reads it */
+  float   threshold, knee;   /* soft threshold on exposure * luminance; 0 and 0 = everything scatters (energy conserving) */
+  float   scatter;     /* [0, 1]: how much of each coarser level is carried into the finer one on the way up */
+  float   strength;    /* [0, 1]: out = s + strength * (bloom - s) */
+} ArtBloomParams;
+int  art_bloom_device(const ArtBloomParams* p, const float* color3f, const void* exposure_state /* or NULL */,
+                      float* out3f /* or NULL */, float* bloom3f /* or NULL */, void* hip_stream);
+
 /* ---- guided upsampling of a low-resolution render ------------------------------------------------------
  * Joint bilateral upsampling (Kopf et al. 2007): a colour plane traced at lo_width x lo_height ("lo") becomes a width x height picture
  * ("hi"), every hi pixel a weighted mean of the lo pixels around it, the weights stopped at edges by feature buffers given at BOTH
