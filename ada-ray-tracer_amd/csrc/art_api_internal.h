@@ -54,7 +54,8 @@ struct Options {
   int queue_segments = 8;       // the live-ray queue is cut into this many contiguous segments, one per XCD (1 = a single cursor)
   int ray_chunk = 48;            // trace records a wave claims per atomic (and prefetches): 16 -> 48 is worth 1 % on C4, 4 % on C3, 10 % on C5 (the claim stalls the wave)
   bool shadow_anyhit = true;   // shadow rays use the visibility rule instead of a full closest-hit search (same decision)
-  bool skip_null_shadow = false;   // DevFrame::skip_null_shadow: shadow rays that cannot change the picture are not traced (fewer rays than the reference issues: off by default)
+  bool skip_null_shadow = false;   // DevFrame::skip_null_shadow: true: shadow rays that cannot change the picture are neither traced nor counted (fewer rays than the reference
+                                   // issues: off by default).  false: the record schedule still answers them without a walk, and counts them as the reference issues them (make_frame)
   bool inst_coop = true;       // instanced scenes: the cooperative kernel crosses the instance boundary (k_trace_coop<.., INST>); false: k_trace_inst, one ray per lane (A/B, cross-check)
   // Items per thread of k_shade_compact (256 x per items and one global atomic per workgroup): 4 or 2.  Neither wins everywhere (inside one
   // process 2 is 5 % faster on C4, 3 % slower on C5, equal on S4: profiles/r6_shade/trial_check_*.txt; round 5's "+7 % / -10 %" of ab12 were
@@ -80,7 +81,7 @@ struct Options {
 };
 
 enum Counter {           // the words of Ctx::d_counters, which the kernels bump through pointers the host hands them
-  CNT_RAYS = 0,          // rays issued by raygen and the shade stages (ArtStats::rays)
+  CNT_RAYS = 0,          // queries issued by raygen and the shade stages (ArtStats::rays: the reference's Find_Closest_Hit / Compute_Shadow calls, walked or not)
   CNT_STATS = 3, CNT_TRACED = 7,      // [3..7]: box tests, triangle tests, node visits, leaf visits, rays of counting traces (TraceArgs::stats) | the last of them
   CNT_NODE_ITERS = 8, CNT_LEAF_ITERS = 9, CNT_WAVE_ITERS = 10, CNT_LOST = 15, kCounters = 16      // the cooperative kernel's phase counters | paths lost by the wavefront stages (must stay 0)
 };

@@ -204,7 +204,10 @@ void make_frame(const ArtPassParams* p, DevFrame& f) {
   std::memcpy(f.background, p->background, 12);
   const float fov = kHalfPi;                                   // ray_tracer.adb:63  Pi/2.0
   f.cam_z = -(float)c.width / safe_tan(fov / 2.0f);            // ray_tracer.adb:67
-  f.skip_null_shadow = c.opt.skip_null_shadow ? 1 : 0;
+  // null shadow rays (DevFrame::skip_null_shadow): the record schedule answers them without a walk and counts them, as it does a camera
+  // query that shares its ray; the counting variant and the one-ray-per-lane schedule walk every one of them
+  const bool walk_all = c.opt.count_tests || c.opt.trace_kernel != TRACE_COOP;
+  f.skip_null_shadow = c.opt.skip_null_shadow ? kNullShadowDropped : (walk_all ? kNullShadowTraced : kNullShadowCounted);
 }
 
 // The batch shape of a pass (plan_batch: pc * sc <= batch_paths) and a path state that holds one batch.  The result does not depend on

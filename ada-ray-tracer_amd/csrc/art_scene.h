@@ -115,11 +115,18 @@ struct DevFrame {
   uint32_t seed_lo, seed_hi;
   float background[3];
   float cam_z;          // -float(width)/safe_tan(fov/2)   ray_tracer.adb:67 (computed once on the host)
-  // Option skip_null_shadow (default 0 = the reference's work: Compute_Shadow for every surface hit, integrators.adb:270).  1: a shadow ray
-  // whose explicit colour is exactly zero whatever its verdict -- the light sample lies behind the surface (cosTheta1 = 0) or the BxDF is
-  // zero there -- is not traced.  The picture is the same bits (a zero that is not added is a zero); the RAY COUNT is not the reference's.
+  // What a stage does with a NULL shadow ray: one whose explicit colour is exactly zero whatever its verdict -- the light sample lies behind
+  // the surface (cosTheta1 = 0) or the BxDF is zero there (a NaN colour compares unequal: not null).  The reference calls Compute_Shadow for
+  // it (integrators.adb:270) and nothing can depend on the answer: the picture is the same bits either way (a zero that is not added is a zero).
+  //   kNullShadowTraced  (0) the ray is traced and counted: the counting variant (count_tests: "equal to the oracle's walk"), the one-ray-per-
+  //                          lane schedule and the host simulation;
+  //   kNullShadowDropped (1) option skip_null_shadow = 1: not traced and NOT counted -- the RAY COUNT is not the reference's;
+  //   kNullShadowCounted (2) the record schedule's default (make_frame): not traced, counted.  ArtStats::rays counts the reference's
+  //                          Find_Closest_Hit / Compute_Shadow calls; a camera query that shares its ray (DevPaths::cam_dedup) and a null
+  //                          shadow query are both counted as the reference issues them and answered without a tree walk.
   int32_t skip_null_shadow;
 };
+enum NullShadowMode : int32_t { kNullShadowTraced = 0, kNullShadowDropped = 1, kNullShadowCounted = 2 };
 
 // Record schedule (round 5): a bank's per-item arrays are ONE block, field f of item w at hot[f * stride + w] (stride: P rounded up to 64
 // items), and the fold arrays ONE block `cold`.  k_shade_compact addresses everything from these two bases with scalar arithmetic: held as

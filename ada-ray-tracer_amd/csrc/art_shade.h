@@ -645,7 +645,8 @@ ART_HD bool item_survives(const DevFrame& f, const DevScene& s, const DevPaths& 
   return item_class(s, qi, w, cx) != CLS_CHEAP && stage_keeps_surfaces(f, bounce);
 }
 
-// Returns the number of rays the item emits (the closest-hit queries of the next trace: Mrays/s counts them).
+// Returns the number of queries the item issues (the closest-hit queries of the next trace: Mrays/s counts them): its rays, and under
+// kNullShadowCounted the null shadow query it answers without a ray (DevFrame::skip_null_shadow).
 // hint != nullptr: the item is a surface item and *hint holds its hit key and material index (k_shade_compact's classification): the
 // triangle's normals and the material record are then requested together with the item's own words, one round trip instead of three
 // dependent ones (hit -> triangle shading record -> material).
@@ -833,7 +834,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
         s_tfar = (bound > 0.0f) ? bound : 0.0f;
         sh_min = 10.0f * eps;
         // (DevFrame::skip_null_shadow: a candidate of exactly zero stays zero under either verdict; NaN compares unequal and is traced)
-        null_shadow = f.skip_null_shadow && cand.x == 0.0f && cand.y == 0.0f && cand.z == 0.0f;
+        null_shadow = (f.skip_null_shadow != kNullShadowTraced) && cand.x == 0.0f && cand.y == 0.0f && cand.z == 0.0f;
         shadow = !null_shadow;
         if (shadow) fl |= FLAG_SHADOW_PENDING;
         else if (!dense) { qi.e_r[li] = cand.x; qi.e_g[li] = cand.y; qi.e_b[li] = cand.z; }      // (nobody will resolve it: the level's explicit light is this zero)
@@ -858,6 +859,9 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   }
   ART_PROBE(40);
   ART_TPROBE(cx.tprobe, 74);        // bsdf_sample done (all lanes)
+  // the item's Compute_Shadow call as ArtStats::rays and the self-check see it: a traced ray, or a null one that is answered without a walk
+  // and still counted (kNullShadowCounted; kNullShadowDropped: the option's "fewer rays than the reference issues")
+  const bool shadow_query = shadow || (null_shadow && f.skip_null_shadow == kNullShadowCounted);
   if (dense) {                      // dense stores: consecutive items, consecutive addresses
     const size_t l0 = (size_t)bounce * P;                   // (the level's base is wave-uniform: a scalar add; the item's offset stays 32 bits)
     const int32_t cw = fold_child_word((rec_child == -2 && wo >= 0) ? wo : rec_child, rec_shadowed);
@@ -866,7 +870,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
   }
   // ---- the output item
   if (wo < 0) {
-    if (lost != nullptr && (alive || shadow)) {
+    if (lost != nullptr && (alive || shadow_query)) {
 #if defined(__HIP_DEVICE_COMPILE__)
       atomicAdd(lost, 1ull);
 #endif
@@ -880,7 +884,7 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
     put_s(hotf<uint32_t>(qo, HF_FLAGS), wo, fl);
     put_s(hotf<float>(qo, HF_PDF), wo, new_pdf);
     if (shadow) put_s(hotf<float>(qo, HF_SHMIN), wo, sh_min);
-    if (shadow || null_shadow) {      // (null_shadow: the ray is not traced, DevFrame::skip_null_shadow -- the level's explicit light is still this exact zero)
+    if (shadow || null_shadow) {      // (null_shadow: the ray is not traced, DevFrame::skip_null_shadow -- the level's explicit light is still this exact zero; its record below says "no ray")
       put_s(cold_e(qi, 0, bounce + 1), wo, cand.x); put_s(cold_e(qi, 1, bounce + 1), wo, cand.y); put_s(cold_e(qi, 2, bounce + 1), wo, cand.z);
     }
     if (alive) {
@@ -914,12 +918,12 @@ ART_HD int shade_item(const DevFrame& f, const DevScene& s, const DevPaths& qi, 
     ART_TPROBE(cx.tprobe, 76);    // extension ray's record out
     if (mode != REC_EXT) emit_ray(s, qo, (batch || qo.sh_t) ? (size_t)(kShadowWord | (uint32_t)wo) : so_i, rec_slot(mode, wo, true), shadow, so, sd, s_tfar, qo.shadow_rule ? sh_min : -1.0f, cx, blocks ? cx.stage_item : per * cx.stage_item + (per - 1), 1);
     ART_TPROBE(cx.tprobe, 77);      // shadow ray's record out
-    if (lost != nullptr && ((mode == REC_SHADOW && alive) || (mode == REC_EXT && shadow))) {
+    if (lost != nullptr && ((mode == REC_SHADOW && alive) || (mode == REC_EXT && shadow_query))) {
 #if defined(__HIP_DEVICE_COMPILE__)
       atomicAdd(lost, 1ull);
 #endif
     }
-    return (alive ? 1 : 0) + (shadow ? 1 : 0);
+    return (alive ? 1 : 0) + (shadow_query ? 1 : 0);
   }
   qo.ray_tfar[wo] = alive ? kInfinity : -1.0f;
   qo.ray_tfar[so_i] = shadow ? s_tfar : -1.0f;

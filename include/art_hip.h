@@ -1339,7 +1339,8 @@ int  art_get_camera_rays_traced(uint64_t* out);
  * per node, 4 or 8;  "bvh_builder" [3] 3 binned SAH on the GPU (the tree of 0, built in milliseconds), 0 binned SAH on the host, 1 LBVH on the GPU, 2 PLOC on the GPU;  "bvh_ploc_radius" [8];  "bvh_spatial_splits" [0];  "bvh_max_leaf" [width];
  * "bvh_leaf_base_milli", "bvh_node_cost_milli", "bvh_tri_cost_milli".  The wavefront stages: "shade_per" [0 = measured; 2 | 4 items per thread],
  * "skip_null_shadow" [0] (1: a shadow ray whose explicit colour is exactly zero under either verdict -- the light sample behind the
- * surface, a BxDF that is zero there -- is not traced: the same picture 7-10 % sooner, but fewer rays than the reference issues, integrators.adb:270).  Instanced scenes: "inst_coop" [1] the cooperative kernel crosses the instance boundary (0: one ray per lane, the cross-check);
+ * surface, a BxDF that is zero there -- is neither traced nor counted: the same picture, but fewer rays in ArtStats than the reference issues, integrators.adb:270.
+ * 0: the cooperative schedule still answers such a query without a tree walk and counts it; "count_tests" = 1 and "trace_kernel" = 1 walk every one).  Instanced scenes: "inst_coop" [1] the cooperative kernel crosses the instance boundary (0: one ray per lane, the cross-check);
  * "inst_open" [0] entry points per instance the instance tree ends at (1 whole instances, n > 1 about n subtrees of the mesh's tree per
  * instance, 0 chosen from how much the instances' boxes overlap; takes effect at the next art_upload_scene).  How the path state is mapped
  * (round 6, profiles/r6_bimodal: the shade stage's rate depends on the size of the pieces its 35-74 GB are mapped in; the picture never does):
